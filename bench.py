@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|raw|fused84|fused84_f32|fused84_f32_ref|fused84_newest|car|car_fma|
                     tournament|tournament_full|protocol] [--envs E] [--gather none|scalars|obs|descriptors] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
 
 A "step" is one VecEnv.step over this rank's shard of envs with synthetic (pre-generated, device-resident) random
 actions, auto-reset included, no host sync inside the timed loop.  The headline (``metric`` / ``value``) is
@@ -17,6 +18,10 @@ what the numbers mean -- workload definitions, roofline models, CPU baseline sam
 under ``torch.distributed.run`` the RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* of the environment are used.  Envs shard
 across GPUs with no data-path collective (weak scaling: 65 536 envs per GPU); ``--gather obs|scalars`` adds the RCCL
 all-gather of BASELINE config #5 (one packed collective per step on a side stream, overlapped with the next step).
+
+``--dump-outputs DIR`` writes, after each workload's timed steps, the tensors its last timed step returned to the caller as
+DIR/<workload>_<field>.npy (float32 / float64, a fixed sample of envs where the whole would pass 64 MB in all; dump_outputs), so
+that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -57,6 +62,8 @@ def parse_args():
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default 65536; 16384 for car)")
     ap.add_argument("--gather", choices=["none", "scalars", "obs", "descriptors"], default="none")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what each workload's last timed step returned as DIR/<workload>_<field>.npy")
     return ap.parse_args()
 
 
@@ -240,6 +247,43 @@ def _r(x, nd=5):
     return x
 
 
+DUMP_BUDGET = 60_000_000  # bytes of .npy that --dump-outputs writes over all workloads of the run (at most 64 MB)
+DUMP_LIMIT = 64_000_000
+
+
+def dump_outputs(G, name, arrays):
+    """--dump-outputs DIR (rank 0): the device tensors the timed path handed its caller in the last timed step, as
+    DIR/<name>_<field>.npy, float64 for float64 / int64 data and float32 otherwise.  Every array has the envs on axis 0.  The
+    workload's share of DUMP_BUDGET decides: arrays of at most an eighth of the share are written whole, the others for one fixed
+    sample of envs (np.random.RandomState(0) over the env count, sorted; the same indices in each of them).  The inputs are
+    seeded, so the same arguments give the same files from run to run.  Returns the bytes written."""
+    import numpy as np
+    import torch
+
+    if G["rank"] != 0 or not G["dump_dir"]:
+        return 0
+    torch.cuda.synchronize()
+    share = G["dump_share"]
+    arrays = {k: torch.as_tensor(t) for k, t in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    assert all(t.shape[0] == n for t in arrays.values()), {k: tuple(t.shape) for k, t in arrays.items()}
+    dtypes = {k: torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32 for k, t in arrays.items()}
+    nbytes = {k: t.numel() * dtypes[k].itemsize for k, t in arrays.items()}
+    small = {k for k in arrays if nbytes[k] <= share // 8}
+    large_per_env = sum(nbytes[k] // n for k in arrays if k not in small)
+    rest = share - sum(nbytes[k] for k in small)
+    count = min(n, max(1, rest // large_per_env)) if large_per_env else n
+    idx = np.sort(np.random.RandomState(0).choice(n, count, replace=False))
+    written = 0
+    for k, t in arrays.items():
+        if k not in small and count < n:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.to(dtypes[k]).cpu().numpy()
+        np.save(os.path.join(G["dump_dir"], f"{name}_{k}.npy"), a)
+        written += a.nbytes
+    return written
+
+
 def timed_loop(G, args, step, after=None):
     """W warm-up calls of step(i), then exactly K timed ones between barrier + synchronize on both sides; max over ranks."""
     torch, dist, dev, world = G["torch"], G["dist"], G["dev"], G["world"]
@@ -292,6 +336,7 @@ def run_protocol(args, G):
     def leg_step_envs(i):
         out = crl.step_envs(pool[i % 16], env, books["ep"], cur["fst"], books["rr"], books["lr"], books["steps"], books["episodes"], dev, False)
         books["episodes"], books["steps"] = out[5], out[6]
+        cur["out"] = out
 
     def stack(dtype, bind):
         """the training scripts' preamble: a fresh stack, the env reset, its first observation pushed"""
@@ -336,6 +381,11 @@ def run_protocol(args, G):
         res[key] = dt / args.steps * 1e3
         if st is not None:
             fused[key] = cur["fst"].fused_updates
+        if key == "step_envs":  # the headline leg: what step_envs returned in its last timed call, and the stack it left
+            obs, reward, ended, _, masks, _, _, ep = cur["out"]
+            views = {f"obs{v}": o for v, o in enumerate(obs)} if isinstance(obs, tuple) else {"obs": obs}
+            G["dumped"] += dump_outputs(G, "protocol", dict(views, reward=reward, done=ended, masks=masks, episode_rewards=ep,
+                                                            frame_stack=cur["fst"].get()))
     env.close()
     base = res["step_device"]
     stack_bytes = 4 * 84 * 84 * 4
@@ -422,6 +472,7 @@ def run_workload(name, args, G):
         torch.cuda.synchronize()
 
     gather_state, dist_on = G.get("gather"), G["dist_on"]
+    last = {}
 
     def step(i):
         if dist_on and args.gather == "obs" and name not in ("tournament", "tournament_full"):
@@ -429,6 +480,7 @@ def run_workload(name, args, G):
             out = env.step_device(pool[i % 16], obs_out=gather_state.obs_slot(inner._obs[0].shape, inner._obs[0].dtype, dev))
         else:
             out = env.step_device(pool[i % 16])
+        last["out"] = out
         if dist_on and args.gather != "none":
             if args.gather == "descriptors":
                 # 64 bytes of frame descriptors per env over the links; every rank then re-draws the GLOBAL batch (inside wait())
@@ -487,6 +539,8 @@ def run_workload(name, args, G):
     touch_ms, touch_n, touch_max = inner.kernel_time_stats(2) if is_car else (0.0, 0, 0.0)
     final_state = env.get_state() if episodes_before is not None else None
     resets = int(final_state["episode"].astype("int64").sum() - episodes_before - int(warm_resets.item())) if episodes_before is not None else None
+    obs, rew, done = last["out"]
+    G["dumped"] += dump_outputs(G, name, {"obs": obs, "reward": rew, "done": done})
     env.close()
     res = {"value": world * n * args.steps / dt, "unit": "env-steps/s", "ms_per_step": dt / args.steps * 1e3, "dtype": dtype,
            "config": {"workload": WORKLOADS[name], "envs_per_gpu": n}}
@@ -572,7 +626,10 @@ def main():
     # CRL_BENCH_FORCE_DIST=1: a single rank goes through the process group all the same (RCCL world of one: barriers, the max over ranks, the
     # --gather collective) -- what a one-GPU box can run of the N > 1 path, tests/test_hip_round2.py
     dist_on = world > 1 or os.environ.get("CRL_BENCH_FORCE_DIST") == "1"
-    G = dict(torch=torch, crl=crl, dist=dist, dev=dev, world=world, rank=rank, dist_on=dist_on)
+    G = dict(torch=torch, crl=crl, dist=dist, dev=dev, world=world, rank=rank, dist_on=dist_on, dump_dir=args.dump_outputs,
+             dump_share=DUMP_BUDGET // len(names), dumped=0)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if dist_on:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group("nccl", device_id=dev)
@@ -585,6 +642,8 @@ def main():
         else:
             results[nm] = run_workload(nm, args, G)
         torch.cuda.empty_cache()
+    if G["dumped"] > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs wrote {G['dumped']} bytes, more than {DUMP_LIMIT}")
     if rank == 0:
         head = results[names[0]]
         metric = {"car": "env-steps/sec (whole node), cCarRacingDouble 16384 envs per GPU",

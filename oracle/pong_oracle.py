@@ -31,8 +31,10 @@ assert STATE_DT.itemsize == 120 and FRAME_DT.itemsize == 8
 
 def build(force=False):
     """(Re)builds liboracle.so / liboracle_libm.so when the sources changed.  Staleness is decided by a content hash kept
-    beside each library (file times do not survive a copy of the tree), and the whole check runs under a file lock: the
-    subprocess CPU baseline starts one worker per host thread, and all of them come through here at once."""
+    beside each library (file times do not survive a copy of the tree), and a rebuild runs under a file lock: the
+    subprocess CPU baseline starts one worker per host thread, and all of them come through here at once.  When every
+    library is current nothing is written, not even the lock: a tree built by one user can be used by another who may
+    not write to it."""
     import fcntl
     import hashlib
     inc = os.path.join(os.path.dirname(HERE), "include")
@@ -42,14 +44,21 @@ def build(force=False):
     for f in srcs:
         h.update(open(f, "rb").read())
     want = h.hexdigest()
+    libs = (LIB, LIB_LIBM) + (() if _SUFFIX else (LIB_FMA,))
+
+    def stale(lib_):  # (the stamp is written after its library is complete)
+        stamp = lib_ + ".stamp"
+        have = open(stamp).read().strip() if os.path.exists(stamp) else ""
+        return force or not os.path.exists(lib_) or have != want
+
+    if not any(stale(lib_) for lib_ in libs):
+        return LIB
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        for lib_ in (LIB, LIB_LIBM) + (() if _SUFFIX else (LIB_FMA,)):
-            stamp = lib_ + ".stamp"
-            have = open(stamp).read().strip() if os.path.exists(stamp) else ""
-            if force or not os.path.exists(lib_) or have != want:
+        for lib_ in libs:
+            if stale(lib_):
                 subprocess.check_call(["make", "-C", HERE, "-B", os.path.basename(lib_)], stdout=subprocess.DEVNULL)
-                with open(stamp, "w") as f:
+                with open(lib_ + ".stamp", "w") as f:
                     f.write(want)
     return LIB
 

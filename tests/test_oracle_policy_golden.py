@@ -90,6 +90,26 @@ def test_reference_checkpoint_loader_matches_shipped_weights(name):
         assert np.array_equal(a[k], b[k]), k
 
 
+@pytest.mark.parametrize("name", ["weak", "medium"])
+def test_checkpoint_loader_reads_the_reference_format(name, tmp_path):
+    """The same loader on a checkpoint written in the reference's format (policy_serving.py:33-36: torch.save of {"model":
+    LightActorCritic's state_dict, "optimizer": ...}, the legacy serialisation) from the shipped tensors: it finds every tensor
+    under the module's own names and yields exactly the shipped arrays."""
+    import torch
+
+    from competitive_rl_amd.policy_serving import load_light_weights
+
+    w = weights(name)
+    names = {"conv1": "conv1", "conv2": "conv2", "actor": "actor_linear", "critic": "critic_linear"}
+    sd = {f"{long}.{p}": torch.from_numpy(np.array(w[f"{short}_{p[0]}"])) for short, long in names.items() for p in ("weight", "bias")}
+    pkl = str(tmp_path / ("checkpoint-%s.pkl" % name))
+    torch.save({"model": sd, "optimizer": {"state": {}, "param_groups": []}}, pkl, _use_new_zipfile_serialization=False)
+    a = load_light_weights(pkl)
+    assert sorted(a) == sorted(f"{s}_{p}" for s in ("conv1", "conv2", "actor") for p in "wb")
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], w[k]), k
+
+
 def test_full_size_network_matches_the_reference_module():
     """ActorCritic (utils/network.py:14-70; STRONG / ALPHA_PONG's model, no checkpoint in the reference tree): the numpy restatement
     against logits and values the reference's own torch module produced on seeded weights (tests/golden/gen_policy_full_golden.py)."""
