@@ -16,8 +16,10 @@ Two ways the update runs on a GPU, same values:
   falling back: the env's newest learner observation with ``mask`` = 1 - done of that step, which is what ``step_envs`` passes
   (``_from_env`` marks its calls), or the observation of ``envs.reset()`` without a mask.  Anything else -- a foreign
   observation, a mask of the caller's own, two updates for one env step, an env step without an update -- is served by the
-  generic kernel below and the binding is re-checked against the env's history (one comparison on the device) before it is
-  used again.  ``dtype=torch.uint8`` (opt-in, not the reference's contract) keeps the stack as bytes: a quarter of the traffic.
+  generic kernel below and the binding is re-checked against the env's history (one comparison on the device, at the next env
+  step) before it is used again.  A call that rewrites the env's history behind the stack's back (``set_state`` /
+  ``load_state_dict``) moves the env's history epoch: a bound stack that is not all zeros is then re-checked the same way.
+  ``dtype=torch.uint8`` (opt-in, not the reference's contract) keeps the stack as bytes: a quarter of the traffic.
 * **generic** -- one kernel of libcrl_hip.so (csrc/frame_stack.hip): the observation is taken where it lies in HBM -- uint8 or
   float32, also a strided view such as agent 0's half of the (N, 2, K, R, R) buffer -- and widened on the fly.
   ``out_of_place=True`` (default): the reference's own data flow -- its ``self.current_obs = self.current_obs.roll(...)`` binds a
@@ -26,12 +28,14 @@ Two ways the update runs on a GPU, same values:
 
 Lifetime of the returned tensor (both ways, two buffers): the tensor handed out by ``get()`` / ``update()`` stays intact through
 the NEXT update and is recycled by the one after (the reference's old tensor lives as long as someone holds it; a rollout buffer
-copies what it stores, as the reference's does).  The second buffer doubles the footprint (7.4 GB more at 65 536 x (4, 84, 84)
-float32): it is allocated by the first update and released by ``reset()``; ``out_of_place=False`` never allocates it (and is
-never bound).
+copies what it stores, as the reference's does).  The bound path draws that one's state at the env step before it, which is when
+the re-check of a binding runs too.  The second buffer doubles the footprint (7.4 GB more at 65 536 x (4, 84, 84) float32): it is
+allocated by the first update and released by ``reset()``; ``out_of_place=False`` never allocates it (and is never bound).  Where
+the stack's newest plane IS the env's observation (``HipPongVecEnv._stack_alias``), neither a draw nor ``reset()`` writes over the
+observation the env handed out last: the stack takes a fresh buffer instead.
 
-``device="cpu"`` keeps the class usable with host-resident vector envs (numpy observations); that path is
-plain tensor arithmetic and is not part of the GPU hot path.  A CUDA device without the library raises.
+``device="cpu"`` keeps the class usable with host-resident vector envs (numpy observations); that path is plain tensor
+arithmetic (with the same two buffers) and is not part of the GPU hot path.  A CUDA device without the library raises.
 """
 import ctypes as C
 import weakref
@@ -40,6 +44,12 @@ import numpy as np
 import torch
 
 from . import _native as N
+
+
+def _hist_epoch(env):
+    """The env's history epoch: moved by every call that rewrites its plane history other than step / reset (HipPongVecEnv.set_state);
+    an env without one never does."""
+    return getattr(env, "_hist_epoch", 0)
 
 
 _MASK_OF_LAST_STEP = object()  # update_from_env: "1 - done of the env's last step", built only if the generic kernel needs it
@@ -69,15 +79,21 @@ class FrameStackTensor:
         self._zero = True         # the tensor is known to be all zeros (fresh, or reset())
         self._synced = False      # the env's plane history == this tensor's content (the fused draw may replace the generic update)
         self._env_serial = -1     # the env's step counter at the last update that consumed an env observation
-        self._pre = None          # (env serial, buffer) of a stack state the env's last step / reset drew ahead
+        self._env_epoch = -1      # the env's history epoch (moved by set_state) that the synced content follows
+        self._pre = None          # (env serial, buffer, kind, epoch) of a stack state the env's last step / reset drew ahead
+        self._recheck = False     # compare the tensor with the env's history at the next env step (_predraw)
         self._verify_left = 8     # re-checks of an unsynced binding before it is given up
+        self._lender = None       # weakref to the env whose newest observation may be a view of one of the two buffers (its last draw)
         self.fused_updates = 0    # (statistics: how many updates were pointer swaps)
 
     # ------------------------------------------------------------------ reference interface
     def reset(self):
-        self.current_obs.zero_()
+        if self._lends(self.current_obs):
+            self.current_obs = torch.zeros_like(self.current_obs)  # (zeroing in place would zero the env's observation too)
+        else:
+            self.current_obs.zero_()
         self._spare = None  # the second buffer is re-allocated by the next update (reset() used to leave it alive and stale)
-        self._age, self._zero, self._pre = 0, True, None
+        self._age, self._zero, self._pre, self._recheck = 0, True, None, False
         if self._env is not None and self._env() is not None:
             self._synced, self._verify_left = True, 8  # an all-zero stack follows any history: only planes younger than now are drawn
 
@@ -130,20 +146,25 @@ class FrameStackTensor:
         env._bound_stack = weakref.ref(self)
         self._pre, self._verify_left = None, 8
         self._synced = self._zero  # an all-zero stack needs no check; anything else is compared with the env's history on first use
-        if not self._synced:
-            self._verify(env)
+        self._recheck = not self._synced
         return True
 
     def unbind(self):
         env = self._env() if self._env is not None else None
         if env is not None and env._bound_stack is not None and env._bound_stack() is self:
             env._bound_stack = None
-        self._env, self._pre, self._synced = None, None, False
+        self._env, self._pre, self._synced, self._recheck = None, None, False, False
 
     def _other_buffer(self):
-        if self._spare is None:
+        if self._spare is None or self._lends(self._spare):
             self._spare = torch.empty_like(self.current_obs)
         return self._spare
+
+    def _lends(self, buf):
+        """Is the env's newest learner observation a view of ``buf`` (drawn as this stack's newest plane, ``HipPongVecEnv._stack_alias``)?"""
+        env = self._lender() if self._lender is not None else None
+        lives_in = getattr(env, "_obs_lives_in", None)  # (an env without the hook never hands out a stack's plane as its observation)
+        return lives_in is not None and lives_in(buf)
 
     def _stack_desc(self, buf, valid, alias):
         return N.CrlStackDesc(stack_dev=buf.data_ptr(), planes=self.frame_stack, dtype=N.CRL_OBS_F32 if self.dtype == torch.float32 else N.CRL_OBS_U8,
@@ -153,6 +174,13 @@ class FrameStackTensor:
         """Called by the env inside step / reset (before it counts the call): the buffer the launch should draw this stack's NEXT state
         into and its descriptor, or None (not synced: the env then draws its observation only)."""
         self._pre = None
+        if self._synced and not self._zero and _hist_epoch(env) != self._env_epoch:
+            self._synced, self._recheck = False, True  # the history was rewritten (set_state): does it still explain the tensor?
+        if self._recheck and kind == "step":
+            # (here rather than behind the generic update: the other buffer is the tensor the update before that handed out, promised
+            # intact through that update, and the draw below recycles it now anyway)
+            self._recheck = False
+            self._verify(env)
         if not self._synced:
             return None
         # exactly one env step since the last update that consumed one -- or a stack without history, which follows any; an env reset
@@ -164,14 +192,15 @@ class FrameStackTensor:
         return buf, self._stack_desc(buf, min(self._age + 1, self.frame_stack), env._stack_alias(self))
 
     def _predrawn(self, env, buf, kind):
-        self._pre = (env._serial, buf, kind)
+        self._pre = (env._serial, buf, kind, _hist_epoch(env))
+        self._lender = self._env  # (the env's newest observation may be this buffer's newest plane now)
 
     def _try_commit(self, obs, mask, from_env):
         pre, self._pre = self._pre, None
         env = self._env() if self._env is not None else None
         if pre is None or env is None or env.closed or not self._synced:
             return False
-        serial, buf, kind = pre
+        serial, buf, kind, epoch = pre
         if serial != env._serial or not env._is_latest_learner_obs(obs):
             return False
         if kind == "step":
@@ -181,7 +210,7 @@ class FrameStackTensor:
             return False
         self._spare, self.current_obs = self.current_obs, buf
         self._age = min(self._age + 1, self.frame_stack)
-        self._zero, self._env_serial = False, env._serial
+        self._zero, self._env_serial, self._env_epoch = False, env._serial, epoch
         self.fused_updates += 1
         return True
 
@@ -200,17 +229,24 @@ class FrameStackTensor:
         if self._verify_left <= 0:
             self.unbind()
             return
-        self._verify(env)
+        self._recheck = True
 
     def _verify(self, env):
-        """Is this tensor what the env's plane history draws for a stack of this age?  One draw into the other buffer + one comparison on
-        the device (a host synchronisation: after a bind of a used stack or a generic update, at most eight times in a row)."""
+        """Called before an env step: are the planes of this tensor that the step keeps (all but the oldest) what the env's plane history
+        draws for a stack of this age?  One draw into the other buffer + one comparison on the device (a host synchronisation: at the env
+        step after a bind of a used stack, a generic update or a set_state, at most eight times in a row); none for one plane.  (The oldest
+        plane is left out: it rolls out with the step, and a set_state does not restore it -- crl_pong_env_state keeps three.)"""
         self._verify_left -= 1
-        buf = self._other_buffer()
-        env._draw_stack_into(self._stack_desc(buf, min(self._age, self.frame_stack), False))
-        if bool(torch.equal(buf, self.current_obs)):
-            self._synced, self._env_serial, self._verify_left = True, env._serial, 8
-        return self._synced
+        kept = self.num_channels * (self.frame_stack - 1)
+        if kept:
+            buf = self._other_buffer()
+            env._draw_stack_into(self._stack_desc(buf, min(self._age, self.frame_stack), False))
+            ok = bool(torch.equal(buf[:, -kept:], self.current_obs[:, -kept:]))
+        else:
+            ok = True
+        if ok:
+            self._synced, self._env_serial, self._env_epoch, self._verify_left = True, env._serial, _hist_epoch(env), 8
+        return ok
 
     # ------------------------------------------------------------------ generic update
     def _as_mask(self, mask):
@@ -257,7 +293,8 @@ class FrameStackTensor:
                 N.check(self._lib.crl_frame_stack_update(C.c_void_p(self.current_obs.data_ptr()), C.c_void_p(o.data_ptr()), *tail))
 
     def _update_host(self, o, m):
-        """Plain tensor arithmetic: host-resident stacks only (device="cpu", numpy observations)."""
+        """Plain tensor arithmetic: host-resident stacks only (device="cpu", numpy observations).  Out of place into the other buffer
+        (the lifetime contract of the module docstring) unless ``out_of_place=False``."""
         c, buf = self.num_channels, self.current_obs
         kept = buf[:, c:]
         if m is not None:
@@ -265,5 +302,8 @@ class FrameStackTensor:
             kept = kept * (mm if self.dtype == torch.float32 else (mm != 0).to(torch.uint8))
         else:
             kept = kept.clone()
-        buf[:, :buf.shape[1] - c] = kept
-        buf[:, buf.shape[1] - c:] = o.to(self.dtype)
+        dst = self._other_buffer() if self.out_of_place else buf
+        dst[:, :buf.shape[1] - c] = kept
+        dst[:, buf.shape[1] - c:] = o.to(self.dtype)
+        if self.out_of_place:
+            self._spare, self.current_obs = self.current_obs, dst

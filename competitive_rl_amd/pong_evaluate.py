@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from .utils import _per_env_done
+from .utils import _own_hook, _per_env_done
 
 __all__ = ["evaluate_two_policies", "evaluate_two_policies_in_batch"]
 
@@ -54,7 +54,7 @@ def evaluate_two_policies_in_batch(compute_action0, compute_action1, envs, num_e
     device = obs[0].device if on_device else None
     episode_rewards = (torch.zeros((envs.num_envs, 2), dtype=torch.float64, device=device) if on_device
                        else np.zeros([envs.num_envs, 2], dtype=np.float64))
-    early = getattr(envs, "done_host", None)
+    early = _own_hook(envs, "done_host")
     while True:
         actions = _actions(compute_action0(obs[0]), compute_action1(obs[1]), device)
         obs, reward, done, info = envs.step(actions)
@@ -91,7 +91,7 @@ def evaluate_two_policies(compute_action0, compute_action1, env, num_episode, re
     vec = hasattr(env, "num_envs")
     if vec and env.num_envs != 1:
         raise ValueError("evaluate_two_policies plays ONE env; use evaluate_two_policies_in_batch for a batch")
-    early = getattr(env, "done_host", None) if vec else None
+    early = _own_hook(env, "done_host") if vec else None
     obs = None
     for episode in range(num_episode):
         matchTotalReward = [0.0, 0.0]

@@ -18,12 +18,24 @@ With the HIP env everything the step produced is already in HBM: the device ``Fr
 the first call (``FrameStackTensor.bind``: ``envs.step`` then draws the stack's next state in the launch that draws the
 observation, and the update here is a pointer swap; other envs / stacks: one kernel), masks are built on the device, and
 ``episode_rewards`` may itself be a device tensor.  The only host traffic is the N done flags (the recorders are host lists) and, for a numpy
-``episode_rewards``, the N x A rewards.
+``episode_rewards``, the N x A rewards.  Both shortcuts (the early done flags and the bound stack) are taken only from ``envs`` itself: a
+``VecEnvWrapper`` whose ``step_wait`` changes ``done`` (a time limit, say) is followed by its own ``done`` -- it opts in by defining
+``done_host`` / ``_stack_env`` in its class.
 """
 import numpy as np
 import torch
 
+from .vec_env import VecEnvWrapper
+
 __all__ = ["step_envs", "evaluate"]
+
+
+def _own_hook(envs, name):
+    """``envs.<name>`` unless only a ``VecEnvWrapper``'s attribute forwarding finds it (on the env below, whose done flags and plane history
+    the wrapper's ``step_wait`` may not pass on), else None."""
+    if isinstance(envs, VecEnvWrapper) and not envs._own(name):
+        return None
+    return getattr(envs, name, None)
 
 
 def _per_env_done(done):
@@ -67,14 +79,15 @@ class _Returns:
 def step_envs(cpu_actions, envs, episode_rewards, frame_stack_tensor, reward_recorder, length_recorder, total_steps,
               total_episodes, device, test):
     shape_before = episode_rewards.shape
-    if not getattr(frame_stack_tensor, "_bind_tried", True):
+    stack_env = _own_hook(envs, "_stack_env")
+    if stack_env is not None and not getattr(frame_stack_tensor, "_bind_tried", True):
         frame_stack_tensor.bind(envs)  # (once: from now on envs.step draws the stack's next state, frame_stack.py)
     obs, reward, done, info = envs.step(cpu_actions)
     learner_obs = obs[0] if isinstance(obs, tuple) else obs  # two-agent Pong: the learner is agent 0
     num_envs = learner_obs.shape[0]
 
     ended = _per_env_done(done)
-    early = getattr(envs, "done_host", None)  # the HIP Pong env hands the flags over while the step's draw still runs (vec_env.py)
+    early = _own_hook(envs, "done_host")  # the HIP Pong env hands the flags over while the step's draw still runs (vec_env.py)
     ended_host = early() if early is not None else (ended.cpu().numpy() if isinstance(ended, torch.Tensor) else ended)
 
     returns = _Returns(episode_rewards)
@@ -95,7 +108,7 @@ def step_envs(cpu_actions, envs, episode_rewards, frame_stack_tensor, reward_rec
     else:
         masks = torch.from_numpy((~ended_host).astype(np.float32)).to(device).reshape(num_envs, 1)
     stack_mask = masks if test else masks.reshape(num_envs, 1, 1, 1)
-    if getattr(frame_stack_tensor, "_env", None) is not None:
+    if stack_env is not None and getattr(frame_stack_tensor, "_env", None) is not None:
         frame_stack_tensor.update(learner_obs, stack_mask, _from_env=envs)  # (a bound stack: the pointer swap)
     else:
         frame_stack_tensor.update(learner_obs, stack_mask)

@@ -364,6 +364,7 @@ class HipPongVecEnv(VecEnv):
         self._bound_stack = None       # weakref
         self._last_kind = None         # "reset" | "step": what produced the newest observation
         self._learner_obs = None       # agent 0's newest observation as handed out (torch output only)
+        self._hist_epoch = 0           # moved by every call that rewrites the plane history other than step / reset (set_state)
 
     # ------------------------------------------------------------------ helpers
     def _stream(self):
@@ -448,6 +449,11 @@ class HipPongVecEnv(VecEnv):
         mine = self._learner_obs
         return (mine is not None and isinstance(obs, torch.Tensor) and obs.data_ptr() == mine.data_ptr() and obs.shape == mine.shape
                 and obs.dtype == mine.dtype and obs.stride() == mine.stride())
+
+    def _obs_lives_in(self, buf):
+        """Is agent 0's newest observation a view of ``buf`` (a bound stack's buffer, ``_stack_alias``)?"""
+        mine = self._learner_obs
+        return mine is not None and mine.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr()
 
     def _latest_learner_obs(self):
         if self._learner_obs is None:
@@ -622,6 +628,7 @@ class HipPongVecEnv(VecEnv):
         st = np.ascontiguousarray(st, N.STATE_DT)
         assert len(st) == self.num_envs
         N.check(self._L.crl_set_state(self._h, st.ctypes.data_as(C.c_void_p), 0, self.num_envs, self._stream()))
+        self._hist_epoch += 1  # the plane history is the loaded one: a bound stack re-checks before its next draw (frame_stack.py)
 
     def state_dict(self):
         """Checkpoint of the whole batch in torch's idiom (SURVEY section 5 "checkpoint / resume"): a plain dict that ``torch.save`` /

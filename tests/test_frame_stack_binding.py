@@ -12,13 +12,15 @@ from competitive_rl_amd.frame_stack import FrameStackTensor
 
 class FakeRingEnv:
     """What frame_stack.py uses of HipPongVecEnv, over synthetic one-plane observations: step() / reset() keep the last four planes per
-    env (None = erased), draw a bound stack's next state into the buffer it offers, and hand out the newest plane as the observation."""
+    env (None = erased), draw a bound stack's next state into the buffer it offers, and hand out the newest plane as the observation.
+    get_state() / set_state() replace the planes behind the stack's back (and move the history epoch, as the HIP env's set_state does).
+    ``alias=True``: float32 observations, and a drawn stack's newest plane IS the observation handed out (HipPongVecEnv._stack_alias)."""
 
-    def __init__(self, n, shape=(1, 6, 6), seed=0):
-        self.n, self.shape, self.rs = n, shape, np.random.RandomState(seed)
+    def __init__(self, n, shape=(1, 6, 6), seed=0, alias=False):
+        self.n, self.shape, self.rs, self.alias = n, shape, np.random.RandomState(seed), alias
         self.device, self.closed = torch.device("cpu"), False
         self._bound_stack = None
-        self._serial, self._last_kind, self._learner = 0, None, None
+        self._serial, self._last_kind, self._learner, self._hist_epoch = 0, None, None, 0
         self.ring = [[None] * 4 for _ in range(n)]
         self._done = torch.zeros(n, dtype=torch.uint8)
         self.draws = 0
@@ -31,7 +33,10 @@ class FakeRingEnv:
         return fst.num_envs == self.n and fst.num_channels == 1 and fst.frame_stack <= 4 and fst.plane_shape == self.shape[1:] and fst.device == self.device
 
     def _stack_alias(self, fst):
-        return False
+        return self.alias and fst.dtype == torch.float32
+
+    def _obs_lives_in(self, buf):
+        return self._learner is not None and self._learner.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr()
 
     def _is_latest_learner_obs(self, obs):
         return self._learner is not None and isinstance(obs, torch.Tensor) and obs.data_ptr() == self._learner.data_ptr() and obs.shape == self._learner.shape
@@ -70,19 +75,29 @@ class FakeRingEnv:
         self._serial += 1
         self._last_kind = kind
         self._done = torch.from_numpy(done.astype(np.uint8))
-        self._learner = torch.from_numpy(new.copy())
+        self._learner = torch.from_numpy(new.astype(np.float32) if self.alias else new.copy())
         if pre is not None:
             buf, desc = pre
             self._paint(buf, desc.planes, desc.valid_planes)
+            if desc.alias_newest:
+                self._learner = buf[:, desc.planes - 1:desc.planes]
             fst._predrawn(self, buf, kind)
         return self._learner
 
     def reset(self):
         return self._advance("reset", np.zeros(self.n, bool))
 
-    def step(self, p_done=0.2):
-        done = self.rs.random_sample(self.n) < p_done
-        return self._advance("step", done), done
+    def step(self, p_done=0.2, done=None):
+        if done is None:
+            done = self.rs.random_sample(self.n) < p_done
+        return self._advance("step", np.asarray(done, bool)), np.asarray(done, bool)
+
+    def get_state(self):
+        return [list(r) for r in self.ring]
+
+    def set_state(self, st):
+        self.ring = [list(r) for r in st]
+        self._hist_epoch += 1
 
 
 class RefStack:
@@ -132,14 +147,22 @@ def test_the_regular_loop_is_all_pointer_swaps(k):
     assert fst.fused_updates == 41
 
 
-def test_binding_a_used_stack_checks_it_against_the_history_first():
+def test_binding_a_used_stack_checks_it_against_the_history_at_the_next_step():
+    """bind() of a used stack draws nothing: its other buffer is the tensor the update before last handed out, still held by the
+    caller.  The check (one draw + one comparison) runs at the next env step, whose draw ahead recycles that buffer anyway."""
     env, fst, ref = _pair()
     obs = env.reset()
-    fst.update(obs), ref.update(obs.numpy())          # unbound: the generic update
-    assert fst.fused_updates == 0 and not fst._zero
-    draws = env.draws
-    assert fst.bind(env) and env.draws == draws + 1 and fst._synced   # one draw + one comparison: the tensor is what the history draws
-    for _ in range(6):
+    held = fst.update(obs)                             # unbound: the generic update
+    ref.update(obs.numpy())
+    obs, done = env.step(0.0)
+    fst.update(obs, torch.ones(5, 1, 1, 1)), ref.update(obs.numpy(), np.ones((5, 1, 1, 1), np.float32))
+    assert fst.fused_updates == 0 and not fst._zero and _same(fst, ref)
+    copy, draws = held.clone(), env.draws
+    assert fst.bind(env) and env.draws == draws and not fst._synced
+    assert torch.equal(held, copy)                     # the tensor of the update before last is intact through the bind
+    _step_envs_like(env, fst, ref)
+    assert env.draws == draws + 2 and fst._synced and fst.fused_updates == 1   # at the step: one draw + one comparison, then the draw ahead
+    for _ in range(5):
         _step_envs_like(env, fst, ref)
     assert fst.fused_updates == 6
     # a stack whose content the env's history canNOT explain binds, stays generic, and comes back once the strange planes have rolled out
@@ -216,6 +239,34 @@ def test_what_falls_back_to_the_generic_update_and_how_the_binding_returns():
     assert fst._synced and fst.fused_updates > before
 
 
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_set_state_under_a_bound_stack_falls_back_until_the_loaded_planes_roll_out(k):
+    """A set_state rewrites the history behind the stack: the trainer's older planes are its own, so the updates after it are generic until
+    the pre-load planes have rolled out (k - 1 of them matter), then every update is a pointer swap again; a reset() stack follows any history."""
+    env, fst, ref = _pair(k=k)
+    fst.bind(env)
+    obs = env.reset()
+    fst.update(obs), ref.update(obs.numpy())
+    for _ in range(3):
+        _step_envs_like(env, fst, ref, p_done=0.0)
+    snap = env.get_state()
+    for _ in range(5):
+        _step_envs_like(env, fst, ref, p_done=0.0)
+    env.set_state(snap)
+    generic = 0
+    for _ in range(k + 3):
+        before = fst.fused_updates
+        _step_envs_like(env, fst, ref, p_done=0.0)                 # (asserts the reference's bytes)
+        generic += fst.fused_updates == before
+    assert generic == k - 1 and fst._synced, generic
+    fst.reset(), ref.reset()
+    env.set_state(snap)
+    before = fst.fused_updates
+    for _ in range(3):
+        _step_envs_like(env, fst, ref, p_done=0.0)
+    assert fst.fused_updates == before + 3
+
+
 def test_one_env_draws_one_stack_and_a_closed_env_lets_go():
     env, f1, r1 = _pair()
     f2 = FrameStackTensor(5, env.shape, 4, "cpu")
@@ -232,3 +283,107 @@ def test_one_env_draws_one_stack_and_a_closed_env_lets_go():
     assert not FrameStackTensor(5, env.shape, 4, "cpu", out_of_place=False).bind(FakeRingEnv(5))
     assert not FrameStackTensor(5, (2, 6, 6), 2, "cpu").bind(FakeRingEnv(5))     # two channels per observation: not what the env's history holds
     assert not FrameStackTensor(5, env.shape, 4, "cpu").bind(object())
+
+
+class HeldTensors:
+    """The lifetime contract of frame_stack.py: a tensor handed out by get() / update() stays byte-identical through the next update;
+    the first env call or update after that one may recycle its buffer (the bound path draws the next state at the env step)."""
+
+    def __init__(self):
+        self.items = []   # [tensor, copy taken when handed out, updates since]
+
+    def hand_out(self, t):
+        self.items.append([t, t.clone(), 0])
+
+    def before_env_or_update(self):
+        self.items = [it for it in self.items if it[2] < 1]
+
+    def before_stack_reset(self, current):
+        self.items = [it for it in self.items if it[0].data_ptr() != current.data_ptr()]   # (zeroed by reset(), as the reference's)
+
+    def updated(self):
+        for it in self.items:
+            it[2] += 1
+
+    def check(self, where):
+        for t, copy, age in self.items:
+            assert torch.equal(t, copy), (where, age)
+
+
+OPS = ["step"] * 6 + ["step_ends"] * 2 + ["run", "set_state", "env_reset", "stack_reset", "foreign", "skip", "rebind", "own_mask"]
+
+
+@pytest.mark.parametrize("alias", [False, True])
+@pytest.mark.parametrize("k", [1, 2, 4])
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_random_operation_sequences_against_the_reference_update(seed, k, alias):
+    """300 operations drawn from everything a trainer may do between two updates of a bound stack -- the step_envs update, forced episode
+    ends, set_state to an earlier snapshot, an env reset pushed without a mask, stack.reset(), a foreign observation, an env step without
+    an update, unbind / bind, a mask of the caller's own -- and after EVERY one: (a) the stack is the reference's update sequence, byte for
+    byte; (b) every tensor handed out is intact through the next update; (c) the env's newest observation is untouched by the stack.  And
+    the fast path stays: k + 1 plain steps in a row on a bound stack end in a pointer swap."""
+    n = 6
+    env = FakeRingEnv(n, seed=100 + seed, alias=alias)
+    fst = FrameStackTensor(n, env.shape, k, "cpu")
+    ref = RefStack(n, env.shape, k)
+    held = HeldTensors()
+    rs = np.random.RandomState(seed)
+    assert fst.bind(env)
+    held.before_env_or_update()
+    obs = env.reset()
+    env_copy = obs.clone()
+    assert fst.update(obs) is fst.get()
+    ref.update(obs.numpy())
+    held.updated()
+    snaps, plain_run, long_runs, seen = [env.get_state()], 0, 0, set()
+
+    def push(o, mask=None, from_env=None):
+        out = fst.update(o, None if mask is None else torch.from_numpy(mask), _from_env=from_env)
+        assert out is fst.get()
+        ref.update(o.numpy(), mask)
+        held.updated()
+
+    queue = []
+    for t in range(300):
+        if not queue:
+            op = OPS[rs.randint(len(OPS))]
+            seen.add(op)
+            queue = ["step"] * (k + 2) if op == "run" else [op]   # ("run": a stretch of plain steps, long enough for the binding to return)
+        op = queue.pop()
+        fused_before = fst.fused_updates
+        plain_run = plain_run + 1 if op == "step" else 0
+        if op in ("step", "step_ends", "env_reset", "foreign", "skip", "own_mask"):
+            held.before_env_or_update()
+        if op in ("step", "step_ends", "skip", "own_mask"):
+            obs, done = env.step(0.15) if op != "step_ends" else env.step(done=rs.random_sample(n) < 0.5)
+            env_copy = obs.clone()
+            if rs.random_sample() < 0.3:
+                snaps.append(env.get_state())
+            if op in ("step", "step_ends"):
+                push(obs, (1.0 - done.astype(np.float32)).reshape(-1, 1, 1, 1), env)      # what step_envs passes
+            elif op == "own_mask":
+                push(obs, (rs.random_sample(n) < 0.7).astype(np.float32).reshape(-1, 1, 1, 1))
+        elif op == "set_state":
+            env.set_state(snaps[rs.randint(len(snaps))])
+        elif op == "env_reset":
+            obs = env.reset()
+            env_copy = obs.clone()
+            push(obs)
+        elif op == "stack_reset":
+            held.before_stack_reset(fst.get())
+            fst.reset(), ref.reset()
+        elif op == "foreign":
+            push(torch.from_numpy(rs.randint(0, 256, (n, *env.shape)).astype(np.uint8)))
+        elif op == "rebind":
+            if fst._env is None:
+                assert fst.bind(env)
+            else:
+                fst.unbind()
+        held.hand_out(fst.get())
+        assert _same(fst, ref), (t, op)                                                  # (a)
+        held.check((t, op))                                                              # (b)
+        assert torch.equal(env._latest_learner_obs(), env_copy), (t, op)                 # (c)
+        if op == "step" and plain_run >= k + 1 and fst._env is not None:
+            assert fst.fused_updates == fused_before + 1, (t, plain_run)
+            long_runs += 1
+    assert seen == set(OPS) and fst.fused_updates >= 15 and long_runs >= 5, (seen, fst.fused_updates, long_runs)
