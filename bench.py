@@ -2,17 +2,21 @@
 """bench.py -- env-steps/sec of the cPongDouble hot path on N MI355X (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|raw|fused84|fused84_f32|fused84_f32_ref|fused84_newest|car|car_fma|
-                    tournament|tournament_full|protocol] [--envs E] [--gather none|scalars|obs|descriptors] [--no-cpu-baseline]
+                    tournament|tournament_full|protocol] [--envs E] [--gather none|scalars|obs|descriptors] [--full] [--no-cpu-baseline]
                     [--dump-outputs DIR]
 
 A "step" is one VecEnv.step over this rank's shard of envs with synthetic (pre-generated, device-resident) random
 actions, auto-reset included, no host sync inside the timed loop.  The headline (``metric`` / ``value``) is
 BASELINE.json configs[1]: cPongDouble-v0, 65 536 envs per GPU, raw (N, 2, 210, 160, 3) uint8 observations, 1 env-step =
-1 frame.  With the default ``--workload all`` on one GPU the same process then measures every other single-GPU
-configuration (fused gray+84x84+4-stack u8 and its float32 variant, cCarRacingDouble, the tournament loop) the same way
-and attaches them under ``"configs"``, each with its own ``roofline`` and ``cpu_baseline``, plus a flat ``"configs_brief"``
-{name: [env-steps/s, ms/step, roofline frac]}.  ONE JSON line on rank 0, numbers only (< 6 KB: the driver keeps 8 KB of stdout);
-what the numbers mean -- workload definitions, roofline models, CPU baseline samples -- is DESIGN.md section 7.
+1 frame.  A plain run measures that one workload (or the one ``--workload`` names) and nothing else (but see ``--dump-outputs``).
+
+``--full`` adds everything else the benchmark measures: first the CPU baselines of the measured workloads (unless
+``--no-cpu-baseline``), and with the default ``--workload all`` on one GPU every other single-GPU configuration (fused
+gray+84x84+4-stack u8 and its float32 variant, cCarRacingDouble, the tournament loop, the drop-in protocol), measured the same
+way after the headline in the same process and attached under ``"configs"``, each with its own ``roofline`` and
+``cpu_baseline``, plus a flat ``"configs_brief"`` {name: [env-steps/s, ms/step, roofline frac]}.  ONE JSON line on rank 0,
+numbers only (< 6 KB: the driver keeps 8 KB of stdout); what the numbers mean -- workload definitions, roofline models, CPU
+baseline samples -- is DESIGN.md section 7.
 
 ``--gpus N`` without a launcher starts N fresh worker processes itself (one per GPU, before anything touches the GPU);
 under ``torch.distributed.run`` the RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* of the environment are used.  Envs shard
@@ -21,7 +25,9 @@ all-gather of BASELINE config #5 (one packed collective per step on a side strea
 
 ``--dump-outputs DIR`` writes, after each workload's timed steps, the tensors its last timed step returned to the caller as
 DIR/<workload>_<field>.npy (float32 / float64, a fixed sample of envs where the whole would pass 64 MB in all; dump_outputs), so
-that two builds run with the same arguments can be compared output for output.
+that two builds run with the same arguments can be compared output for output.  With ``--workload all`` on one GPU it runs
+every workload for its outputs, ``--full`` or not: the files are the same either way, and only ``--full`` adds the other
+workloads' figures (and the CPU baselines) to the line.
 """
 import argparse
 import json
@@ -61,9 +67,12 @@ def parse_args():
                     choices=["all", "raw", "fused84", "fused84_f32", "fused84_f32_ref", "fused84_newest", "car", "car_fma", "tournament", "tournament_full", "protocol"])
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default 65536; 16384 for car)")
     ap.add_argument("--gather", choices=["none", "scalars", "obs", "descriptors"], default="none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and, with --workload all on one GPU, every other workload (configs, configs_brief)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what each workload's last timed step returned as DIR/<workload>_<field>.npy")
+                    help="after the timed steps, write what each workload's last timed step returned as DIR/<workload>_<field>.npy "
+                         "(with --workload all on one GPU: every workload, --full or not)")
     return ap.parse_args()
 
 
@@ -107,7 +116,7 @@ def effective_cores():
 
 
 def cpu_baselines(workloads, budget_s=float(os.environ.get("CRL_BENCH_CPU_BUDGET_S", "8.0"))):
-    """Rank 0, one GPU only, BEFORE the GPU is touched: the oracle timed on this host's cores on bounded samples of
+    """--full only; rank 0, one GPU only, BEFORE the GPU is touched: the oracle timed on this host's cores on bounded samples of
     the same workloads -- (a) in the reference's SubprocVecEnv architecture (one process per env, pipes, pickled
     observations; oracle/subproc_baseline.py), which is the reported ``value``; (b) as one OpenMP batch over all
     cores (upper bound of a compiled port); plus BASELINE config #1 (4 envs, synchronous).  ``cores`` = effective_cores(): the
@@ -609,11 +618,13 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    multi = args.workload == "all" and world == 1
-    names = ALL if multi else [("raw" if args.workload == "all" else args.workload)]
+    every = args.workload == "all" and world == 1
+    multi = every and args.full  # the line carries every workload (configs, configs_brief)
+    # --full measures every workload of ALL, --dump-outputs runs them all for their outputs; a plain run times the headline alone
+    names = ALL if every and (args.full or args.dump_outputs) else [("raw" if args.workload == "all" else args.workload)]
     # the CPU baselines run first: worker processes are started while this process has not initialised the GPU
     cpu = {}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baselines(names)
 
     import torch

@@ -702,7 +702,7 @@ def test_car_full_resets_with_the_walk_ahead_running_give_the_same_tracks():
 
 
 def test_default_bench_line_fits_the_drivers_buffer():
-    """``python bench.py`` (every workload, CPU baselines included) prints ONE JSON line, and the driver keeps 8 KB of stdout: the line
+    """``python bench.py --full`` (every workload, CPU baselines included) prints ONE JSON line, and the driver keeps 8 KB of stdout: the line
     must stay well under that whatever digits the numbers have (small batches here: the line's structure does not depend on the size)."""
     _need_gpu()
     import json
@@ -711,8 +711,8 @@ def test_default_bench_line_fits_the_drivers_buffer():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--envs", "2048"], capture_output=True, text=True,
-                         timeout=900, env=dict(os.environ, CRL_BENCH_CAR_PREROLL="20", CRL_BENCH_CPU_BUDGET_S="1.0"))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--envs", "2048"], capture_output=True,
+                         text=True, timeout=900, env=dict(os.environ, CRL_BENCH_CAR_PREROLL="20", CRL_BENCH_CPU_BUDGET_S="1.0"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines[:3]
@@ -725,3 +725,38 @@ def test_default_bench_line_fits_the_drivers_buffer():
     assert car["step_frac"] > 0 and car["critical_path"]["kernel"] == "car_touch_kernel" and car["critical_path"]["max_us"] >= car["critical_path"]["mean_us"] > 0
     legs = line["configs"]["protocol"]["legs_ms_per_step"]
     assert {"step_envs", "step_envs_u8_stack", "step_envs_unbound"} <= set(legs) and line["configs"]["protocol"]["fused_updates"]["step_envs"] == 4
+
+
+def test_plain_bench_run_measures_the_headline_alone(tmp_path):
+    """``python bench.py`` without ``--full`` reports the headline workload (raw) alone: no CPU baseline, no other configuration, the
+    headline's fields as the full line has them.  With --dump-outputs it still runs every workload for its outputs and writes the same
+    files, byte for byte, as a ``--full`` run."""
+    _need_gpu()
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    envs, lines = 2048, {}
+    for mode, extra in (("plain", []), ("plain_dump", ["--dump-outputs", str(tmp_path / "plain")]),
+                        ("full", ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *extra, "--steps", "3", "--warmup", "1", "--envs", str(envs)],
+                             capture_output=True, text=True, timeout=900, env=dict(os.environ, CRL_BENCH_CAR_PREROLL="20"))
+        assert out.returncode == 0, (mode, out.stderr[-3000:])
+        found = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(found) == 1, (mode, found[:3])
+        lines[mode] = json.loads(found[0])
+    full = lines["full"]
+    assert "configs_brief" in full and "cpu_baseline" not in full
+    for mode in ("plain", "plain_dump"):
+        plain = lines[mode]
+        assert not {"configs", "configs_brief", "cpu_baseline"} & set(plain), (mode, sorted(plain))
+        for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus"):
+            assert plain[k] == full[k], (mode, k)
+        assert plain["config"] == full["config"] and plain["roofline"]["kernel"] == "pong_raster_raw_sweep_kernel"
+        assert abs(plain["value"] - envs * 3 / (plain["ms_per_step"] * 3e-3)) <= 1e-3 * plain["value"]
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files == sorted(os.listdir(tmp_path / "full")) and {f.split("_")[0] for f in files} >= {"raw", "car", "tournament", "protocol"}, files
+    for f in files:
+        assert (tmp_path / "plain" / f).read_bytes() == (tmp_path / "full" / f).read_bytes(), f

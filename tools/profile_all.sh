@@ -13,9 +13,10 @@ for wl in car car_fma; do
   python3 tools/car_timeline_summary.py > gpurun_out/${RND}_${wl}_timeline_summary.txt 2>&1
   rm -rf gpurun_out/car_timeline
 done
-# the default bench line (all configs + CPU baselines), as the driver runs it
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/${RND}_bench_all.json 2> gpurun_out/${RND}_bench_all.err
-tail -c 600 gpurun_out/${RND}_bench_all.json
+# the full bench line (all configs + CPU baselines: --full), into the folder the second argument names (default: the working directory)
+RES=${2:-.}
+python3 bench.py --full --steps 20 --warmup 5 > "$RES/${RND}_bench_all.json" 2> "$RES/${RND}_bench_all.err"
+tail -c 600 "$RES/${RND}_bench_all.json"
 # sustained CarRacing rate (the walk-ahead queue must not grow): 6 000 steps at 16 384 envs, both arithmetics
 python3 bench.py --workload car --steps 6000 --warmup 5 --no-cpu-baseline > gpurun_out/${RND}_bench_car_long.json 2> gpurun_out/${RND}_bench_car_long.err
 python3 bench.py --workload car_fma --steps 6000 --warmup 5 --no-cpu-baseline > gpurun_out/${RND}_bench_car_fma_long.json 2> gpurun_out/${RND}_bench_car_fma_long.err
