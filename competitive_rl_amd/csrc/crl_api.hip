@@ -568,6 +568,25 @@ int crl_step_stack(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float
     return draw_obs(c, obs_dev, st, &sk);
 }
 
+int crl_draw_raw_delta(crl_ctx *c, uint8_t *obs_dev, uint64_t *drawn_dev, int32_t drawn_valid, void *stream) {
+    CRL_ENTER(c);
+    if (!c || !obs_dev || !drawn_dev) return fail(CRL_EINVAL, "null argument");
+    if (c->car || c->o.obs_mode != CRL_OBS_RAW_RGB) return fail(CRL_ESTATE, "crl_draw_raw_delta needs a Pong RAW_RGB context");
+    if ((uintptr_t)obs_dev % 16) return fail(CRL_EINVAL, "crl_draw_raw_delta: obs_dev must be 16-byte aligned");
+    if ((uintptr_t)drawn_dev % 8) return fail(CRL_EINVAL, "crl_draw_raw_delta: drawn_dev must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    begin_timed(c, 1, st);
+    if (drawn_valid) {
+        launch_pong_raster_raw_delta(c->s.obs_frames, drawn_dev, c->n, c->atlas_rgb, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
+    } else {
+        launch_pong_raster_raw(c->s.obs_frames, c->n, c->atlas_rgb, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
+        HIP_TRY(hipMemcpyAsync(drawn_dev, c->s.obs_frames, (size_t)c->n * 8, hipMemcpyDeviceToDevice, st));
+    }
+    end_timed(c, 1, st);
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
+}
+
 int crl_set_flags_event(crl_ctx *c, void *event) {
     CRL_ENTER(c);
     if (!c) return fail(CRL_EINVAL, "null ctx");

@@ -159,6 +159,115 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
     }
 }
 
+// Delta writer: the buffer an env draws into holds the frame of an earlier descriptor `drawn[env]` (the caller's record, see
+// crl_draw_raw_delta), and a frame is a pure function of its descriptor, so only the chunks whose bytes can differ between the
+// two descriptors are stored -- each still built by raw_chunk(), so the result is the full draw's, bit for bit.  Dirty set (a
+// superset of the differing chunks for ANY pair of descriptors):
+//   exactly one descriptor blank ..................... the whole frame;
+//   both blank ....................................... nothing;
+//   otherwise (sl, sr) differ ........................ every chunk of the score-band ink rows [ink_row0, ink_row1);
+//            and in rows TOP..BOTTOM-1, per object:   ball: the chunks of both 4 x 4 rectangles;
+//                                                     bat:  its chunk column in the rows of the symmetric difference of its old
+//                                                           and new 15-row spans (<= 8 rows for a 4-px move).
+// A pixel of the court is white iff the ball or a bat covers it, so a pixel that changes lies in the symmetric difference of
+// some object's two rectangles; rows outside the court and the ink rows are white in every non-blank frame.
+// Mapping: a workgroup holds 64 envs and one wavefront per (view, object), so every wavefront is uniform in what it draws and
+// its descriptor loads are coalesced.  Whole frames and score bands (a few envs per step) are drawn cooperatively by the
+// view's three wavefronts: a ballot, then a loop over the flagged envs with the 192 lanes striding over the chunks.
+// The record is written by the same launch, after a barrier that follows every read of it.
+static constexpr int kBatLc0 = 3 * CRL_PONG_BATL_X / 16, kBatLc1 = (3 * (CRL_PONG_BATL_X + CRL_PONG_BAT_W) - 1) / 16;
+static constexpr int kBatRc0 = 3 * CRL_PONG_BATR_X / 16, kBatRc1 = (3 * (CRL_PONG_BATR_X + CRL_PONG_BAT_W) - 1) / 16;
+
+// stores output chunks (rows [r0, r1) clamped to the court) x (source chunks [c0, c1]) of one view: the mirrored view's rows are
+// the byte-reversed chunk (29 - c), which raw_chunk derives from the output position q
+__device__ __forceinline__ void delta_rect(uint4 *__restrict__ out, const Frame &f, int view, int r0, int r1, int c0, int c1,
+                                           const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
+    r0 = max(r0, CRL_PONG_TOP), r1 = min(r1, CRL_PONG_BOTTOM);
+    const bool mirror = view != 0;  // (court rows are all >= CRL_PONG_MIRROR_ROW)
+    for (int row = r0; row < r1; row++)
+        for (int sc = c0; sc <= c1; sc++) {
+            const int q = view * kFrameChunks + row * kRowChunks + (mirror ? kRowChunks - 1 - sc : sc);
+            out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
+        }
+}
+
+// the rows of the symmetric difference of [a, a + h) and [b, b + h): [lo, lo + k) and [hi + h - k, hi + h), k = min(|a - b|, h)
+__device__ __forceinline__ void delta_bat(uint4 *__restrict__ out, const Frame &f, int view, int a, int b, int c0, int c1,
+                                          const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
+    if (a == b) return;
+    const int lo = min(a, b), hi = max(a, b), k = min(hi - lo, CRL_PONG_BAT_H);
+    delta_rect(out, f, view, lo, lo + k, c0, c1, atlas_rgb, ink_row0, ink_row1);
+    delta_rect(out, f, view, hi + CRL_PONG_BAT_H - k, hi + CRL_PONG_BAT_H, c0, c1, atlas_rgb, ink_row0, ink_row1);
+}
+
+__device__ __forceinline__ void delta_ball(uint4 *__restrict__ out, const Frame &f, const Frame &g, int view,
+                                           const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
+    const int b0 = max(3 * g.x, 0), b1 = min(3 * (g.x + CRL_PONG_BALL), kRowBytes);  // bytes of the row the ball covers
+    if (b0 < b1) delta_rect(out, f, view, g.y, g.y + CRL_PONG_BALL, b0 / 16, (b1 - 1) / 16, atlas_rgb, ink_row0, ink_row1);
+}
+
+template <int VIEWS>
+__global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
+                                                                             const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
+                                                                             uint4 *__restrict__ obs, int64_t n) {
+    constexpr int per_env = VIEWS * kFrameChunks;
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int view = wave / 3, obj = wave - 3 * view;  // obj: 0 ball, 1 left bat, 2 right bat
+    const int64_t env = (int64_t)blockIdx.x * 64 + lane;
+    const bool valid = env < n;
+    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
+    __syncthreads();  // every wavefront has read drawn[] of this workgroup's envs
+    if (wave == 0 && valid) drawn[env] = pn;
+    const Frame f = unpack_frame(pn), g = unpack_frame(po);
+    const bool blank_n = f.sl == 255, blank_o = g.sl == 255;
+    const bool whole = blank_n != blank_o;
+    const bool band = !blank_n && !blank_o && (f.sl != g.sl || f.sr != g.sr) && ink_row1 > ink_row0;
+
+    // cooperative part: whole frames, then score bands, of the flagged envs (every wavefront of the view sees the same flags)
+    const int t = obj * 64 + lane;  // 0 .. 191 within the view
+    for (uint64_t m = __ballot(whole); m; m &= m - 1) {
+        const int l = __builtin_ctzll(m);
+        const int64_t e = (int64_t)blockIdx.x * 64 + l;
+        const Frame fe = unpack_frame(frames[e]);
+        uint4 *__restrict__ out = obs + e * per_env;
+        for (int c = t; c < kFrameChunks; c += 192) out[view * kFrameChunks + c] = raw_chunk(fe, view * kFrameChunks + c, atlas_rgb, ink_row0, ink_row1, 0);
+    }
+    for (uint64_t m = __ballot(band); m; m &= m - 1) {
+        const int l = __builtin_ctzll(m);
+        const int64_t e = (int64_t)blockIdx.x * 64 + l;
+        const Frame fe = unpack_frame(frames[e]);
+        uint4 *__restrict__ out = obs + e * per_env;
+        const int c0 = view * kFrameChunks + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
+        for (int c = t; c < cn; c += 192) out[c0 + c] = raw_chunk(fe, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
+    }
+    if (!valid || whole || blank_n) return;  // (a whole frame is drawn above; two blank frames are equal)
+
+    // per-lane part: this env's object in this view
+    uint4 *__restrict__ out = obs + env * per_env;
+    if (obj == 0) {
+        if (f.x != g.x || f.y != g.y) {
+            delta_ball(out, f, g, view, atlas_rgb, ink_row0, ink_row1);
+            delta_ball(out, f, f, view, atlas_rgb, ink_row0, ink_row1);
+        }
+    } else if (obj == 1) {
+        delta_bat(out, f, view, g.bl, f.bl, kBatLc0, kBatLc1, atlas_rgb, ink_row0, ink_row1);
+    } else {
+        delta_bat(out, f, view, g.br, f.br, kBatRc0, kBatRc1, atlas_rgb, ink_row0, ink_row1);
+    }
+}
+
+void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
+                                  uint8_t *obs, int views, hipStream_t st) {
+    if (n <= 0 || (views != 1 && views != 2)) return;
+    const unsigned blocks = (unsigned)((n + 63) / 64);
+    const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
+    uint4 *ob = reinterpret_cast<uint4 *>(obs);
+    if (views == 2)
+        hipLaunchKernelGGL((pong_raster_raw_delta_kernel<2>), dim3(blocks), dim3(384), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
+    else
+        hipLaunchKernelGGL((pong_raster_raw_delta_kernel<1>), dim3(blocks), dim3(192), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
+}
+
 void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
                             uint8_t *obs, int views, hipStream_t st) {
     if (n <= 0) return;

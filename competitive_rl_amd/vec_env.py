@@ -295,6 +295,13 @@ class HipPongVecEnv(VecEnv):
     mode="raw": the unwrapped env under a DummyVecEnv -- obs tuple of two
     (N, 210, 160, 3) uint8 tensors, 1 step = 1 frame.
     Observations are views into a double buffer: valid until the next-but-one step().
+
+    Raw observations are read-only views.  A step draws into the buffer of the step before last and stores only the bytes
+    that differ from the frame that buffer still holds (crl_draw_raw_delta): the env keeps, per buffer, the frame descriptors
+    it last drew there and a stamp (address, torch version counter) taken right after that draw.  An in-place torch op on a
+    handed-out view moves the version counter, and the next draw into that buffer is a whole one.  Writes that bypass the
+    counter (``.data``, DLPack consumers, raw pointers) are NOT detected and leave wrong pixels in later observations:
+    clone an observation before mutating it.
     """
 
     def __init__(self, num_envs, seed=0, mode="wrapped", resized_dim=84, frame_stack=1, device=None,
@@ -348,6 +355,9 @@ class HipPongVecEnv(VecEnv):
         self._buf_dtype = torch.float32 if (obs_dtype != "uint8" and mode == "wrapped") else torch.uint8
         self._obs = [torch.empty(self._obs_shape, dtype=self._buf_dtype, device=dev) for _ in range(2)]
         self._flip = 0
+        # raw mode: the descriptors each buffer holds (int64 (n,), written by crl_draw_raw_delta) and the stamp that vouches for them
+        self._drawn = [torch.empty((n,), dtype=torch.int64, device=dev) for _ in range(2)] if mode == "raw" else None
+        self._drawn_stamp = [None, None]
         self._serial = 0  # steps + resets so far: lazy infos check it before drawing terminal observations
         self._rew = torch.zeros((n,) if self.single else (n, 2), dtype=torch.float32, device=dev)
         self._done = torch.zeros((n,), dtype=torch.uint8, device=dev)
@@ -379,6 +389,16 @@ class HipPongVecEnv(VecEnv):
         if self.output == "numpy":
             views = [v.cpu().numpy() for v in views]
         return views[0] if self.single else tuple(views)
+
+    def _draw_raw(self, k):
+        """Draws the current state into ``_obs[k]`` (raw mode): only the chunks that differ from the frame the buffer holds when
+        its record still describes it -- the stamp taken right after the env's own last draw there is unchanged -- else all of it."""
+        buf = self._obs[k]
+        stamp, self._drawn_stamp[k] = self._drawn_stamp[k], None
+        valid = stamp is not None and stamp == (buf.data_ptr(), buf._version)
+        N.check(self._L.crl_draw_raw_delta(self._h, C.c_void_p(buf.data_ptr()), C.c_void_p(self._drawn[k].data_ptr()), int(valid),
+                                           self._stream()))
+        self._drawn_stamp[k] = (buf.data_ptr(), buf._version)
 
     def _check_open(self):
         if self.closed:
@@ -484,6 +504,7 @@ class HipPongVecEnv(VecEnv):
     def reset(self):
         self._check_open()
         buf = self._obs[self._flip]
+        self._drawn_stamp[self._flip] = None  # (drawn whole by the reset; its record is not kept)
         fst, sbuf, desc = self._stack_predraw("reset")
         N.check(self._L.crl_reset(self._h, None if desc is not None else C.c_void_p(buf.data_ptr()), self._stream()))
         if desc is not None:  # the first observation and the bound stack's first state in one launch
@@ -522,9 +543,12 @@ class HipPongVecEnv(VecEnv):
         # (the library first: a refused call -- e.g. the report of an earlier out-of-range action -- has not stepped the envs,
         # so the buffer flip and the serial that lazy infos check stay where they are)
         fst, sbuf, desc = self._stack_predraw("step")
-        N.check(self._L.crl_step_stack(self._h, C.c_void_p(self._actions.data_ptr()), C.c_void_p(buf.data_ptr()),
+        raw = self.mode == "raw"  # (raw contexts take no stack: desc is None)
+        N.check(self._L.crl_step_stack(self._h, C.c_void_p(self._actions.data_ptr()), None if raw else C.c_void_p(buf.data_ptr()),
                                        C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                        None if desc is None else C.byref(desc), self._stream()))
+        if raw:
+            self._draw_raw(self._flip)
         self._flip ^= 1
         self._serial += 1
         self._flags_armed = self._serial if self._flags_event is not None else -1
@@ -711,10 +735,13 @@ class HipPongVecEnv(VecEnv):
         # (a bound FrameStackTensor is drawn too -- FrameStackTensor.update_from_env then swaps it in; the whole observation
         # buffer is written here, no tile is left to the stack: the caller gets `buf` itself)
         fst, sbuf, desc = self._stack_predraw("step", alias_ok=False) if render else (None, None, None)
+        raw = self.mode == "raw"  # (render=False leaves the buffer and its record as they are)
         N.check(self._L.crl_step_stack(self._h, C.c_void_p(actions_i32.data_ptr()),
-                                       C.c_void_p(buf.data_ptr()) if render else None,
+                                       C.c_void_p(buf.data_ptr()) if render and not raw else None,
                                        C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                        None if desc is None else C.byref(desc), self._stream()))
+        if render and raw:
+            self._draw_raw(self._flip)
         self._prev_buf = self._obs[self._flip ^ 1]  # (after the call: a refused call has not stepped the envs)
         self._flip ^= 1
         self._serial += 1

@@ -54,6 +54,8 @@ int main(int argc, char **argv) {
     HIP_OK(hipMalloc(&done, n));
     HIP_OK(hipMalloc(&rew, n * 2 * sizeof(float)));
     HIP_OK(hipMalloc(&act, n * 2 * sizeof(int32_t)));
+    uint64_t *drawn = nullptr;
+    HIP_OK(hipMalloc(&drawn, n * sizeof(uint64_t)));
     std::vector<int32_t> a(n * 2);
     for (int64_t i = 0; i < n * 2; i++) a[i] = (int32_t)((i * 2654435761u >> 7) % 3);
     HIP_OK(hipMemcpy(act, a.data(), a.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -66,7 +68,12 @@ int main(int argc, char **argv) {
     int64_t dsum = 0;
     HIP_OK(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
-    for (int t = 0; t < steps; t++) CRL_OK_(crl_step(ctx, act, obs, rew, done, st));
+    // the step without its draw, then the draw of only what differs from the frame `obs` holds (crl_draw_raw_delta): `drawn` records
+    // the descriptors of that frame -- unknown after the reset, so the first draw is a whole one and writes the record
+    for (int t = 0; t < steps; t++) {
+        CRL_OK_(crl_step(ctx, act, nullptr, rew, done, st));
+        CRL_OK_(crl_draw_raw_delta(ctx, obs, drawn, t > 0, st));
+    }
     HIP_OK(hipStreamSynchronize(st));
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     HIP_OK(hipMemcpy(r.data(), rew, r.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -89,7 +96,7 @@ int main(int argc, char **argv) {
     // zero-sum rewards, a frame that is mostly the white borders + black court
     bool ok = rsum == 0.0 && white > 3 * CRL_PONG_W * (CRL_PONG_TOP + CRL_PONG_H - CRL_PONG_BOTTOM) && white < CRL_PONG_FRAME_BYTES / 2;
     crl_destroy(ctx);
-    (void)hipFree(obs), (void)hipFree(done), (void)hipFree(rew);
+    (void)hipFree(obs), (void)hipFree(done), (void)hipFree(rew), (void)hipFree(drawn);
 
     // ---- the trainer's frame stack, twice (reference utils/utils.py:23-60, 145-173): context A has the step DRAW agent 0's float32
     // (4, 84, 84) stack (crl_step_stack: two buffers, alternating); context B steps and then rolls-and-appends it with the generic kernel

@@ -233,6 +233,21 @@ int crl_step_stack(crl_ctx *ctx, const void *actions_dev, uint8_t *obs_dev, floa
  * host mirror compares a trainer's own tensor with before it binds it.  obs_dev (optional) is re-drawn as by crl_render. */
 int crl_draw_stack(crl_ctx *ctx, uint8_t *obs_dev, const crl_stack_desc *stack, void *stream);
 
+/* The raw observation of the CURRENT state drawn into a buffer that already holds an earlier frame of these envs -- the draw of
+ * crl_step / crl_render (VecEnv.step's observation, dummy_vec_env.py:48-63; PongGame.draw + the mirrored second view,
+ * pong/base_pong_env.py:259-266, 149-155), storing only what differs.  RAW_RGB Pong contexts (CRL_ESTATE otherwise).
+ *   obs_dev      (N, views, 210, 160, 3) u8 as crl_step's, 16-byte aligned
+ *   drawn_dev    uint64 (N), 8-byte aligned, the caller's record: the descriptors (crl_pong_frame) obs_dev holds now; written with
+ *                the descriptors drawn by this call.  Must not overlap obs_dev.
+ *   drawn_valid  0: the record is unknown -- the whole observation is drawn and the record written; otherwise the call stores only the
+ *                16-byte chunks whose bytes can differ between the record and the current state (ball and bat rectangles, the score
+ *                band when a score changed, the whole frame when exactly one of the two is blank), each with the same bytes the full
+ *                draw stores.
+ * The caller vouches that nothing has written obs_dev since the call that recorded drawn_dev: a record that does not match the buffer
+ * gives a wrong observation.  Timed in slot 1 (crl_kernel_timing) like the draw of crl_step.  Use crl_step_stack with obs_dev NULL
+ * to step without drawing. */
+int crl_draw_raw_delta(crl_ctx *ctx, uint8_t *obs_dev, uint64_t *drawn_dev, int32_t drawn_valid, void *stream);
+
 /* A hipEvent_t of the caller's (NULL: none) that every crl_step / crl_step_stack records on the step's stream right BEHIND the kernel
  * that writes rew_dev / done_dev and IN FRONT of the observation's draw.  The reference's step_envs walks the done flags on the host
  * after every step (utils/utils.py:33-42); a stream that waits for this event can copy them out while the step's 1-2 ms of raster
