@@ -26,7 +26,13 @@ SYMBOLS = ["crl_create", "crl_destroy", "crl_seed", "crl_reset", "crl_step", "cr
            "crl_policy_create", "crl_policy_create_full", "crl_policy_destroy", "crl_policy_reset", "crl_policy_act", "crl_policy_get_stack",
            "crl_policy_set_stack", "crl_terminal_observation_dev", "crl_check", "crl_car_info", "crl_car_copy_info", "crl_frame_stack_update", "crl_frame_stack_update_to", "crl_frame_stack_update_u8", "crl_ctx_last_error",
            "crl_obs_descriptors", "crl_render_frames_dev", "crl_car_cap_hits", "crl_selftest_sincosf", "crl_step_stack", "crl_draw_stack", "crl_set_flags_event", "crl_kernel_time_stats",
-           "crl_draw_raw_delta"]
+           "crl_draw_raw_delta",
+           "crl_league_create", "crl_league_destroy", "crl_league_add_builtin", "crl_league_add_light", "crl_league_seed",
+           "crl_league_set_assignment", "crl_league_get_assignment", "crl_league_resample", "crl_league_get_lists", "crl_league_act",
+           "crl_league_reset", "crl_league_get_stack", "crl_league_set_stack"]
+CRL_LEAGUE_MAX_AGENTS = 16
+CRL_LEAGUE_RANDOM, CRL_LEAGUE_RULE_BASED, CRL_LEAGUE_LIGHT = 0, 1, 2
+CRL_LEAGUE_DOMAIN_OPPONENT, CRL_LEAGUE_DOMAIN_ACTION = 0x4C47554F, 0x4C475541
 
 FRAME_DT = np.dtype([("ball_x", "<i2"), ("ball_y", "<i2"), ("bat_l_y", "u1"), ("bat_r_y", "u1"),
                      ("score_l", "u1"), ("score_r", "u1")])
@@ -141,13 +147,27 @@ def load():
     L.crl_policy_act.argtypes = [vp, vp, i64, vp, i64, vp, vp]
     L.crl_policy_get_stack.argtypes = [vp, vp, vp]
     L.crl_policy_set_stack.argtypes = [vp, vp, vp]
+    L.crl_league_create.argtypes = [i32, i64, i64, u64, C.POINTER(vp)]
+    L.crl_league_destroy.argtypes = [vp]
+    L.crl_league_destroy.restype = None
+    L.crl_league_add_builtin.argtypes = [vp, i32]
+    L.crl_league_add_light.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.crl_league_seed.argtypes = [vp, u64, vp]
+    L.crl_league_set_assignment.argtypes = [vp, vp, i32, vp]
+    L.crl_league_get_assignment.argtypes = [vp, vp, vp]
+    L.crl_league_resample.argtypes = [vp, vp, vp]
+    L.crl_league_get_lists.argtypes = [vp, vp, vp, vp]
+    L.crl_league_act.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.crl_league_reset.argtypes = [vp, vp]
+    L.crl_league_get_stack.argtypes = [vp, vp, vp]
+    L.crl_league_set_stack.argtypes = [vp, vp, vp]
     L.crl_last_error.restype = C.c_char_p
     L.crl_ctx_last_error.restype = C.c_char_p
     L.crl_ctx_last_error.argtypes = [vp]
     L.crl_version.restype = C.c_char_p
     for name in SYMBOLS:
         getattr(L, name)
-        if name not in ("crl_destroy", "crl_policy_destroy", "crl_obs_bytes_per_env", "crl_last_error", "crl_ctx_last_error", "crl_version"):
+        if name not in ("crl_destroy", "crl_policy_destroy", "crl_league_destroy", "crl_obs_bytes_per_env", "crl_last_error", "crl_ctx_last_error", "crl_version"):
             getattr(L, name).restype = i32
     _lib = L
     return L

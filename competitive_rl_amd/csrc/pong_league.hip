@@ -1,0 +1,317 @@
+// pong_league.hip -- per-env opponents for cPongTournament-v0: which agent plays the right-hand bat is an int32 per env ON THE
+// DEVICE, the draws of it and of RANDOM's actions are counter-based, and no opponent action touches the host.
+//
+// Stands in for what a population of the reference's workers does together: every worker's TournamentEnvWrapper draws its own
+// opponent (competitive_pong_env.py:27-33 reset_opponent -> random.choice(agent_names)), RANDOM plays np.random.randint(3)
+// (builtin_policies.py:51-58), RULE_BASED the cheat code (:44-48), WEAK / MEDIUM a LightActorCritic on the last four frames
+// (:61-91, utils/policy_serving.py:46-66).  Here one batch holds the whole population.
+//
+// A step is: one fill launch (one lane per env: RANDOM's Philox action, 999 for RULE_BASED, and the frame push of every env that
+// no network visits) and one list launch of pong_policy_mfma_kernel per CNN agent of the pool (weights differ per launch; an agent
+// without envs costs an empty persistent launch).  The lists come from the partition kernel, which runs when the assignment
+// changed.  ONE ring of the last four opponent-view frames per env serves every CNN agent and is pushed every step whichever agent
+// is assigned (one `head` for all envs), so an env that changes hands is judged on the frames it really showed.  Exactly one
+// writer per env and step for the ring slot and for the action: the fill kernel for envs of RANDOM / RULE_BASED, the env's own
+// agent's list launch otherwise.
+#include <string.h>
+
+#include <vector>
+
+#include "crl_internal.h"
+#include "pong_device.h"
+#include "pong_league.h"
+#include "pong_policy_full.h"
+
+namespace crl {
+
+static constexpr int kLPlane = CRL_POLICY_DIM * CRL_POLICY_DIM;       // 1764 bytes
+static constexpr int kLPlaneWords = kLPlane / 4;                       // 441
+static constexpr int kLRingBytes = CRL_POLICY_STACK * kRingPlanePad;   // 7104 per env
+static constexpr int kLThreads = 256;
+static constexpr int kMaxAgents = CRL_LEAGUE_MAX_AGENTS;
+
+// include/crl.h "league draws": value = floor(x0 * m / 2^32) of Philox4x32-10, counter (gid lo, gid hi, n, domain), key = seed
+__device__ inline uint32_t league_draw(uint64_t seed, uint64_t gid, uint32_t n, uint32_t domain, uint32_t m) {
+    uint32_t c[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), n, domain};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (uint32_t)(((uint64_t)c[0] * m) >> 32);
+}
+
+struct LeagueLists {
+    int32_t *list[kMaxAgents];  // CNN agents: env indices of the agent (order free); nullptr for RANDOM / RULE_BASED
+};
+
+// Re-draws the opponent of every env (redraw_all) or of the envs whose flag in `done` is set, then rebuilds the per-agent counts and
+// the CNN agents' lists: ballot + popcount + one atomic per wavefront and agent (car_step_kernel's coupled list does the same).
+__global__ __launch_bounds__(kLThreads) void league_partition_kernel(LeagueLists T, int agents, int32_t *__restrict__ assign,
+                                                                    uint32_t *__restrict__ draw_ctr, const uint8_t *__restrict__ done, int redraw_all,
+                                                                    uint64_t seed, int64_t env_id_base, int64_t n, unsigned *__restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * kLThreads + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int a = -1;
+    if (i < n) {
+        a = assign[i];
+        if (redraw_all || (done && done[i])) {
+            const uint32_t ctr = draw_ctr[i];
+            a = (int)league_draw(seed, (uint64_t)(env_id_base + i), ctr, CRL_LEAGUE_DOMAIN_OPPONENT, (uint32_t)agents);
+            draw_ctr[i] = ctr + 1, assign[i] = a;
+        }
+    }
+    for (int k = 0; k < agents; k++) {
+        const unsigned long long m = __ballot(a == k);
+        if (!m) continue;  // (uniform)
+        const int leader = __ffsll(m) - 1;
+        unsigned base = 0;
+        if (lane == leader) base = atomicAdd(&counts[k], (unsigned)__popcll(m));
+        base = __shfl(base, leader);
+        if (a == k && T.list[k]) T.list[k][base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
+    }
+}
+
+// One lane per env.  RANDOM: action = league_draw(.., step, ACTION domain, 3); RULE_BASED (and an id outside the pool): 999, resolved by
+// the step kernel.  Then the wavefront pushes the newest frame of each of its envs that no list launch visits into ring plane `head`
+// (441 dwords per env, 64 lanes side by side; frames are 4-byte aligned like crl_policy_act's).
+__global__ __launch_bounds__(kLThreads) void league_fill_kernel(const int32_t *__restrict__ kinds, int agents, const int32_t *__restrict__ assign,
+                                                               uint8_t *__restrict__ ring, int head, const uint8_t *__restrict__ frame, int64_t frame_stride,
+                                                               int32_t *__restrict__ actions, int64_t action_stride, uint64_t seed, int64_t env_id_base,
+                                                               uint32_t step, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kLThreads + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool mine = false;
+    if (i < n) {
+        const int a = assign[i];
+        const int kind = (a >= 0 && a < agents) ? kinds[a] : CRL_LEAGUE_RULE_BASED;
+        mine = kind != CRL_LEAGUE_LIGHT;
+        if (kind == CRL_LEAGUE_RANDOM) actions[i * action_stride] = (int32_t)league_draw(seed, (uint64_t)(env_id_base + i), step, CRL_LEAGUE_DOMAIN_ACTION, 3u);
+        else if (mine) actions[i * action_stride] = CRL_PONG_CHEAT;
+    }
+    unsigned long long m = __ballot(mine);
+    const int64_t w0 = i - lane;
+    while (m) {  // (uniform)
+        const int b = __ffsll(m) - 1;
+        m &= m - 1;
+        const int64_t e = w0 + b;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(frame + e * frame_stride);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(ring + e * (int64_t)kLRingBytes + head * kRingPlanePad);
+#pragma unroll
+        for (int q = 0; q < 7; q++) {
+            const int d = q * 64 + lane;
+            if (d < kLPlaneWords) dst[d] = src[d];
+        }
+    }
+}
+
+__global__ void league_fill_assignment_kernel(int32_t *__restrict__ assign, int32_t value, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) assign[i] = value;
+}
+
+}  // namespace crl
+
+using namespace crl;
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
+
+struct crl_league {
+    int device = 0;
+    int64_t n = 0, n_pad = 0, env_id_base = 0;
+    uint64_t seed = 0;
+    int cus = 256;
+    int head = 0;        // ring plane holding the OLDEST frame (the next one to be replaced), one for all envs
+    uint32_t step = 0;   // crl_league_act calls since create / seed: the counter of RANDOM's action draws
+    int agents = 0;
+    int kind[kMaxAgents] = {};
+    float *raw[kMaxAgents] = {};  // CNN agents: the checkpoint tensors (pong_league.h kLightRawFloats)
+    LeagueLists T{};
+    uint8_t *ring = nullptr;
+    int32_t *assign = nullptr;
+    uint32_t *draw_ctr = nullptr;
+    unsigned *ctrl = nullptr;  // [0, 16): tickets of the list launches, [16, 32): counts, [32, 48): kinds (int32)
+};
+
+static unsigned *league_counts(crl_league *l) { return l->ctrl + kMaxAgents; }
+static int32_t *league_kinds(crl_league *l) { return reinterpret_cast<int32_t *>(l->ctrl + 2 * kMaxAgents); }
+
+static int league_partition(crl_league *l, const uint8_t *done_dev, int redraw_all, hipStream_t st) {
+    if (l->agents <= 0) return crl_fail(CRL_ESTATE, "crl_league: the pool is empty (crl_league_add_builtin / _add_light first)");
+    HIP_TRY(hipMemsetAsync(league_counts(l), 0, kMaxAgents * sizeof(unsigned), st));
+    hipLaunchKernelGGL(league_partition_kernel, dim3((unsigned)((l->n + kLThreads - 1) / kLThreads)), dim3(kLThreads), 0, st, l->T, l->agents, l->assign,
+                       l->draw_ctr, done_dev, redraw_all, l->seed, l->env_id_base, l->n, league_counts(l));
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
+}
+
+static int league_add(crl_league *l, int kind, const float *raw_host) {
+    if (l->agents >= kMaxAgents) return crl_fail(CRL_EINVAL, "crl_league: at most %d agents in a pool", kMaxAgents);
+    HIP_TRY(hipSetDevice(l->device));
+    const int a = l->agents;
+    if (kind == CRL_LEAGUE_LIGHT) {
+        HIP_TRY(hipMalloc(&l->raw[a], kLightRawFloats * sizeof(float)));
+        HIP_TRY(hipMemcpy(l->raw[a], raw_host, kLightRawFloats * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t)));
+        HIP_TRY(hipMemset(l->T.list[a], 0, (size_t)(l->n_pad + 8) * sizeof(int32_t)));  // (entries past the count are read, never used)
+        HIP_TRY(policy_light_list_prepare());
+    }
+    l->kind[a] = kind;
+    const int32_t k32 = kind;
+    HIP_TRY(hipMemcpy(league_kinds(l) + a, &k32, sizeof(k32), hipMemcpyHostToDevice));
+    l->agents = a + 1;
+    // the assignment in force (all zeros after create) gets its counts and lists for the grown pool
+    HIP_TRY(hipDeviceSynchronize());
+    int rc = league_partition(l, nullptr, 0, nullptr);
+    if (rc != CRL_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return CRL_OK;
+}
+
+extern "C" {
+
+int crl_league_create(int32_t device, int64_t num_envs, int64_t env_id_base, uint64_t seed, crl_league **out) {
+    crl_fail_no_ctx();
+    if (!out || num_envs <= 0 || num_envs > 0x7fffffff || env_id_base < 0) return crl_fail(CRL_EINVAL, "crl_league_create: bad arguments");
+    HIP_TRY(hipSetDevice(device));
+    crl_league *l = new crl_league();
+    l->device = device, l->n = num_envs, l->n_pad = (num_envs + 7) / 8 * 8, l->env_id_base = env_id_base, l->seed = seed;
+    if (hipDeviceGetAttribute(&l->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || l->cus <= 0) l->cus = 256;
+    hipError_t e = hipMalloc(&l->ring, (size_t)num_envs * kLRingBytes);
+    if (e == hipSuccess) e = hipMemset(l->ring, 0, (size_t)num_envs * kLRingBytes);
+    if (e == hipSuccess) e = hipMalloc(&l->assign, (size_t)num_envs * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(l->assign, 0, (size_t)num_envs * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&l->draw_ctr, (size_t)num_envs * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(l->draw_ctr, 0, (size_t)num_envs * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&l->ctrl, 3 * kMaxAgents * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(l->ctrl, 0, 3 * kMaxAgents * sizeof(unsigned));
+    if (e != hipSuccess) {
+        crl_league_destroy(l);
+        return crl_fail(e == hipErrorOutOfMemory ? CRL_ENOMEM : CRL_EHIP, "crl_league_create: %s", hipGetErrorString(e));
+    }
+    *out = l;
+    return CRL_OK;
+}
+
+void crl_league_destroy(crl_league *l) {
+    if (!l) return;
+    (void)hipSetDevice(l->device);
+    for (int a = 0; a < kMaxAgents; a++) {
+        if (l->raw[a]) (void)hipFree(l->raw[a]);
+        if (l->T.list[a]) (void)hipFree(l->T.list[a]);
+    }
+    if (l->ring) (void)hipFree(l->ring);
+    if (l->assign) (void)hipFree(l->assign);
+    if (l->draw_ctr) (void)hipFree(l->draw_ctr);
+    if (l->ctrl) (void)hipFree(l->ctrl);
+    delete l;
+}
+
+int crl_league_add_builtin(crl_league *l, int32_t kind) {
+    crl_fail_no_ctx();
+    if (!l || (kind != CRL_LEAGUE_RANDOM && kind != CRL_LEAGUE_RULE_BASED))
+        return crl_fail(CRL_EINVAL, "crl_league_add_builtin: kind must be CRL_LEAGUE_RANDOM or CRL_LEAGUE_RULE_BASED");
+    return league_add(l, kind, nullptr);
+}
+
+int crl_league_add_light(crl_league *l, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *actor_w,
+                         const float *actor_b) {
+    crl_fail_no_ctx();
+    if (!l || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b) return crl_fail(CRL_EINVAL, "crl_league_add_light: null argument");
+    std::vector<float> raw(kLightRawFloats, 0.f);
+    memcpy(raw.data(), conv1_w, 1024 * 4), memcpy(raw.data() + 1024, conv1_b, 16 * 4), memcpy(raw.data() + 1040, conv2_w, 1024 * 4);
+    memcpy(raw.data() + 2064, conv2_b, 16 * 4), memcpy(raw.data() + 2080, actor_w, 4800 * 4), memcpy(raw.data() + 6880, actor_b, 3 * 4);
+    return league_add(l, CRL_LEAGUE_LIGHT, raw.data());
+}
+
+int crl_league_seed(crl_league *l, uint64_t seed, void *stream) {
+    crl_fail_no_ctx();
+    if (!l) return crl_fail(CRL_EINVAL, "crl_league_seed: null league");
+    HIP_TRY(hipMemsetAsync(l->draw_ctr, 0, (size_t)l->n * sizeof(uint32_t), (hipStream_t)stream));
+    l->seed = seed, l->step = 0;
+    return CRL_OK;
+}
+
+int crl_league_set_assignment(crl_league *l, const int32_t *ids_dev, int32_t all, void *stream) {
+    crl_fail_no_ctx();
+    if (!l) return crl_fail(CRL_EINVAL, "crl_league_set_assignment: null league");
+    hipStream_t st = (hipStream_t)stream;
+    if (ids_dev) {
+        HIP_TRY(hipMemcpyAsync(l->assign, ids_dev, (size_t)l->n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    } else {
+        if (all < 0 || all >= l->agents) return crl_fail(CRL_EINVAL, "crl_league_set_assignment: agent %d is not in the pool of %d", all, l->agents);
+        hipLaunchKernelGGL(league_fill_assignment_kernel, dim3((unsigned)((l->n + 255) / 256)), dim3(256), 0, st, l->assign, all, l->n);
+        HIP_TRY(hipGetLastError());
+    }
+    return league_partition(l, nullptr, 0, st);
+}
+
+int crl_league_get_assignment(crl_league *l, int32_t *ids_out_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !ids_out_dev) return crl_fail(CRL_EINVAL, "crl_league_get_assignment: null argument");
+    HIP_TRY(hipMemcpyAsync(ids_out_dev, l->assign, (size_t)l->n * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CRL_OK;
+}
+
+int crl_league_resample(crl_league *l, const uint8_t *done_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l) return crl_fail(CRL_EINVAL, "crl_league_resample: null league");
+    return league_partition(l, done_dev, done_dev == nullptr, (hipStream_t)stream);
+}
+
+int crl_league_get_lists(crl_league *l, int32_t *counts_out_dev, int32_t *lists_out_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !counts_out_dev) return crl_fail(CRL_EINVAL, "crl_league_get_lists: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(counts_out_dev, league_counts(l), kMaxAgents * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (lists_out_dev)
+        for (int a = 0; a < l->agents; a++)
+            if (l->T.list[a])
+                HIP_TRY(hipMemcpyAsync(lists_out_dev + (int64_t)a * l->n, l->T.list[a], (size_t)l->n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return CRL_OK;
+}
+
+int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride, int32_t *actions_dev, int64_t action_stride, float *logits_dev,
+                   void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !frame_dev || !actions_dev) return crl_fail(CRL_EINVAL, "crl_league_act: null argument");
+    if (frame_stride < kLPlane || (frame_stride & 3) || ((uintptr_t)frame_dev & 3) || action_stride < 1)
+        return crl_fail(CRL_EINVAL, "crl_league_act: frame_stride must be a multiple of 4 and >= 1764, frames 4-byte aligned");
+    if (l->agents <= 0) return crl_fail(CRL_ESTATE, "crl_league_act: the pool is empty");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(l->ctrl, 0, kMaxAgents * sizeof(unsigned), st));  // the tickets
+    hipLaunchKernelGGL(league_fill_kernel, dim3((unsigned)((l->n + kLThreads - 1) / kLThreads)), dim3(kLThreads), 0, st, league_kinds(l), l->agents,
+                       l->assign, l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, l->seed, l->env_id_base, l->step, l->n);
+    HIP_TRY(hipGetLastError());
+    for (int a = 0; a < l->agents; a++)
+        if (l->kind[a] == CRL_LEAGUE_LIGHT)
+            HIP_TRY(policy_light_act_list(l->raw[a], l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, l->T.list[a],
+                                          league_counts(l) + a, l->n, l->cus, l->ctrl + a, st));
+    l->head = (l->head + 1) & 3;
+    l->step++;
+    return CRL_OK;
+}
+
+int crl_league_reset(crl_league *l, void *stream) {
+    crl_fail_no_ctx();
+    if (!l) return crl_fail(CRL_EINVAL, "crl_league_reset: null league");
+    HIP_TRY(hipMemsetAsync(l->ring, 0, (size_t)l->n * kLRingBytes, (hipStream_t)stream));
+    l->head = 0;
+    return CRL_OK;
+}
+
+int crl_league_get_stack(crl_league *l, uint8_t *stack_out_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !stack_out_dev) return crl_fail(CRL_EINVAL, "crl_league_get_stack: null argument");
+    HIP_TRY(policy_copy_stack(l->ring, stack_out_dev, l->head, l->n, 0, (hipStream_t)stream));
+    return CRL_OK;
+}
+
+int crl_league_set_stack(crl_league *l, const uint8_t *stack_in_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !stack_in_dev) return crl_fail(CRL_EINVAL, "crl_league_set_stack: null argument");
+    HIP_TRY(policy_copy_stack(l->ring, const_cast<uint8_t *>(stack_in_dev), l->head, l->n, 1, (hipStream_t)stream));
+    return CRL_OK;
+}
+
+}  // extern "C"

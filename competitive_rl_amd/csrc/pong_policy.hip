@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "crl_internal.h"
+#include "pong_league.h"
 #include "pong_policy_full.h"
 
 namespace crl {
@@ -409,13 +410,39 @@ static constexpr int kMBuf = kME * CRL_POLICY_STACK * kPlanePad;  // 56 832 byte
 static constexpr int kMLdsRest = (3 * 1600 + 2 * kME * kPos * 3 + 4) * 4;
 static constexpr int kMLds = 2 * kMBuf + kMLdsRest;
 
+// LIST: the group's eight envs are entries of an env-index list (the league, pong_league.hip) instead of env0 .. env0 + 7.  The
+// entries sit in SGPRs before the first request of the group is issued (GroupIdx::load / pin): a load that returned between two
+// LDS-DMA requests would be waited for with a vmcnt that drains the requests in front of it.
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+struct GroupIdx {
+    i32x4 lo, hi;  // (two register vectors, constant subscripts only: nothing of this may live in scratch, whose loads count in vmcnt)
+};
+__device__ inline void group_idx_load(i32x4 &a, i32x4 &b, const int32_t *__restrict__ list, int64_t slot0) {
+    const i32x4 *p = reinterpret_cast<const i32x4 *>(list + slot0);  // slot0 is a multiple of 8, the list 256-byte aligned and padded to whole groups
+    a = p[0], b = p[1];
+}
+__device__ inline void group_idx_pin(GroupIdx &ix, i32x4 a, i32x4 b) {
+    asm volatile("" : "+v"(a), "+v"(b));  // both loads have RETURNED here, in front of every later volatile statement (the requests)
+    ix.lo = i32x4{__builtin_amdgcn_readfirstlane(a.x), __builtin_amdgcn_readfirstlane(a.y), __builtin_amdgcn_readfirstlane(a.z), __builtin_amdgcn_readfirstlane(a.w)};
+    ix.hi = i32x4{__builtin_amdgcn_readfirstlane(b.x), __builtin_amdgcn_readfirstlane(b.y), __builtin_amdgcn_readfirstlane(b.z), __builtin_amdgcn_readfirstlane(b.w)};
+}
+template <bool LIST>
+__device__ inline int64_t group_env(const GroupIdx ix, int64_t env0, int fe) {
+    if constexpr (!LIST) return env0 + fe;
+    int32_t e = ix.lo.x;
+    e = fe == 1 ? ix.lo.y : e, e = fe == 2 ? ix.lo.z : e, e = fe == 3 ? ix.lo.w : e;
+    e = fe == 4 ? ix.hi.x : e, e = fe == 5 ? ix.hi.y : e, e = fe == 6 ? ix.hi.z : e, e = fe == 7 ? ix.hi.w : e;
+    return e;
+}
+
+template <bool LIST>
 __device__ inline void group_request_m(uint8_t *shbuf, const uint8_t *__restrict__ ring, int head, const uint8_t *__restrict__ frame,
-                                       int64_t frame_stride, int64_t env0, int envs_here, int wave, int lane) {
+                                       int64_t frame_stride, int64_t env0, const GroupIdx ix, int envs_here, int wave, int lane) {
     for (int s = wave; s < kME * 3; s += kMWaves) {
         const int fe = s / 3, j = s - fe * 3;
         if (fe >= envs_here) continue;
         const int pp = (head + 1 + j) & 3;
-        const uint8_t *src = ring + (env0 + fe) * (int64_t)kRingBytes + pp * kPlanePad;
+        const uint8_t *src = ring + group_env<LIST>(ix, env0, fe) * (int64_t)kRingBytes + pp * kPlanePad;
         uint8_t *dst = shbuf + (fe * CRL_POLICY_STACK + pp) * kPlanePad;
 #pragma unroll
         for (int half = 0; half < 2; half++) {
@@ -427,7 +454,7 @@ __device__ inline void group_request_m(uint8_t *shbuf, const uint8_t *__restrict
         const int fe = s / 7, q = s - fe * 7;
         if (fe >= envs_here) continue;
         const int d = q * 64 + lane;
-        const uint8_t *src = frame + (env0 + fe) * frame_stride;
+        const uint8_t *src = frame + group_env<LIST>(ix, env0, fe) * frame_stride;
         uint8_t *dst = shbuf + (fe * CRL_POLICY_STACK + head) * kPlanePad + q * 256;
         if (d < kPlaneWords) lds_dma_b32(src + d * 4, lds_addr(dst));
     }
@@ -449,11 +476,17 @@ __device__ inline uint32_t pk_bf16(float a, float b) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
-template <bool BF>
+// LIST: env_list[0 .. *count_dev) are the envs of this launch (`n_arg` is unused; the host does not know the count after a device-side
+// re-draw, so the grid is sized by an upper bound and a launch with an empty list ends at once); every ring, frame, action and logit
+// address goes through the list.  An env's logits are reduced in a shape of their own (finish_group), so its action does not depend
+// on which group or slot it sits in.  LIST = false is the launch of crl_policy_act.
+template <bool BF, bool LIST>
 __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWeightsM W, uint8_t *__restrict__ ring, int head,
                                                                   const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                   int32_t *__restrict__ actions, int64_t action_stride,
-                                                                  float *__restrict__ logits_out, int64_t n, unsigned *__restrict__ ticket, int dbg_arg) {
+                                                                  float *__restrict__ logits_out, int64_t n_arg, unsigned *__restrict__ ticket, int dbg_arg,
+                                                                  const int32_t *__restrict__ env_list, const unsigned *__restrict__ count_dev) {
+    const int64_t n = LIST ? (int64_t)*count_dev : n_arg;
     const int dbg = CRL_ABL(dbg_arg);  // timing ablations / phase stamps: profiling build only
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *sh_buf = smem;                                             // [2][kME][4][kPlanePad]
@@ -521,10 +554,17 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
     // (a returning global atomic takes microseconds: it is requested at the top of an iteration and read at its end).
     int64_t g = blockIdx.x, g1 = ngroups, gprev = -1;
     int cur = 0;  // parity of the group being computed: staging buffer, partial buffer; the ticket lands in slot cur ^ 1
+    const i32x4 zero4 = {0, 0, 0, 0};
+    GroupIdx ix_prev = {zero4, zero4}, ix_cur = ix_prev, ix_next = ix_prev;  // LIST: the list entries of groups gprev, g, g1
     if (g < ngroups) {
         const int64_t env0 = g * kME;
         if (tid == 0) sh_ticket[0] = atomicAdd(ticket, 1u);
-        group_request_m(sh_buf, ring, head, frame, frame_stride, env0, (int)((n - env0) < kME ? (n - env0) : kME), wave, lane);
+        if constexpr (LIST) {
+            i32x4 ia, ib;
+            group_idx_load(ia, ib, env_list, env0);
+            group_idx_pin(ix_cur, ia, ib);
+        }
+        group_request_m<LIST>(sh_buf, ring, head, frame, frame_stride, env0, ix_cur, (int)((n - env0) < kME ? (n - env0) : kME), wave, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         g1 = (int64_t)gridDim.x + sh_ticket[0];
@@ -532,7 +572,7 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
     // A finished group's 100 partial logits per env and action are summed in a fixed shape (lane j: positions j, j + 32, j + 64,
     // j + 96; then a 32-lane butterfly) by ONE wavefront per env, at the top of the NEXT group's iteration -- beside the other
     // wavefronts' matrix work instead of between two workgroup barriers.
-    auto finish_group = [&](int64_t gp, int par) {
+    auto finish_group = [&](int64_t gp, int par, const GroupIdx ixg) {
         const int64_t e0 = gp * kME;
         const int envs = (int)((n - e0) < kME ? (n - e0) : kME);
         const float *part = sh_part + par * (kME * kPos * 3);
@@ -555,9 +595,10 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                 float bv = a0;
                 if (a1 > bv) best = 1, bv = a1;
                 if (a2 > bv) best = 2;
-                actions[(e0 + pe) * action_stride] = best;
+                const int64_t env = group_env<LIST>(ixg, e0, pe);
+                actions[env * action_stride] = best;
                 if (logits_out) {
-                    float *lo = logits_out + (e0 + pe) * 3;
+                    float *lo = logits_out + env * 3;
                     lo[0] = a0, lo[1] = a1, lo[2] = a2;
                 }
             }
@@ -578,19 +619,31 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
         float *part_out = sh_part + cur * (kME * kPos * 3);
         if (tid == 0) sh_ticket[cur ^ 1] = atomicAdd(ticket, 1u);
         MTICK(3)
-        if (gprev >= 0) finish_group(gprev, cur ^ 1);
+        // LIST: the next group's list entries are requested here and awaited behind the reduction and the write-back below -- the
+        // one place of the iteration where nothing of this workgroup is in flight that the wait could drain
+        i32x4 ia, ib;
+        if constexpr (LIST)
+            if (g1 < ngroups) group_idx_load(ia, ib, env_list, g1 * kME);
+        if (gprev >= 0) finish_group(gprev, cur ^ 1, ix_prev);
         MTICK(4)
-        if (g1 < ngroups) {  // the next group streams into the other buffer during the convolutions
-            const int64_t e1 = g1 * kME;
-            group_request_m(sh_buf + (cur ^ 1) * kMBuf, ring, head, frame, frame_stride, e1, (int)((n - e1) < kME ? (n - e1) : kME), wave, lane);
-        }
+        if constexpr (!LIST)
+            if (g1 < ngroups) {  // the next group streams into the other buffer during the convolutions
+                const int64_t e1 = g1 * kME;
+                group_request_m<false>(sh_buf + (cur ^ 1) * kMBuf, ring, head, frame, frame_stride, e1, ix_next, (int)((n - e1) < kME ? (n - e1) : kME), wave, lane);
+            }
         MTICK(5)
         // the new frame also replaces plane `head` of the ring in HBM
         for (int i = tid; i < envs_here * kPlaneChunks; i += kMThreads) {
             const int fe = i / kPlaneChunks, c = i - fe * kPlaneChunks;
-            reinterpret_cast<uint4 *>(ring + (env0 + fe) * (int64_t)kRingBytes + head * kPlanePad)[c] =
+            reinterpret_cast<uint4 *>(ring + group_env<LIST>(ix_cur, env0, fe) * (int64_t)kRingBytes + head * kPlanePad)[c] =
                 reinterpret_cast<const uint4 *>(buf + (fe * CRL_POLICY_STACK + head) * kPlanePad)[c];
         }
+        if constexpr (LIST)
+            if (g1 < ngroups) {
+                const int64_t e1 = g1 * kME;
+                group_idx_pin(ix_next, ia, ib);
+                group_request_m<true>(sh_buf + (cur ^ 1) * kMBuf, ring, head, frame, frame_stride, e1, ix_next, (int)((n - e1) < kME ? (n - e1) : kME), wave, lane);
+            }
         MTICK(0)
         // The patch of tile t + kMWaves is gathered and converted WHILE tile t's MFMAs run: the two are independent, so the
         // scheduler threads the vector work between the matrix instructions (a wavefront that converts first and multiplies
@@ -729,8 +782,9 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
         g = g1;
         g1 = (int64_t)gridDim.x + sh_ticket[cur ^ 1];
         cur ^= 1;
+        if constexpr (LIST) ix_prev = ix_cur, ix_cur = ix_next;
     }
-    if (gprev >= 0) finish_group(gprev, cur ^ 1);
+    if (gprev >= 0) finish_group(gprev, cur ^ 1, ix_prev);
     if ((dbg & 4) && logits_out && lane == 0 && blockIdx.x < 64) {  // profiling: cycles per phase of every wavefront of the first workgroups
         float *o = logits_out + (blockIdx.x * kMWaves + wave) * 8;
         for (int k = 0; k < 7; k++) o[k] = (float)tk[k];
@@ -750,6 +804,29 @@ __global__ void pong_policy_copy_stack_kernel(uint8_t *__restrict__ ring, uint8_
     uint32_t *ep = reinterpret_cast<uint32_t *>(ext) + i;
     if (to_ring) *rp = *ep;
     else *ep = *rp;
+}
+
+// ---- what the league (pong_league.hip) shares with the policies: the list launch of the kernel above and the ring <-> stack copy
+hipError_t policy_light_list_prepare() {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+}
+
+hipError_t policy_light_act_list(const float *raw, uint8_t *ring, int head, const uint8_t *frame, int64_t frame_stride, int32_t *actions,
+                                 int64_t action_stride, float *logits, const int32_t *env_list, const unsigned *count_dev, int64_t max_envs, int cus,
+                                 unsigned *ticket, hipStream_t st) {
+    PolicyWeightsM W;
+    W.w1 = raw, W.b1 = raw + 1024, W.w2 = raw + 1040, W.b2 = raw + 2064, W.wa = raw + 2080, W.ba = raw + 6880;
+    const int64_t groups = (max_envs + kME - 1) / kME;  // an upper bound: the kernel reads the count itself
+    const unsigned grid = (unsigned)(groups < cus ? groups : cus);
+    hipLaunchKernelGGL((pong_policy_mfma_kernel<true, true>), dim3(grid), dim3(kMThreads), kMLds, st, W, ring, head, frame, frame_stride, actions,
+                       action_stride, logits, (int64_t)0, ticket, 0, env_list, count_dev);
+    return hipGetLastError();
+}
+
+hipError_t policy_copy_stack(uint8_t *ring, uint8_t *ext, int head, int64_t n, int to_ring, hipStream_t st) {
+    const int64_t words = n * CRL_POLICY_STACK * kPlaneWords;
+    hipLaunchKernelGGL(pong_policy_copy_stack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ring, ext, head, words, to_ring);
+    return hipGetLastError();
 }
 
 }  // namespace crl
@@ -815,8 +892,8 @@ int crl_policy_create(int32_t device, int64_t num_envs, const float *conv1_w, co
         memcpy(raw.data() + 2064, conv2_b, 16 * 4), memcpy(raw.data() + 2080, actor_w, 4800 * 4), memcpy(raw.data() + 6880, actor_b, 3 * 4);
         e = hipMalloc(&p->raw, raw.size() * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(p->raw, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
         if (e != hipSuccess) {
             crl_policy_destroy(p);
             return crl_fail(CRL_EHIP, "crl_policy_create (mfma weights): %s", hipGetErrorString(e));
@@ -893,12 +970,12 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
         const unsigned mgrid = (unsigned)(mgroups < p->cus ? mgroups : p->cus);  // persistent: one workgroup per CU
 #ifdef CRL_ABLATION
         if (use_mfma != 3)
-            hipLaunchKernelGGL(pong_policy_mfma_kernel<false>, dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
-                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg);
+            hipLaunchKernelGGL((pong_policy_mfma_kernel<false, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
+                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr);
         else
 #endif
-            hipLaunchKernelGGL(pong_policy_mfma_kernel<true>, dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
-                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg);
+            hipLaunchKernelGGL((pong_policy_mfma_kernel<true, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
+                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr);
         HIP_TRY(hipGetLastError());
         p->head = (p->head + 1) & 3;
         return CRL_OK;

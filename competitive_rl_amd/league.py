@@ -1,0 +1,290 @@
+"""LeagueEnvWrapper: cPongTournament with an opponent PER ENV, chosen and served on the device.
+
+The reference's ``TournamentEnvWrapper`` (competitive_rl/pong/competitive_pong_env.py:9-53) has one ``current_agent`` for all its envs;
+a trainer gets a mixed population of opponents because it runs many worker processes, each drawing its own
+(``reset_opponent`` -> ``random.choice(agent_names)``, :27-33).  On this backend one batch is the population, so the league keeps an
+int32 ``assignment`` per env on the device (index into ``agent_names``) and serves every env's opponent in the step:
+
+* pool: any of RANDOM, RULE_BASED, WEAK, MEDIUM, plus LightActorCritic weight sets of the caller's own (``add_agent``); the full-size
+  ActorCritic is not served inside the league (use ``TournamentEnvWrapper.add_agent`` for a whole batch against one);
+* ``set_opponents`` / ``reset_opponent(name)`` assign, ``reset_opponent()`` draws one opponent per env, ``resample_on_done=True``
+  re-draws the opponent of every env whose episode ended, inside the step -- all without a host synchronisation;
+* every draw is Philox4x32-10 keyed by (seed, GLOBAL env id) with a per-env counter (include/crl.h "league draws"), so the result does
+  not depend on how a batch is cut into shards.  RANDOM here is therefore ANOTHER stream than the reference's ``np.random.randint(3)``
+  (``get_random_policy`` is untouched and still numpy's);
+* history: ONE ring of the opponent view's last four frames per env, pushed every step whichever agent is assigned and never cleared at
+  episode ends (the rule of ``Policy``'s private stack); every CNN agent reads it.  An env that changes hands is judged on the four
+  frames it really showed.  With an assignment that never changes this is ``TournamentEnvWrapper`` with that opponent, bit for bit.
+
+The forward pass, the draws and the partition of the envs by agent are HIP behind ``crl_league_*`` (csrc/pong_league.hip,
+csrc/pong_policy.hip); there is no torch model and no CPU path in this module.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .policy_serving import _KEYS, _SHAPES, BUILTIN_CHECKPOINTS, Policy, load_light_weights
+from .tournament import get_builtin_agent_names
+from .vec_env import CHEAT_CODES  # noqa: F401  (RULE_BASED's action, written by the fill kernel)
+
+_BUILTIN_KINDS = {"RANDOM": N.CRL_LEAGUE_RANDOM, "RULE_BASED": N.CRL_LEAGUE_RULE_BASED}
+
+
+def _light_weights(name, source):
+    """A LightActorCritic weight set from a checkpoint path, a dict of arrays in torch layout or a light ``Policy``."""
+    if isinstance(source, Policy):
+        if not source.use_light_model:
+            raise ValueError(f"{name}: the full-size ActorCritic is not served inside the league (LightActorCritic weight sets only); "
+                             "TournamentEnvWrapper.add_agent takes such a policy for a whole batch")
+        source = source.weights
+    if isinstance(source, str):
+        return load_light_weights(source)
+    if not isinstance(source, dict):
+        raise TypeError(f"{name}: pass a checkpoint path, a dict of LightActorCritic arrays or a light Policy, not {type(source).__name__}")
+    if "conv3_w" in source:
+        raise ValueError(f"{name}: the full-size ActorCritic is not served inside the league (LightActorCritic weight sets only)")
+    w = {k: np.ascontiguousarray(source[k], np.float32) for k in _KEYS}
+    for k in _KEYS:
+        if w[k].shape != _SHAPES[k]:
+            raise ValueError(f"{name}: {k} has shape {w[k].shape}, LightActorCritic on (4, 42, 42) needs {_SHAPES[k]}")
+    return w
+
+
+class LeagueEnvWrapper:
+    """Same single-agent protocol as ``TournamentEnvWrapper`` (step / step_device / reset / reset_opponent / get_agent_names / seed /
+    close); see the module docstring for what differs.  ``env_id_base``: the global id of env 0 (default: the wrapped env's)."""
+
+    def __init__(self, env, num_envs, agent_names=None, seed=0, resample_on_done=False, env_id_base=None):
+        self.env, self.num_envs = env, int(num_envs)
+        device = getattr(env, "device", None)
+        if device is None:
+            raise RuntimeError("LeagueEnvWrapper needs the HIP vector env (there is no CPU fallback)")
+        self.device = torch.device(device)
+        names = get_builtin_agent_names() if agent_names is None else list(agent_names)
+        cnn = [n for n in names if n in BUILTIN_CHECKPOINTS]
+        if cnn and getattr(env, "R", 42) != 42:
+            raise ValueError(f"{cnn} are trained on 42x42 frames (builtin_policies.py:36); make the env with resized_dim=42 "
+                             "or pass agent_names without them")
+        self.resample_on_done = bool(resample_on_done)
+        self.env_id_base = int(getattr(env, "env_id_base", 0) if env_id_base is None else env_id_base)
+        self.observation_space, self.action_space = env.observation_space[0], env.action_space[0]
+        self.prev_opponent_obs = None  # what the opponents act on: the right-hand view of the previous step / reset
+        self.record_logits = False     # tests: keep the CNN agents' logits of every step (``logits()``)
+        self._L = N.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_league_create(self.device.index or 0, self.num_envs, self.env_id_base, int(seed) & (2 ** 64 - 1), C.byref(h)))
+        self._h = h
+        self.agent_names, self._kinds = [], []
+        self._act = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
+        self._logits = torch.zeros((self.num_envs, 3), dtype=torch.float32, device=self.device)
+        for name in names:
+            if name in _BUILTIN_KINDS:
+                self._add(name, _BUILTIN_KINDS[name], None)
+            elif name in BUILTIN_CHECKPOINTS:
+                self._add(name, N.CRL_LEAGUE_LIGHT, load_light_weights(BUILTIN_CHECKPOINTS[name]))
+            else:
+                raise ValueError("Unknown agent name: {}".format(name))
+        if not self.agent_names:
+            raise ValueError("the pool is empty")
+        self.set_opponents("RULE_BASED" if "RULE_BASED" in self.agent_names else 0)  # the reference starts with RULE_BASED
+
+    # ---- pool
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _add(self, name, kind, weights):
+        assert name not in self.agent_names, name
+        if len(self.agent_names) >= N.CRL_LEAGUE_MAX_AGENTS:
+            raise ValueError(f"a league holds at most {N.CRL_LEAGUE_MAX_AGENTS} agents")
+        with torch.cuda.device(self.device):
+            if kind == N.CRL_LEAGUE_LIGHT:
+                N.check(self._L.crl_league_add_light(self._h, *[weights[k].ctypes.data_as(C.c_void_p) for k in _KEYS]))
+            else:
+                N.check(self._L.crl_league_add_builtin(self._h, kind))
+        self.agent_names.append(name)
+        self._kinds.append(kind)
+
+    def add_agent(self, name, weights_or_checkpoint):
+        """Beyond the reference: a LightActorCritic opponent of one's own -- a checkpoint path (``.npz`` or a reference checkpoint), a
+        dict of the six arrays in torch layout, or a light ``Policy``.  Future draws include it; the assignment in force stays."""
+        if getattr(self.env, "R", 42) != 42:
+            raise ValueError("LightActorCritic opponents act on 42x42 frames: make the env with resized_dim=42")
+        self._add(name, N.CRL_LEAGUE_LIGHT, _light_weights(name, weights_or_checkpoint))
+
+    def get_agent_names(self):
+        return self.agent_names
+
+    # ---- assignment
+    def set_opponents(self, ids):
+        """``ids``: an agent name or index for every env, or one index per env ((N,) array / tensor; a device tensor stays there)."""
+        if isinstance(ids, str):
+            assert ids in self.agent_names, self.agent_names
+            ids = self.agent_names.index(ids)
+        if isinstance(ids, (int, np.integer)):
+            assert 0 <= int(ids) < len(self.agent_names), ids
+            N.check(self._L.crl_league_set_assignment(self._h, None, int(ids), self._stream()))
+            return
+        t = torch.as_tensor(ids).to(self.device, torch.int32).reshape(-1).contiguous()
+        if t.numel() != self.num_envs:
+            raise ValueError(f"one opponent per env: expected {self.num_envs} ids, got {t.numel()}")
+        if int(t.min()) < 0 or int(t.max()) >= len(self.agent_names):
+            raise ValueError(f"opponent ids must index agent_names (0..{len(self.agent_names) - 1})")
+        N.check(self._L.crl_league_set_assignment(self._h, C.c_void_p(t.data_ptr()), 0, self._stream()))
+
+    def reset_opponent(self, agent_name=None):
+        """A name: that opponent for every env (competitive_pong_env.py:27-33).  None: one fresh draw PER ENV, on the device."""
+        if agent_name is None:
+            N.check(self._L.crl_league_resample(self._h, None, self._stream()))
+        else:
+            self.set_opponents(agent_name)
+
+    @property
+    def assignment(self):
+        """int32 (N,) device tensor: a copy of the assignment in force (enqueued on the current stream, no synchronisation)."""
+        out = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+        N.check(self._L.crl_league_get_assignment(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def _lists(self, want_lists):
+        a = len(self.agent_names)
+        counts = torch.zeros((N.CRL_LEAGUE_MAX_AGENTS,), dtype=torch.int32, device=self.device)
+        lists = torch.full((a, self.num_envs), -1, dtype=torch.int32, device=self.device) if want_lists else None
+        N.check(self._L.crl_league_get_lists(self._h, C.c_void_p(counts.data_ptr()), C.c_void_p(lists.data_ptr()) if want_lists else None,
+                                             self._stream()))
+        return counts[:a].cpu().numpy().astype(np.int64), lists
+
+    def counts(self):
+        """Envs per agent, in ``agent_names`` order (host array; synchronises)."""
+        return self._lists(False)[0]
+
+    def agent_lists(self):
+        """Debug: {name: env indices the kernels visit for that CNN agent} (sorted host arrays; synchronises)."""
+        counts, lists = self._lists(True)
+        lists = lists.cpu().numpy()
+        return {n: np.sort(lists[a, :counts[a]]) for a, n in enumerate(self.agent_names) if self._kinds[a] == N.CRL_LEAGUE_LIGHT}
+
+    # ---- the shared history
+    def reset_history(self):
+        """Zeroes the shared frame ring (``Policy.reset``)."""
+        N.check(self._L.crl_league_reset(self._h, self._stream()))
+
+    def get_stack(self):
+        out = torch.empty((self.num_envs, 4, 42, 42), dtype=torch.uint8, device=self.device)
+        N.check(self._L.crl_league_get_stack(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def set_stack(self, stack):
+        s = torch.as_tensor(stack).to(self.device, torch.uint8).contiguous()
+        assert tuple(s.shape) == (self.num_envs, 4, 42, 42)
+        N.check(self._L.crl_league_set_stack(self._h, C.c_void_p(s.data_ptr()), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def logits(self):
+        """float32 (N, 3): with ``record_logits`` set, the logits of the last step for envs on a CNN agent (other rows keep what they held)."""
+        return self._logits
+
+    # ---- FrameStackTensor binding and early done flags: the wrapped env's, as this wrapper's own hooks
+    def _stack_env(self):
+        """The env a FrameStackTensor binds to (frame_stack.py): agent 0's observation of the wrapped env is this wrapper's."""
+        return getattr(self.env, "_stack_env", lambda: None)()
+
+    def done_host(self):
+        """The last step's done flags on the host, ahead of the observation (HipPongVecEnv.done_host)."""
+        return self.env.done_host()
+
+    # ---- VecEnv protocol, agent 0's view
+    def _frames(self, obs):
+        if isinstance(obs, np.ndarray):
+            obs = torch.from_numpy(np.ascontiguousarray(obs))
+        if obs.device != self.device:
+            obs = obs.to(self.device)
+        if obs.dtype != torch.uint8:  # float32 observations hold 0..255 integers
+            obs = obs.to(torch.uint8)
+        if obs.shape[-1] != 42 or obs.shape[-2] != 42:
+            raise ValueError("the league's frame history holds 42x42 frames: make the env with resized_dim=42")
+        obs = obs.reshape(self.num_envs, 42, 42) if obs.dim() != 4 else obs[:, -1]  # the newest plane
+        if obs.stride(2) != 1 or obs.stride(1) != 42 or obs.stride(0) % 4 or obs.data_ptr() % 4:
+            obs = obs.contiguous()
+        return obs
+
+    def _fill_actions(self, mine_i32):
+        """column 0 <- the caller's actions, column 1 <- every env's own opponent's, written in place by the league's kernels"""
+        self._act[:, 0] = mine_i32
+        f = self._frames(self.prev_opponent_obs)
+        N.check(self._L.crl_league_act(self._h, C.c_void_p(f.data_ptr()), f.stride(0) if self.num_envs > 1 else 1764,
+                                       C.c_void_p(self._act.data_ptr() + 4), 2,
+                                       C.c_void_p(self._logits.data_ptr()) if self.record_logits else None, self._stream()))
+        return self._act
+
+    def _after_step(self, done_u8):
+        if self.resample_on_done:
+            N.check(self._L.crl_league_resample(self._h, C.c_void_p(done_u8.data_ptr()), self._stream()))
+
+    def step(self, action):
+        if self.prev_opponent_obs is None:
+            raise RuntimeError("reset() the league before its first step")
+        if not isinstance(action, torch.Tensor):
+            action = torch.as_tensor(np.asarray(action).reshape(-1), dtype=torch.int32)
+        obs, rew, done, info = self.env.step(self._fill_actions(action.to(self.device, torch.int32).reshape(-1)))
+        self.prev_opponent_obs = obs[1]
+        done = done[:, 0] if done.ndim == 2 else done
+        if self.resample_on_done:
+            self._after_step(torch.as_tensor(done).to(self.device, torch.uint8).contiguous())
+        return obs[0], rew[:, 0].reshape(-1, 1), done.reshape(-1, 1), info
+
+    def step_device(self, actions_i32):
+        """Hot-loop entry (no host work, no clones, no sync): ``actions_i32`` is an int32 (N,) device tensor; returns the env's device
+        buffers (obs (N, 2, K, R, R) -- view 0 is the caller's --, rewards (N, 2), done (N,)) like HipPongVecEnv.step_device.  With
+        ``resample_on_done`` the envs whose flag is set get their next opponent behind the step, on the same stream."""
+        if self.prev_opponent_obs is None:
+            raise RuntimeError("reset() the league before its first step")
+        buf, rew, done = self.env.step_device(self._fill_actions(actions_i32))
+        self.prev_opponent_obs = buf[:, 1]
+        self._after_step(done)
+        return buf, rew, done
+
+    def reset(self, **kwargs):
+        views = self.env.reset(**kwargs)
+        self.prev_opponent_obs = views[1]
+        return views[0]
+
+    def seed(self, s):
+        """Seeds the wrapped env and re-keys the league's draws (all draw counters start over)."""
+        self.env.seed(s)
+        N.check(self._L.crl_league_seed(self._h, int(s or 0) & (2 ** 64 - 1), self._stream()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            torch.cuda.synchronize(self.device)
+            self._L.crl_league_destroy(self._h)
+            self._h = None
+            self.env.close()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._L.crl_league_destroy(self._h)
+                self._h = None
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def league_draw_reference(seed, gid, counter, domain, m):
+    """The league's draw rule in numpy (include/crl.h "league draws"): Philox4x32-10 word 0 of counter (gid lo, gid hi, counter,
+    domain) under key (seed lo, seed hi), scaled to [0, m) by a multiply-high.  Arrays broadcast; returns int64.  Host code for
+    tests and for callers that want to predict an assignment; the kernels do not use it."""
+    gid = np.asarray(gid, np.uint64)
+    counter = np.asarray(counter, np.uint64)
+    shape = np.broadcast(gid, counter).shape
+    mask = np.uint64(0xFFFFFFFF)
+    c = [np.broadcast_to(gid & mask, shape).copy(), np.broadcast_to(gid >> np.uint64(32), shape).copy(),
+         np.broadcast_to(counter & mask, shape).copy(), np.full(shape, int(domain) & 0xFFFFFFFF, np.uint64)]
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return ((c[0] * np.uint64(m)) >> np.uint64(32)).astype(np.int64)

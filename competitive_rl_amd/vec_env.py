@@ -319,6 +319,7 @@ class HipPongVecEnv(VecEnv):
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.mode, self.R, self.K = mode, int(resized_dim), int(frame_stack)
+        self.env_id_base = int(env_id_base)  # global id of env 0: keys every per-env random stream (serves, the league's draws)
         self.output, self.obs_dtype, self.dones_kind = output, obs_dtype, dones
         self.closed = False
         self.single, self.V = bool(single_player), 1 if single_player else 2

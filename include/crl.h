@@ -453,6 +453,68 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
 int crl_policy_get_stack(crl_policy *p, uint8_t *stack_out_dev, void *stream);
 int crl_policy_set_stack(crl_policy *p, const uint8_t *stack_in_dev, void *stream);
 
+/* ---- league: per-env opponents of cPongTournament-v0 on the device --------------------------
+ * Stands in for what a POPULATION of the reference's workers does together: each worker's TournamentEnvWrapper draws an opponent
+ * of its own (pong/competitive_pong_env.py:27-33 reset_opponent -> random.choice(agent_names)) out of RANDOM (np.random.randint(3),
+ * pong/builtin_policies.py:51-58), RULE_BASED (the cheat code, :44-48) and LightActorCritic checkpoints (:61-91,
+ * utils/policy_serving.py:46-66).  Here one batch holds the population: `assignment` is an int32 per env on the device (index
+ * into the pool, in the order the agents were added), and neither a draw nor an opponent's action touches the host.
+ *
+ * History: the league owns ONE ring of the last four 42x42 opponent-view frames per env, in crl_policy's layout and with its rule
+ * (never cleared at episode ends, one head for all envs).  Every crl_league_act pushes every env's frame, whichever agent the env
+ * is assigned to; every LightActorCritic agent reads that ring.  With an assignment that never changes, an env's actions are
+ * those of a crl_policy of that agent fed the same frames.
+ *
+ * League draws (tests restate this in numpy; it does not depend on how a batch is cut into shards):
+ *   x = Philox4x32-10(counter = (gid & 0xFFFFFFFF, gid >> 32, n, domain), key = (seed & 0xFFFFFFFF, seed >> 32)), word 0 of the
+ *   result; gid = env_id_base + i, the env's GLOBAL id; the same round function, multipliers (0xD2511F53, 0xCD9E8D57) and key
+ *   increments (0x9E3779B9, 0xBB67AE85) as the serve sampler, whose domain word is 0x504F4E47.
+ *   value = (uint64(x) * m) >> 32      -- an integer in [0, m)
+ *   opponent of env i: domain = CRL_LEAGUE_DOMAIN_OPPONENT, m = agents in the pool, n = the number of opponent draws env i has had
+ *                      since crl_league_create / crl_league_seed (a per-env counter; 0 for the first draw);
+ *   RANDOM's action:   domain = CRL_LEAGUE_DOMAIN_ACTION, m = 3, n = the number of crl_league_act calls since create / seed
+ *                      (0 for the first call; drawn only for envs assigned to RANDOM, the counter moves for all).
+ * RANDOM is therefore another stream than the reference's np.random. */
+#define CRL_LEAGUE_MAX_AGENTS 16
+#define CRL_LEAGUE_DOMAIN_OPPONENT 0x4C47554Fu /* "LGUO" */
+#define CRL_LEAGUE_DOMAIN_ACTION 0x4C475541u   /* "LGUA" */
+enum crl_league_kind { CRL_LEAGUE_RANDOM = 0, CRL_LEAGUE_RULE_BASED = 1, CRL_LEAGUE_LIGHT = 2 };
+typedef struct crl_league crl_league;
+/* TournamentEnvWrapper.__init__ (competitive_pong_env.py:10-25) for num_envs envs whose global ids start at env_id_base; the pool is
+ * empty, every env is assigned agent 0. */
+int crl_league_create(int32_t device, int64_t num_envs, int64_t env_id_base, uint64_t seed, crl_league **out);
+void crl_league_destroy(crl_league *l);
+/* get_compute_action_function("RANDOM" / "RULE_BASED") (builtin_policies.py:61-91): appends the agent to the pool. */
+int crl_league_add_builtin(crl_league *l, int32_t kind);
+/* get_compute_action_function("WEAK" / "MEDIUM") or a LightActorCritic checkpoint of the caller's (builtin_policies.py:68-83,
+ * utils/network.py:73-93): appends the agent; weights as for crl_policy_create. */
+int crl_league_add_light(crl_league *l, const float *conv1_w_host /*[16,4,4,4]*/, const float *conv1_b_host /*[16]*/,
+                         const float *conv2_w_host /*[16,16,2,2]*/, const float *conv2_b_host /*[16]*/,
+                         const float *actor_w_host /*[3,1600]*/, const float *actor_b_host /*[3]*/);
+/* TournamentEnvWrapper.seed's share for the draws (competitive_pong_env.py:50-51): new key, all draw counters back to 0. */
+int crl_league_seed(crl_league *l, uint64_t seed, void *stream);
+/* reset_opponent(agent_name) (competitive_pong_env.py:27-33) per env: ids_dev int32 [N] on the device (each in [0, agents); an id
+ * outside plays RULE_BASED and is in nobody's list), or ids_dev = NULL and agent `all` for every env.  Rebuilds counts and lists. */
+int crl_league_set_assignment(crl_league *l, const int32_t *ids_dev, int32_t all, void *stream);
+int crl_league_get_assignment(crl_league *l, int32_t *ids_out_dev, void *stream);
+/* reset_opponent() without a name (competitive_pong_env.py:28-29), once per env: a fresh league draw for every env whose byte in
+ * done_dev [N] is non-zero, or for every env when done_dev is NULL.  Rebuilds counts and lists.  No host synchronisation. */
+int crl_league_resample(crl_league *l, const uint8_t *done_dev, void *stream);
+/* Debug / tests: counts_out_dev int32 [CRL_LEAGUE_MAX_AGENTS] (envs per agent); lists_out_dev optional int32 [agents][N]: row a
+ * holds the env indices of LightActorCritic agent a in its first counts[a] entries (in no particular order), other rows are
+ * left as they are. */
+int crl_league_get_lists(crl_league *l, int32_t *counts_out_dev, int32_t *lists_out_dev, void *stream);
+/* TournamentEnvWrapper.step's opponent half (competitive_pong_env.py:35-41 `self.current_agent(self.prev_opponent_obs)`), per env:
+ * pushes env i's frame (frame_dev + i * frame_stride, as crl_policy_act) onto the shared ring and writes the action of the env's
+ * agent to actions_dev[i * action_stride].  logits_dev: optional float32 [N, 3]; rows of envs on RANDOM / RULE_BASED are left as
+ * they are. */
+int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride, int32_t *actions_dev, int64_t action_stride,
+                   float *logits_dev, void *stream);
+/* Policy.reset (policy_serving.py:46-47) for the shared ring; the stack as crl_policy_get_stack / _set_stack hand it over. */
+int crl_league_reset(crl_league *l, void *stream);
+int crl_league_get_stack(crl_league *l, uint8_t *stack_out_dev, void *stream);
+int crl_league_set_stack(crl_league *l, const uint8_t *stack_in_dev, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
