@@ -29,10 +29,17 @@ SYMBOLS = ["crl_create", "crl_destroy", "crl_seed", "crl_reset", "crl_step", "cr
            "crl_draw_raw_delta",
            "crl_league_create", "crl_league_destroy", "crl_league_add_builtin", "crl_league_add_light", "crl_league_seed",
            "crl_league_set_assignment", "crl_league_get_assignment", "crl_league_resample", "crl_league_get_lists", "crl_league_act",
-           "crl_league_reset", "crl_league_get_stack", "crl_league_set_stack"]
+           "crl_league_reset", "crl_league_get_stack", "crl_league_set_stack",
+           "crl_ledger_create", "crl_ledger_destroy", "crl_ledger_seed", "crl_ledger_reset", "crl_ledger_set_agents", "crl_ledger_set_weights",
+           "crl_ledger_get_weights", "crl_ledger_pfsp_weights", "crl_ledger_get_counters", "crl_ledger_set_counters", "crl_ledger_get_env_state",
+           "crl_ledger_set_env_state", "crl_ledger_step"]
 CRL_LEAGUE_MAX_AGENTS = 16
 CRL_LEAGUE_RANDOM, CRL_LEAGUE_RULE_BASED, CRL_LEAGUE_LIGHT = 0, 1, 2
 CRL_LEAGUE_DOMAIN_OPPONENT, CRL_LEAGUE_DOMAIN_ACTION = 0x4C47554F, 0x4C475541
+CRL_LEDGER_DOMAIN_OPPONENT = 0x4C475557
+CRL_LEDGER_COUNTERS = 6  # rows of the counters tensor, in this order (enum crl_ledger_counter)
+CRL_LEDGER_COUNTER_NAMES = ("episodes", "wins", "losses", "draws", "return_sum", "length_sum")
+CRL_LEDGER_PFSP_HARD, CRL_LEDGER_PFSP_VARIANCE = 0, 1
 
 FRAME_DT = np.dtype([("ball_x", "<i2"), ("ball_y", "<i2"), ("bat_l_y", "u1"), ("bat_r_y", "u1"),
                      ("score_l", "u1"), ("score_r", "u1")])
@@ -161,13 +168,27 @@ def load():
     L.crl_league_reset.argtypes = [vp, vp]
     L.crl_league_get_stack.argtypes = [vp, vp, vp]
     L.crl_league_set_stack.argtypes = [vp, vp, vp]
+    L.crl_ledger_create.argtypes = [i32, i64, i64, u64, i32, C.POINTER(vp)]
+    L.crl_ledger_destroy.argtypes = [vp]
+    L.crl_ledger_destroy.restype = None
+    L.crl_ledger_seed.argtypes = [vp, u64, vp]
+    L.crl_ledger_reset.argtypes = [vp, vp]
+    L.crl_ledger_set_agents.argtypes = [vp, i32, vp]
+    L.crl_ledger_set_weights.argtypes = [vp, vp, i32, vp]
+    L.crl_ledger_get_weights.argtypes = [vp, vp, vp]
+    L.crl_ledger_pfsp_weights.argtypes = [vp, vp, i32, i32, C.c_uint32, vp]
+    L.crl_ledger_get_counters.argtypes = [vp, vp, vp, vp]
+    L.crl_ledger_set_counters.argtypes = [vp, vp, vp, vp]
+    L.crl_ledger_get_env_state.argtypes = [vp, vp, vp, vp, vp]
+    L.crl_ledger_set_env_state.argtypes = [vp, vp, vp, vp, vp]
+    L.crl_ledger_step.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
     L.crl_last_error.restype = C.c_char_p
     L.crl_ctx_last_error.restype = C.c_char_p
     L.crl_ctx_last_error.argtypes = [vp]
     L.crl_version.restype = C.c_char_p
     for name in SYMBOLS:
         getattr(L, name)
-        if name not in ("crl_destroy", "crl_policy_destroy", "crl_league_destroy", "crl_obs_bytes_per_env", "crl_last_error", "crl_ctx_last_error", "crl_version"):
+        if name not in ("crl_destroy", "crl_policy_destroy", "crl_league_destroy", "crl_ledger_destroy", "crl_obs_bytes_per_env", "crl_last_error", "crl_ctx_last_error", "crl_version"):
             getattr(L, name).restype = i32
     _lib = L
     return L

@@ -14,7 +14,10 @@ int32 ``assignment`` per env on the device (index into ``agent_names``) and serv
   (``get_random_policy`` is untouched and still numpy's);
 * history: ONE ring of the opponent view's last four frames per env, pushed every step whichever agent is assigned and never cleared at
   episode ends (the rule of ``Policy``'s private stack); every CNN agent reads it.  An env that changes hands is judged on the four
-  frames it really showed.  With an assignment that never changes this is ``TournamentEnvWrapper`` with that opponent, bit for bit.
+  frames it really showed.  With an assignment that never changes this is ``TournamentEnvWrapper`` with that opponent, bit for bit;
+* ``ledger=True`` (or a ``LeagueLedger``) books every finished episode to the opponent that played it, on the device, behind the step;
+  with ``resample_on_done`` the next opponent is then the LEDGER's weighted draw (``LeagueLedger.set_weights`` / ``pfsp_weights``)
+  instead of the uniform one.  Without a ledger the wrapper runs the launches it always ran.
 
 The forward pass, the draws and the partition of the envs by agent are HIP behind ``crl_league_*`` (csrc/pong_league.hip,
 csrc/pong_policy.hip); there is no torch model and no CPU path in this module.
@@ -54,9 +57,11 @@ def _light_weights(name, source):
 
 class LeagueEnvWrapper:
     """Same single-agent protocol as ``TournamentEnvWrapper`` (step / step_device / reset / reset_opponent / get_agent_names / seed /
-    close); see the module docstring for what differs.  ``env_id_base``: the global id of env 0 (default: the wrapped env's)."""
+    close); see the module docstring for what differs.  ``env_id_base``: the global id of env 0 (default: the wrapped env's).
+    ``ledger``: None (no books), True (the wrapper builds a ``LeagueLedger`` with its own seed and id base, and closes it) or a
+    ``LeagueLedger`` of the caller's (used as given, not closed)."""
 
-    def __init__(self, env, num_envs, agent_names=None, seed=0, resample_on_done=False, env_id_base=None):
+    def __init__(self, env, num_envs, agent_names=None, seed=0, resample_on_done=False, env_id_base=None, ledger=None):
         self.env, self.num_envs = env, int(num_envs)
         device = getattr(env, "device", None)
         if device is None:
@@ -90,6 +95,19 @@ class LeagueEnvWrapper:
         if not self.agent_names:
             raise ValueError("the pool is empty")
         self.set_opponents("RULE_BASED" if "RULE_BASED" in self.agent_names else 0)  # the reference starts with RULE_BASED
+        self.ledger, self._own_ledger = None, ledger is True
+        if ledger is not None and ledger is not False:
+            from .ledger import LeagueLedger
+
+            if ledger is True:
+                ledger = LeagueLedger(self.num_envs, len(self.agent_names), self.device, seed=seed, env_id_base=self.env_id_base)
+            if not isinstance(ledger, LeagueLedger):
+                raise TypeError(f"ledger: None, True or a LeagueLedger, not {type(ledger).__name__}")
+            if ledger.num_envs != self.num_envs or ledger.agents != len(self.agent_names) or (ledger.device.index or 0) != (self.device.index or 0):
+                raise ValueError(f"ledger: {ledger.num_envs} envs x {ledger.agents} agents on {ledger.device}, the league has "
+                                 f"{self.num_envs} x {len(self.agent_names)} on {self.device}")
+            self.ledger = ledger
+            self._ids = [torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device) for _ in range(2)]  # played / next
 
     # ---- pool
     def _stream(self):
@@ -113,6 +131,8 @@ class LeagueEnvWrapper:
         if getattr(self.env, "R", 42) != 42:
             raise ValueError("LightActorCritic opponents act on 42x42 frames: make the env with resized_dim=42")
         self._add(name, N.CRL_LEAGUE_LIGHT, _light_weights(name, weights_or_checkpoint))
+        if self.ledger is not None:
+            self.ledger.set_agents(len(self.agent_names))
 
     def get_agent_names(self):
         return self.agent_names
@@ -219,8 +239,16 @@ class LeagueEnvWrapper:
                                        C.c_void_p(self._logits.data_ptr()) if self.record_logits else None, self._stream()))
         return self._act
 
-    def _after_step(self, done_u8):
-        if self.resample_on_done:
+    def _after_step(self, done_u8, rew_f32=None):
+        if self.ledger is not None:
+            # the books want the opponent that PLAYED the step: a device-to-device copy of the assignment, taken before any redraw; the
+            # ids go straight to crl_league_set_assignment (set_opponents' range check would read them on the host)
+            played, nxt = self._ids
+            N.check(self._L.crl_league_get_assignment(self._h, C.c_void_p(played.data_ptr()), self._stream()))
+            self.ledger.update(played, rew_f32, done_u8, redraw=self.resample_on_done, out=nxt)
+            if self.resample_on_done:
+                N.check(self._L.crl_league_set_assignment(self._h, C.c_void_p(nxt.data_ptr()), 0, self._stream()))
+        elif self.resample_on_done:
             N.check(self._L.crl_league_resample(self._h, C.c_void_p(done_u8.data_ptr()), self._stream()))
 
     def step(self, action):
@@ -231,19 +259,22 @@ class LeagueEnvWrapper:
         obs, rew, done, info = self.env.step(self._fill_actions(action.to(self.device, torch.int32).reshape(-1)))
         self.prev_opponent_obs = obs[1]
         done = done[:, 0] if done.ndim == 2 else done
-        if self.resample_on_done:
+        if self.ledger is not None:
+            self._after_step(torch.as_tensor(done).to(self.device, torch.uint8).contiguous(), torch.as_tensor(rew).to(self.device, torch.float32))
+        elif self.resample_on_done:
             self._after_step(torch.as_tensor(done).to(self.device, torch.uint8).contiguous())
         return obs[0], rew[:, 0].reshape(-1, 1), done.reshape(-1, 1), info
 
     def step_device(self, actions_i32):
         """Hot-loop entry (no host work, no clones, no sync): ``actions_i32`` is an int32 (N,) device tensor; returns the env's device
         buffers (obs (N, 2, K, R, R) -- view 0 is the caller's --, rewards (N, 2), done (N,)) like HipPongVecEnv.step_device.  With
-        ``resample_on_done`` the envs whose flag is set get their next opponent behind the step, on the same stream."""
+        ``resample_on_done`` the envs whose flag is set get their next opponent behind the step, on the same stream; with a ledger
+        the step's results are booked there as well (and that next opponent is the ledger's weighted draw)."""
         if self.prev_opponent_obs is None:
             raise RuntimeError("reset() the league before its first step")
         buf, rew, done = self.env.step_device(self._fill_actions(actions_i32))
         self.prev_opponent_obs = buf[:, 1]
-        self._after_step(done)
+        self._after_step(done, rew)
         return buf, rew, done
 
     def reset(self, **kwargs):
@@ -252,15 +283,19 @@ class LeagueEnvWrapper:
         return views[0]
 
     def seed(self, s):
-        """Seeds the wrapped env and re-keys the league's draws (all draw counters start over)."""
+        """Seeds the wrapped env and re-keys the league's draws and its ledger's (all draw counters start over)."""
         self.env.seed(s)
         N.check(self._L.crl_league_seed(self._h, int(s or 0) & (2 ** 64 - 1), self._stream()))
+        if self.ledger is not None:
+            self.ledger.seed(s)
 
     def close(self):
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
             self._L.crl_league_destroy(self._h)
             self._h = None
+            if self._own_ledger and self.ledger is not None:
+                self.ledger.close()
             self.env.close()
 
     def __del__(self):

@@ -515,6 +515,75 @@ int crl_league_reset(crl_league *l, void *stream);
 int crl_league_get_stack(crl_league *l, uint8_t *stack_out_dev, void *stream);
 int crl_league_set_stack(crl_league *l, const uint8_t *stack_in_dev, void *stream);
 
+/* ---- league ledger: per-opponent results and win-rate-weighted opponent draws on the device ---
+ * What a league trainer keeps beside a crl_league (an object of its own; crl_league_* knows nothing of it): how the learner fares
+ * against every agent of the pool, and a draw of the next opponent that is weighted by it (prioritised fictitious self-play).
+ * All work is ordered on the caller's stream; no call synchronises with the host, the getters hand over device memory.
+ *
+ * State.  Per env: ret int32 (sum of the learner's step rewards in the running episode), len int32 (its steps), draw_ctr uint32
+ * (the ledger's own draw counter).  Per agent (CRL_LEAGUE_MAX_AGENTS rows): CRL_LEDGER_COUNTERS int64 counters, laid out
+ * [counter][agent] in the order of enum crl_ledger_counter; one int64 `ignored`.  A weight table uint32 w[CRL_LEAGUE_MAX_AGENTS]
+ * (1 for every agent of the pool after create, 0 beyond the pool).
+ *
+ * crl_ledger_step, one launch with one lane per env:
+ *   1. ret += (int)reward[i * reward_stride]; len += 1  (Pong's step rewards are integers held in float32);
+ *   2. where done[i] != 0 the episode is credited to assign[i], the agent that PLAYED it: episodes += 1, one of wins (ret > 0) /
+ *      losses (ret < 0) / draws (ret == 0) += 1, return_sum += ret, length_sum += len; then ret = len = 0.  An id outside
+ *      [0, agents) is credited nowhere and counted in `ignored`.  All sums are 64-bit integers, so the totals do not depend on
+ *      the order in which wavefronts arrive;
+ *   3. ids_out[i] = assign[i], replaced by a ledger draw where done[i] != 0 and redraw != 0 (draw_ctr[i] += 1 there).
+ *      ids_out may be assign itself.
+ *
+ * Ledger draws (tests restate this in numpy; beside "league draws" above, same generator and key):
+ *   x = word 0 of Philox4x32-10(counter = (gid & 0xFFFFFFFF, gid >> 32, n, CRL_LEDGER_DOMAIN_OPPONENT), key = seed),
+ *   gid = env_id_base + i, n = draw_ctr[i] (0 for an env's first draw since crl_ledger_create / crl_ledger_seed);
+ *   T = sum of w[a] over the table, 0 < T < 2^32;  r = (uint64(x) * T) >> 32  -- an integer in [0, T);
+ *   the drawn agent is the smallest a with w[0] + ... + w[a] > r.  An agent of weight 0 is never drawn.
+ * A draw depends on (seed, global env id, counter, table) alone: shards that hold the same table draw what the whole batch would.
+ * crl_ledger_set_weights refuses a table with T == 0 or T >= 2^32.  crl_ledger_pfsp_weights cannot look at its result without a
+ * synchronisation: it refuses a floor with which agents * (floor + 65535) reaches 2^32, and should a table made with floor = 0
+ * sum to 0, a step keeps the assignment of the envs it would have redrawn and leaves their draw_ctr alone.
+ *
+ * PFSP weights (one wavefront; float64, one rounding per operation, numpy reproduces them bit for bit), agent a < agents:
+ *   p = ((wins + 0.5 * draws) + 1.0) / (episodes + 2.0)       -- 0.5 for an agent that was never played
+ *   CRL_LEDGER_PFSP_HARD:     f = (1 - p)^k, k = exponent >= 1, as k - 1 multiplications f = f * (1 - p) from f = 1 - p
+ *   CRL_LEDGER_PFSP_VARIANCE: f = p * (1 - p)                  (exponent is not used)
+ *   w[a] = floor + (uint32)floor(f * 65535.0);  w[a] = 0 for a >= agents. */
+#define CRL_LEDGER_DOMAIN_OPPONENT 0x4C475557u /* "LGUW" */
+#define CRL_LEDGER_COUNTERS 6
+enum crl_ledger_counter { CRL_LEDGER_EPISODES = 0, CRL_LEDGER_WINS = 1, CRL_LEDGER_LOSSES = 2, CRL_LEDGER_DRAWS = 3,
+                          CRL_LEDGER_RETURN_SUM = 4, CRL_LEDGER_LENGTH_SUM = 5 };
+enum crl_ledger_pfsp { CRL_LEDGER_PFSP_HARD = 0, CRL_LEDGER_PFSP_VARIANCE = 1 };
+typedef struct crl_ledger crl_ledger;
+/* A ledger for num_envs envs whose global ids start at env_id_base and a pool of `agents` (1..CRL_LEAGUE_MAX_AGENTS) agents. */
+int crl_ledger_create(int32_t device, int64_t num_envs, int64_t env_id_base, uint64_t seed, int32_t agents, crl_ledger **out);
+void crl_ledger_destroy(crl_ledger *l);
+/* New key for the draws, every draw_ctr back to 0 (results and weights stay). */
+int crl_ledger_seed(crl_ledger *l, uint64_t seed, void *stream);
+/* Zeroes the counters, `ignored` and every env's ret / len (weights, key and draw counters stay). */
+int crl_ledger_reset(crl_ledger *l, void *stream);
+/* The pool grew or shrank: rows that enter the pool get weight 1, rows that leave it weight 0; counters stay. */
+int crl_ledger_set_agents(crl_ledger *l, int32_t agents, void *stream);
+/* w_host: uint32 [count] on the HOST, count == agents (read before the call returns; the table changes in stream order). */
+int crl_ledger_set_weights(crl_ledger *l, const uint32_t *w_host, int32_t count, void *stream);
+/* w_out_dev: uint32 [CRL_LEAGUE_MAX_AGENTS] on the device. */
+int crl_ledger_get_weights(crl_ledger *l, uint32_t *w_out_dev, void *stream);
+/* Fills the weight table by the PFSP rule above from counters_dev (int64 [CRL_LEDGER_COUNTERS][CRL_LEAGUE_MAX_AGENTS] on the
+ * device, e.g. counters all-reduced over the shards so that every rank holds the same table), or from the ledger's own counters
+ * when counters_dev is NULL. */
+int crl_ledger_pfsp_weights(crl_ledger *l, const int64_t *counters_dev, int32_t mode, int32_t exponent, uint32_t floor, void *stream);
+/* Counters as int64 [CRL_LEDGER_COUNTERS][CRL_LEAGUE_MAX_AGENTS] and `ignored` as int64 [1] (optional), device memory. */
+int crl_ledger_get_counters(crl_ledger *l, int64_t *counters_out_dev, int64_t *ignored_out_dev, void *stream);
+int crl_ledger_set_counters(crl_ledger *l, const int64_t *counters_dev, const int64_t *ignored_dev, void *stream);
+/* Checkpoints / tests: the per-env values, each [N] on the device, each optional. */
+int crl_ledger_get_env_state(crl_ledger *l, int32_t *ret_out_dev, int32_t *len_out_dev, uint32_t *draw_ctr_out_dev, void *stream);
+int crl_ledger_set_env_state(crl_ledger *l, const int32_t *ret_dev, const int32_t *len_dev, const uint32_t *draw_ctr_dev, void *stream);
+/* The per-step call described above.  assign_dev int32 [N] (crl_league_get_assignment's copy, taken BEFORE any redraw);
+ * reward_dev float32, env i at reward_dev[i * reward_stride] (the env's reward buffer, column 0: stride 2 for cPongDouble);
+ * done_dev uint8 [N]; ids_out_dev int32 [N] (for crl_league_set_assignment). */
+int crl_ledger_step(crl_ledger *l, const int32_t *assign_dev, const float *reward_dev, int64_t reward_stride, const uint8_t *done_dev,
+                    int32_t redraw, int32_t *ids_out_dev, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
