@@ -18,21 +18,6 @@ CRL_OBS_RAW_RGB, CRL_OBS_GRAY_RESIZED = 0, 1
 PONG_FRAME_BYTES = 210 * 160 * 3
 ATLAS_BYTES = 22 * 22 * 34 * 160
 
-# every symbol include/crl.h declares (tests check the library exports all of them)
-SYMBOLS = ["crl_create", "crl_destroy", "crl_seed", "crl_reset", "crl_step", "crl_render", "crl_info", "crl_copy_info",
-           "crl_terminal_observation", "crl_get_state", "crl_set_state", "crl_set_replay", "crl_render_raw",
-           "crl_obs_bytes_per_env", "crl_kernel_timing", "crl_kernel_time_ms", "crl_last_error", "crl_version",
-           "crl_car_get_state", "crl_car_set_state", "crl_car_get_track", "crl_car_set_track", "crl_car_get_map", "crl_car_set_replay",
-           "crl_policy_create", "crl_policy_create_full", "crl_policy_destroy", "crl_policy_reset", "crl_policy_act", "crl_policy_get_stack",
-           "crl_policy_set_stack", "crl_terminal_observation_dev", "crl_check", "crl_car_info", "crl_car_copy_info", "crl_frame_stack_update", "crl_frame_stack_update_to", "crl_frame_stack_update_u8", "crl_ctx_last_error",
-           "crl_obs_descriptors", "crl_render_frames_dev", "crl_car_cap_hits", "crl_selftest_sincosf", "crl_step_stack", "crl_draw_stack", "crl_set_flags_event", "crl_kernel_time_stats",
-           "crl_draw_raw_delta",
-           "crl_league_create", "crl_league_destroy", "crl_league_add_builtin", "crl_league_add_light", "crl_league_seed",
-           "crl_league_set_assignment", "crl_league_get_assignment", "crl_league_resample", "crl_league_get_lists", "crl_league_act",
-           "crl_league_reset", "crl_league_get_stack", "crl_league_set_stack",
-           "crl_ledger_create", "crl_ledger_destroy", "crl_ledger_seed", "crl_ledger_reset", "crl_ledger_set_agents", "crl_ledger_set_weights",
-           "crl_ledger_get_weights", "crl_ledger_pfsp_weights", "crl_ledger_get_counters", "crl_ledger_set_counters", "crl_ledger_get_env_state",
-           "crl_ledger_set_env_state", "crl_ledger_step"]
 CRL_LEAGUE_MAX_AGENTS = 16
 CRL_LEAGUE_RANDOM, CRL_LEAGUE_RULE_BASED, CRL_LEAGUE_LIGHT = 0, 1, 2
 CRL_LEAGUE_DOMAIN_OPPONENT, CRL_LEAGUE_DOMAIN_ACTION = 0x4C47554F, 0x4C475541
@@ -83,6 +68,87 @@ class CrlStackDesc(C.Structure):
                 ("valid_planes", C.c_int32), ("alias_newest", C.c_int32), ("reserved", C.c_int32)]
 
 
+vp, i64, u64, i32, u32, f64, cstr, P = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_uint32, C.c_double, C.c_char_p, C.POINTER
+# every symbol include/crl.h declares -> (restype, argtypes); load() applies it, tests check the library exports all of them
+SIGNATURES = {
+    "crl_create": (i32, [P(CrlOpts), vp, P(vp)]),
+    "crl_destroy": (None, [vp]),
+    "crl_seed": (i32, [vp, u64]),
+    "crl_reset": (i32, [vp, vp, vp]),
+    "crl_step": (i32, [vp, vp, vp, vp, vp, vp]),
+    "crl_render": (i32, [vp, vp, vp]),
+    "crl_info": (i32, [vp, P(vp), P(vp)]),
+    "crl_copy_info": (i32, [vp, vp, vp, vp]),
+    "crl_terminal_observation": (i32, [vp, vp, i64, vp, vp]),
+    "crl_get_state": (i32, [vp, vp, i64, i64, vp]),
+    "crl_set_state": (i32, [vp, vp, i64, i64, vp]),
+    "crl_set_replay": (i32, [vp, vp, vp, vp, i64]),
+    "crl_render_raw": (i32, [vp, vp, i64, vp, vp]),
+    "crl_obs_bytes_per_env": (i64, [vp]),
+    "crl_kernel_timing": (i32, [vp, i32]),
+    "crl_kernel_time_ms": (i32, [vp, i32, P(f64), P(i64)]),
+    "crl_last_error": (cstr, []),
+    "crl_version": (cstr, []),
+    "crl_car_get_state": (i32, [vp, vp, i64, i64, vp]),
+    "crl_car_set_state": (i32, [vp, vp, i64, i64, vp]),
+    "crl_car_get_track": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "crl_car_set_track": (i32, [vp, i64, i32, vp, vp, vp, vp, vp]),
+    "crl_car_get_map": (i32, [vp, i64, vp, vp, vp]),
+    "crl_car_set_replay": (i32, [vp, vp, vp, i64]),
+    "crl_policy_create": (i32, [i32, i64, vp, vp, vp, vp, vp, vp, P(vp)]),
+    "crl_policy_create_full": (i32, [i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, P(vp)]),
+    "crl_policy_destroy": (None, [vp]),
+    "crl_policy_reset": (i32, [vp, vp]),
+    "crl_policy_act": (i32, [vp, vp, i64, vp, i64, vp, vp]),
+    "crl_policy_get_stack": (i32, [vp, vp, vp]),
+    "crl_policy_set_stack": (i32, [vp, vp, vp]),
+    "crl_terminal_observation_dev": (i32, [vp, vp, i64, vp, vp]),
+    "crl_check": (i32, [vp, vp]),
+    "crl_car_info": (i32, [vp, P(vp), P(vp)]),
+    "crl_car_copy_info": (i32, [vp, vp, vp, vp, vp]),
+    "crl_frame_stack_update": (i32, [vp, vp, i32, i64, vp, i64, i32, i32, i64, vp]),
+    "crl_frame_stack_update_to": (i32, [vp, vp, vp, i32, i64, vp, i64, i32, i32, i64, vp]),
+    "crl_frame_stack_update_u8": (i32, [vp, vp, vp, i32, i64, vp, i64, i32, i32, i64, vp]),
+    "crl_ctx_last_error": (cstr, [vp]),
+    "crl_obs_descriptors": (i32, [vp, vp, vp]),
+    "crl_render_frames_dev": (i32, [vp, vp, i64, vp, vp]),
+    "crl_car_cap_hits": (i32, [vp, vp, vp]),
+    "crl_selftest_sincosf": (i32, [i32, u64, u64, vp]),
+    "crl_step_stack": (i32, [vp, vp, vp, vp, vp, P(CrlStackDesc), vp]),
+    "crl_draw_stack": (i32, [vp, vp, P(CrlStackDesc), vp]),
+    "crl_set_flags_event": (i32, [vp, vp]),
+    "crl_kernel_time_stats": (i32, [vp, i32, P(f64), P(i64), P(f64)]),
+    "crl_draw_raw_delta": (i32, [vp, vp, vp, i32, vp]),
+    "crl_league_create": (i32, [i32, i64, i64, u64, P(vp)]),
+    "crl_league_destroy": (None, [vp]),
+    "crl_league_add_builtin": (i32, [vp, i32]),
+    "crl_league_add_light": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "crl_league_seed": (i32, [vp, u64, vp]),
+    "crl_league_set_assignment": (i32, [vp, vp, i32, vp]),
+    "crl_league_get_assignment": (i32, [vp, vp, vp]),
+    "crl_league_resample": (i32, [vp, vp, vp]),
+    "crl_league_get_lists": (i32, [vp, vp, vp, vp]),
+    "crl_league_act": (i32, [vp, vp, i64, vp, i64, vp, vp]),
+    "crl_league_reset": (i32, [vp, vp]),
+    "crl_league_get_stack": (i32, [vp, vp, vp]),
+    "crl_league_set_stack": (i32, [vp, vp, vp]),
+    "crl_ledger_create": (i32, [i32, i64, i64, u64, i32, P(vp)]),
+    "crl_ledger_destroy": (None, [vp]),
+    "crl_ledger_seed": (i32, [vp, u64, vp]),
+    "crl_ledger_reset": (i32, [vp, vp]),
+    "crl_ledger_set_agents": (i32, [vp, i32, vp]),
+    "crl_ledger_set_weights": (i32, [vp, vp, i32, vp]),
+    "crl_ledger_get_weights": (i32, [vp, vp, vp]),
+    "crl_ledger_pfsp_weights": (i32, [vp, vp, i32, i32, u32, vp]),
+    "crl_ledger_get_counters": (i32, [vp, vp, vp, vp]),
+    "crl_ledger_set_counters": (i32, [vp, vp, vp, vp]),
+    "crl_ledger_get_env_state": (i32, [vp, vp, vp, vp, vp]),
+    "crl_ledger_set_env_state": (i32, [vp, vp, vp, vp, vp]),
+    "crl_ledger_step": (i32, [vp, vp, vp, i64, vp, i32, vp, vp]),
+}
+SYMBOLS = list(SIGNATURES)
+
+
 class CrlError(RuntimeError):
     pass
 
@@ -105,91 +171,9 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m competitive_rl_amd.build` "
             "(hipcc, gfx950).  competitive_rl_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, i64, u64, i32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int
-    L.crl_create.argtypes = [C.POINTER(CrlOpts), vp, C.POINTER(vp)]
-    L.crl_destroy.argtypes = [vp]
-    L.crl_destroy.restype = None
-    L.crl_seed.argtypes = [vp, u64]
-    L.crl_reset.argtypes = [vp, vp, vp]
-    L.crl_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.crl_step_stack.argtypes = [vp, vp, vp, vp, vp, C.POINTER(CrlStackDesc), vp]
-    L.crl_draw_stack.argtypes = [vp, vp, C.POINTER(CrlStackDesc), vp]
-    L.crl_set_flags_event.argtypes = [vp, vp]
-    L.crl_draw_raw_delta.argtypes = [vp, vp, vp, C.c_int32, vp]
-    L.crl_info.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.crl_render.argtypes = [vp, vp, vp]
-    L.crl_copy_info.argtypes = [vp, vp, vp, vp]
-    L.crl_terminal_observation.argtypes = [vp, vp, i64, vp, vp]
-    L.crl_terminal_observation_dev.argtypes = [vp, vp, i64, vp, vp]
-    L.crl_check.argtypes = [vp, vp]
-    L.crl_car_info.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.crl_car_copy_info.argtypes = [vp, vp, vp, vp, vp]
-    L.crl_frame_stack_update.argtypes = [vp, vp, i32, i64, vp, i64, i32, i32, i64, vp]
-    L.crl_frame_stack_update_to.argtypes = [vp, vp, vp, i32, i64, vp, i64, i32, i32, i64, vp]
-    L.crl_frame_stack_update_u8.argtypes = [vp, vp, vp, i32, i64, vp, i64, i32, i32, i64, vp]
-    L.crl_get_state.argtypes = [vp, vp, i64, i64, vp]
-    L.crl_set_state.argtypes = [vp, vp, i64, i64, vp]
-    L.crl_set_replay.argtypes = [vp, vp, vp, vp, i64]
-    L.crl_render_raw.argtypes = [vp, vp, i64, vp, vp]
-    L.crl_obs_descriptors.argtypes = [vp, vp, vp]
-    L.crl_render_frames_dev.argtypes = [vp, vp, i64, vp, vp]
-    L.crl_obs_bytes_per_env.argtypes = [vp]
-    L.crl_obs_bytes_per_env.restype = i64
-    L.crl_kernel_timing.argtypes = [vp, i32]
-    L.crl_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]
-    L.crl_kernel_time_stats.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
-    L.crl_car_get_state.argtypes = [vp, vp, i64, i64, vp]
-    L.crl_car_set_state.argtypes = [vp, vp, i64, i64, vp]
-    L.crl_car_get_track.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.crl_car_set_track.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
-    L.crl_car_get_map.argtypes = [vp, i64, vp, vp, vp]
-    L.crl_car_cap_hits.argtypes = [vp, vp, vp]
-    L.crl_selftest_sincosf.argtypes = [C.c_int32, u64, u64, vp]
-    L.crl_car_set_replay.argtypes = [vp, vp, vp, i64]
-    L.crl_policy_create.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
-    L.crl_policy_create_full.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
-    L.crl_policy_destroy.argtypes = [vp]
-    L.crl_policy_destroy.restype = None
-    L.crl_policy_reset.argtypes = [vp, vp]
-    L.crl_policy_act.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    L.crl_policy_get_stack.argtypes = [vp, vp, vp]
-    L.crl_policy_set_stack.argtypes = [vp, vp, vp]
-    L.crl_league_create.argtypes = [i32, i64, i64, u64, C.POINTER(vp)]
-    L.crl_league_destroy.argtypes = [vp]
-    L.crl_league_destroy.restype = None
-    L.crl_league_add_builtin.argtypes = [vp, i32]
-    L.crl_league_add_light.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.crl_league_seed.argtypes = [vp, u64, vp]
-    L.crl_league_set_assignment.argtypes = [vp, vp, i32, vp]
-    L.crl_league_get_assignment.argtypes = [vp, vp, vp]
-    L.crl_league_resample.argtypes = [vp, vp, vp]
-    L.crl_league_get_lists.argtypes = [vp, vp, vp, vp]
-    L.crl_league_act.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    L.crl_league_reset.argtypes = [vp, vp]
-    L.crl_league_get_stack.argtypes = [vp, vp, vp]
-    L.crl_league_set_stack.argtypes = [vp, vp, vp]
-    L.crl_ledger_create.argtypes = [i32, i64, i64, u64, i32, C.POINTER(vp)]
-    L.crl_ledger_destroy.argtypes = [vp]
-    L.crl_ledger_destroy.restype = None
-    L.crl_ledger_seed.argtypes = [vp, u64, vp]
-    L.crl_ledger_reset.argtypes = [vp, vp]
-    L.crl_ledger_set_agents.argtypes = [vp, i32, vp]
-    L.crl_ledger_set_weights.argtypes = [vp, vp, i32, vp]
-    L.crl_ledger_get_weights.argtypes = [vp, vp, vp]
-    L.crl_ledger_pfsp_weights.argtypes = [vp, vp, i32, i32, C.c_uint32, vp]
-    L.crl_ledger_get_counters.argtypes = [vp, vp, vp, vp]
-    L.crl_ledger_set_counters.argtypes = [vp, vp, vp, vp]
-    L.crl_ledger_get_env_state.argtypes = [vp, vp, vp, vp, vp]
-    L.crl_ledger_set_env_state.argtypes = [vp, vp, vp, vp, vp]
-    L.crl_ledger_step.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
-    L.crl_last_error.restype = C.c_char_p
-    L.crl_ctx_last_error.restype = C.c_char_p
-    L.crl_ctx_last_error.argtypes = [vp]
-    L.crl_version.restype = C.c_char_p
-    for name in SYMBOLS:
-        getattr(L, name)
-        if name not in ("crl_destroy", "crl_policy_destroy", "crl_league_destroy", "crl_ledger_destroy", "crl_obs_bytes_per_env", "crl_last_error", "crl_ctx_last_error", "crl_version"):
-            getattr(L, name).restype = i32
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

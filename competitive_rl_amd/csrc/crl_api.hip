@@ -14,17 +14,6 @@
 #include "crl_internal.h"
 #include "pong_device.h"
 
-namespace crl {
-void pong_gray_print_ticks();  // CRL_GRAY_DEBUG & 128
-void launch_pong_gray_templates(const GrayParams &p, const uint8_t *x_first, const uint8_t *x_last, const uint8_t *y_first,
-                                const uint8_t *y_last, int band_rows, int band_chunks, uint8_t *band, uint8_t *rest,
-                                hipStream_t st);
-void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int zero_row0, int zero_row1,
-                                const uint8_t *x_first, const uint8_t *x_last, const uint8_t *y_first,
-                                const uint8_t *y_last, int band_chunks, const uint8_t *tab_blob, const GrayTabOfs &tofs,
-                                hipStream_t st);
-}  // namespace crl
-
 using namespace crl;
 
 // Error text: per calling thread (crl_last_error: also covers crl_create, which has no context yet) and per context
@@ -47,13 +36,6 @@ int crl_fail(int code, const char *fmt, ...) {
     if (g_ctx_err) *g_ctx_err = buf;
     return code;
 }
-#define fail crl_fail
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(CRL_EHIP, "%s: %s", #expr, hipGetErrorString(e_));       \
-    } while (0)
 
 struct AreaTab {
     std::vector<int32_t> ofs, si;  // ofs[d] .. ofs[d+1]: taps of output index d
@@ -92,16 +74,8 @@ struct crl_ctx {
     uint8_t *atlas_rgb = nullptr;
     int ink_row0 = 0, ink_row1 = 0;
     // gray mode
-    uint8_t *atlas_gray = nullptr, *band = nullptr, *rest = nullptr;
-    uint8_t *x_first = nullptr, *x_last = nullptr, *y_first = nullptr, *y_last = nullptr;
-    int32_t *xofs = nullptr, *yofs = nullptr, *xsi = nullptr, *ysi = nullptr;
-    float *xalpha = nullptr, *yalpha = nullptr;
-    int band_rows = 0, band_chunks = 0, zero_row0 = 0, zero_row1 = 0;
-    uint8_t *tab_blob = nullptr;
-    GrayTabOfs tofs{};
+    GrayTables gray{};
     uint8_t *tile_hdr = nullptr;  // [n * views * K] 64-byte tile headers of the address-linear gray writer
-    float *f32_top = nullptr, *f32_bot = nullptr;  // CRL_OBS_F32_REF: court-without-objects tables (GrayParams)
-    int f32_bot0 = 0, f32_xtaps = 0, f32_ytaps = 0, f32_map_row0 = 0, f32_map_rows = 0;
     // replay
     double *ru = nullptr;
     uint8_t *rbx = nullptr, *rby = nullptr;
@@ -170,7 +144,8 @@ static PongMode pong_mode(const crl_ctx *c) {
 static int pong_views(const crl_ctx *c) { return c->o.env_kind == CRL_ENV_PONG_SINGLE ? 1 : 2; }
 
 static int setup_gray(crl_ctx *c) {
-    const int R = c->o.resized_dim;
+    GrayTables &t = c->gray;
+    const int R = t.R = c->o.resized_dim;
     AreaTab xt = area_table(CRL_PONG_W, R), yt = area_table(CRL_PONG_H, R);
     std::vector<uint8_t> xf(CRL_PONG_W, 255), xl(CRL_PONG_W, 0), yf(CRL_PONG_H, 255), yl(CRL_PONG_H, 0);
     int band_rows = 0;
@@ -184,11 +159,11 @@ static int setup_gray(crl_ctx *c) {
         }
     }
     for (int i = 0; i < CRL_PONG_W; i++)
-        if (xf[i] == 255) return fail(CRL_ESTATE, "source col %d feeds no output col", i);
+        if (xf[i] == 255) return crl_fail(CRL_ESTATE, "source col %d feeds no output col", i);
     for (int i = 0; i < CRL_PONG_H; i++)
-        if (yf[i] == 255) return fail(CRL_ESTATE, "source row %d feeds no output row", i);
-    c->band_rows = band_rows;
-    c->band_chunks = (band_rows * R + 15) / 16;
+        if (yf[i] == 255) return crl_fail(CRL_ESTATE, "source row %d feeds no output row", i);
+    t.band_rows = band_rows;
+    t.band_chunks = (band_rows * R + 15) / 16;
     // dense tables for the LDS-resident fast evaluator
     {
         GrayTabOfs o{};
@@ -250,7 +225,7 @@ static int setup_gray(crl_ctx *c) {
         o.total = (int)blob.size();
         o.fast_ok = ok ? 1 : 0;
         o.max_taps = max_taps;
-        if (o.total > 6144) return fail(CRL_ESTATE, "tap tables (%d B) exceed the LDS budget", o.total);
+        if (o.total > 6144) return crl_fail(CRL_ESTATE, "tap tables (%d B) exceed the LDS budget", o.total);
         {
             std::vector<int32_t> b32;
             for (auto *v : {&xf, &xl, &yf, &yl})
@@ -258,47 +233,42 @@ static int setup_gray(crl_ctx *c) {
             o.box32 = put(b32.data(), b32.size() * 4);
             blob.resize((blob.size() + 15) & ~size_t(15));
         }
-        int rc2 = dev_upload(c, &c->tab_blob, blob);
+        int rc2 = dev_upload(c, &t.tab_blob, blob);
         if (rc2) return rc2;
-        c->tofs = o;
+        t.tofs = o;
     }
     const int chunks = (R * R + 15) / 16;
     int rc;
-    if ((rc = dev_upload(c, &c->xofs, xt.ofs))) return rc;
-    if ((rc = dev_upload(c, &c->yofs, yt.ofs))) return rc;
-    if ((rc = dev_upload(c, &c->xsi, xt.si))) return rc;
-    if ((rc = dev_upload(c, &c->ysi, yt.si))) return rc;
-    if ((rc = dev_upload(c, &c->xalpha, xt.alpha))) return rc;
-    if ((rc = dev_upload(c, &c->yalpha, yt.alpha))) return rc;
-    if ((rc = dev_upload(c, &c->x_first, xf))) return rc;
-    if ((rc = dev_upload(c, &c->x_last, xl))) return rc;
-    if ((rc = dev_upload(c, &c->y_first, yf))) return rc;
-    if ((rc = dev_upload(c, &c->y_last, yl))) return rc;
-    if ((rc = dev_upload(c, &c->atlas_gray, c->atlas_host))) return rc;
-    if ((rc = dev_alloc(c, &c->band, (size_t)3 * 484 * 2 * c->band_chunks * 16))) return rc;
-    if ((rc = dev_alloc(c, &c->rest, (size_t)chunks * 16))) return rc;
+    if ((rc = dev_upload(c, &t.xofs, xt.ofs))) return rc;
+    if ((rc = dev_upload(c, &t.yofs, yt.ofs))) return rc;
+    if ((rc = dev_upload(c, &t.xsi, xt.si))) return rc;
+    if ((rc = dev_upload(c, &t.ysi, yt.si))) return rc;
+    if ((rc = dev_upload(c, &t.xalpha, xt.alpha))) return rc;
+    if ((rc = dev_upload(c, &t.yalpha, yt.alpha))) return rc;
+    if ((rc = dev_upload(c, &t.x_first, xf))) return rc;
+    if ((rc = dev_upload(c, &t.x_last, xl))) return rc;
+    if ((rc = dev_upload(c, &t.y_first, yf))) return rc;
+    if ((rc = dev_upload(c, &t.y_last, yl))) return rc;
+    if ((rc = dev_upload(c, &t.atlas_gray, c->atlas_host))) return rc;
+    if ((rc = dev_alloc(c, &t.band, (size_t)3 * 484 * 2 * t.band_chunks * 16))) return rc;
+    if ((rc = dev_alloc(c, &t.rest, (size_t)chunks * 16))) return rc;
     if ((rc = dev_alloc(c, &c->tile_hdr, (size_t)c->n * pong_views(c) * c->o.frame_stack * (64 + 8 + 2)))) return rc;
-    HIP_TRY(hipMemset(c->rest, 0, (size_t)chunks * 16));
-    GrayParams p{};
-    p.R = R, p.K = c->o.frame_stack, p.atlas_gray = c->atlas_gray;
-    p.xofs = c->xofs, p.yofs = c->yofs, p.xsi = c->xsi, p.ysi = c->ysi, p.xalpha = c->xalpha, p.yalpha = c->yalpha;
-    launch_pong_gray_templates(p, c->x_first, c->x_last, c->y_first, c->y_last, c->band_rows, c->band_chunks, c->band,
-                               c->rest, nullptr);
+    HIP_TRY(hipMemset(t.rest, 0, (size_t)chunks * 16));
+    launch_pong_gray_templates(t, nullptr);
     HIP_TRY(hipGetLastError());
     if (c->o.obs_dtype == CRL_OBS_F32_REF) {  // the unrounded float32 path's tables: 484 score pairs x 3 kinds x 2 views x {unrounded, rounded}
-        c->f32_bot0 = yf[CRL_PONG_BOTTOM], c->f32_xtaps = (int)xt.si.size(), c->f32_ytaps = (int)yt.si.size();
-        c->f32_map_row0 = yf[CRL_PONG_TOP], c->f32_map_rows = yl[CRL_PONG_BOTTOM - 1] - yf[CRL_PONG_TOP] + 1;
-        p.band_rows = c->band_rows, p.f32_bot0 = c->f32_bot0;
+        t.f32_bot0 = yf[CRL_PONG_BOTTOM], t.f32_xtaps = (int)xt.si.size(), t.f32_ytaps = (int)yt.si.size();
+        t.f32_map_row0 = yf[CRL_PONG_TOP], t.f32_map_rows = yl[CRL_PONG_BOTTOM - 1] - yf[CRL_PONG_TOP] + 1;
         // x 3 "kinds": both kept frames with this score pair | the left / the right score one higher in one of them (a point scored between them)
-        if ((rc = dev_alloc(c, &c->f32_top, (size_t)484 * 3 * 4 * c->band_rows * R))) return rc;
-        if ((rc = dev_alloc(c, &c->f32_bot, (size_t)2 * (R - c->f32_bot0) * R))) return rc;
-        launch_pong_gray_f32ref_tables(p, c->f32_top, c->f32_bot, nullptr);
+        if ((rc = dev_alloc(c, &t.f32_top, (size_t)484 * 3 * 4 * t.band_rows * R))) return rc;
+        if ((rc = dev_alloc(c, &t.f32_bot, (size_t)2 * (R - t.f32_bot0) * R))) return rc;
+        launch_pong_gray_f32ref_tables(t, nullptr);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipDeviceSynchronize());
     // longest run of all-zero template rows below the score rows = the empty court
     std::vector<uint8_t> rest((size_t)R * R);
-    HIP_TRY(hipMemcpy(rest.data(), c->rest, rest.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rest.data(), t.rest, rest.size(), hipMemcpyDeviceToHost));
     int best0 = 0, best1 = 0, run0 = -1;
     for (int r = band_rows; r <= R; r++) {
         bool zero = r < R;
@@ -311,7 +281,7 @@ static int setup_gray(crl_ctx *c) {
             run0 = -1;
         }
     }
-    c->zero_row0 = best0, c->zero_row1 = best1;
+    t.zero_row0 = best0, t.zero_row1 = best1;
     return CRL_OK;
 }
 
@@ -324,25 +294,25 @@ const char *crl_version(void) { return "crl-hip 0.1 (gfx950)"; }
 
 int crl_create(const crl_opts *opts, const uint8_t *score_atlas_host, crl_ctx **out) {
     g_ctx_err = nullptr;
-    if (!opts || !out) return fail(CRL_EINVAL, "null argument");
+    if (!opts || !out) return crl_fail(CRL_EINVAL, "null argument");
     const bool is_car = opts->env_kind == CRL_ENV_CAR_DOUBLE || opts->env_kind == CRL_ENV_CAR_SINGLE;
-    if (!score_atlas_host && !is_car) return fail(CRL_EINVAL, "null argument");
+    if (!score_atlas_host && !is_car) return crl_fail(CRL_EINVAL, "null argument");
     if (opts->env_kind != CRL_ENV_PONG_DOUBLE && opts->env_kind != CRL_ENV_CAR_DOUBLE && opts->env_kind != CRL_ENV_PONG_SINGLE &&
         opts->env_kind != CRL_ENV_CAR_SINGLE)
-        return fail(CRL_EINVAL, "unknown env_kind %d", opts->env_kind);
-    if (opts->num_envs <= 0) return fail(CRL_EINVAL, "num_envs must be positive");
-    if (opts->reserved != 0) return fail(CRL_EINVAL, "crl_opts.reserved must be 0 (zero-initialise the struct)");
+        return crl_fail(CRL_EINVAL, "unknown env_kind %d", opts->env_kind);
+    if (opts->num_envs <= 0) return crl_fail(CRL_EINVAL, "num_envs must be positive");
+    if (opts->reserved != 0) return crl_fail(CRL_EINVAL, "crl_opts.reserved must be 0 (zero-initialise the struct)");
     if (opts->env_kind == CRL_ENV_CAR_DOUBLE || opts->env_kind == CRL_ENV_CAR_SINGLE) {
-        if (opts->frame_stack < 0 || opts->frame_stack > 8) return fail(CRL_EINVAL, "frame_stack must be 1..8");
-        if (opts->action_repeat < 0 || opts->action_repeat > 16) return fail(CRL_EINVAL, "action_repeat %d out of range (0..16)", opts->action_repeat);
+        if (opts->frame_stack < 0 || opts->frame_stack > 8) return crl_fail(CRL_EINVAL, "frame_stack must be 1..8");
+        if (opts->action_repeat < 0 || opts->action_repeat > 16) return crl_fail(CRL_EINVAL, "action_repeat %d out of range (0..16)", opts->action_repeat);
         if (opts->done_policy != CRL_CAR_DONE_ANY && opts->done_policy != CRL_CAR_DONE_CAR0)
-            return fail(CRL_EINVAL, "unknown done_policy %d", opts->done_policy);
+            return crl_fail(CRL_EINVAL, "unknown done_policy %d", opts->done_policy);
         if (opts->done_policy == CRL_CAR_DONE_CAR0 && opts->env_kind != CRL_ENV_CAR_DOUBLE)
-            return fail(CRL_EINVAL, "CRL_CAR_DONE_CAR0 needs a two-car context");
-        if (opts->obs_dtype != CRL_OBS_U8) return fail(CRL_EINVAL, "CarRacing observations are uint8");
+            return crl_fail(CRL_EINVAL, "CRL_CAR_DONE_CAR0 needs a two-car context");
+        if (opts->obs_dtype != CRL_OBS_U8) return crl_fail(CRL_EINVAL, "CarRacing observations are uint8");
         int nd = 0;
         HIP_TRY(hipGetDeviceCount(&nd));
-        if (opts->device < 0 || opts->device >= nd) return fail(CRL_EINVAL, "device %d of %d", opts->device, nd);
+        if (opts->device < 0 || opts->device >= nd) return crl_fail(CRL_EINVAL, "device %d of %d", opts->device, nd);
         HIP_TRY(hipSetDevice(opts->device));
         crl_ctx *cc = new crl_ctx();
         cc->o = *opts, cc->n = opts->num_envs;
@@ -352,19 +322,19 @@ int crl_create(const crl_opts *opts, const uint8_t *score_atlas_host, crl_ctx **
         return CRL_OK;
     }
     if (opts->action_repeat != 0 || opts->done_policy != 0)
-        return fail(CRL_EINVAL, "action_repeat / done_policy are CarRacing options (must be 0 for Pong)");
+        return crl_fail(CRL_EINVAL, "action_repeat / done_policy are CarRacing options (must be 0 for Pong)");
     if (opts->obs_dtype != CRL_OBS_U8 && !((opts->obs_dtype == CRL_OBS_F32 || opts->obs_dtype == CRL_OBS_F32_REF) && opts->obs_mode == CRL_OBS_GRAY_RESIZED))
-        return fail(CRL_EINVAL, "obs_dtype %d unsupported for this obs_mode", opts->obs_dtype);
+        return crl_fail(CRL_EINVAL, "obs_dtype %d unsupported for this obs_mode", opts->obs_dtype);
     if (opts->obs_mode == CRL_OBS_GRAY_RESIZED) {
         if (opts->resized_dim < 8 || opts->resized_dim > 84 || (opts->resized_dim * opts->resized_dim) % 4)
-            return fail(CRL_EINVAL, "resized_dim %d unsupported (8..84, R*R %% 4 == 0)", opts->resized_dim);
-        if (opts->frame_stack < 1 || opts->frame_stack > 4) return fail(CRL_EINVAL, "frame_stack must be 1..4");
+            return crl_fail(CRL_EINVAL, "resized_dim %d unsupported (8..84, R*R %% 4 == 0)", opts->resized_dim);
+        if (opts->frame_stack < 1 || opts->frame_stack > 4) return crl_fail(CRL_EINVAL, "frame_stack must be 1..4");
     } else if (opts->obs_mode != CRL_OBS_RAW_RGB) {
-        return fail(CRL_EINVAL, "unknown obs_mode %d", opts->obs_mode);
+        return crl_fail(CRL_EINVAL, "unknown obs_mode %d", opts->obs_mode);
     }
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
-    if (opts->device < 0 || opts->device >= ndev) return fail(CRL_EINVAL, "device %d of %d", opts->device, ndev);
+    if (opts->device < 0 || opts->device >= ndev) return crl_fail(CRL_EINVAL, "device %d of %d", opts->device, ndev);
     HIP_TRY(hipSetDevice(opts->device));
     crl_ctx *c = new crl_ctx();
     c->o = *opts;
@@ -395,7 +365,7 @@ int crl_create(const crl_opts *opts, const uint8_t *score_atlas_host, crl_ctx **
         }
         if (e != hipSuccess) {
             crl_destroy(c);
-            return fail(CRL_EHIP, "create: state initialisation: %s", hipGetErrorString(e));
+            return crl_fail(CRL_EHIP, "create: state initialisation: %s", hipGetErrorString(e));
         }
         c->s.bad_action = c->bad_action_dev;
     }
@@ -417,7 +387,7 @@ int crl_create(const crl_opts *opts, const uint8_t *score_atlas_host, crl_ctx **
     }
     if (rc) { crl_destroy(c); return rc; }
     hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) { crl_destroy(c); return fail(CRL_EHIP, "create: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { crl_destroy(c); return crl_fail(CRL_EHIP, "create: %s", hipGetErrorString(e)); }
     *out = c;
     return CRL_OK;
 }
@@ -428,7 +398,7 @@ void crl_destroy(crl_ctx *c) {
     hipSetDevice(c->o.device);
     hipDeviceSynchronize();
 #ifdef CRL_ABLATION
-    if (getenv("CRL_GRAY_DEBUG") && (atoi(getenv("CRL_GRAY_DEBUG")) & 128)) crl::pong_gray_print_ticks();
+    if (getenv("CRL_GRAY_DEBUG") && (atoi(getenv("CRL_GRAY_DEBUG")) & 128)) pong_gray_print_ticks();
 #endif
     if (c->car) crl_car_destroy(c->car);
     for (void *p : c->allocs) hipFree(p);
@@ -446,57 +416,64 @@ void crl_destroy(crl_ctx *c) {
 
 int crl_seed(crl_ctx *c, uint64_t seed) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
     if (c->car) crl_car_seed(c->car, seed);
     c->src.seed = seed;
     return CRL_OK;
 }
 
 // crl_stack_desc -> what the gray launch needs; refuses what the fused draw cannot do (the caller then keeps crl_frame_stack_update)
-static int stack_of(const crl_ctx *c, const crl_stack_desc *sd, const uint8_t *obs_dev, GrayStack *out) {
+static int stack_of(const crl_ctx *c, const crl_stack_desc *sd, GrayStack *out) {
     *out = GrayStack{};
     if (!sd) return CRL_OK;
-    if (c->car || c->o.obs_mode != CRL_OBS_GRAY_RESIZED) return fail(CRL_ESTATE, "a fused frame stack needs a GRAY_RESIZED Pong context");
+    if (c->car || c->o.obs_mode != CRL_OBS_GRAY_RESIZED) return crl_fail(CRL_ESTATE, "a fused frame stack needs a GRAY_RESIZED Pong context");
     if (c->o.flags & CRL_FLAG_STACK_REPLICATE)
-        return fail(CRL_ESTATE, "a fused frame stack follows FrameStackTensor's zero-on-done history; this context keeps the FrameStack wrapper's (CRL_FLAG_STACK_REPLICATE)");
-    if (!sd->stack_dev || sd->reserved != 0) return fail(CRL_EINVAL, "crl_stack_desc: null stack / reserved must be 0");
-    if (sd->planes < 1 || sd->planes > 4) return fail(CRL_EINVAL, "crl_stack_desc.planes %d: the context keeps the descriptors of the last 4 planes", sd->planes);
-    if (sd->agent < 0 || sd->agent >= pong_views(c)) return fail(CRL_EINVAL, "crl_stack_desc.agent %d of %d", sd->agent, pong_views(c));
-    if (sd->valid_planes < 0) return fail(CRL_EINVAL, "crl_stack_desc.valid_planes %d", sd->valid_planes);
+        return crl_fail(CRL_ESTATE, "a fused frame stack follows FrameStackTensor's zero-on-done history; this context keeps the FrameStack wrapper's (CRL_FLAG_STACK_REPLICATE)");
+    if (!sd->stack_dev || sd->reserved != 0) return crl_fail(CRL_EINVAL, "crl_stack_desc: null stack / reserved must be 0");
+    if (sd->planes < 1 || sd->planes > 4) return crl_fail(CRL_EINVAL, "crl_stack_desc.planes %d: the context keeps the descriptors of the last 4 planes", sd->planes);
+    if (sd->agent < 0 || sd->agent >= pong_views(c)) return crl_fail(CRL_EINVAL, "crl_stack_desc.agent %d of %d", sd->agent, pong_views(c));
+    if (sd->valid_planes < 0) return crl_fail(CRL_EINVAL, "crl_stack_desc.valid_planes %d", sd->valid_planes);
     const int want_f32 = c->o.obs_dtype != CRL_OBS_U8;
-    if (sd->dtype != CRL_OBS_U8 && sd->dtype != CRL_OBS_F32) return fail(CRL_EINVAL, "crl_stack_desc.dtype %d (CRL_OBS_U8 or CRL_OBS_F32)", sd->dtype);
-    if (want_f32 && sd->dtype != CRL_OBS_F32) return fail(CRL_EINVAL, "a float32 context's stack is float32");
+    if (sd->dtype != CRL_OBS_U8 && sd->dtype != CRL_OBS_F32) return crl_fail(CRL_EINVAL, "crl_stack_desc.dtype %d (CRL_OBS_U8 or CRL_OBS_F32)", sd->dtype);
+    if (want_f32 && sd->dtype != CRL_OBS_F32) return crl_fail(CRL_EINVAL, "a float32 context's stack is float32");
     if (sd->alias_newest) {
-        if (c->o.frame_stack != 1) return fail(CRL_EINVAL, "alias_newest needs a context with frame_stack 1 (the observation IS the stack's newest plane)");
-        if ((sd->dtype == CRL_OBS_F32) != (want_f32 != 0)) return fail(CRL_EINVAL, "alias_newest needs the stack and the observation in one element type");
+        if (c->o.frame_stack != 1) return crl_fail(CRL_EINVAL, "alias_newest needs a context with frame_stack 1 (the observation IS the stack's newest plane)");
+        if ((sd->dtype == CRL_OBS_F32) != (want_f32 != 0)) return crl_fail(CRL_EINVAL, "alias_newest needs the stack and the observation in one element type");
     }
-    if ((uintptr_t)sd->stack_dev % 16) return fail(CRL_EINVAL, "crl_stack_desc.stack_dev must be 16-byte aligned");
-    (void)obs_dev;
+    if ((uintptr_t)sd->stack_dev % 16) return crl_fail(CRL_EINVAL, "crl_stack_desc.stack_dev must be 16-byte aligned");
     out->out = reinterpret_cast<uint8_t *>(sd->stack_dev), out->k = sd->planes, out->view = sd->agent, out->f32 = sd->dtype == CRL_OBS_F32;
     out->valid = std::min(sd->valid_planes, sd->planes), out->alias = sd->alias_newest ? 1 : 0;
     return CRL_OK;
 }
 
+// Draws `m` envs, K planes each, into `out`.  `src`: what the context's mode draws from (draw_src) -- a ring [8][m] of frame pairs
+// (gray) or the m frames themselves (raw).  `sk`: a fused frame stack; `hdr`: scratch of the address-linear gray writer, sized for
+// the CONTEXT's n -- its own draw alone passes it.
+static int draw_frames(crl_ctx *c, const uint64_t *src, int64_t m, int K, uint8_t *out, hipStream_t st, const GrayStack *sk = nullptr,
+                       void *hdr = nullptr) {
+    if (c->o.obs_mode == CRL_OBS_RAW_RGB) {
+        launch_pong_raster_raw(src, m, c->atlas_rgb, c->ink_row0, c->ink_row1, out, pong_views(c), st);
+    } else {
+        GrayJob p{};
+        p.ring = src, p.n = m, p.K = K, p.views = pong_views(c), p.obs = out, p.obs_f32 = c->o.obs_dtype, p.hdr = hdr;
+        if (sk) p.stack = *sk;
+        launch_pong_raster_gray(c->gray, p, st);
+    }
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
+}
+// draw_frames' `src` for descriptors in the ring layout ([8][m]): a raw context draws the newest plane's first frame
+static const uint64_t *draw_src(const crl_ctx *c, const uint64_t *ring, int64_t m) {
+    return c->o.obs_mode == CRL_OBS_RAW_RGB ? ring + 6 * m : ring;
+}
+
+// the context's own observation (timing slot 1)
 static int draw_obs(crl_ctx *c, uint8_t *obs_dev, hipStream_t st, const GrayStack *sk = nullptr) {
     if (!obs_dev && !(sk && sk->out)) return CRL_OK;
     begin_timed(c, 1, st);
-    if (c->o.obs_mode == CRL_OBS_RAW_RGB) {
-        launch_pong_raster_raw(c->s.obs_frames, c->n, c->atlas_rgb, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
-    } else {
-        GrayParams p{};
-        p.ring = c->s.ring, p.n = c->n, p.R = c->o.resized_dim, p.K = c->o.frame_stack, p.views = pong_views(c);
-        p.atlas_gray = c->atlas_gray, p.band = c->band, p.band_rows = c->band_rows;
-        p.xofs = c->xofs, p.yofs = c->yofs, p.xsi = c->xsi, p.ysi = c->ysi, p.xalpha = c->xalpha, p.yalpha = c->yalpha;
-        p.obs = obs_dev, p.obs_f32 = c->o.obs_dtype, p.hdr = c->tile_hdr;
-        p.f32_top = c->f32_top, p.f32_bot = c->f32_bot, p.f32_bot0 = c->f32_bot0, p.f32_xtaps = c->f32_xtaps, p.f32_ytaps = c->f32_ytaps;
-        p.f32_map_row0 = c->f32_map_row0, p.f32_map_rows = c->f32_map_rows;
-        if (sk) p.stack = *sk;
-        launch_pong_raster_gray_ex(p, c->rest, c->zero_row0, c->zero_row1, c->x_first, c->x_last, c->y_first, c->y_last,
-                                   c->band_chunks, c->tab_blob, c->tofs, st);
-    }
+    int rc = draw_frames(c, c->o.obs_mode == CRL_OBS_RAW_RGB ? c->s.obs_frames : c->s.ring, c->n, c->o.frame_stack, obs_dev, st, sk, c->tile_hdr);
     end_timed(c, 1, st);
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return rc;
 }
 
 // The step kernel raises *bad_action_host (host-mapped memory) when it meets an action outside {0, 1, 2, 999}; reading
@@ -506,20 +483,20 @@ static int pending_action_error(crl_ctx *c, bool clear) {
     const int32_t v = *(volatile int32_t *)c->bad_action_host;
     if (!v) return CRL_OK;
     if (clear) *(volatile int32_t *)c->bad_action_host = 0;
-    return fail(CRL_EACTION, "a Pong action outside {0, 1, 2, %d} was passed to an earlier crl_step (first seen: %d); "
+    return crl_fail(CRL_EACTION, "a Pong action outside {0, 1, 2, %d} was passed to an earlier crl_step (first seen: %d); "
                 "the reference asserts action_space.contains(action) (pong/base_pong_env.py:42)", CRL_PONG_CHEAT, v - 1);
 }
 
 int crl_check(crl_ctx *c, void *stream) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return pending_action_error(c, true);
 }
 
 int crl_reset(crl_ctx *c, uint8_t *obs_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
     hipStream_t st = (hipStream_t)stream;
     if (c->car) return crl_car_reset(c->car, obs_dev, st);
     if (int rc = pending_action_error(c, true)) return rc;  // reported ONCE, by the first call that sees it: the next call proceeds
@@ -530,50 +507,45 @@ int crl_reset(crl_ctx *c, uint8_t *obs_dev, void *stream) {
 
 int crl_render(crl_ctx *c, uint8_t *obs_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c || !obs_dev) return fail(CRL_EINVAL, "null argument");
+    if (!c || !obs_dev) return crl_fail(CRL_EINVAL, "null argument");
     hipStream_t st = (hipStream_t)stream;
     if (c->car) return crl_car_render(c->car, obs_dev, st);
     return draw_obs(c, obs_dev, st);
 }
 
-int crl_step(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, void *stream) {
+// crl_step (`stack` null) and crl_step_stack
+static int step_pong(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, const crl_stack_desc *stack,
+                     void *stream) {
     CRL_ENTER(c);
-    if (!c || !actions_void) return fail(CRL_EINVAL, "null ctx/actions");
+    if (!c || !actions_void) return crl_fail(CRL_EINVAL, "null ctx/actions");
     hipStream_t st = (hipStream_t)stream;
-    if (c->car) return crl_car_step(c->car, (const float *)actions_void, obs_dev, rew_dev, done_dev, st, &c->tm);
-    if (int rc = pending_action_error(c, true)) return rc;  // (reported once; this call did no work)
-    const int32_t *actions_dev = (const int32_t *)actions_void;
-    begin_timed(c, 0, st);
-    launch_pong_dynamics(c->s, c->src, actions_dev, c->n, pong_mode(c), rew_dev, done_dev, st);
-    end_timed(c, 0, st);
-    HIP_TRY(hipGetLastError());
-    if (c->flags_ev) HIP_TRY(hipEventRecord(c->flags_ev, st));
-    return draw_obs(c, obs_dev, st);
-}
-
-int crl_step_stack(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, const crl_stack_desc *stack,
-                   void *stream) {
-    CRL_ENTER(c);
-    if (!c || !actions_void) return fail(CRL_EINVAL, "null ctx/actions");
-    if (!stack) return crl_step(c, actions_void, obs_dev, rew_dev, done_dev, stream);
+    if (c->car && !stack) return crl_car_step(c->car, (const float *)actions_void, obs_dev, rew_dev, done_dev, st, &c->tm);
     GrayStack sk;
-    if (int rc = stack_of(c, stack, obs_dev, &sk)) return rc;  // (before anything is stepped: a refused call has done no work)
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = pending_action_error(c, true)) return rc;
+    if (int rc = stack_of(c, stack, &sk)) return rc;  // (before anything is stepped: a refused call has done no work)
+    if (int rc = pending_action_error(c, true)) return rc;  // (reported once; this call did no work)
     begin_timed(c, 0, st);
     launch_pong_dynamics(c->s, c->src, (const int32_t *)actions_void, c->n, pong_mode(c), rew_dev, done_dev, st);
     end_timed(c, 0, st);
     HIP_TRY(hipGetLastError());
     if (c->flags_ev) HIP_TRY(hipEventRecord(c->flags_ev, st));
-    return draw_obs(c, obs_dev, st, &sk);
+    return draw_obs(c, obs_dev, st, stack ? &sk : nullptr);
+}
+
+int crl_step(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, void *stream) {
+    return step_pong(c, actions_void, obs_dev, rew_dev, done_dev, nullptr, stream);
+}
+
+int crl_step_stack(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, const crl_stack_desc *stack,
+                   void *stream) {
+    return step_pong(c, actions_void, obs_dev, rew_dev, done_dev, stack, stream);
 }
 
 int crl_draw_raw_delta(crl_ctx *c, uint8_t *obs_dev, uint64_t *drawn_dev, int32_t drawn_valid, void *stream) {
     CRL_ENTER(c);
-    if (!c || !obs_dev || !drawn_dev) return fail(CRL_EINVAL, "null argument");
-    if (c->car || c->o.obs_mode != CRL_OBS_RAW_RGB) return fail(CRL_ESTATE, "crl_draw_raw_delta needs a Pong RAW_RGB context");
-    if ((uintptr_t)obs_dev % 16) return fail(CRL_EINVAL, "crl_draw_raw_delta: obs_dev must be 16-byte aligned");
-    if ((uintptr_t)drawn_dev % 8) return fail(CRL_EINVAL, "crl_draw_raw_delta: drawn_dev must be 8-byte aligned");
+    if (!c || !obs_dev || !drawn_dev) return crl_fail(CRL_EINVAL, "null argument");
+    if (c->car || c->o.obs_mode != CRL_OBS_RAW_RGB) return crl_fail(CRL_ESTATE, "crl_draw_raw_delta needs a Pong RAW_RGB context");
+    if ((uintptr_t)obs_dev % 16) return crl_fail(CRL_EINVAL, "crl_draw_raw_delta: obs_dev must be 16-byte aligned");
+    if ((uintptr_t)drawn_dev % 8) return crl_fail(CRL_EINVAL, "crl_draw_raw_delta: drawn_dev must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     begin_timed(c, 1, st);
     if (drawn_valid) {
@@ -589,24 +561,24 @@ int crl_draw_raw_delta(crl_ctx *c, uint8_t *obs_dev, uint64_t *drawn_dev, int32_
 
 int crl_set_flags_event(crl_ctx *c, void *event) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
-    if (c->car) return fail(CRL_ESTATE, "crl_set_flags_event is a Pong entry point");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
+    if (c->car) return crl_fail(CRL_ESTATE, "crl_set_flags_event is a Pong entry point");
     c->flags_ev = (hipEvent_t)event;
     return CRL_OK;
 }
 
 int crl_draw_stack(crl_ctx *c, uint8_t *obs_dev, const crl_stack_desc *stack, void *stream) {
     CRL_ENTER(c);
-    if (!c || !stack) return fail(CRL_EINVAL, "null argument");
+    if (!c || !stack) return crl_fail(CRL_EINVAL, "null argument");
     GrayStack sk;
-    if (int rc = stack_of(c, stack, obs_dev, &sk)) return rc;
+    if (int rc = stack_of(c, stack, &sk)) return rc;
     return draw_obs(c, obs_dev, (hipStream_t)stream, &sk);
 }
 
 int crl_info(crl_ctx *c, const float **real_reward_dev, const int32_t **num_steps_dev) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
-    if (c->car) return fail(CRL_ESTATE, "crl_info is a Pong entry point");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
+    if (c->car) return crl_fail(CRL_ESTATE, "crl_info is a Pong entry point");
     if (real_reward_dev) *real_reward_dev = c->s.real_reward;
     if (num_steps_dev) *num_steps_dev = c->s.num_steps;
     return CRL_OK;
@@ -614,8 +586,8 @@ int crl_info(crl_ctx *c, const float **real_reward_dev, const int32_t **num_step
 
 int crl_copy_info(crl_ctx *c, float *rr_out, int32_t *ns_out, void *stream) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
-    if (c->car) return fail(CRL_ESTATE, "crl_copy_info is a Pong entry point");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
+    if (c->car) return crl_fail(CRL_ESTATE, "crl_copy_info is a Pong entry point");
     hipStream_t st = (hipStream_t)stream;
     if (rr_out) HIP_TRY(hipMemcpyAsync(rr_out, c->s.real_reward, (size_t)c->n * 8, hipMemcpyDeviceToDevice, st));
     if (ns_out) HIP_TRY(hipMemcpyAsync(ns_out, c->s.num_steps, (size_t)c->n * 4, hipMemcpyDeviceToDevice, st));
@@ -624,7 +596,7 @@ int crl_copy_info(crl_ctx *c, float *rr_out, int32_t *ns_out, void *stream) {
 
 int crl_car_info(crl_ctx *c, const uint8_t **done_car_dev, const int32_t **num_steps_dev) {
     CRL_ENTER(c);
-    if (!c || !c->car) return fail(CRL_EINVAL, "not a CarRacing context");
+    if (!c || !c->car) return crl_fail(CRL_EINVAL, "not a CarRacing context");
     if (done_car_dev) *done_car_dev = crl_car_done_flags(c->car);
     if (num_steps_dev) *num_steps_dev = crl_car_info_steps(c->car);
     return CRL_OK;
@@ -632,7 +604,7 @@ int crl_car_info(crl_ctx *c, const uint8_t **done_car_dev, const int32_t **num_s
 
 int crl_car_copy_info(crl_ctx *c, uint8_t *done_car_out, int32_t *num_steps_out, int32_t *elapsed_out, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car) return fail(CRL_EINVAL, "not a CarRacing context");
+    if (!c || !c->car) return crl_fail(CRL_EINVAL, "not a CarRacing context");
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = crl_car_players(c->car);
     if (done_car_out) HIP_TRY(hipMemcpyAsync(done_car_out, crl_car_done_flags(c->car), (size_t)(c->n * P), hipMemcpyDeviceToDevice, st));
@@ -652,21 +624,7 @@ int64_t crl_obs_bytes_per_env(const crl_ctx *c) {
 // Draws `m` frame pairs that already sit in device memory as a single-plane ring ([8][m], planes 0..2 unused).
 static int render_ring(crl_ctx *c, const uint64_t *ring_dev, int64_t m, uint8_t *out_dev, hipStream_t st) {
     if (m == 0) return CRL_OK;
-    if (c->o.obs_mode == CRL_OBS_RAW_RGB) {
-        launch_pong_raster_raw(ring_dev + 6 * m, m, c->atlas_rgb, c->ink_row0, c->ink_row1, out_dev, pong_views(c), st);
-    } else {
-        GrayParams p{};
-        p.ring = ring_dev, p.n = m, p.R = c->o.resized_dim, p.K = 1, p.views = pong_views(c);
-        p.atlas_gray = c->atlas_gray, p.band = c->band, p.band_rows = c->band_rows;
-        p.xofs = c->xofs, p.yofs = c->yofs, p.xsi = c->xsi, p.ysi = c->ysi, p.xalpha = c->xalpha, p.yalpha = c->yalpha;
-        p.obs = out_dev, p.obs_f32 = c->o.obs_dtype;
-        p.f32_top = c->f32_top, p.f32_bot = c->f32_bot, p.f32_bot0 = c->f32_bot0, p.f32_xtaps = c->f32_xtaps, p.f32_ytaps = c->f32_ytaps;
-        p.f32_map_row0 = c->f32_map_row0, p.f32_map_rows = c->f32_map_rows;
-        launch_pong_raster_gray_ex(p, c->rest, c->zero_row0, c->zero_row1, c->x_first, c->x_last, c->y_first, c->y_last,
-                                   c->band_chunks, c->tab_blob, c->tofs, st);
-    }
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return draw_frames(c, draw_src(c, ring_dev, m), m, 1, out_dev, st);
 }
 
 static int ensure_gather(crl_ctx *c, int64_t m) {
@@ -695,7 +653,7 @@ static int render_pairs(crl_ctx *c, const std::vector<uint64_t> &f0, const std::
 
 int crl_terminal_observation_dev(crl_ctx *c, const int64_t *env_idx_dev, int64_t count, uint8_t *out_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c || (count > 0 && (!env_idx_dev || !out_dev))) return fail(CRL_EINVAL, "null argument");
+    if (!c || (count > 0 && (!env_idx_dev || !out_dev))) return crl_fail(CRL_EINVAL, "null argument");
     if (count <= 0) return CRL_OK;
     hipStream_t st = (hipStream_t)stream;
     if (c->car) {
@@ -712,10 +670,10 @@ int crl_terminal_observation_dev(crl_ctx *c, const int64_t *env_idx_dev, int64_t
 
 int crl_terminal_observation(crl_ctx *c, const int64_t *env_idx_host, int64_t count, uint8_t *out_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c || (count > 0 && (!env_idx_host || !out_dev))) return fail(CRL_EINVAL, "null argument");
+    if (!c || (count > 0 && (!env_idx_host || !out_dev))) return crl_fail(CRL_EINVAL, "null argument");
     if (count <= 0) return CRL_OK;
     for (int64_t k = 0; k < count; k++)
-        if (env_idx_host[k] < 0 || env_idx_host[k] >= c->n) return fail(CRL_EINVAL, "env index %lld out of range", (long long)env_idx_host[k]);
+        if (env_idx_host[k] < 0 || env_idx_host[k] >= c->n) return crl_fail(CRL_EINVAL, "env index %lld out of range", (long long)env_idx_host[k]);
     hipStream_t st = (hipStream_t)stream;
     if (count > c->idx_cap) {
         HIP_TRY(hipDeviceSynchronize());
@@ -733,8 +691,8 @@ int crl_terminal_observation(crl_ctx *c, const int64_t *env_idx_host, int64_t co
 // frame s -> row 2p + s; raw contexts and K = 1 use the newest plane, rows 6 and 7): 64 bytes per env instead of its pixels.
 int crl_obs_descriptors(crl_ctx *c, crl_pong_frame *desc_out_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c || !desc_out_dev) return fail(CRL_EINVAL, "null argument");
-    if (c->car) return fail(CRL_ESTATE, "crl_obs_descriptors is a Pong entry point");
+    if (!c || !desc_out_dev) return crl_fail(CRL_EINVAL, "null argument");
+    if (c->car) return crl_fail(CRL_ESTATE, "crl_obs_descriptors is a Pong entry point");
     hipStream_t st = (hipStream_t)stream;
     uint64_t *out = reinterpret_cast<uint64_t *>(desc_out_dev);
     if (c->o.obs_mode == CRL_OBS_RAW_RGB) {
@@ -751,33 +709,17 @@ int crl_obs_descriptors(crl_ctx *c, crl_pong_frame *desc_out_dev, void *stream) 
 // descriptors holds every shard's observation (BASELINE config #5 without moving pixels).
 int crl_render_frames_dev(crl_ctx *c, const crl_pong_frame *desc_dev, int64_t count, uint8_t *out_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c || (count > 0 && (!desc_dev || !out_dev))) return fail(CRL_EINVAL, "null argument");
-    if (c->car) return fail(CRL_ESTATE, "crl_render_frames_dev is a Pong entry point");
+    if (!c || (count > 0 && (!desc_dev || !out_dev))) return crl_fail(CRL_EINVAL, "null argument");
+    if (c->car) return crl_fail(CRL_ESTATE, "crl_render_frames_dev is a Pong entry point");
     if (count <= 0) return CRL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t *ring = reinterpret_cast<const uint64_t *>(desc_dev);
-    if (c->o.obs_mode == CRL_OBS_RAW_RGB) {
-        launch_pong_raster_raw(ring + 6 * count, count, c->atlas_rgb, c->ink_row0, c->ink_row1, out_dev, pong_views(c), st);
-    } else {
-        GrayParams p{};
-        p.ring = ring, p.n = count, p.R = c->o.resized_dim, p.K = c->o.frame_stack, p.views = pong_views(c);
-        p.atlas_gray = c->atlas_gray, p.band = c->band, p.band_rows = c->band_rows;
-        p.xofs = c->xofs, p.yofs = c->yofs, p.xsi = c->xsi, p.ysi = c->ysi, p.xalpha = c->xalpha, p.yalpha = c->yalpha;
-        p.obs = out_dev, p.obs_f32 = c->o.obs_dtype;
-        p.f32_top = c->f32_top, p.f32_bot = c->f32_bot, p.f32_bot0 = c->f32_bot0, p.f32_xtaps = c->f32_xtaps, p.f32_ytaps = c->f32_ytaps;
-        p.f32_map_row0 = c->f32_map_row0, p.f32_map_rows = c->f32_map_rows;
-        launch_pong_raster_gray_ex(p, c->rest, c->zero_row0, c->zero_row1, c->x_first, c->x_last, c->y_first, c->y_last,
-                                   c->band_chunks, c->tab_blob, c->tofs, st);
-    }
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return draw_frames(c, draw_src(c, reinterpret_cast<const uint64_t *>(desc_dev), count), count, c->o.frame_stack, out_dev, (hipStream_t)stream);
 }
 
 int crl_render_raw(crl_ctx *c, const crl_pong_frame *frames_host, int64_t count, uint8_t *out_dev, void *stream) {
     CRL_ENTER(c);
-    if (!c || !frames_host || !out_dev) return fail(CRL_EINVAL, "null argument");
-    if (c->car) return fail(CRL_ESTATE, "crl_render_raw is a Pong entry point");
-    if (c->o.obs_mode != CRL_OBS_RAW_RGB) return fail(CRL_ESTATE, "crl_render_raw needs a RAW_RGB context");
+    if (!c || !frames_host || !out_dev) return crl_fail(CRL_EINVAL, "null argument");
+    if (c->car) return crl_fail(CRL_ESTATE, "crl_render_raw is a Pong entry point");
+    if (c->o.obs_mode != CRL_OBS_RAW_RGB) return crl_fail(CRL_ESTATE, "crl_render_raw needs a RAW_RGB context");
     std::vector<uint64_t> f(count);
     memcpy(f.data(), frames_host, (size_t)count * 8);
     return render_pairs(c, f, f, out_dev, (hipStream_t)stream);
@@ -813,8 +755,8 @@ extern "C" {
 
 int crl_get_state(crl_ctx *c, crl_pong_env_state *out, int64_t first, int64_t count, void *stream) {
     CRL_ENTER(c);
-    if (!c || !out || first < 0 || count < 0 || first + count > c->n) return fail(CRL_EINVAL, "bad range");
-    if (c->car) return fail(CRL_ESTATE, "use crl_car_get_state for CarRacing contexts");
+    if (!c || !out || first < 0 || count < 0 || first + count > c->n) return crl_fail(CRL_EINVAL, "bad range");
+    if (c->car) return crl_fail(CRL_ESTATE, "use crl_car_get_state for CarRacing contexts");
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> sx, sy;
     std::vector<int32_t> bx, by, bl, br, sl, sr, ro, stp, ws;
@@ -845,8 +787,8 @@ int crl_get_state(crl_ctx *c, crl_pong_env_state *out, int64_t first, int64_t co
 
 int crl_set_state(crl_ctx *c, const crl_pong_env_state *in, int64_t first, int64_t count, void *stream) {
     CRL_ENTER(c);
-    if (!c || !in || first < 0 || count < 0 || first + count > c->n) return fail(CRL_EINVAL, "bad range");
-    if (c->car) return fail(CRL_ESTATE, "use crl_car_set_state for CarRacing contexts");
+    if (!c || !in || first < 0 || count < 0 || first + count > c->n) return crl_fail(CRL_EINVAL, "bad range");
+    if (c->car) return crl_fail(CRL_ESTATE, "use crl_car_set_state for CarRacing contexts");
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> sx(count), sy(count);
     std::vector<int32_t> bx(count), by(count), bl(count), br(count), sl(count), sr(count), ro(count), stp(count), ws(count);
@@ -882,13 +824,13 @@ int crl_set_state(crl_ctx *c, const crl_pong_env_state *in, int64_t first, int64
 
 int crl_set_replay(crl_ctx *c, const double *u, const uint8_t *bx, const uint8_t *by, int64_t per_env) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
-    if (c->car) return fail(CRL_ESTATE, "use crl_car_set_replay for CarRacing contexts");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
+    if (c->car) return crl_fail(CRL_ESTATE, "use crl_car_set_replay for CarRacing contexts");
     HIP_TRY(hipDeviceSynchronize());
     if (c->ru) hipFree(c->ru), hipFree(c->rbx), hipFree(c->rby), c->ru = nullptr, c->rbx = c->rby = nullptr;
     c->src.ru = nullptr, c->src.rbx = c->src.rby = nullptr, c->src.per_env = 0;
     if (per_env <= 0) return CRL_OK;
-    if (!u || !bx || !by) return fail(CRL_EINVAL, "null replay arrays");
+    if (!u || !bx || !by) return crl_fail(CRL_EINVAL, "null replay arrays");
     const size_t m = (size_t)c->n * per_env;
     HIP_TRY(hipMalloc((void **)&c->ru, m * 8));
     HIP_TRY(hipMalloc((void **)&c->rbx, m));
@@ -902,7 +844,7 @@ int crl_set_replay(crl_ctx *c, const double *u, const uint8_t *bx, const uint8_t
 
 int crl_kernel_timing(crl_ctx *c, int enable) {
     CRL_ENTER(c);
-    if (!c) return fail(CRL_EINVAL, "null ctx");
+    if (!c) return crl_fail(CRL_EINVAL, "null ctx");
     c->tm.on = enable != 0;
     // the event pairs of the first few hundred timed launches are created HERE, not inside the caller's timed loop
     // (later ones come back through the pool when crl_kernel_time_ms reads them out)
@@ -922,7 +864,7 @@ int crl_kernel_timing(crl_ctx *c, int enable) {
 
 int crl_kernel_time_stats(crl_ctx *c, int which, double *total_ms, int64_t *launches, double *max_ms) {
     CRL_ENTER(c);
-    if (!c || which < 0 || which >= kTimerSlots) return fail(CRL_EINVAL, "bad argument");
+    if (!c || which < 0 || which >= kTimerSlots) return crl_fail(CRL_EINVAL, "bad argument");
     crl_timer &t = c->tm;
     for (auto &p : t.ev[which]) {
         HIP_TRY(hipEventSynchronize(p.b));
@@ -946,39 +888,39 @@ int crl_kernel_time_ms(crl_ctx *c, int which, double *total_ms, int64_t *launche
 
 int crl_car_get_state(crl_ctx *c, crl_car_env_state *out, int64_t first, int64_t count, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car || !out) return fail(CRL_EINVAL, "not a CarRacing context / null argument");
+    if (!c || !c->car || !out) return crl_fail(CRL_EINVAL, "not a CarRacing context / null argument");
     return crl_car_get_state_impl(c->car, out, first, count, (hipStream_t)stream);
 }
 int crl_car_set_state(crl_ctx *c, const crl_car_env_state *in, int64_t first, int64_t count, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car || !in) return fail(CRL_EINVAL, "not a CarRacing context / null argument");
+    if (!c || !c->car || !in) return crl_fail(CRL_EINVAL, "not a CarRacing context / null argument");
     return crl_car_set_state_impl(c->car, in, first, count, (hipStream_t)stream);
 }
 int crl_car_get_track(crl_ctx *c, int64_t env, int32_t *n, float *tile_poly, float *border_poly, uint8_t *border,
                       float *start_pose, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car) return fail(CRL_EINVAL, "not a CarRacing context");
+    if (!c || !c->car) return crl_fail(CRL_EINVAL, "not a CarRacing context");
     return crl_car_get_track_impl(c->car, env, n, tile_poly, border_poly, border, start_pose, (hipStream_t)stream);
 }
 int crl_car_set_track(crl_ctx *c, int64_t env, int32_t n, const double *tile_poly, const double *border_poly, const uint8_t *border,
                       const float *start_pose, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car) return fail(CRL_EINVAL, "not a CarRacing context");
+    if (!c || !c->car) return crl_fail(CRL_EINVAL, "not a CarRacing context");
     return crl_car_set_track_impl(c->car, env, n, tile_poly, border_poly, border, start_pose, (hipStream_t)stream);
 }
 int crl_car_cap_hits(crl_ctx *c, int32_t *out4_host, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car || !out4_host) return fail(CRL_EINVAL, "not a CarRacing context / null argument");
+    if (!c || !c->car || !out4_host) return crl_fail(CRL_EINVAL, "not a CarRacing context / null argument");
     return crl_car_cap_hits_impl(c->car, out4_host, (hipStream_t)stream);
 }
 int crl_car_get_map(crl_ctx *c, int64_t env, uint8_t *palette_host, int32_t *overflow, void *stream) {
     CRL_ENTER(c);
-    if (!c || !c->car) return fail(CRL_EINVAL, "not a CarRacing context");
+    if (!c || !c->car) return crl_fail(CRL_EINVAL, "not a CarRacing context");
     return crl_car_get_map_impl(c->car, env, palette_host, overflow, (hipStream_t)stream);
 }
 int crl_car_set_replay(crl_ctx *c, const double *u, const uint8_t *swap, int64_t attempts) {
     CRL_ENTER(c);
-    if (!c || !c->car) return fail(CRL_EINVAL, "not a CarRacing context");
+    if (!c || !c->car) return crl_fail(CRL_EINVAL, "not a CarRacing context");
     return crl_car_set_replay_impl(c->car, u, swap, attempts);
 }
 

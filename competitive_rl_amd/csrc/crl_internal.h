@@ -10,6 +10,24 @@
 int crl_fail(int code, const char *fmt, ...);
 void crl_fail_no_ctx(void);  // first line of every entry point without a crl_ctx argument
 
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
+
+// a failed HIP call of the create function `what`: CRL_ENOMEM when the device is out of memory, else CRL_EHIP
+inline int crl_hip_fail(hipError_t e, const char *what) {
+    return crl_fail(e == hipErrorOutOfMemory ? CRL_ENOMEM : CRL_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
+// *p = `bytes` of zeroed device memory (on failure *p is what hipMalloc left: null, or memory its owner's destroy frees)
+template <class T>
+int crl_dev_zalloc(T **p, size_t bytes, const char *what) {
+    hipError_t e = hipMalloc((void **)p, bytes);
+    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+    return e == hipSuccess ? CRL_OK : crl_hip_fail(e, what);
+}
+
 // Timing ablations that give WRONG results (skip a phase to size it) exist only in a profiling build (-DCRL_ABLATION):
 // in the shipped library their switches read as zero and the compiler drops the branches.
 #ifdef CRL_ABLATION

@@ -237,28 +237,41 @@ struct GrayStack {
     int valid;      // updates since the stack's reset(), capped at k: the k - valid oldest planes are zeros
     int alias;      // 1: the observation tensor's (view, newest plane) tile is not written -- its reader takes the stack's newest plane
 };
-struct GrayParams {
-    const uint64_t *ring;    // [8][n] frame pairs of the 4 stack planes; plane 3 = newest (K=1 draws only it)
-    int64_t n;
-    int R, K, views;
-    const uint8_t *atlas_gray;  // [22*22][34][160]
-    const uint8_t *band;        // pre-resized top band [22*22][2 views][band_rows][R]
-    int band_rows;
-    const int32_t *xofs, *yofs;     // [R+1] first tap of each output col / row
-    const int32_t *xsi, *ysi;       // source index per tap
-    const float *xalpha, *yalpha;   // weight per tap
-    uint8_t *obs;                   // [n][2][K][R][R]
-    int obs_f32;                    // crl_obs_dtype of obs: 1 = float32, same values, widened in the store epilogue; 2 = the reference's unrounded float32 path
-    void *hdr;                      // scratch for the address-linear writer: 64 B per (env, view, plane) tile, or nullptr
+// What the gray draw reads that is fixed after crl_create: device tables, filled once by crl_api.hip's setup_gray.
+struct GrayTables {
+    int R;
+    uint8_t *atlas_gray;            // [22*22][34][160]
+    uint8_t *band;                  // pre-resized top band [22*22][2 views][band_rows][R]
+    int band_rows, band_chunks;
+    int32_t *xofs, *yofs;           // [R+1] first tap of each output col / row
+    int32_t *xsi, *ysi;             // source index per tap
+    float *xalpha, *yalpha;         // weight per tap
+    uint8_t *rest;                  // [R*R] score-independent template
+    int zero_row0, zero_row1;       // output rows [zero_row0, zero_row1) of the template are all 0
+    uint8_t *x_first, *x_last;      // [160] first / last output col fed by a source col
+    uint8_t *y_first, *y_last;      // [210]
+    uint8_t *tab_blob;              // dense tap tables + first/last maps, staged into LDS per workgroup
+    GrayTabOfs tofs;
     // CRL_OBS_F32_REF: the planes of a court WITHOUT ball and bats, per score pair (pong_raster_gray.hip pong_gray_f32ref_kernel)
-    const float *f32_top;           // [484][2 views][2: unrounded, rounded][band_rows][R] output rows fed by the score band
-    const float *f32_bot;           // [2][R - f32_bot0][R] output rows fed by the white band under the court (score-independent)
+    float *f32_top;                 // [484][2 views][2: unrounded, rounded][band_rows][R] output rows fed by the score band
+    float *f32_bot;                 // [2][R - f32_bot0][R] output rows fed by the white band under the court (score-independent)
     int f32_bot0;                   // first output row with a tap under the court
     int f32_xtaps, f32_ytaps;       // entries of xsi / ysi (the kernel stages the tap tables in LDS)
     int f32_map_row0, f32_map_rows; // output rows fed by the court's source rows (where a ball or a bat can change a pixel)
-    GrayStack stack;                // fused FrameStackTensor (out == nullptr: none); obs may then be nullptr (stack only)
 };
-void launch_pong_gray_f32ref_tables(const GrayParams &p, float *top, float *bot, hipStream_t st);
-void launch_pong_raster_gray(const GrayParams &p, hipStream_t st);
+// What differs from one draw to the next.
+struct GrayJob {
+    const uint64_t *ring;  // [8][n] frame pairs of the 4 stack planes; plane 3 = newest (K=1 draws only it)
+    int64_t n;
+    int K, views;
+    uint8_t *obs;          // [n][views][K][R][R]
+    int obs_f32;           // crl_obs_dtype of obs: 1 = float32, same values, widened in the store epilogue; 2 = the reference's unrounded float32 path
+    void *hdr;             // scratch for the address-linear writer: 64 B per (env, view, plane) tile, or nullptr
+    GrayStack stack;       // fused FrameStackTensor (out == nullptr: none); obs may then be nullptr (stack only)
+};
+void launch_pong_gray_templates(const GrayTables &t, hipStream_t st);      // fills t.band and t.rest
+void launch_pong_gray_f32ref_tables(const GrayTables &t, hipStream_t st);  // fills t.f32_top and t.f32_bot
+void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t st);
+void pong_gray_print_ticks();  // profiling build: CRL_GRAY_DEBUG & 128
 
 }  // namespace crl

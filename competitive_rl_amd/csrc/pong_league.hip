@@ -110,12 +110,6 @@ __global__ void league_fill_assignment_kernel(int32_t *__restrict__ assign, int3
 
 using namespace crl;
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 struct crl_league {
     int device = 0;
     int64_t n = 0, n_pad = 0, env_id_base = 0;
@@ -152,8 +146,8 @@ static int league_add(crl_league *l, int kind, const float *raw_host) {
     if (kind == CRL_LEAGUE_LIGHT) {
         HIP_TRY(hipMalloc(&l->raw[a], kLightRawFloats * sizeof(float)));
         HIP_TRY(hipMemcpy(l->raw[a], raw_host, kLightRawFloats * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t)));
-        HIP_TRY(hipMemset(l->T.list[a], 0, (size_t)(l->n_pad + 8) * sizeof(int32_t)));  // (entries past the count are read, never used)
+        // (entries past the count are read, never used)
+        if (int rc = crl_dev_zalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t), "crl_league_add_light")) return rc;
         HIP_TRY(policy_light_list_prepare());
     }
     l->kind[a] = kind;
@@ -177,17 +171,14 @@ int crl_league_create(int32_t device, int64_t num_envs, int64_t env_id_base, uin
     crl_league *l = new crl_league();
     l->device = device, l->n = num_envs, l->n_pad = (num_envs + 7) / 8 * 8, l->env_id_base = env_id_base, l->seed = seed;
     if (hipDeviceGetAttribute(&l->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || l->cus <= 0) l->cus = 256;
-    hipError_t e = hipMalloc(&l->ring, (size_t)num_envs * kLRingBytes);
-    if (e == hipSuccess) e = hipMemset(l->ring, 0, (size_t)num_envs * kLRingBytes);
-    if (e == hipSuccess) e = hipMalloc(&l->assign, (size_t)num_envs * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(l->assign, 0, (size_t)num_envs * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&l->draw_ctr, (size_t)num_envs * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(l->draw_ctr, 0, (size_t)num_envs * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&l->ctrl, 3 * kMaxAgents * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(l->ctrl, 0, 3 * kMaxAgents * sizeof(unsigned));
-    if (e != hipSuccess) {
+    const char *what = "crl_league_create";
+    int rc = crl_dev_zalloc(&l->ring, (size_t)num_envs * kLRingBytes, what);
+    if (!rc) rc = crl_dev_zalloc(&l->assign, (size_t)num_envs * sizeof(int32_t), what);
+    if (!rc) rc = crl_dev_zalloc(&l->draw_ctr, (size_t)num_envs * sizeof(uint32_t), what);
+    if (!rc) rc = crl_dev_zalloc(&l->ctrl, 3 * kMaxAgents * sizeof(unsigned), what);
+    if (rc) {
         crl_league_destroy(l);
-        return crl_fail(e == hipErrorOutOfMemory ? CRL_ENOMEM : CRL_EHIP, "crl_league_create: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = l;
     return CRL_OK;

@@ -128,12 +128,6 @@ __global__ void ledger_resize_kernel(int before, int after, uint32_t *__restrict
 
 using namespace crl;
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 struct crl_ledger {
     int device = 0;
     int64_t n = 0, env_id_base = 0;
@@ -160,24 +154,21 @@ int crl_ledger_create(int32_t device, int64_t num_envs, int64_t env_id_base, uin
     crl_ledger *l = new crl_ledger();
     l->device = device, l->n = num_envs, l->env_id_base = env_id_base, l->seed = seed, l->agents = agents;
     const size_t per_env = (size_t)num_envs * sizeof(int32_t), books = (kGCounters + 1) * sizeof(unsigned long long);
-    hipError_t e = hipMalloc(&l->ret, per_env);
-    if (e == hipSuccess) e = hipMemset(l->ret, 0, per_env);
-    if (e == hipSuccess) e = hipMalloc(&l->len, per_env);
-    if (e == hipSuccess) e = hipMemset(l->len, 0, per_env);
-    if (e == hipSuccess) e = hipMalloc(&l->draw_ctr, per_env);
-    if (e == hipSuccess) e = hipMemset(l->draw_ctr, 0, per_env);
-    if (e == hipSuccess) e = hipMalloc(&l->counters, books);
-    if (e == hipSuccess) e = hipMemset(l->counters, 0, books);
-    if (e == hipSuccess) e = hipMalloc(&l->w, kGAgents * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(l->w, 0, kGAgents * sizeof(uint32_t));
-    if (e == hipSuccess) {
+    const char *what = "crl_ledger_create";
+    int rc = crl_dev_zalloc(&l->ret, per_env, what);
+    if (!rc) rc = crl_dev_zalloc(&l->len, per_env, what);
+    if (!rc) rc = crl_dev_zalloc(&l->draw_ctr, per_env, what);
+    if (!rc) rc = crl_dev_zalloc(&l->counters, books, what);
+    if (!rc) rc = crl_dev_zalloc(&l->w, kGAgents * sizeof(uint32_t), what);
+    if (!rc) {
         hipLaunchKernelGGL(ledger_resize_kernel, dim3(1), dim3(64), 0, nullptr, 0, agents, l->w);
-        e = hipGetLastError();
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = crl_hip_fail(e, what);
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
+    if (rc) {
         crl_ledger_destroy(l);
-        return crl_fail(e == hipErrorOutOfMemory ? CRL_ENOMEM : CRL_EHIP, "crl_ledger_create: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = l;
     return CRL_OK;

@@ -833,12 +833,6 @@ hipError_t policy_copy_stack(uint8_t *ring, uint8_t *ext, int head, int64_t n, i
 
 using namespace crl;
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 struct crl_policy {
     int device = 0;
     int64_t n = 0;

@@ -907,10 +907,10 @@ __global__ __launch_bounds__(256) void pong_gray_f32ref_table_kernel(GrayCtx g, 
     }
 }
 
-void launch_pong_gray_f32ref_tables(const GrayParams &p, float *top, float *bot, hipStream_t st) {
-    GrayCtx g = {p.atlas_gray, p.xofs, p.yofs, p.xsi, p.ysi, p.xalpha, p.yalpha};
-    const int64_t total = (int64_t)484 * 12 * p.band_rows * p.R + (int64_t)2 * (p.R - p.f32_bot0) * p.R;
-    hipLaunchKernelGGL(pong_gray_f32ref_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g, p.R, p.band_rows, p.f32_bot0, top, bot);
+void launch_pong_gray_f32ref_tables(const GrayTables &t, hipStream_t st) {
+    GrayCtx g = {t.atlas_gray, t.xofs, t.yofs, t.xsi, t.ysi, t.xalpha, t.yalpha};
+    const int64_t total = (int64_t)484 * 12 * t.band_rows * t.R + (int64_t)2 * (t.R - t.f32_bot0) * t.R;
+    hipLaunchKernelGGL(pong_gray_f32ref_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g, t.R, t.band_rows, t.f32_bot0, t.f32_top, t.f32_bot);
 }
 
 // One wavefront per (env, view, plane) tile.  Usual case (both kept frames show the same scores): the plane is the score pair's
@@ -1125,37 +1125,32 @@ __global__ __launch_bounds__(256, CRL_F32REF_LB) void pong_gray_f32ref_kernel(co
     }
 }
 
-void launch_pong_gray_templates(const GrayParams &p, const uint8_t *x_first, const uint8_t *x_last, const uint8_t *y_first,
-                                const uint8_t *y_last, int band_rows, int band_chunks, uint8_t *band, uint8_t *rest,
-                                hipStream_t st) {
-    GrayCtx g = {p.atlas_gray, p.xofs, p.yofs, p.xsi, p.ysi, p.xalpha, p.yalpha};
+void launch_pong_gray_templates(const GrayTables &t, hipStream_t st) {
+    GrayCtx g = {t.atlas_gray, t.xofs, t.yofs, t.xsi, t.ysi, t.xalpha, t.yalpha};
     GrayGeom q = {};
-    q.R = p.R, q.K = p.K, q.band_rows = band_rows, q.band_chunks = band_chunks;
-    const int total = 3 * 484 * 2 * band_chunks * 16 + p.R * p.R;
-    hipLaunchKernelGGL(pong_gray_template_kernel, dim3((total + 255) / 256), dim3(256), 0, st, g, q, band, rest);
+    q.R = t.R, q.band_rows = t.band_rows, q.band_chunks = t.band_chunks;
+    const int total = 3 * 484 * 2 * t.band_chunks * 16 + t.R * t.R;
+    hipLaunchKernelGGL(pong_gray_template_kernel, dim3((total + 255) / 256), dim3(256), 0, st, g, q, t.band, t.rest);
 }
 
-void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int zero_row0, int zero_row1,
-                                const uint8_t *x_first, const uint8_t *x_last, const uint8_t *y_first,
-                                const uint8_t *y_last, int band_chunks, const uint8_t *tab_blob, const GrayTabOfs &tofs,
-                                hipStream_t st) {
+void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t st) {
     if (p.n <= 0) return;
-    GrayCtx g = {p.atlas_gray, p.xofs, p.yofs, p.xsi, p.ysi, p.xalpha, p.yalpha};
+    GrayCtx g = {t.atlas_gray, t.xofs, t.yofs, t.xsi, t.ysi, t.xalpha, t.yalpha};
     if (p.obs_f32 == 2) {  // CRL_OBS_F32_REF
         const int views = p.views > 0 ? p.views : 2;
         const int64_t tiles = p.n * ((p.stack.out ? p.stack.k : 0) + (p.obs ? views * p.K - (p.stack.out && p.stack.alias ? 1 : 0) : 0));
         static const int dbg = CRL_ABL(getenv("CRL_GRAY_DEBUG") != nullptr) ? atoi(getenv("CRL_GRAY_DEBUG")) : 0;
-        const F32RefGeom fq = {p.f32_top, p.f32_bot, p.band_rows, p.f32_bot0, x_first, x_last, y_first, y_last, p.f32_xtaps, p.f32_ytaps, dbg,
-                               p.f32_map_row0, p.f32_map_rows};
-        hipLaunchKernelGGL(pong_gray_f32ref_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p.ring, p.n, g, fq, p.R, p.K, views,
+        const F32RefGeom fq = {t.f32_top, t.f32_bot, t.band_rows, t.f32_bot0, t.x_first, t.x_last, t.y_first, t.y_last, t.f32_xtaps, t.f32_ytaps, dbg,
+                               t.f32_map_row0, t.f32_map_rows};
+        hipLaunchKernelGGL(pong_gray_f32ref_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p.ring, p.n, g, fq, t.R, p.K, views,
                            reinterpret_cast<float *>(p.obs), p.stack);
         return;
     }
     GrayGeom q;
-    q.R = p.R, q.K = p.K, q.views = p.views > 0 ? p.views : 2, q.band_rows = p.band_rows, q.band_chunks = band_chunks;
-    q.band = p.band, q.rest = rest, q.zero_row0 = zero_row0, q.zero_row1 = zero_row1;
-    q.x_first = x_first, q.x_last = x_last, q.y_first = y_first, q.y_last = y_last;
-    q.tab_blob = tab_blob, q.t = tofs;
+    q.R = t.R, q.K = p.K, q.views = p.views > 0 ? p.views : 2, q.band_rows = t.band_rows, q.band_chunks = t.band_chunks;
+    q.band = t.band, q.rest = t.rest, q.zero_row0 = t.zero_row0, q.zero_row1 = t.zero_row1;
+    q.x_first = t.x_first, q.x_last = t.x_last, q.y_first = t.y_first, q.y_last = t.y_last;
+    q.tab_blob = t.tab_blob, q.t = t.tofs;
     q.debug = 0;
 #ifdef CRL_ABLATION
     const int64_t tiles = p.n * q.views * p.K;
@@ -1174,17 +1169,17 @@ void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int ze
     // bit-exact, but 1.0-2.0 ms against the env kernel's 0.75 ms at 65 536 envs -- every block has to read per-tile metadata
     // first, and a dependent read in a store-saturated memory system takes microseconds.
     static const int sweep_env = getenv("CRL_GRAY_SWEEP") ? atoi(getenv("CRL_GRAY_SWEEP")) : 0;
-    if (sweep_env && p.obs_f32 != 2 && (!p.obs_f32 || p.R == 84) && !p.stack.out && !q.debug && p.hdr && (p.R * p.R) % 16 == 0 && tofs.max_taps <= 3 && tofs.fast_ok && tiles * (p.R * p.R >> 4) < (1ll << 31) && (p.R * p.R >> 4) <= 512) {
+    if (sweep_env && p.obs_f32 != 2 && (!p.obs_f32 || t.R == 84) && !p.stack.out && !q.debug && p.hdr && (t.R * t.R) % 16 == 0 && t.tofs.max_taps <= 3 && t.tofs.fast_ok && tiles * (t.R * t.R >> 4) < (1ll << 31) && (t.R * t.R >> 4) <= 512) {
         GrayTileHdr *hdr = reinterpret_cast<GrayTileHdr *>(p.hdr);
         hipLaunchKernelGGL(pong_gray_header_kernel, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, st, p.ring, p.n, q, hdr);
         static const int sdbg = getenv("CRL_GRAY_SWEEP_DEBUG") ? atoi(getenv("CRL_GRAY_SWEEP_DEBUG")) : 0;
         static const int nb_env = getenv("CRL_GRAY_SWEEP_NB") ? atoi(getenv("CRL_GRAY_SWEEP_NB")) : 2;
-        const int64_t wblocks = (tiles * (p.R * p.R >> 4) + 63) / 64;   // 1-KiB blocks of the whole tensor
+        const int64_t wblocks = (tiles * (t.R * t.R >> 4) + 63) / 64;   // 1-KiB blocks of the whole tensor
         const int nb = wblocks < 8192 ? 1 : nb_env;
         const int stride = (int)(((wblocks + nb - 1) / nb + 3) / 4 * 4);  // blocks per round, a multiple of the 4 waves of a workgroup
         const dim3 grid((unsigned)(stride / 4));
         const int sweep_mode = sweep_env;
-        if ((sweep_mode == 2 || sweep_mode == 3 || sweep_mode == 4) && p.R == 84) {  // skeletons: 64-byte headers | dense 8-byte records | dense 2-byte records
+        if ((sweep_mode == 2 || sweep_mode == 3 || sweep_mode == 4) && t.R == 84) {  // skeletons: 64-byte headers | dense 8-byte records | dense 2-byte records
             const int dense = sweep_mode - 2;
 #define CRL_SKEL(NBv) do { if (p.obs_f32) hipLaunchKernelGGL((pong_gray_sweep_skeleton_kernel<NBv, true>), grid, dim3(256), 0, st, hdr, (int)tiles, q, p.obs, stride, dense); \
                            else hipLaunchKernelGGL((pong_gray_sweep_skeleton_kernel<NBv, false>), grid, dim3(256), 0, st, hdr, (int)tiles, q, p.obs, stride, dense); } while (0)
@@ -1201,7 +1196,7 @@ void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int ze
             return;
         }
 #define CRL_SWEEP(RTv, NBv) hipLaunchKernelGGL((pong_raster_gray_sweep_kernel<RTv, NBv>), grid, dim3(256), 0, st, hdr, (int)tiles, g, q, p.obs, sdbg, p.ring, p.n, stride)
-        if (p.R == 84) {
+        if (t.R == 84) {
             if (nb == 1) CRL_SWEEP(84, 1);
             else if (nb == 2) CRL_SWEEP(84, 2);
             else if (nb == 8) CRL_SWEEP(84, 8);
@@ -1231,7 +1226,7 @@ void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int ze
         if (jpw_env < 0) jpw = jobs;  // (profiling build: CRL_GRAY_JPW=-1 = all of the env's jobs)
         const int64_t waves = p.n * ((jobs + jpw - 1) / jpw);
         const dim3 grid((unsigned)((waves + 3) / 4));
-        const int ti = tofs.max_taps <= 3 ? 0 : (p.R * p.R <= 2048 && !small_off) ? 1 : 2;
+        const int ti = t.tofs.max_taps <= 3 ? 0 : (t.R * t.R <= 2048 && !small_off) ? 1 : 2;
 #define CRL_STACK_LAUNCH(MT, TIv, OF, SF) \
     hipLaunchKernelGGL((pong_raster_gray_env_kernel<MT, false, TIv, OF, true, SF>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, jpw, sk)
 #define CRL_STACK_TI(OF, SF)                           \
@@ -1251,9 +1246,9 @@ void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int ze
     const int64_t waves = p.n * (p.K / ppw);
     const dim3 grid((unsigned)((waves + 3) / 4));
     if (p.obs_f32) {
-        if (tofs.max_taps <= 3)
+        if (t.tofs.max_taps <= 3)
             hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, false, 7, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
-        else if (p.R * p.R <= 2048 && !small_off)
+        else if (t.R * t.R <= 2048 && !small_off)
             hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 2, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         else
             hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 7, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
@@ -1261,7 +1256,7 @@ void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int ze
     }
 #ifdef CRL_ABLATION
     if (q.debug & ~16) {  // any ablation switch: the instrumented instance
-        if (tofs.max_taps <= 3) hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, true, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+        if (t.tofs.max_taps <= 3) hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, true, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         else hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, true, 2, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         return;
     }
@@ -1272,18 +1267,18 @@ void launch_pong_raster_gray_ex(const GrayParams &p, const uint8_t *rest, int ze
 #ifndef CRL_GRAY_EPWV_N
 #define CRL_GRAY_EPWV_N 4  // (measured at 65 536 envs, 84 x 84: 1 / 4 envs per wavefront 237 / 221 us)
 #endif
-    if (p.K == 1 && ppw == 1 && p.n >= 8192 * CRL_GRAY_EPWV_N && epwv_env != 1 && (tofs.max_taps <= 3 || (p.R * p.R <= 2048 && !small_off))) {
+    if (p.K == 1 && ppw == 1 && p.n >= 8192 * CRL_GRAY_EPWV_N && epwv_env != 1 && (t.tofs.max_taps <= 3 || (t.R * t.R <= 2048 && !small_off))) {
         constexpr int E = CRL_GRAY_EPWV_N;
         const dim3 grid4((unsigned)(((p.n + E - 1) / E + 3) / 4));
-        if (tofs.max_taps <= 3)
+        if (t.tofs.max_taps <= 3)
             hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, false, 7, false, false, false, E>), grid4, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         else
             hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 2, false, false, false, E>), grid4, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         return;
     }
-    if (tofs.max_taps <= 3)
+    if (t.tofs.max_taps <= 3)
         hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, false, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
-    else if (p.R * p.R <= 2048 && !small_off)
+    else if (t.R * t.R <= 2048 && !small_off)
         hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 2, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
     else
         hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);

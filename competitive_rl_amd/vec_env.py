@@ -537,23 +537,35 @@ class HipPongVecEnv(VecEnv):
         check (device-resident actions are validated by the kernel; the bat of such an action does not move)."""
         N.check(self._L.crl_check(self._h, self._stream()))
 
-    def step_wait(self):
-        self._check_open()
-        buf = self._obs[self._flip]
-        self.waiting = False
+    def _step(self, actions, alias_ok, render=True, obs_out=None):
+        """One crl_step_stack call and the books that follow it.  The observation goes into the env's own buffer (which then flips), into
+        the caller's ``obs_out`` (no flip), or -- ``render=False`` -- nowhere: the own buffer still flips, undrawn, with its raw record
+        as it was.  A bound FrameStackTensor is drawn with every rendered step.  Returns (buffer, agent 0's observation)."""
+        own = obs_out is None
+        buf = self._obs[self._flip] if own else obs_out.view(self._obs_shape)
+        fst, sbuf, desc = self._stack_predraw("step", alias_ok) if render else (None, None, None)
+        delta = render and own and self.mode == "raw"  # (raw contexts take no stack: desc is None)
         # (the library first: a refused call -- e.g. the report of an earlier out-of-range action -- has not stepped the envs,
-        # so the buffer flip and the serial that lazy infos check stay where they are)
-        fst, sbuf, desc = self._stack_predraw("step")
-        raw = self.mode == "raw"  # (raw contexts take no stack: desc is None)
-        N.check(self._L.crl_step_stack(self._h, C.c_void_p(self._actions.data_ptr()), None if raw else C.c_void_p(buf.data_ptr()),
+        # so the buffer flip, the serial that lazy infos check and _prev_buf stay where they are)
+        N.check(self._L.crl_step_stack(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(buf.data_ptr()) if render and not delta else None,
                                        C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                        None if desc is None else C.byref(desc), self._stream()))
-        if raw:
+        if delta:
             self._draw_raw(self._flip)
-        self._flip ^= 1
+        if own:
+            self._prev_buf = self._obs[self._flip ^ 1]  # the observation before this step (still intact)
+            self._flip ^= 1
         self._serial += 1
         self._flags_armed = self._serial if self._flags_event is not None else -1
-        learner = self._note_obs("step", buf, sbuf, fst, bool(desc is not None and desc.alias_newest))
+        if not render:
+            self._last_kind, self._learner_obs = "step", None
+            return buf, None
+        return buf, self._note_obs("step", buf, sbuf, fst, bool(desc is not None and desc.alias_newest))
+
+    def step_wait(self):
+        self._check_open()
+        self.waiting = False
+        buf, learner = self._step(self._actions, alias_ok=True)
         done = self._done.bool()
         if self.dones_kind == "dummy":  # scalar done broadcast over the agents (dummy_vec_env.py:39-40)
             done_out = done[:, None].expand(-1, self.V)
@@ -566,7 +578,6 @@ class HipPongVecEnv(VecEnv):
         rew = self._rew.clone()
         if self.single and self.dones_kind == "dummy":
             rew = rew[:, None]  # buf_rews is (N, multi_agent = 1)
-        self._prev_buf = self._obs[self._flip]  # the observation before this step (still intact)
         if self.output == "numpy":
             return self._format_obs(buf), rew.cpu().numpy(), done_out.cpu().numpy().copy(), infos
         return self._format_obs(buf, learner), rew, done_out.clone(), infos
@@ -723,34 +734,9 @@ class HipPongVecEnv(VecEnv):
             if not (obs_out.is_contiguous() and obs_out.dtype == self._buf_dtype and obs_out.device == self.device
                     and obs_out.numel() == self._obs[0].numel()):
                 raise AssertionError("obs_out must be a contiguous tensor of the observation buffer's size and dtype on the env's device")
-            fst, sbuf, desc = self._stack_predraw("step", alias_ok=False)
-            N.check(self._L.crl_step_stack(self._h, C.c_void_p(actions_i32.data_ptr()), C.c_void_p(obs_out.data_ptr()),
-                                           C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
-                                           None if desc is None else C.byref(desc), self._stream()))
-            self._serial += 1
-            self._flags_armed = self._serial if self._flags_event is not None else -1
-            out = obs_out.view(self._obs[0].shape)
-            self._note_obs("step", out, sbuf, fst)
-            return out, self._rew, self._done
-        buf = self._obs[self._flip]
         # (a bound FrameStackTensor is drawn too -- FrameStackTensor.update_from_env then swaps it in; the whole observation
-        # buffer is written here, no tile is left to the stack: the caller gets `buf` itself)
-        fst, sbuf, desc = self._stack_predraw("step", alias_ok=False) if render else (None, None, None)
-        raw = self.mode == "raw"  # (render=False leaves the buffer and its record as they are)
-        N.check(self._L.crl_step_stack(self._h, C.c_void_p(actions_i32.data_ptr()),
-                                       C.c_void_p(buf.data_ptr()) if render and not raw else None,
-                                       C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
-                                       None if desc is None else C.byref(desc), self._stream()))
-        if render and raw:
-            self._draw_raw(self._flip)
-        self._prev_buf = self._obs[self._flip ^ 1]  # (after the call: a refused call has not stepped the envs)
-        self._flip ^= 1
-        self._serial += 1
-        self._flags_armed = self._serial if self._flags_event is not None else -1
-        if render:
-            self._note_obs("step", buf, sbuf, fst)
-        else:
-            self._last_kind, self._learner_obs = "step", None
+        # buffer is written here, no tile is left to the stack: the caller gets the buffer itself)
+        buf, _ = self._step(actions_i32, alias_ok=False, render=render or obs_out is not None, obs_out=obs_out)
         return buf, self._rew, self._done
 
     def kernel_timing(self, enable=True):
