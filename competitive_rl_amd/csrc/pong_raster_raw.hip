@@ -171,45 +171,141 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 //                                                           and new 15-row spans (<= 8 rows for a 4-px move).
 // A pixel of the court is white iff the ball or a bat covers it, so a pixel that changes lies in the symmetric difference of
 // some object's two rectangles; rows outside the court and the ink rows are white in every non-blank frame.
-// Mapping: a workgroup holds 64 envs and one wavefront per (view, object), so every wavefront is uniform in what it draws and
-// its descriptor loads are coalesced.  Whole frames and score bands (a few envs per step) are drawn cooperatively by the
-// view's three wavefronts: a ballot, then a loop over the flagged envs with the 192 lanes striding over the chunks.
-// The record is written by the same launch, after a barrier that follows every read of it.
+// Mapping: a group of L lanes owns one (env, view) and strides over that view's dirty slots, so the stores of one instruction
+// go side by side into one frame instead of into 64 frames 201 600 B apart.  The dirty set is a list of six rectangles (new
+// ball, old ball, two row spans per bat) in output-chunk coordinates; slot s of the running sum maps back to (rectangle, row,
+// block, chunk of the block) with the chunk fastest, then the block, then the row.  A slot is one 16-byte chunk of an aligned
+// block of G chunks (production G = 4: a whole 64-byte memory request from four adjacent lanes), all of them built from the NEW
+// descriptor: the chunks of a block that are not dirty are rewritten with the bytes they hold.  Slots of the old ball's rectangle that the
+// new one covers are stored once.  Two lanes may still store the same block (the ball over a bat's column): both write the new
+// frame's bytes, so the race is benign.  Whole frames and score bands (a few envs per step) are strided over by the same lanes.
+// The record is read and then written by the env's own wavefront (behind a barrier where the env's two views are two wavefronts).
+// Measured on MI355X at 65 536 envs, two views, the launch inside the bench's event brackets (profiles/r08_raw_summary.txt):
+//   one lane per env, 16-byte chunks (round 7) ........ 164 us   3.5 M memory write requests, 95 % of them 32-byte with a mask
+//   L = 32, G = 1 / G = 2 (whole 32-byte sectors) ..... 168 / 164 us   (the requests neither merge nor get cheaper)
+//   L = 32, G = 4 (whole 64-byte blocks) ..............  97 us   (88.6 against the round-7 mapping's 151 on a second box)
+//   L = 16 / 64, G = 4 ................................ 101 / 108 us on that second box
+// The cost was the partial memory request, not the byte count (G = 4 writes 198 MB against 118.7) and not the lane order.
 static constexpr int kBatLc0 = 3 * CRL_PONG_BATL_X / 16, kBatLc1 = (3 * (CRL_PONG_BATL_X + CRL_PONG_BAT_W) - 1) / 16;
 static constexpr int kBatRc0 = 3 * CRL_PONG_BATR_X / 16, kBatRc1 = (3 * (CRL_PONG_BATR_X + CRL_PONG_BAT_W) - 1) / 16;
 
-// stores output chunks (rows [r0, r1) clamped to the court) x (source chunks [c0, c1]) of one view: the mirrored view's rows are
-// the byte-reversed chunk (29 - c), which raw_chunk derives from the output position q
-__device__ __forceinline__ void delta_rect(uint4 *__restrict__ out, const Frame &f, int view, int r0, int r1, int c0, int c1,
-                                           const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
+// rows [r0, r0 + nr) of the court x output chunks [o0, o1] of each row (at most two), the view's mirroring applied
+struct DeltaRect {
+    int r0, nr, o0, o1;
+};
+
+// (rows [r0, r1) clamped to the court) x (source chunks [c0, c1]): the mirrored view's chunk of source chunk c is 29 - c
+__device__ __forceinline__ DeltaRect delta_rect(int view, int r0, int r1, int c0, int c1) {
     r0 = max(r0, CRL_PONG_TOP), r1 = min(r1, CRL_PONG_BOTTOM);
     const bool mirror = view != 0;  // (court rows are all >= CRL_PONG_MIRROR_ROW)
-    for (int row = r0; row < r1; row++)
-        for (int sc = c0; sc <= c1; sc++) {
-            const int q = view * kFrameChunks + row * kRowChunks + (mirror ? kRowChunks - 1 - sc : sc);
+    DeltaRect r;
+    r.r0 = r0, r.nr = max(r1 - r0, 0);
+    r.o0 = mirror ? kRowChunks - 1 - c1 : c0, r.o1 = mirror ? kRowChunks - 1 - c0 : c1;
+    return r;
+}
+
+// the rows of the symmetric difference of [a, a + h) and [b, b + h): [lo, lo + k) and [hi + h - k, hi + h), k = min(|a - b|, h)
+__device__ __forceinline__ void delta_bat(DeltaRect *r, int view, int a, int b, int c0, int c1) {
+    const int lo = min(a, b), hi = max(a, b), k = min(hi - lo, CRL_PONG_BAT_H);
+    r[0] = delta_rect(view, lo, lo + k, c0, c1);
+    r[1] = delta_rect(view, hi + CRL_PONG_BAT_H - k, hi + CRL_PONG_BAT_H, c0, c1);
+}
+
+__device__ __forceinline__ DeltaRect delta_ball(int view, const Frame &g, bool moved) {
+    const int b0 = max(3 * g.x, 0), b1 = min(3 * (g.x + CRL_PONG_BALL), kRowBytes);  // bytes of the row the ball covers
+    DeltaRect r = delta_rect(view, g.y, g.y + CRL_PONG_BALL, b0 / 16, (max(b1, 1) - 1) / 16);
+    if (!moved || b0 >= b1) r.nr = 0;
+    return r;
+}
+
+// blocks of G = 1 << SH chunks a rectangle's row touches: the block of its first chunk counts from the view's first chunk, and a
+// row starts 0 or 2 chunks into a 4-chunk block, so the larger of the two counts (slots past a row's last block store nothing)
+template <int SH>
+__device__ __forceinline__ int delta_blocks(const DeltaRect &r) {
+    const int n0 = (r.o1 >> SH) - (r.o0 >> SH) + 1, n2 = ((r.o1 + 2) >> SH) - ((r.o0 + 2) >> SH) + 1;
+    return max(n0, n2);
+}
+
+template <int VIEWS, int L, int G>
+__global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
+                                                                    const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
+                                                                    uint4 *__restrict__ obs, int64_t n) {
+    static_assert((L == 16 || L == 32 || L == 64) && (G == 1 || G == 2 || G == 4) && (VIEWS == 1 || VIEWS == 2), "");
+    constexpr int per_env = VIEWS * kFrameChunks, SH = G == 4 ? 2 : G == 2 ? 1 : 0;
+    constexpr int GW = 64 / L;  // groups per wavefront
+    const int64_t gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);  // this wavefront, of the grid
+    const int lane = (int)threadIdx.x & (L - 1);
+    int64_t env;
+    int view;
+    if constexpr (GW >= VIEWS) {  // a wavefront holds GW / VIEWS whole envs: one env -> uniform descriptor loads
+        constexpr int E = GW / VIEWS;
+        const int sub = ((int)threadIdx.x & 63) / L;
+        env = gw * E + (E > 1 ? sub / VIEWS : 0), view = sub % VIEWS;
+    } else {  // L = 64, two views: an env is two wavefronts of one workgroup
+        env = gw / VIEWS, view = (int)(gw % VIEWS);
+    }
+    const bool valid = env < n;
+    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
+    if constexpr (GW < VIEWS) __syncthreads();  // both wavefronts of the env have read its record
+    if (valid && view == 0 && lane == 0) drawn[env] = pn;
+    const Frame f = unpack_frame(pn), g = unpack_frame(po);
+    const bool blank_n = f.sl == 255, blank_o = g.sl == 255;
+    if (!valid || (blank_n && blank_o)) return;  // (two blank frames are equal)
+    uint4 *__restrict__ out = obs + env * per_env;
+    const int q_view = view * kFrameChunks;
+    if (blank_n != blank_o) {  // the whole frame
+        for (int c = lane; c < kFrameChunks; c += L) out[q_view + c] = raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0);
+        return;
+    }
+    if ((f.sl != g.sl || f.sr != g.sr) && ink_row1 > ink_row0) {  // the score band's ink rows
+        const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
+        for (int c = lane; c < cn; c += L) out[c0 + c] = raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
+    }
+
+    DeltaRect r[6];
+    const bool moved = f.x != g.x || f.y != g.y;
+    r[0] = delta_ball(view, f, moved), r[1] = delta_ball(view, g, moved);
+    delta_bat(r + 2, view, g.bl, f.bl, kBatLc0, kBatLc1);
+    delta_bat(r + 4, view, g.br, f.br, kBatRc0, kBatRc1);
+    int nb[6], end[6], S = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) nb[i] = delta_blocks<SH>(r[i]), S += r[i].nr * nb[i] * G, end[i] = S;
+    for (int s = lane; s < S; s += L) {
+        int k = 0;  // the rectangle slot s falls into, and its index there
+#pragma unroll
+        for (int i = 0; i < 5; i++) k += s >= end[i];
+        DeltaRect rc = r[0];
+        int t = s, nbk = nb[0];
+#pragma unroll
+        for (int i = 1; i < 6; i++)
+            if (k == i) rc = r[i], t = s - end[i - 1], nbk = nb[i];
+        const int j = t & (G - 1), u = t >> SH;                             // chunk of the block; (row, block) of the rectangle
+        const int dr = nbk == 2 ? u >> 1 : u, b = nbk == 2 ? u & 1 : 0;  // (a rectangle's row touches one or two blocks)
+        const int q_row = q_view + (rc.r0 + dr) * kRowChunks;
+        const int blk = ((q_row + rc.o0) >> SH) + b;
+        if (blk > ((q_row + rc.o1) >> SH)) continue;
+        if (k == 1 && dr + rc.r0 >= r[0].r0 && dr + rc.r0 < r[0].r0 + r[0].nr && blk >= ((q_row + r[0].o0) >> SH) &&
+            blk <= ((q_row + r[0].o1) >> SH))
+            continue;  // the new ball's rectangle stores this block
+        const int q = (blk << SH) + j;
+        out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
+    }
+}
+
+#ifdef CRL_ABLATION  // superseded mapping (one lane per env, one wavefront per (view, object) of 64 envs): profiling build only, CRL_RAW_DELTA_LANES=1
+__device__ __forceinline__ void delta_store(uint4 *__restrict__ out, const Frame &f, const DeltaRect &r, int view, const uint4 *__restrict__ atlas_rgb,
+                                            int ink_row0, int ink_row1) {
+    for (int row = r.r0; row < r.r0 + r.nr; row++)
+        for (int o = r.o0; o <= r.o1; o++) {
+            const int q = view * kFrameChunks + row * kRowChunks + o;
             out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
         }
 }
 
-// the rows of the symmetric difference of [a, a + h) and [b, b + h): [lo, lo + k) and [hi + h - k, hi + h), k = min(|a - b|, h)
-__device__ __forceinline__ void delta_bat(uint4 *__restrict__ out, const Frame &f, int view, int a, int b, int c0, int c1,
-                                          const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
-    if (a == b) return;
-    const int lo = min(a, b), hi = max(a, b), k = min(hi - lo, CRL_PONG_BAT_H);
-    delta_rect(out, f, view, lo, lo + k, c0, c1, atlas_rgb, ink_row0, ink_row1);
-    delta_rect(out, f, view, hi + CRL_PONG_BAT_H - k, hi + CRL_PONG_BAT_H, c0, c1, atlas_rgb, ink_row0, ink_row1);
-}
-
-__device__ __forceinline__ void delta_ball(uint4 *__restrict__ out, const Frame &f, const Frame &g, int view,
-                                           const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
-    const int b0 = max(3 * g.x, 0), b1 = min(3 * (g.x + CRL_PONG_BALL), kRowBytes);  // bytes of the row the ball covers
-    if (b0 < b1) delta_rect(out, f, view, g.y, g.y + CRL_PONG_BALL, b0 / 16, (b1 - 1) / 16, atlas_rgb, ink_row0, ink_row1);
-}
-
 template <int VIEWS>
-__global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
-                                                                             const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
-                                                                             uint4 *__restrict__ obs, int64_t n) {
+__global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_lanes_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
+                                                                                   const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
+                                                                                   uint4 *__restrict__ obs, int64_t n) {
     constexpr int per_env = VIEWS * kFrameChunks;
     const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
     const int view = wave / 3, obj = wave - 3 * view;  // obj: 0 ball, 1 left bat, 2 right bat
@@ -244,28 +340,68 @@ __global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_kernel(c
 
     // per-lane part: this env's object in this view
     uint4 *__restrict__ out = obs + env * per_env;
+    DeltaRect r[2];
     if (obj == 0) {
-        if (f.x != g.x || f.y != g.y) {
-            delta_ball(out, f, g, view, atlas_rgb, ink_row0, ink_row1);
-            delta_ball(out, f, f, view, atlas_rgb, ink_row0, ink_row1);
-        }
+        const bool moved = f.x != g.x || f.y != g.y;
+        r[0] = delta_ball(view, g, moved), r[1] = delta_ball(view, f, moved);
     } else if (obj == 1) {
-        delta_bat(out, f, view, g.bl, f.bl, kBatLc0, kBatLc1, atlas_rgb, ink_row0, ink_row1);
+        delta_bat(r, view, g.bl, f.bl, kBatLc0, kBatLc1);
     } else {
-        delta_bat(out, f, view, g.br, f.br, kBatRc0, kBatRc1, atlas_rgb, ink_row0, ink_row1);
+        delta_bat(r, view, g.br, f.br, kBatRc0, kBatRc1);
     }
+    delta_store(out, f, r[0], view, atlas_rgb, ink_row0, ink_row1);
+    delta_store(out, f, r[1], view, atlas_rgb, ink_row0, ink_row1);
 }
+#endif  // CRL_ABLATION
+
+static constexpr int kDeltaL = 32, kDeltaG = 4;  // production: lanes per (env, view); chunks per block (4: whole 64-byte memory requests)
 
 void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
                                   uint8_t *obs, int views, hipStream_t st) {
     if (n <= 0 || (views != 1 && views != 2)) return;
-    const unsigned blocks = (unsigned)((n + 63) / 64);
     const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
     uint4 *ob = reinterpret_cast<uint4 *>(obs);
-    if (views == 2)
-        hipLaunchKernelGGL((pong_raster_raw_delta_kernel<2>), dim3(blocks), dim3(384), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
-    else
-        hipLaunchKernelGGL((pong_raster_raw_delta_kernel<1>), dim3(blocks), dim3(192), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
+#define CRL_LAUNCH_DELTA(V, L, G)                                                                                                       \
+    hipLaunchKernelGGL((pong_raster_raw_delta_kernel<V, L, G>), dim3((unsigned)((n * V * L + 255) / 256)), dim3(256), 0, st, frames, drawn, at, \
+                       ink_row0, ink_row1, ob, n)
+#ifdef CRL_ABLATION
+    // (profiling build only: CRL_RAW_DELTA_L / CRL_RAW_DELTA_G select the lanes per (env, view) and the chunks per block that lost the
+    // measurement, CRL_RAW_DELTA_LANES=1 the superseded lane-per-env mapping)
+    static const int abl_lanes = getenv("CRL_RAW_DELTA_LANES") ? atoi(getenv("CRL_RAW_DELTA_LANES")) : 0;
+    static const int abl_l = getenv("CRL_RAW_DELTA_L") ? atoi(getenv("CRL_RAW_DELTA_L")) : kDeltaL;
+    static const int abl_g = getenv("CRL_RAW_DELTA_G") ? atoi(getenv("CRL_RAW_DELTA_G")) : kDeltaG;
+    if (abl_lanes) {
+        const unsigned blocks = (unsigned)((n + 63) / 64);
+        if (views == 2)
+            hipLaunchKernelGGL((pong_raster_raw_delta_lanes_kernel<2>), dim3(blocks), dim3(384), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
+        else
+            hipLaunchKernelGGL((pong_raster_raw_delta_lanes_kernel<1>), dim3(blocks), dim3(192), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
+        return;
+    }
+    if (abl_l != kDeltaL || abl_g != kDeltaG) {
+        const int g = (uintptr_t)obs % (16 * abl_g) ? 1 : abl_g;
+#define CRL_DELTA_CASE(L, G)                \
+    if (abl_l == L && g == G) {             \
+        if (views == 2) CRL_LAUNCH_DELTA(2, L, G); \
+        else CRL_LAUNCH_DELTA(1, L, G);     \
+        return;                             \
+    }
+        CRL_DELTA_CASE(16, 1) CRL_DELTA_CASE(16, 2) CRL_DELTA_CASE(16, 4) CRL_DELTA_CASE(32, 1) CRL_DELTA_CASE(32, 2) CRL_DELTA_CASE(32, 4)
+        CRL_DELTA_CASE(64, 1) CRL_DELTA_CASE(64, 2) CRL_DELTA_CASE(64, 4)
+#undef CRL_DELTA_CASE
+        return;  // (no such variant: nothing is drawn, which the tests see)
+    }
+#endif
+    // a block is a whole sector only in a buffer aligned to it; crl_draw_raw_delta admits any 16-byte-aligned one: single chunks there
+    const bool blocks_ok = (uintptr_t)obs % (16 * kDeltaG) == 0;
+    if (views == 2) {
+        if (blocks_ok) CRL_LAUNCH_DELTA(2, kDeltaL, kDeltaG);
+        else CRL_LAUNCH_DELTA(2, kDeltaL, 1);
+    } else {
+        if (blocks_ok) CRL_LAUNCH_DELTA(1, kDeltaL, kDeltaG);
+        else CRL_LAUNCH_DELTA(1, kDeltaL, 1);
+    }
+#undef CRL_LAUNCH_DELTA
 }
 
 void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
