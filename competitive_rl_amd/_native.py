@@ -25,6 +25,9 @@ CRL_LEDGER_DOMAIN_OPPONENT = 0x4C475557
 CRL_LEDGER_COUNTERS = 6  # rows of the counters tensor, in this order (enum crl_ledger_counter)
 CRL_LEDGER_COUNTER_NAMES = ("episodes", "wins", "losses", "draws", "return_sum", "length_sum")
 CRL_LEDGER_PFSP_HARD, CRL_LEDGER_PFSP_VARIANCE = 0, 1
+CRL_ARENA_DOMAIN_PAIR = 0x4C475550
+CRL_ARENA_COUNTERS = 6  # planes of the counters tensor, in this order (enum crl_arena_counter); each plane is [left][right]
+CRL_ARENA_COUNTER_NAMES = ("episodes", "left_wins", "right_wins", "draws", "return_sum", "length_sum")
 
 FRAME_DT = np.dtype([("ball_x", "<i2"), ("ball_y", "<i2"), ("bat_l_y", "u1"), ("bat_r_y", "u1"),
                      ("score_l", "u1"), ("score_r", "u1")])
@@ -145,6 +148,20 @@ SIGNATURES = {
     "crl_ledger_get_env_state": (i32, [vp, vp, vp, vp, vp]),
     "crl_ledger_set_env_state": (i32, [vp, vp, vp, vp, vp]),
     "crl_ledger_step": (i32, [vp, vp, vp, i64, vp, i32, vp, vp]),
+    "crl_arena_create": (i32, [i32, i64, i64, u64, i32, P(vp)]),
+    "crl_arena_destroy": (None, [vp]),
+    "crl_arena_seed": (i32, [vp, u64, vp]),
+    "crl_arena_reset": (i32, [vp, vp]),
+    "crl_arena_set_agents": (i32, [vp, i32, vp]),
+    "crl_arena_set_weights": (i32, [vp, vp, i32, vp]),
+    "crl_arena_get_weights": (i32, [vp, vp, vp]),
+    "crl_arena_balance_weights": (i32, [vp, vp, i32, u32, vp]),
+    "crl_arena_get_counters": (i32, [vp, vp, vp, vp]),
+    "crl_arena_set_counters": (i32, [vp, vp, vp, vp]),
+    "crl_arena_get_env_state": (i32, [vp, vp, vp, vp, vp]),
+    "crl_arena_set_env_state": (i32, [vp, vp, vp, vp, vp]),
+    "crl_arena_draw": (i32, [vp, vp, vp, vp]),
+    "crl_arena_step": (i32, [vp, vp, vp, i64, vp, i32, vp, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

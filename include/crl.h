@@ -584,6 +584,82 @@ int crl_ledger_set_env_state(crl_ledger *l, const int32_t *ret_dev, const int32_
 int crl_ledger_step(crl_ledger *l, const int32_t *assign_dev, const float *reward_dev, int64_t reward_stride, const uint8_t *done_dev,
                     int32_t redraw, int32_t *ids_out_dev, void *stream);
 
+/* ---- arena: every agent of a pool against every other, both seats served, pair results on the device ---
+ * Stands in for evaluate_two_policies_in_batch (pong/evaluate.py:6-88) called once for every pair of a pool: the reference plays
+ * ONE pair of policies per call and the host walks every step.  Here one batch holds the whole round-robin: env i plays the pair
+ * (pairs[2i], pairs[2i+1]) = (left agent, right agent), both indices into a pool of up to CRL_LEAGUE_MAX_AGENTS agents.  Serving the
+ * two bats is a crl_league of 2N virtual envs (virtual env 2i + seat; its int32 [2N] assignment IS the array of pairs); the arena
+ * is an object beside it, as crl_ledger is: crl_arena_* never reaches into a league, the caller passes the pairs in and takes the
+ * next pairs out.  All work is ordered on the caller's stream; no call synchronises with the host.
+ *
+ * State.  Per env: ret int32 (sum of the LEFT agent's step rewards in the running episode), len int32 (its steps), draw_ctr uint32.
+ * Per cell (CRL_LEAGUE_MAX_AGENTS^2 cells, cell = left * 16 + right): CRL_ARENA_COUNTERS int64 counters, laid out [counter][cell]
+ * in the order of enum crl_arena_counter; one int64 `ignored`.  A weight table uint32 w[16][16] (after create: 1 for every
+ * off-diagonal cell of the pool, 0 elsewhere).
+ *
+ * Arena books -- crl_arena_step, one launch with one lane per env:
+ *   1. ret += (int)reward[i * reward_stride]; len += 1  (the left agent's reward: column 0 of the env's reward buffer, stride 2);
+ *   2. where done[i] != 0 the episode goes to cell (pairs[2i], pairs[2i+1]), the pair that PLAYED it: episodes += 1, one of
+ *      left_wins (ret > 0) / right_wins (ret < 0) / draws (ret == 0) += 1, return_sum += ret, length_sum += len; then ret = len = 0.
+ *      If either id is outside [0, agents) nothing is booked to a cell and `ignored` is counted.  All sums are 64-bit integers, so
+ *      the totals do not depend on the order in which wavefronts arrive;
+ *   3. pairs_out[2i], pairs_out[2i+1] = the pair played, replaced by an arena draw where done[i] != 0 and redraw != 0
+ *      (draw_ctr[i] += 1 there).  pairs_out may be pairs itself.  A table that sums to 0 keeps the pair and leaves the counter alone.
+ *
+ * Arena draws (tests restate this in numpy; beside "league draws" above, same generator and key):
+ *   x = word 0 of Philox4x32-10(counter = (gid & 0xFFFFFFFF, gid >> 32, n, CRL_ARENA_DOMAIN_PAIR), key = seed),
+ *   gid = env_id_base + i, the REAL env's global id (not a virtual env's), n = draw_ctr[i];
+ *   T = sum of all 256 weights, 0 < T < 2^32;  r = (uint64(x) * T) >> 32  -- an integer in [0, T);
+ *   the drawn cell is the smallest row-major index c = left * 16 + right whose cumulative weight w[0] + ... + w[c] exceeds r (the
+ *   kernel walks the 16 row sums and then the row: the same cell in 32 steps).  A cell of weight 0 is never drawn.
+ * A draw depends on (seed, global env id, counter, table) alone: shards that hold the same table draw what the whole batch would.
+ *
+ * Balance weights (one workgroup, one lane per cell; integers only, numpy reproduces them exactly): over the SCHEDULED cells -- left
+ * and right in the pool, left != right unless include_mirror -- e = EPISODES[cell], m = the largest e;
+ *   w[cell] = floor + min(m - e, 65535) for a scheduled cell, 0 for every other.
+ * Pairs played less are drawn more; with floor >= 1 every scheduled pair stays reachable.  The call refuses a floor with which
+ * agents^2 * (floor + 65535) reaches 2^32. */
+#define CRL_ARENA_DOMAIN_PAIR 0x4C475550u /* "LGUP" */
+#define CRL_ARENA_COUNTERS 6
+enum crl_arena_counter { CRL_ARENA_EPISODES = 0, CRL_ARENA_LEFT_WINS = 1, CRL_ARENA_RIGHT_WINS = 2, CRL_ARENA_DRAWS = 3,
+                         CRL_ARENA_RETURN_SUM = 4, CRL_ARENA_LENGTH_SUM = 5 };
+typedef struct crl_arena crl_arena;
+/* The books of evaluate_two_policies_in_batch (pong/evaluate.py:6-88) for every pair of a pool at once: num_envs envs whose global
+ * ids start at env_id_base, a pool of `agents` (1..CRL_LEAGUE_MAX_AGENTS) agents. */
+int crl_arena_create(int32_t device, int64_t num_envs, int64_t env_id_base, uint64_t seed, int32_t agents, crl_arena **out);
+void crl_arena_destroy(crl_arena *a);
+/* New key for the draws, every draw_ctr back to 0 (results and weights stay). */
+int crl_arena_seed(crl_arena *a, uint64_t seed, void *stream);
+/* Zeroes the counters, `ignored` and every env's ret / len (weights, key and draw counters stay). */
+int crl_arena_reset(crl_arena *a, void *stream);
+/* The pool grew or shrank: cells that enter it get weight 1 off the diagonal and 0 on it, cells that leave it weight 0. */
+int crl_arena_set_agents(crl_arena *a, int32_t agents, void *stream);
+/* w_host: uint32 [agents][agents] on the HOST, count == agents * agents (read before the call returns; the table changes in stream
+ * order).  Refuses T == 0 and T >= 2^32. */
+int crl_arena_set_weights(crl_arena *a, const uint32_t *w_host, int32_t count, void *stream);
+/* w_out_dev: uint32 [CRL_LEAGUE_MAX_AGENTS][CRL_LEAGUE_MAX_AGENTS] on the device. */
+int crl_arena_get_weights(crl_arena *a, uint32_t *w_out_dev, void *stream);
+/* Fills the table by the balance rule above from counters_dev (int64 [CRL_ARENA_COUNTERS][256] on the device, e.g. counters
+ * all-reduced over the shards so that every rank holds the same table), or from the arena's own counters when counters_dev is NULL:
+ * the schedule that evens out the episodes per pair which evaluate.py:6-88 gets by being called once per pair. */
+int crl_arena_balance_weights(crl_arena *a, const int64_t *counters_dev, int32_t include_mirror, uint32_t floor, void *stream);
+/* Counters as int64 [CRL_ARENA_COUNTERS][256] and `ignored` as int64 [1] (optional), device memory: the per-pair totals that
+ * evaluate.py:6-88 returns for its one pair. */
+int crl_arena_get_counters(crl_arena *a, int64_t *counters_out_dev, int64_t *ignored_out_dev, void *stream);
+int crl_arena_set_counters(crl_arena *a, const int64_t *counters_dev, const int64_t *ignored_dev, void *stream);
+/* Checkpoints / tests: the per-env values, each [N] on the device, each optional. */
+int crl_arena_get_env_state(crl_arena *a, int32_t *ret_out_dev, int32_t *len_out_dev, uint32_t *draw_ctr_out_dev, void *stream);
+int crl_arena_set_env_state(crl_arena *a, const int32_t *ret_dev, const int32_t *len_dev, const uint32_t *draw_ctr_dev, void *stream);
+/* A fresh arena draw for EVERY env (draw_ctr += 1 each): pairs_out_dev int32 [2N], which may be pairs_dev; a table that sums to 0
+ * hands pairs_dev through.  The choice of the pair to play that a caller of evaluate.py:6-88 makes on the host. */
+int crl_arena_draw(crl_arena *a, const int32_t *pairs_dev, int32_t *pairs_out_dev, void *stream);
+/* The per-step call described above ("arena books"): the episode accounting of evaluate.py:6-88's loop for every pair at once.
+ * pairs_dev int32 [2N] (the pairs that played this step); reward_dev float32, env i at reward_dev[i * reward_stride] (the env's
+ * reward buffer, column 0: stride 2 for cPongDouble); done_dev uint8 [N]; pairs_out_dev int32 [2N] (for
+ * crl_league_set_assignment of the 2N-virtual-env league). */
+int crl_arena_step(crl_arena *a, const int32_t *pairs_dev, const float *reward_dev, int64_t reward_stride, const uint8_t *done_dev,
+                   int32_t redraw, int32_t *pairs_out_dev, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
