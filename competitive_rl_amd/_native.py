@@ -20,7 +20,7 @@ ATLAS_BYTES = 22 * 22 * 34 * 160
 
 CRL_LEAGUE_MAX_AGENTS = 16
 CRL_LEAGUE_RANDOM, CRL_LEAGUE_RULE_BASED, CRL_LEAGUE_LIGHT = 0, 1, 2
-CRL_LEAGUE_DOMAIN_OPPONENT, CRL_LEAGUE_DOMAIN_ACTION = 0x4C47554F, 0x4C475541
+CRL_LEAGUE_DOMAIN_OPPONENT, CRL_LEAGUE_DOMAIN_ACTION, CRL_LEAGUE_DOMAIN_SAMPLE = 0x4C47554F, 0x4C475541, 0x4C475553
 CRL_LEDGER_DOMAIN_OPPONENT = 0x4C475557
 CRL_LEDGER_COUNTERS = 6  # rows of the counters tensor, in this order (enum crl_ledger_counter)
 CRL_LEDGER_COUNTER_NAMES = ("episodes", "wins", "losses", "draws", "return_sum", "length_sum")
@@ -72,6 +72,7 @@ class CrlStackDesc(C.Structure):
 
 
 vp, i64, u64, i32, u32, f64, cstr, P = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_uint32, C.c_double, C.c_char_p, C.POINTER
+f32 = C.c_float
 # every symbol include/crl.h declares -> (restype, argtypes); load() applies it, tests check the library exports all of them
 SIGNATURES = {
     "crl_create": (i32, [P(CrlOpts), vp, P(vp)]),
@@ -105,6 +106,7 @@ SIGNATURES = {
     "crl_policy_act": (i32, [vp, vp, i64, vp, i64, vp, vp]),
     "crl_policy_get_stack": (i32, [vp, vp, vp]),
     "crl_policy_set_stack": (i32, [vp, vp, vp]),
+    "crl_policy_set_sampling": (i32, [vp, f32, f32, u64, i64]),
     "crl_terminal_observation_dev": (i32, [vp, vp, i64, vp, vp]),
     "crl_check": (i32, [vp, vp]),
     "crl_car_info": (i32, [vp, P(vp), P(vp)]),
@@ -126,6 +128,8 @@ SIGNATURES = {
     "crl_league_destroy": (None, [vp]),
     "crl_league_add_builtin": (i32, [vp, i32]),
     "crl_league_add_light": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "crl_sampling_set_agent": (i32, [vp, i32, f32, f32]),
+    "crl_sampling_get_agent": (i32, [vp, i32, P(f32), P(f32)]),
     "crl_league_seed": (i32, [vp, u64, vp]),
     "crl_league_set_assignment": (i32, [vp, vp, i32, vp]),
     "crl_league_get_assignment": (i32, [vp, vp, vp]),

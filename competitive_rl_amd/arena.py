@@ -9,7 +9,8 @@ each env holds a pair, the whole round-robin runs side by side, and the env's ne
   ``i`` out of the env's ``(N, 2, K, 42, 42)`` observation buffer and writes ``actions[i, seat]``; its int32 ``[2N]`` assignment is the
   array of (left, right) pairs.  The launches are the league's own (one partition, one fill, one list launch per CNN agent for both
   seats together).  That league is created with ``env_id_base = 2 * (the env's)``, so RANDOM's action stream is keyed by
-  ``2 * gid + seat`` (``league_draw_reference(seed, 2 * gid + seat, step, CRL_LEAGUE_DOMAIN_ACTION, 3)``);
+  ``2 * gid + seat`` (``league_draw_reference(seed, 2 * gid + seat, step, CRL_LEAGUE_DOMAIN_ACTION, 3)``), and so is the stream of
+  the agents' sampled and explored actions (``set_sampling``; ``league_sample_reference(seed, 2 * gid + seat, step, ...)``);
 * the books and the pair draws are ``crl_arena_*`` (csrc/pong_arena.hip), an object beside the league as ``crl_ledger`` is:
   ``ArenaBooks`` below is its thin binding (device tensors in, device tensors out), ``LeagueArena`` ties it to an env and a league;
 * nothing synchronises with the host unless the caller asks for host values (``counters()``, ``payoff()``, ``weights()``,
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .league import _BUILTIN_KINDS, _light_weights, league_draw_reference
+from .league import _BUILTIN_KINDS, _get_sampling, _light_weights, _set_sampling, check_sampling, league_draw_reference
 from .policy_serving import _KEYS, BUILTIN_CHECKPOINTS, load_light_weights
 from .tournament import get_builtin_agent_names
 
@@ -213,7 +214,8 @@ class LeagueArena:
     and uint8 observations (``make_envs("cPongDouble-v0", ..., resized_dim=42, frame_stack=None)``).  ``agent_names``: any of RANDOM,
     RULE_BASED, WEAK, MEDIUM (default: all four); ``add_agent`` adds LightActorCritic weight sets of the caller's own.
     ``env_id_base``: the global id of env 0 (default: the env's); the pair draws are keyed by that REAL id, the league that serves the
-    bats is created with twice it, so RANDOM's action stream is keyed by ``2 * gid + seat``.  ``include_mirror``: schedule an agent
+    bats is created with twice it, so RANDOM's action stream and the sample stream of ``set_sampling`` are keyed by ``2 * gid + seat``.
+    ``include_mirror``: schedule an agent
     against itself too.  After construction env with global id g holds the (g mod cells)-th scheduled pair in row-major order;
     ``draw_pairs()`` replaces that by arena draws."""
 
@@ -280,11 +282,24 @@ class LeagueArena:
         self.agent_names.append(name)
         self._kinds.append(kind)
 
-    def add_agent(self, name, weights_or_checkpoint):
+    def add_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0):
         """A LightActorCritic agent of one's own -- a checkpoint path, a dict of the six arrays in torch layout or a light ``Policy``
-        (a trainer's snapshot).  Its cells enter the draw table with weight 1; the pairs in force stay.  Full-size networks are refused."""
+        (a trainer's snapshot).  Its cells enter the draw table with weight 1; the pairs in force stay.  Full-size networks are refused.
+        ``temperature`` / ``epsilon``: its play style (``set_sampling``); the default is greedy."""
+        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
         self._add(name, N.CRL_LEAGUE_LIGHT, _light_weights(name, weights_or_checkpoint))
+        if temperature or epsilon:
+            self.set_sampling(name, temperature, epsilon)
         self.books.set_agents(len(self.agent_names))
+
+    def set_sampling(self, agent, temperature=1.0, epsilon=0.0):
+        """The play style of ``agent`` (a name or an index) in either seat, from the next step on (``LeagueEnvWrapper.set_sampling``):
+        temperature 0 plays the argmax, T > 0 samples from softmax(logits / T); epsilon is the share of uniform actions."""
+        _set_sampling(self, agent, temperature, epsilon)
+
+    def sampling(self):
+        """Host dict ``name -> (temperature, epsilon)`` of the whole pool (no GPU work)."""
+        return _get_sampling(self)
 
     def get_agent_names(self):
         return self.agent_names
@@ -418,7 +433,7 @@ class LeagueArena:
         N.check(self._L.crl_league_reset(self._h, self._stream()))
 
     def seed(self, s):
-        """Seeds the env and re-keys RANDOM's actions and the pair draws (all draw counters start over)."""
+        """Seeds the env and re-keys RANDOM's actions, the sampled and explored actions and the pair draws (all draw counters start over)."""
         self._seed = int(s or 0) & (2 ** 64 - 1)
         self.env.seed(s)
         N.check(self._L.crl_league_seed(self._h, self._seed, self._stream()))
@@ -426,12 +441,15 @@ class LeagueArena:
 
     def state_dict(self):
         """The arena's own state as host arrays (synchronises): the books, the pairs, both seats' frame rings and the observation
-        buffer the next step acts on.  The env's state is the env's (``env.state_dict()``).  RANDOM's action counter is the league's
-        and starts over with ``load_state_dict``: a pool with RANDOM continues with other RANDOM actions than the original run."""
+        buffer the next step acts on, and the pool's play styles (``sampling``: [temperature, epsilon] rows in pool order).  The env's
+        state is the env's (``env.state_dict()``).  RANDOM's action counter is the league's -- it is the counter of the sampled and
+        explored actions too -- and starts over with ``load_state_dict``: a pool with RANDOM, or with an agent that samples or explores,
+        continues with other such actions than the original run."""
         stack = torch.empty((2 * self.num_envs, 4, 42, 42), dtype=torch.uint8, device=self.device)
         N.check(self._L.crl_league_get_stack(self._h, _p(stack), self._stream()))
         return {"agent_names": list(self.agent_names), "books": self.books.state_dict(), "pairs": self._pairs.cpu().numpy(),
-                "stack": stack.cpu().numpy(), "obs": None if self._buf is None else self._buf.cpu().numpy(), "redraw_on_done": self.redraw_on_done}
+                "stack": stack.cpu().numpy(), "obs": None if self._buf is None else self._buf.cpu().numpy(), "redraw_on_done": self.redraw_on_done,
+                "sampling": np.array([self.sampling()[n] for n in self.agent_names], np.float32).reshape(-1, 2)}
 
     def load_state_dict(self, sd):
         if list(sd["agent_names"]) != self.agent_names:
@@ -449,8 +467,18 @@ class LeagueArena:
             raise ValueError(f"load_state_dict: an observation buffer of shape {tuple(np.shape(obs))} into an env of {self.env._obs_shape}")
         if not np.asarray(books["weights"]).any() and self.books.weights().any():
             raise ValueError("load_state_dict: an all-zero weight table cannot be set (crl_arena_set_weights refuses a sum of 0)")
+        styles = None  # (a state dict from before the play styles leaves them as they are)
+        if sd.get("sampling") is not None:
+            styles = np.asarray(sd["sampling"], np.float32)
+            if styles.shape != (len(self.agent_names), 2):
+                raise ValueError(f"load_state_dict: sampling must hold a (temperature, epsilon) row per agent, got shape {styles.shape}")
+            for t, e in styles:
+                check_sampling(t, e)
         self._seed = int(books["seed"])
         N.check(self._L.crl_league_seed(self._h, self._seed, self._stream()))
+        if styles is not None:
+            for a, (t, e) in enumerate(styles):
+                self.set_sampling(a, float(t), float(e))
         self.books.load_state_dict(books)
         self.set_pairs(p[:, 0], p[:, 1])
         stack = torch.from_numpy(np.ascontiguousarray(stack, np.uint8)).to(self.device)

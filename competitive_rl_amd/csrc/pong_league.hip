@@ -6,8 +6,8 @@
 // (builtin_policies.py:51-58), RULE_BASED the cheat code (:44-48), WEAK / MEDIUM a LightActorCritic on the last four frames
 // (:61-91, utils/policy_serving.py:46-66).  Here one batch holds the whole population.
 //
-// A step is: one fill launch (one lane per env: RANDOM's Philox action, 999 for RULE_BASED, and the frame push of every env that
-// no network visits) and one list launch of pong_policy_mfma_kernel per CNN agent of the pool (weights differ per launch; an agent
+// A step is: one fill launch (one lane per env: RANDOM's Philox action, 999 for RULE_BASED -- or its explore draw, include/crl.h
+// "sampled actions" --, and the frame push of every env that no network visits) and one list launch of pong_policy_mfma_kernel per CNN agent of the pool (weights differ per launch; an agent
 // without envs costs an empty persistent launch).  The lists come from the partition kernel, which runs when the assignment
 // changed.  ONE ring of the last four opponent-view frames per env serves every CNN agent and is pushed every step whichever agent
 // is assigned (one `head` for all envs), so an env that changes hands is judged on the frames it really showed.  Exactly one
@@ -21,6 +21,7 @@
 #include "pong_device.h"
 #include "pong_league.h"
 #include "pong_policy_full.h"
+#include "pong_sample.h"
 
 namespace crl {
 
@@ -36,6 +37,10 @@ __device__ inline uint32_t league_draw(uint64_t seed, uint64_t gid, uint32_t n, 
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     return (uint32_t)(((uint64_t)c[0] * m) >> 32);
 }
+
+struct LeagueExplore {
+    uint32_t eps_q[kMaxAgents];  // RULE_BASED agents: the explore threshold of "sampled actions" (0: always the cheat code); 0 for every other kind
+};
 
 struct LeagueLists {
     int32_t *list[kMaxAgents];  // CNN agents: env indices of the agent (order free); nullptr for RANDOM / RULE_BASED
@@ -69,12 +74,12 @@ __global__ __launch_bounds__(kLThreads) void league_partition_kernel(LeagueLists
 }
 
 // One lane per env.  RANDOM: action = league_draw(.., step, ACTION domain, 3); RULE_BASED (and an id outside the pool): 999, resolved by
-// the step kernel.  Then the wavefront pushes the newest frame of each of its envs that no list launch visits into ring plane `head`
+// the step kernel -- unless the agent explores (E.eps_q) and this step's sample draw says so.  Then the wavefront pushes the newest frame of each of its envs that no list launch visits into ring plane `head`
 // (441 dwords per env, 64 lanes side by side; frames are 4-byte aligned like crl_policy_act's).
 __global__ __launch_bounds__(kLThreads) void league_fill_kernel(const int32_t *__restrict__ kinds, int agents, const int32_t *__restrict__ assign,
                                                                uint8_t *__restrict__ ring, int head, const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                int32_t *__restrict__ actions, int64_t action_stride, uint64_t seed, int64_t env_id_base,
-                                                               uint32_t step, int64_t n) {
+                                                               uint32_t step, int64_t n, LeagueExplore E) {
     const int64_t i = (int64_t)blockIdx.x * kLThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
     bool mine = false;
@@ -83,7 +88,16 @@ __global__ __launch_bounds__(kLThreads) void league_fill_kernel(const int32_t *_
         const int kind = (a >= 0 && a < agents) ? kinds[a] : CRL_LEAGUE_RULE_BASED;
         mine = kind != CRL_LEAGUE_LIGHT;
         if (kind == CRL_LEAGUE_RANDOM) actions[i * action_stride] = (int32_t)league_draw(seed, (uint64_t)(env_id_base + i), step, CRL_LEAGUE_DOMAIN_ACTION, 3u);
-        else if (mine) actions[i * action_stride] = CRL_PONG_CHEAT;
+        else if (mine) {
+            int act = CRL_PONG_CHEAT;
+            const uint32_t eps_q = (a >= 0 && a < agents) ? E.eps_q[a] : 0u;
+            if (eps_q) {
+                uint32_t x0;
+                const int explored = sample_explore(seed, (uint64_t)(env_id_base + i), step, eps_q, x0);
+                if (explored >= 0) act = explored;
+            }
+            actions[i * action_stride] = act;
+        }
     }
     unsigned long long m = __ballot(mine);
     const int64_t w0 = i - lane;
@@ -120,6 +134,8 @@ struct crl_league {
     int agents = 0;
     int kind[kMaxAgents] = {};
     float *raw[kMaxAgents] = {};  // CNN agents: the checkpoint tensors (pong_league.h kLightRawFloats)
+    float temperature[kMaxAgents] = {}, epsilon[kMaxAgents] = {};  // crl_sampling_set_agent, as given
+    SampleArgs sample[kMaxAgents] = {};                            // ... and as the launches take it (inv_t, eps_q)
     LeagueLists T{};
     uint8_t *ring = nullptr;
     int32_t *assign = nullptr;
@@ -215,6 +231,24 @@ int crl_league_add_light(crl_league *l, const float *conv1_w, const float *conv1
     return league_add(l, CRL_LEAGUE_LIGHT, raw.data());
 }
 
+int crl_sampling_set_agent(crl_league *l, int32_t agent, float temperature, float epsilon) {
+    crl_fail_no_ctx();
+    SampleArgs S{};
+    if (int rc = sample_args_from(temperature, epsilon, "crl_sampling_set_agent", &S)) return rc;
+    if (!l) return crl_fail(CRL_EINVAL, "crl_sampling_set_agent: null league");
+    if (agent < 0 || agent >= l->agents) return crl_fail(CRL_EINVAL, "crl_sampling_set_agent: agent %d is not in the pool of %d", agent, l->agents);
+    l->temperature[agent] = temperature, l->epsilon[agent] = epsilon, l->sample[agent] = S;
+    return CRL_OK;
+}
+
+int crl_sampling_get_agent(crl_league *l, int32_t agent, float *temperature, float *epsilon) {
+    crl_fail_no_ctx();
+    if (!l || !temperature || !epsilon) return crl_fail(CRL_EINVAL, "crl_sampling_get_agent: null argument");
+    if (agent < 0 || agent >= l->agents) return crl_fail(CRL_EINVAL, "crl_sampling_get_agent: agent %d is not in the pool of %d", agent, l->agents);
+    *temperature = l->temperature[agent], *epsilon = l->epsilon[agent];
+    return CRL_OK;
+}
+
 int crl_league_seed(crl_league *l, uint64_t seed, void *stream) {
     crl_fail_no_ctx();
     if (!l) return crl_fail(CRL_EINVAL, "crl_league_seed: null league");
@@ -271,13 +305,20 @@ int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride
     if (l->agents <= 0) return crl_fail(CRL_ESTATE, "crl_league_act: the pool is empty");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(l->ctrl, 0, kMaxAgents * sizeof(unsigned), st));  // the tickets
+    LeagueExplore E{};
+    for (int a = 0; a < l->agents; a++)
+        if (l->kind[a] == CRL_LEAGUE_RULE_BASED) E.eps_q[a] = l->sample[a].eps_q;
     hipLaunchKernelGGL(league_fill_kernel, dim3((unsigned)((l->n + kLThreads - 1) / kLThreads)), dim3(kLThreads), 0, st, league_kinds(l), l->agents,
-                       l->assign, l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, l->seed, l->env_id_base, l->step, l->n);
+                       l->assign, l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, l->seed, l->env_id_base, l->step, l->n, E);
     HIP_TRY(hipGetLastError());
     for (int a = 0; a < l->agents; a++)
-        if (l->kind[a] == CRL_LEAGUE_LIGHT)
+        if (l->kind[a] == CRL_LEAGUE_LIGHT) {
+            SampleArgs S = l->sample[a];  // an agent at (0, 0) -- every agent, until crl_sampling_set_agent -- keeps the greedy launch
+            const bool sampled = S.inv_t != 0.f || S.eps_q != 0;
+            S.seed = l->seed, S.id_base = l->env_id_base, S.n = l->step;
             HIP_TRY(policy_light_act_list(l->raw[a], l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, l->T.list[a],
-                                          league_counts(l) + a, l->n, l->cus, l->ctrl + a, st));
+                                          league_counts(l) + a, l->n, l->cus, l->ctrl + a, sampled ? &S : nullptr, st));
+        }
     l->head = (l->head + 1) & 3;
     l->step++;
     return CRL_OK;

@@ -28,6 +28,7 @@
 #include "crl_internal.h"
 #include "pong_league.h"
 #include "pong_policy_full.h"
+#include "pong_sample.h"
 
 namespace crl {
 
@@ -147,12 +148,13 @@ __device__ inline void group_write_back(const uint8_t *shbuf, uint8_t *__restric
 // (1) and (3) and the patch gather of (2) keep the FMA pipes idle; the two workgroups of a CU drift apart, so
 // one's idle phases run under the other's convolutions.  Tables that do not depend on the group (actor weights,
 // biases) are staged once.
-template <int DBG>  // 0 production, 1 ablation switches (CRL_POLICY_DEBUG bits 1, 2), 2 production code + phase cycle counters (4)
+// SAMPLE: the action epilogue follows include/crl.h "sampled actions" (sample_action) instead of the plain argmax.
+template <int DBG, bool SAMPLE = false>  // DBG: 0 production, 1 ablation switches (CRL_POLICY_DEBUG bits 1, 2), 2 production code + phase cycle counters (4)
 __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(PolicyWeights W, uint8_t *__restrict__ ring, int head,
                                                                            const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                            int32_t *__restrict__ actions, int64_t action_stride,
                                                                            float *__restrict__ logits_out, int64_t n, int dbg_arg, int phase_sleeps,
-                                                                           unsigned *__restrict__ ticket) {
+                                                                           unsigned *__restrict__ ticket, SampleArgs S) {
     const int dbg = DBG == 1 ? dbg_arg : 0;  // CRL_POLICY_DEBUG (profiling only): 1 skip the convolutions, 2 skip the patch gather
     const bool timed = DBG != 0 && (dbg_arg & 4) && n >= 8192;  // the counters go into logits_out (needs n * 12 >= 66 560 bytes)
     __shared__ __attribute__((aligned(16))) uint8_t sh_in[kEnvsPerWg][CRL_POLICY_STACK][kPlanePad];
@@ -347,6 +349,7 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
             float bv = a0;
             if (a1 > bv) best = 1, bv = a1;
             if (a2 > bv) best = 2;
+            if constexpr (SAMPLE) best = sample_action(S, env0 + tid, a0, a1, a2, best);
             actions[(env0 + tid) * action_stride] = best;
             if (logits_out) {
                 float *lo = logits_out + (env0 + tid) * 3;
@@ -480,12 +483,15 @@ __device__ inline uint32_t pk_bf16(float a, float b) {
 // re-draw, so the grid is sized by an upper bound and a launch with an empty list ends at once); every ring, frame, action and logit
 // address goes through the list.  An env's logits are reduced in a shape of their own (finish_group), so its action does not depend
 // on which group or slot it sits in.  LIST = false is the launch of crl_policy_act.
-template <bool BF, bool LIST>
+// SAMPLE: the lane that writes an env's action draws it by include/crl.h "sampled actions" (sample_action, one Philox call) instead of
+// keeping the argmax.  A template parameter, not a branch on a kernel argument: the greedy instantiations are then the code they were
+// (same registers, same LDS, same schedule around the matrix instructions), whatever the compiler makes of the sampling epilogue.
+template <bool BF, bool LIST, bool SAMPLE>
 __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWeightsM W, uint8_t *__restrict__ ring, int head,
                                                                   const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                   int32_t *__restrict__ actions, int64_t action_stride,
                                                                   float *__restrict__ logits_out, int64_t n_arg, unsigned *__restrict__ ticket, int dbg_arg,
-                                                                  const int32_t *__restrict__ env_list, const unsigned *__restrict__ count_dev) {
+                                                                  const int32_t *__restrict__ env_list, const unsigned *__restrict__ count_dev, SampleArgs S) {
     const int64_t n = LIST ? (int64_t)*count_dev : n_arg;
     const int dbg = CRL_ABL(dbg_arg);  // timing ablations / phase stamps: profiling build only
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -596,6 +602,7 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                 if (a1 > bv) best = 1, bv = a1;
                 if (a2 > bv) best = 2;
                 const int64_t env = group_env<LIST>(ixg, e0, pe);
+                if constexpr (SAMPLE) best = sample_action(S, env, a0, a1, a2, best);
                 actions[env * action_stride] = best;
                 if (logits_out) {
                     float *lo = logits_out + env * 3;
@@ -808,18 +815,24 @@ __global__ void pong_policy_copy_stack_kernel(uint8_t *__restrict__ ring, uint8_
 
 // ---- what the league (pong_league.hip) shares with the policies: the list launch of the kernel above and the ring <-> stack copy
 hipError_t policy_light_list_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+    return e;
 }
 
 hipError_t policy_light_act_list(const float *raw, uint8_t *ring, int head, const uint8_t *frame, int64_t frame_stride, int32_t *actions,
                                  int64_t action_stride, float *logits, const int32_t *env_list, const unsigned *count_dev, int64_t max_envs, int cus,
-                                 unsigned *ticket, hipStream_t st) {
+                                 unsigned *ticket, const SampleArgs *sample, hipStream_t st) {
     PolicyWeightsM W;
     W.w1 = raw, W.b1 = raw + 1024, W.w2 = raw + 1040, W.b2 = raw + 2064, W.wa = raw + 2080, W.ba = raw + 6880;
     const int64_t groups = (max_envs + kME - 1) / kME;  // an upper bound: the kernel reads the count itself
     const unsigned grid = (unsigned)(groups < cus ? groups : cus);
-    hipLaunchKernelGGL((pong_policy_mfma_kernel<true, true>), dim3(grid), dim3(kMThreads), kMLds, st, W, ring, head, frame, frame_stride, actions,
-                       action_stride, logits, (int64_t)0, ticket, 0, env_list, count_dev);
+    if (sample)
+        hipLaunchKernelGGL((pong_policy_mfma_kernel<true, true, true>), dim3(grid), dim3(kMThreads), kMLds, st, W, ring, head, frame, frame_stride, actions,
+                           action_stride, logits, (int64_t)0, ticket, 0, env_list, count_dev, *sample);
+    else
+        hipLaunchKernelGGL((pong_policy_mfma_kernel<true, true, false>), dim3(grid), dim3(kMThreads), kMLds, st, W, ring, head, frame, frame_stride, actions,
+                           action_stride, logits, (int64_t)0, ticket, 0, env_list, count_dev, SampleArgs{});
     return hipGetLastError();
 }
 
@@ -845,6 +858,8 @@ struct crl_policy {
     float *raw = nullptr;        // the checkpoint tensors in torch layout (MFMA kernel): w1 1024 | b1 16 | w2 1024 | b2 16 | wa 4800 | ba 3
     PolicyWeightsM WM{};
     PolicyFull *full = nullptr;  // crl_policy_create_full: ActorCritic instead of LightActorCritic (pong_policy_full.hip)
+    bool sampling = false;       // crl_policy_set_sampling with a temperature or an epsilon that is not 0: the SAMPLE kernels
+    SampleArgs S{};              // S.n: crl_policy_act calls since create / crl_policy_set_sampling
 };
 
 extern "C" {
@@ -886,8 +901,9 @@ int crl_policy_create(int32_t device, int64_t num_envs, const float *conv1_w, co
         memcpy(raw.data() + 2064, conv2_b, 16 * 4), memcpy(raw.data() + 2080, actor_w, 4800 * 4), memcpy(raw.data() + 6880, actor_b, 3 * 4);
         e = hipMalloc(&p->raw, raw.size() * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(p->raw, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
         if (e != hipSuccess) {
             crl_policy_destroy(p);
             return crl_fail(CRL_EHIP, "crl_policy_create (mfma weights): %s", hipGetErrorString(e));
@@ -947,8 +963,11 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
     if (frame_stride < kPlane || (frame_stride & 3) || ((uintptr_t)frame_dev & 3) || action_stride < 1)
         return crl_fail(CRL_EINVAL, "crl_policy_act: frame_stride must be a multiple of 4 and >= 1764, frames 4-byte aligned");
     hipStream_t main_st = (hipStream_t)stream;
+    const SampleArgs S = p->S;  // this call's counter; the next call's is one further, whichever kernel serves it
+    p->S.n++;
     if (p->full) {
-        HIP_TRY(policy_full_act(p->full, p->ring, p->head, p->n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, main_st));
+        HIP_TRY(policy_full_act(p->full, p->ring, p->head, p->n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev,
+                                p->sampling ? &S : nullptr, main_st));
         p->head = (p->head + 1) & 3;
         return CRL_OK;
     }
@@ -964,12 +983,16 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
         const unsigned mgrid = (unsigned)(mgroups < p->cus ? mgroups : p->cus);  // persistent: one workgroup per CU
 #ifdef CRL_ABLATION
         if (use_mfma != 3)
-            hipLaunchKernelGGL((pong_policy_mfma_kernel<false, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
-                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr);
+            hipLaunchKernelGGL((pong_policy_mfma_kernel<false, false, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
+                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr, S);
         else
 #endif
-            hipLaunchKernelGGL((pong_policy_mfma_kernel<true, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
-                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr);
+        if (p->sampling)
+            hipLaunchKernelGGL((pong_policy_mfma_kernel<true, false, true>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
+                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr, S);
+        else
+            hipLaunchKernelGGL((pong_policy_mfma_kernel<true, false, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
+                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr, S);
         HIP_TRY(hipGetLastError());
         p->head = (p->head + 1) & 3;
         return CRL_OK;
@@ -981,19 +1004,33 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
     const unsigned grid = (unsigned)(groups < per_cu * p->cus ? groups : per_cu * p->cus);  // persistent: two workgroups per CU
     if (dbg == 4)
         hipLaunchKernelGGL(pong_policy_light_kernel<2>, dim3(grid), dim3(kPolicyThreads), 0, (hipStream_t)stream, p->W, p->ring, p->head,
-                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, dbg, phase, p->ticket);
+                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, dbg, phase, p->ticket, S);
     else if (dbg)
         hipLaunchKernelGGL(pong_policy_light_kernel<1>, dim3(grid), dim3(kPolicyThreads), 0, (hipStream_t)stream, p->W, p->ring, p->head,
-                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, dbg, phase, p->ticket);
+                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, dbg, phase, p->ticket, S);
+    else if (p->sampling)
+        hipLaunchKernelGGL((pong_policy_light_kernel<0, true>), dim3(grid), dim3(kPolicyThreads), 0, (hipStream_t)stream, p->W, p->ring, p->head,
+                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, 0, phase, p->ticket, S);
     else
         hipLaunchKernelGGL(pong_policy_light_kernel<0>, dim3(grid), dim3(kPolicyThreads), 0, (hipStream_t)stream, p->W, p->ring, p->head,
-                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, 0, phase, p->ticket);
+                           frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, 0, phase, p->ticket, S);
     HIP_TRY(hipGetLastError());
     p->head = (p->head + 1) & 3;
     return CRL_OK;
 #else
     return crl_fail(CRL_ESTATE, "crl_policy_act: no kernel selected");
 #endif
+}
+
+int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base) {
+    crl_fail_no_ctx();
+    SampleArgs S{};
+    if (int rc = sample_args_from(temperature, epsilon, "crl_policy_set_sampling", &S)) return rc;
+    if (!p || env_id_base < 0) return crl_fail(CRL_EINVAL, "crl_policy_set_sampling: null policy or a negative env_id_base");
+    S.seed = seed, S.id_base = env_id_base, S.n = 0;
+    p->S = S;
+    p->sampling = S.inv_t != 0.f || S.eps_q != 0;
+    return CRL_OK;
 }
 
 static int copy_stack(crl_policy *p, uint8_t *ext, int to_ring, void *stream) {

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "crl_internal.h"
+#include "pong_sample.h"
 
 namespace crl {
 
@@ -255,10 +256,13 @@ __global__ __launch_bounds__(256, 4) void policy_full_conv3_kernel(const float *
     }
 }
 
-// actor_linear + argmax (first maximum, like torch.argmax / numpy): one wavefront per env, a fixed-shape butterfly sum
+// actor_linear + argmax (first maximum, like torch.argmax / numpy): one wavefront per env, a fixed-shape butterfly sum.
+// SAMPLE: lane 0 draws the action by include/crl.h "sampled actions" instead (a template parameter, as in pong_policy.hip: the
+// greedy kernel is the code it was); S.id_base is the global id of this launch's env 0.
+template <bool SAMPLE>
 __global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__restrict__ feat, const float *__restrict__ wa,
                                                                 const float *__restrict__ ba, int32_t *__restrict__ actions,
-                                                                int64_t action_stride, float *__restrict__ logits, int64_t n) {
+                                                                int64_t action_stride, float *__restrict__ logits, int64_t n, SampleArgs S) {
     const int lane = threadIdx.x & 63;
     const int64_t env = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (env >= n) return;
@@ -276,6 +280,7 @@ __global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__r
         int a = 0;
         if (s[1] > s[0]) a = 1;
         if (s[2] > fmaxf(s[0], s[1])) a = 2;
+        if constexpr (SAMPLE) a = sample_action(S, env, s[0], s[1], s[2], a);
         actions[env * action_stride] = a;
         if (logits) logits[env * 3] = s[0], logits[env * 3 + 1] = s[1], logits[env * 3 + 2] = s[2];
     }
@@ -316,7 +321,7 @@ void policy_full_destroy(PolicyFull *f) {
 }
 
 hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
-                           int32_t *actions_dev, int64_t action_stride, float *logits_dev, hipStream_t st) {
+                           int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, hipStream_t st) {
     for (int64_t e0 = 0; e0 < n; e0 += f->chunk) {
         const int64_t c = std::min<int64_t>(f->chunk, n - e0);
         hipLaunchKernelGGL(policy_full_front_kernel, dim3((unsigned)std::min<int64_t>(c, (int64_t)f->cus * 2)), dim3(256), 0, st,
@@ -324,8 +329,15 @@ hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, co
                            f->w + kOffW2, f->w + kOffB2, f->act2, c);
         hipLaunchKernelGGL(policy_full_conv3_kernel, dim3((unsigned)((c + kGM - 1) / kGM), kC3 / kGN), dim3(256), 0, st, f->act2,
                            f->w + kOffW3, f->w + kOffB3, f->feat, c);
-        hipLaunchKernelGGL(policy_full_actor_kernel, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
-                           actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c);
+        if (sample) {
+            SampleArgs S = *sample;
+            S.id_base += e0;
+            hipLaunchKernelGGL(policy_full_actor_kernel<true>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
+                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, S);
+        } else {
+            hipLaunchKernelGGL(policy_full_actor_kernel<false>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
+                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, SampleArgs{});
+        }
     }
     return hipGetLastError();
 }

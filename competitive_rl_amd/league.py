@@ -7,6 +7,12 @@ int32 ``assignment`` per env on the device (index into ``agent_names``) and serv
 
 * pool: any of RANDOM, RULE_BASED, WEAK, MEDIUM, plus LightActorCritic weight sets of the caller's own (``add_agent``); the full-size
   ActorCritic is not served inside the league (use ``TournamentEnvWrapper.add_agent`` for a whole batch against one);
+* every pool entry carries a play style, ``(temperature, epsilon)`` (``set_sampling`` / ``sampling``; default (0, 0) = greedy, today's
+  behaviour): a CNN agent at temperature T samples from the softmax of logits / T as the reference's
+  ``Policy.compute_action(obs, deterministic=False)`` does at T = 1 (utils/policy_serving.py:48-56), any agent but RANDOM plays a
+  uniform action on a share epsilon of its steps.  The draw is made by the lane that writes the action, in the kernels' epilogues
+  (include/crl.h "sampled actions", restated by ``league_sample_reference`` below); the same trained snapshot can sit in a pool
+  twice, as the stochastic policy its trainer improves and as its greedy version;
 * ``set_opponents`` / ``reset_opponent(name)`` assign, ``reset_opponent()`` draws one opponent per env, ``resample_on_done=True``
   re-draws the opponent of every env whose episode ended, inside the step -- all without a host synchronisation;
 * every draw is Philox4x32-10 keyed by (seed, GLOBAL env id) with a per-env counter (include/crl.h "league draws"), so the result does
@@ -125,14 +131,26 @@ class LeagueEnvWrapper:
         self.agent_names.append(name)
         self._kinds.append(kind)
 
-    def add_agent(self, name, weights_or_checkpoint):
+    def add_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0):
         """Beyond the reference: a LightActorCritic opponent of one's own -- a checkpoint path (``.npz`` or a reference checkpoint), a
-        dict of the six arrays in torch layout, or a light ``Policy``.  Future draws include it; the assignment in force stays."""
+        dict of the six arrays in torch layout, or a light ``Policy``.  Future draws include it; the assignment in force stays.
+        ``temperature`` / ``epsilon``: its play style (``set_sampling``); the default is greedy."""
         if getattr(self.env, "R", 42) != 42:
             raise ValueError("LightActorCritic opponents act on 42x42 frames: make the env with resized_dim=42")
+        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
         self._add(name, N.CRL_LEAGUE_LIGHT, _light_weights(name, weights_or_checkpoint))
+        if temperature or epsilon:
+            self.set_sampling(name, temperature, epsilon)
         if self.ledger is not None:
             self.ledger.set_agents(len(self.agent_names))
+
+    def set_sampling(self, agent, temperature=1.0, epsilon=0.0):
+        """The play style of ``agent`` (a name or an index) from the next step on: see ``_set_sampling``."""
+        _set_sampling(self, agent, temperature, epsilon)
+
+    def sampling(self):
+        """Host dict ``name -> (temperature, epsilon)`` of the whole pool (no GPU work)."""
+        return _get_sampling(self)
 
     def get_agent_names(self):
         return self.agent_names
@@ -283,7 +301,8 @@ class LeagueEnvWrapper:
         return views[0]
 
     def seed(self, s):
-        """Seeds the wrapped env and re-keys the league's draws and its ledger's (all draw counters start over)."""
+        """Seeds the wrapped env and re-keys the league's draws (sampled and explored actions included) and its ledger's (all draw
+        counters start over)."""
         self.env.seed(s)
         N.check(self._L.crl_league_seed(self._h, int(s or 0) & (2 ** 64 - 1), self._stream()))
         if self.ledger is not None:
@@ -307,10 +326,52 @@ class LeagueEnvWrapper:
             pass
 
 
-def league_draw_reference(seed, gid, counter, domain, m):
-    """The league's draw rule in numpy (include/crl.h "league draws"): Philox4x32-10 word 0 of counter (gid lo, gid hi, counter,
-    domain) under key (seed lo, seed hi), scaled to [0, m) by a multiply-high.  Arrays broadcast; returns int64.  Host code for
-    tests and for callers that want to predict an assignment; the kernels do not use it."""
+def check_sampling(temperature, epsilon):
+    """What ``crl_sampling_set_agent`` / ``crl_policy_set_sampling`` accept, as float32 values: a finite temperature >= 0 (whose
+    reciprocal is a float32) and an epsilon in [0, 1]."""
+    with np.errstate(over="ignore", divide="ignore"):
+        t, e = np.float32(temperature), np.float32(epsilon)
+        if not (np.isfinite(t) and t >= 0) or (t > 0 and not np.isfinite(np.float32(1) / t)):
+            raise ValueError(f"temperature must be finite and >= 0 (and 1 / temperature a float32), not {temperature}")
+    if not 0 <= e <= 1:
+        raise ValueError(f"epsilon must lie in [0, 1], not {epsilon}")
+    return float(t), float(e)
+
+
+def _agent_index(self, agent):
+    if isinstance(agent, str):
+        if agent not in self.agent_names:
+            raise ValueError(f"{agent} is not in the pool {self.agent_names}")
+        return self.agent_names.index(agent)
+    if not 0 <= int(agent) < len(self.agent_names):
+        raise ValueError(f"agent {agent} is not in the pool of {len(self.agent_names)}")
+    return int(agent)
+
+
+def _set_sampling(self, agent, temperature, epsilon):
+    """``LeagueEnvWrapper.set_sampling`` / ``LeagueArena.set_sampling``: ``temperature`` 0 plays the argmax, T > 0 samples from
+    softmax(logits / T); ``epsilon``: the share of steps with a uniform action instead (RULE_BASED: instead of the cheat code).  Neither
+    has an effect on RANDOM, the temperature none on RULE_BASED.  Host values that travel with the next launches: no synchronisation."""
+    t, e = check_sampling(temperature, epsilon)
+    N.check(self._L.crl_sampling_set_agent(self._h, _agent_index(self, agent), t, e))
+
+
+def _get_sampling(self):
+    out = {}
+    for a, name in enumerate(self.agent_names):
+        t, e = C.c_float(), C.c_float()
+        N.check(self._L.crl_sampling_get_agent(self._h, a, C.byref(t), C.byref(e)))
+        out[name] = (t.value, e.value)
+    return out
+
+
+def sample_eps_q(epsilon):
+    """The explore threshold of "sampled actions": min(floor(epsilon * 2^32), 0xFFFFFFFF), in double from the float32 epsilon."""
+    return min(int(np.floor(float(np.float32(epsilon)) * 4294967296.0)), 0xFFFFFFFF)
+
+
+def _philox4x32_10(gid, counter, domain, seed):
+    """The four result words (uint64 arrays holding 32 bits) of counter (gid lo, gid hi, counter, domain) under key (seed lo, seed hi)."""
     gid = np.asarray(gid, np.uint64)
     counter = np.asarray(counter, np.uint64)
     shape = np.broadcast(gid, counter).shape
@@ -322,4 +383,45 @@ def league_draw_reference(seed, gid, counter, domain, m):
         p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
         c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
         k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c
+
+
+def league_sample_reference(seed, gid, n, logits, temperature, epsilon):
+    """The rule of include/crl.h "sampled actions" in numpy: one Philox4x32-10 call with counter (gid lo, gid hi, n,
+    CRL_LEAGUE_DOMAIN_SAMPLE) under the seed gives x0, x1, x2; if x1 < eps_q the action is (x2 * 3) >> 32 (explored); otherwise the
+    first-index argmax for ``temperature`` 0; otherwise the inverse-CDF draw of softmax(logits * inv_t) at r = (x0 >> 8) * 2^-24, with
+    inv_t = float32(1 / temperature) as the kernels receive it -- computed HERE in float64, so ``margin`` says how far r lay from the
+    nearer boundary: min(|r - e0 / S|, |r - (e0 + e1) / S|), inf for greedy and explored draws.  A kernel's float32 ``exp`` may decide a
+    draw of tiny margin the other way.  ``gid``, ``n`` broadcast against ``logits[..., 3]``; ``temperature`` / ``epsilon`` are scalars.
+    Returns (action int64, explored bool, margin float64).  Host code for tests and for callers that want to predict a draw; the
+    kernels do not use it."""
+    t, _ = check_sampling(temperature, epsilon)
+    lg = np.asarray(logits, np.float64)
+    if lg.shape[-1] != 3:
+        raise ValueError("logits[..., 3]")
+    shape = np.broadcast(np.asarray(gid), np.asarray(n), lg[..., 0]).shape
+    x = _philox4x32_10(np.broadcast_to(np.asarray(gid, np.uint64), shape), np.broadcast_to(np.asarray(n, np.uint64), shape),
+                       N.CRL_LEAGUE_DOMAIN_SAMPLE, seed)
+    lg = np.broadcast_to(lg, shape + (3,))
+    explored = x[1] < np.uint64(sample_eps_q(epsilon))
+    action = ((x[2] * np.uint64(3)) >> np.uint64(32)).astype(np.int64)
+    margin = np.full(shape, np.inf)
+    greedy = np.argmax(lg, axis=-1).astype(np.int64)  # (first index on ties)
+    if t == 0:
+        return np.where(explored, action, greedy), explored, margin
+    z = lg * np.float64(np.float32(1) / np.float32(t))
+    e = np.exp(z - z.max(axis=-1, keepdims=True))
+    s = e.sum(axis=-1)
+    b0, b1 = e[..., 0] / s, (e[..., 0] + e[..., 1]) / s
+    r = (x[0] >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+    sampled = np.where(r < b0, 0, np.where(r < b1, 1, 2)).astype(np.int64)
+    margin = np.where(explored, np.inf, np.minimum(np.abs(r - b0), np.abs(r - b1)))
+    return np.where(explored, action, sampled), explored, margin
+
+
+def league_draw_reference(seed, gid, counter, domain, m):
+    """The league's draw rule in numpy (include/crl.h "league draws"): Philox4x32-10 word 0 of counter (gid lo, gid hi, counter,
+    domain) under key (seed lo, seed hi), scaled to [0, m) by a multiply-high.  Arrays broadcast; returns int64.  Host code for
+    tests and for callers that want to predict an assignment; the kernels do not use it."""
+    c = _philox4x32_10(gid, counter, domain, seed)
     return ((c[0] * np.uint64(m)) >> np.uint64(32)).astype(np.int64)

@@ -2,7 +2,7 @@
 utils/network.py:73-93, pong/builtin_policies.py:61-91).
 
 ``Policy`` has the reference's constructor and call protocol.  The forward pass -- the policy's own
-four-frame stack, the network, argmax -- is hand-written HIP behind the C ABI (``crl_policy_*`` in
+four-frame stack, the network, argmax (or, after ``set_sampling``, a draw from the softmax made in the kernel's epilogue) -- is hand-written HIP behind the C ABI (``crl_policy_*`` in
 include/crl.h); there is no torch model and no CPU path in this module.
 
 ``use_light_model=True``: LightActorCritic (WEAK, MEDIUM; one fused kernel).  ``use_light_model=False``: the
@@ -149,7 +149,7 @@ class Policy:
         return obs
 
     def act_device(self, obs, out=None, want_logits=False):
-        """Push ``obs`` (N, 1, 42, 42) onto the stack and write the greedy actions (int32) into ``out``
+        """Push ``obs`` (N, 1, 42, 42) onto the stack and write the actions (int32; greedy unless ``set_sampling`` said otherwise) into ``out``
         (any int32 device view with one element per env, e.g. ``actions[:, 1]`` of an (N, 2) tensor;
         default: an internal (N,) tensor).  No host synchronisation."""
         f = self._frames(obs)
@@ -163,6 +163,17 @@ class Policy:
     def logits(self):
         """Logits of the last ``act_device(..., want_logits=True)`` call, float32 (N, 3)."""
         return self._logits
+
+    def set_sampling(self, temperature=1.0, epsilon=0.0, seed=0, env_id_base=0):
+        """From the next ``act_device`` / ``__call__`` on the actions are drawn on the device, in the kernel's epilogue, by the rule of
+        include/crl.h "sampled actions" (``league.league_sample_reference``): temperature 0 plays the argmax, T > 0 samples from
+        softmax(logits / T) -- the reference's ``compute_action(obs, deterministic=False)`` at T = 1 --, ``epsilon`` is the share of
+        uniform actions.  ``seed`` keys the draws, env i draws as global id ``env_id_base + i``, and the call counter starts over.
+        ``set_sampling(0, 0)`` is greedy again; ``compute_action`` keeps its own (host-side) sampling."""
+        from .league import check_sampling
+
+        t, e = check_sampling(temperature, epsilon)
+        N.check(self._L.crl_policy_set_sampling(self._h, t, e, int(seed) & (2 ** 64 - 1), int(env_id_base)))
 
     def get_stack(self):
         out = torch.empty((self.num_envs, 4, 42, 42), dtype=torch.uint8, device=self.device)

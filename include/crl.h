@@ -452,6 +452,11 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
 /* The stack as the model sees it: u8 [N, 4, 42, 42], oldest plane first (tests, checkpoints). */
 int crl_policy_get_stack(crl_policy *p, uint8_t *stack_out_dev, void *stream);
 int crl_policy_set_stack(crl_policy *p, const uint8_t *stack_in_dev, void *stream);
+/* Policy.compute_action(obs, deterministic=False) (policy_serving.py:48-56) for crl_policy_act, light and full: from now on the action
+ * of env i is drawn by "sampled actions" (below, beside "league draws") with gid = env_id_base + i, key `seed` and n = the number of
+ * crl_policy_act calls since THIS call (the counter starts over).  temperature 0 and epsilon 0 is the argmax again; a policy that
+ * never had this called plays the argmax.  Refuses (CRL_EINVAL, before any GPU call) what crl_sampling_set_agent refuses. */
+int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base);
 
 /* ---- league: per-env opponents of cPongTournament-v0 on the device --------------------------
  * Stands in for what a POPULATION of the reference's workers does together: each worker's TournamentEnvWrapper draws an opponent
@@ -474,10 +479,27 @@ int crl_policy_set_stack(crl_policy *p, const uint8_t *stack_in_dev, void *strea
  *                      since crl_league_create / crl_league_seed (a per-env counter; 0 for the first draw);
  *   RANDOM's action:   domain = CRL_LEAGUE_DOMAIN_ACTION, m = 3, n = the number of crl_league_act calls since create / seed
  *                      (0 for the first call; drawn only for envs assigned to RANDOM, the counter moves for all).
- * RANDOM is therefore another stream than the reference's np.random. */
+ * RANDOM is therefore another stream than the reference's np.random.
+ *
+ * Sampled actions (tests restate this in numpy: league_sample_reference; same generator, key and gid as "league draws").  Every agent
+ * of a pool, and every crl_policy, carries a play style: temperature (float32, >= 0; 0 = greedy, the default) and epsilon (in
+ * [0, 1], default 0).  Policy.compute_action(obs, deterministic=False) (utils/policy_serving.py:48-56) samples from
+ * Categorical(logits); here the lane that writes env i's action draws it in the kernel's epilogue, nothing touches the host.  At act
+ * call n (the counter of RANDOM's action: crl_league_act / crl_policy_act calls since create / seed, 0 for the first) ONE Philox call
+ * with counter (gid lo, gid hi, n, CRL_LEAGUE_DOMAIN_SAMPLE) gives the words x0, x1, x2:
+ *   1. explore:  eps_q = min(floor(epsilon * 2^32), 0xFFFFFFFF), computed on the host in double from the float32 epsilon.  If
+ *                x1 < eps_q the action is (uint64(x2) * 3) >> 32.  RULE_BASED plays the cheat code when it does not explore; epsilon
+ *                (and temperature) have no effect on RANDOM, temperature has none on RULE_BASED.
+ *   2. greedy:   otherwise, with temperature == 0: the argmax of the logits, first index on ties.
+ *   3. sample:   otherwise, in float32 with one rounding per operation: z_a = l_a * inv_t (inv_t = float32 1 / temperature, divided
+ *                once on the host), m = max z, e_a = exp(z_a - m), S = (e0 + e1) + e2, r = float(x0 >> 8) * 2^-24 (exact, in
+ *                [0, 1)); action 0 if r * S < e0, 1 if r * S < e0 + e1, else 2.  (`exp` is the device library's expf; a draw whose r
+ *                lies within its error of a boundary may fall on either side.)
+ * The logits written to logits_dev are the raw l_a whatever the style. */
 #define CRL_LEAGUE_MAX_AGENTS 16
 #define CRL_LEAGUE_DOMAIN_OPPONENT 0x4C47554Fu /* "LGUO" */
 #define CRL_LEAGUE_DOMAIN_ACTION 0x4C475541u   /* "LGUA" */
+#define CRL_LEAGUE_DOMAIN_SAMPLE 0x4C475553u   /* "LGUS" */
 enum crl_league_kind { CRL_LEAGUE_RANDOM = 0, CRL_LEAGUE_RULE_BASED = 1, CRL_LEAGUE_LIGHT = 2 };
 typedef struct crl_league crl_league;
 /* TournamentEnvWrapper.__init__ (competitive_pong_env.py:10-25) for num_envs envs whose global ids start at env_id_base; the pool is
@@ -491,6 +513,12 @@ int crl_league_add_builtin(crl_league *l, int32_t kind);
 int crl_league_add_light(crl_league *l, const float *conv1_w_host /*[16,4,4,4]*/, const float *conv1_b_host /*[16]*/,
                          const float *conv2_w_host /*[16,16,2,2]*/, const float *conv2_b_host /*[16]*/,
                          const float *actor_w_host /*[3,1600]*/, const float *actor_b_host /*[3]*/);
+/* The play style of agent `agent` of the pool ("sampled actions" above), from the next crl_league_act on; host values, no GPU call.
+ * Refuses (CRL_EINVAL) an agent outside the pool, a negative or non-finite temperature (or one so small that 1 / temperature is no
+ * float32) and an epsilon outside [0, 1].  An agent at (0, 0) is served by the launch it always had.  (Named crl_sampling_*: the
+ * crl_league_* surface stays the thirteen entry points it was.) */
+int crl_sampling_set_agent(crl_league *l, int32_t agent, float temperature, float epsilon);
+int crl_sampling_get_agent(crl_league *l, int32_t agent, float *temperature, float *epsilon);
 /* TournamentEnvWrapper.seed's share for the draws (competitive_pong_env.py:50-51): new key, all draw counters back to 0. */
 int crl_league_seed(crl_league *l, uint64_t seed, void *stream);
 /* reset_opponent(agent_name) (competitive_pong_env.py:27-33) per env: ids_dev int32 [N] on the device (each in [0, agents); an id
