@@ -79,6 +79,33 @@ __device__ __forceinline__ Frame pick_frame(const Frame &f0, const Frame &f1, bo
     return f;
 }
 
+// Court rows only (TOP .. BOTTOM-1) of a frame that is not blank: the 16 bytes of source chunk sc of `row`, byte-reversed for the
+// mirrored view.  What raw_chunk() stores there, without its division, its atlas pointer and its load: the delta writer's loops
+// call this one, so that no store of theirs waits for a load.  The ball's 12 bytes are a shifted constant, each bat lies in one
+// chunk column and enters as a constant mask, and since every pixel is achromatic the mirrored chunk is the chunk of the
+// bit-reversed coverage mask.
+static constexpr int kBallBytes = 3 * CRL_PONG_BALL, kBatBytes = 3 * CRL_PONG_BAT_W;
+static constexpr int kBatLChunk = 3 * CRL_PONG_BATL_X / 16, kBatRChunk = 3 * CRL_PONG_BATR_X / 16;
+static constexpr uint32_t kBatLMask = ((1u << kBatBytes) - 1u) << (3 * CRL_PONG_BATL_X - 16 * kBatLChunk);
+static constexpr uint32_t kBatRMask = ((1u << kBatBytes) - 1u) << (3 * CRL_PONG_BATR_X - 16 * kBatRChunk);
+static_assert(kBallBytes <= 16 && kBatLMask <= 0xFFFFu && kBatRMask <= 0xFFFFu, "a bat's bytes lie in one chunk; the ball's fit a chunk's mask");
+
+__device__ __forceinline__ uint32_t nibble_to_bytes_perm(uint32_t nib) {
+    // bit k of nib (< 16) -> byte k = 0xFF: a byte selector of 12 gives 0x00 and one of 13 gives 0xFF (no 32-bit multiply)
+    return __builtin_amdgcn_perm(0u, 0u, (__umul24(nib, 0x00204081u) & 0x01010101u) | 0x0C0C0C0Cu);
+}
+
+__device__ __forceinline__ uint4 court_chunk(const Frame &f, int row, int sc, bool mirror) {
+    // bits [a, a + 12) of the chunk's 16 are the ball's, a clamped to where the mask is empty: the shift stays within 0..28
+    const int a = min(max(3 * f.x - 16 * sc, -kBallBytes), 16);
+    uint32_t m = (unsigned)(row - f.y) < (unsigned)CRL_PONG_BALL ? ((((1u << kBallBytes) - 1u) << 16) >> (16 - a)) & 0xFFFFu : 0u;
+    if (sc == kBatLChunk && (unsigned)(row - f.bl) < (unsigned)CRL_PONG_BAT_H) m |= kBatLMask;
+    if (sc == kBatRChunk && (unsigned)(row - f.br) < (unsigned)CRL_PONG_BAT_H) m |= kBatRMask;
+    if (mirror) m = __brev(m) >> 16;
+    return make_uint4(nibble_to_bytes_perm(m & 15u), nibble_to_bytes_perm((m >> 4) & 15u), nibble_to_bytes_perm((m >> 8) & 15u),
+                      nibble_to_bytes_perm(m >> 12));
+}
+
 #ifdef CRL_ABLATION  // superseded writers (one workgroup per env; workgroup-contiguous): profiling build only, CRL_RAW_SWEEP=0
 __global__ __launch_bounds__(256) void pong_raster_raw_kernel(const uint64_t *__restrict__ frames,
                                                               const uint4 *__restrict__ atlas_rgb, int ink_row0,
@@ -171,21 +198,123 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 //                                                           and new 15-row spans (<= 8 rows for a 4-px move).
 // A pixel of the court is white iff the ball or a bat covers it, so a pixel that changes lies in the symmetric difference of
 // some object's two rectangles; rows outside the court and the ink rows are white in every non-blank frame.
-// Mapping: a group of L lanes owns one (env, view) and strides over that view's dirty slots, so the stores of one instruction
-// go side by side into one frame instead of into 64 frames 201 600 B apart.  The dirty set is a list of six rectangles (new
-// ball, old ball, two row spans per bat) in output-chunk coordinates; slot s of the running sum maps back to (rectangle, row,
-// block, chunk of the block) with the chunk fastest, then the block, then the row.  A slot is one 16-byte chunk of an aligned
-// block of G chunks (production G = 4: a whole 64-byte memory request from four adjacent lanes), all of them built from the NEW
-// descriptor: the chunks of a block that are not dirty are rewritten with the bytes they hold.  Slots of the old ball's rectangle that the
-// new one covers are stored once.  Two lanes may still store the same block (the ball over a bat's column): both write the new
-// frame's bytes, so the race is benign.  Whole frames and score bands (a few envs per step) are strided over by the same lanes.
-// The record is read and then written by the env's own wavefront (behind a barrier where the env's two views are two wavefronts).
+// Mapping: a group of 32 lanes owns one (env, view), so the stores of one instruction go side by side into one frame instead of
+// into 64 frames 201 600 B apart, and walks the objects one after another: the new ball, the old ball, the left bat, the right bat.
+// Within an object a lane's place is fixed by its lane id alone -- the chunk of the block fastest (G = 4 adjacent lanes: a whole
+// aligned 64-byte memory request), then for a ball the block of the row (its 12 bytes touch at most two), then the row -- and the
+// lane only tests whether that place is dirty: row inside the court, block no further than the rectangle's last.  A ball is one
+// store instruction, a bat one per eight rows of the symmetric difference of its two spans (its single chunk column makes one
+// block a row).  With two views the descriptors are wave-uniform, so the rectangles, the trip counts and every branch are scalar
+// code, and the mirrored view differs by o -> 29 - o per lane.  Blocks are counted from the buffer's start: a row starts 0 or 2
+// chunks into a block, so a ball's block can reach two chunks into the neighbouring row, which is a court row too.  Every chunk
+// stored is built from the NEW descriptor by court_chunk(): the chunks of a block that are not dirty are rewritten with the bytes
+// they hold.  Blocks of the old ball's rectangle that the new one covers are stored once.  Two lanes may still store the same
+// block (the ball over a bat's column): both write the new frame's bytes, so the race is benign.  Whole frames and score bands (a
+// few envs per step) are strided over by the same lanes through raw_chunk().  The record is read and then written by the env's
+// own wavefront.  A buffer that is not 64-byte aligned takes G = 1: single chunks, exactly the dirty set.
 // Measured on MI355X at 65 536 envs, two views, the launch inside the bench's event brackets (profiles/r08_raw_summary.txt):
 //   one lane per env, 16-byte chunks (round 7) ........ 164 us   3.5 M memory write requests, 95 % of them 32-byte with a mask
 //   L = 32, G = 1 / G = 2 (whole 32-byte sectors) ..... 168 / 164 us   (the requests neither merge nor get cheaper)
 //   L = 32, G = 4 (whole 64-byte blocks) ..............  97 us   (88.6 against the round-7 mapping's 151 on a second box)
 //   L = 16 / 64, G = 4 ................................ 101 / 108 us on that second box
 // The cost was the partial memory request, not the byte count (G = 4 writes 198 MB against 118.7) and not the lane order.
+// Round 9 (profiles/r09_raw_summary.txt): the mapping above against the one before it (running sums over six rectangles, slot ->
+// rectangle decoded per trip, chunks built by raw_chunk(); CRL_RAW_DELTA_SLOTS=1 in the profiling build), alternating runs on one box:
+//   vector / scalar instructions per wavefront ........ 516 / 295 -> 272 / 148 (SQ counters); no load and no vmcnt wait in the court code
+//   the launch inside the bench's event brackets ....... 96.4 -> 91.3 us; the step 0.1103 -> 0.1051 ms; same requests, same bytes
+// Half the instructions bought a twentieth of the time: the launch is bound by its 3.1 M scattered 64-byte requests, not by issue.
+static constexpr int kDeltaL = 32, kDeltaG = 4;  // lanes per (env, view); chunks per block (4: whole 64-byte memory requests)
+static_assert(kFrameChunks % kDeltaG == 0, "a view starts on a block boundary");
+
+// one court chunk of the view: q counts the view's chunks, q_row is the first chunk of `row`.  WRAP: q may lie up to two chunks
+// into the row above or below (a ball's block); a bat's block never leaves its row.
+template <bool WRAP>
+__device__ __forceinline__ void court_store(uint4 *__restrict__ out, int q_view, const Frame &f, bool mirror, int row, int q_row, int q) {
+    int o = q - q_row;
+    if (WRAP) {
+        const int w = (o >= kRowChunks) - (o < 0);
+        row += w, o -= w * kRowChunks;
+    }
+    *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (uint32_t)((q_view + q) * 16)) = court_chunk(f, row, mirror ? kRowChunks - 1 - o : o, mirror);
+}
+
+// the source chunks [c0, c1] a ball at x covers; ok: some byte of it lies inside the row
+struct BallCols {
+    int c0, c1;
+    bool ok;
+};
+__device__ __forceinline__ BallCols ball_cols(int x) {
+    const int b0 = max(3 * x, 0), b1 = min(3 * x + kBallBytes, kRowBytes);
+    BallCols c;
+    c.ok = b0 < b1, c.c0 = b0 >> 4, c.c1 = (max(b1, 1) - 1) >> 4;
+    return c;
+}
+
+template <int VIEWS, int G>
+__global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
+                                                                    const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
+                                                                    uint4 *__restrict__ obs, int64_t n) {
+    static_assert((G == 1 || G == 4) && (VIEWS == 1 || VIEWS == 2), "");
+    constexpr int L = kDeltaL, per_env = VIEWS * kFrameChunks, SH = G == 4 ? 2 : 0;
+    constexpr int E = 64 / L / VIEWS;  // whole envs per wavefront: one with two views -> uniform descriptor loads
+    const int64_t gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);  // this wavefront, of the grid
+    const int lane = (int)threadIdx.x & (L - 1), sub = ((int)threadIdx.x & 63) / L;
+    const int64_t env = gw * E + (E > 1 ? sub / VIEWS : 0);
+    const int view = sub % VIEWS;
+    const bool valid = env < n;
+    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
+    if (valid && view == 0 && lane == 0) drawn[env] = pn;
+    const Frame f = unpack_frame(pn), g = unpack_frame(po);
+    const bool blank_n = f.sl == 255, blank_o = g.sl == 255;
+    if (!valid || (blank_n && blank_o)) return;  // (two blank frames are equal)
+    uint4 *__restrict__ out = obs + env * per_env;
+    const int q_view = view * kFrameChunks;
+    if (blank_n != blank_o) {  // the whole frame
+        for (int c = lane; c < kFrameChunks; c += L) out[q_view + c] = raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0);
+        return;
+    }
+    if ((f.sl != g.sl || f.sr != g.sr) && ink_row1 > ink_row0) {  // the score band's ink rows
+        const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
+        for (int c = lane; c < cn; c += L) out[c0 + c] = raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
+    }
+
+    const bool mirror = view != 0;  // (court rows are all >= CRL_PONG_MIRROR_ROW)
+    const int j = lane & (G - 1), u = lane >> SH;  // this lane's chunk of a block; its (row, block) place within an object
+    auto in_court = [](int row) { return (unsigned)(row - CRL_PONG_TOP) < (unsigned)(CRL_PONG_BOTTOM - CRL_PONG_TOP); };
+
+    if (f.x != g.x || f.y != g.y) {  // the two balls: place u = (row of the ball, first or second block of the row)
+        const BallCols cn = ball_cols(f.x), co = ball_cols(g.x);
+        const int n0 = mirror ? kRowChunks - 1 - cn.c1 : cn.c0, n1 = mirror ? kRowChunks - 1 - cn.c0 : cn.c1;
+        const int o0 = mirror ? kRowChunks - 1 - co.c1 : co.c0, o1 = mirror ? kRowChunks - 1 - co.c0 : co.c1;
+        const int dr = u >> 1, b = u & 1;
+        if (cn.ok) {
+            const int row = f.y + dr, q_row = row * kRowChunks, blk = ((q_row + n0) >> SH) + b;
+            if (dr < CRL_PONG_BALL && in_court(row) && blk <= ((q_row + n1) >> SH)) court_store<true>(out, q_view, f, mirror, row, q_row, (blk << SH) + j);
+        }
+        if (co.ok) {
+            const int row = g.y + dr, q_row = row * kRowChunks, blk = ((q_row + o0) >> SH) + b;
+            const bool again = cn.ok && (unsigned)(row - f.y) < (unsigned)CRL_PONG_BALL && blk >= ((q_row + n0) >> SH) && blk <= ((q_row + n1) >> SH);
+            if (dr < CRL_PONG_BALL && in_court(row) && blk <= ((q_row + o1) >> SH) && !again)  // (again: the new ball's rectangle stores this block)
+                court_store<true>(out, q_view, f, mirror, row, q_row, (blk << SH) + j);
+        }
+    }
+    // a bat: the rows of the symmetric difference of [a, a + h) and [b, b + h) are [lo, lo + k) and [hi + h - k, hi + h),
+    // k = min(|a - b|, h); place t = one of these 2k rows, its one block
+    auto bat = [&](int a, int b, int sc) {
+        const int lo = min(a, b), hi = max(a, b), k = min(hi - lo, CRL_PONG_BAT_H), up = hi + CRL_PONG_BAT_H - 2 * k;
+        const int o = mirror ? kRowChunks - 1 - sc : sc;
+        int lo_q = lo * kRowChunks, up_q = up * kRowChunks, u_q = u * kRowChunks;  // row * 30 as a sum of products made once ...
+        asm("" : "+v"(u_q));  // ... which the compiler folds back into a quarter-rate 32-bit multiply per trip unless one term is opaque
+        for (int t0 = 0; t0 < 2 * k; t0 += L >> SH) {
+            const int t = t0 + u, row = (t < k ? lo : up) + t, q_row = (t < k ? lo_q : up_q) + t0 * kRowChunks + u_q;
+            if (t < 2 * k && in_court(row)) court_store<false>(out, q_view, f, mirror, row, q_row, ((q_row + o) & ~(G - 1)) + j);
+        }
+    };
+    bat(g.bl, f.bl, kBatLChunk);
+    bat(g.br, f.br, kBatRChunk);
+}
+
+#ifdef CRL_ABLATION  // superseded mapping (running sums over six rectangles, a slot decode per trip; every L and G): profiling build only, CRL_RAW_DELTA_SLOTS=1
 static constexpr int kBatLc0 = 3 * CRL_PONG_BATL_X / 16, kBatLc1 = (3 * (CRL_PONG_BATL_X + CRL_PONG_BAT_W) - 1) / 16;
 static constexpr int kBatRc0 = 3 * CRL_PONG_BATR_X / 16, kBatRc1 = (3 * (CRL_PONG_BATR_X + CRL_PONG_BAT_W) - 1) / 16;
 
@@ -227,7 +356,7 @@ __device__ __forceinline__ int delta_blocks(const DeltaRect &r) {
 }
 
 template <int VIEWS, int L, int G>
-__global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
+__global__ __launch_bounds__(256) void pong_raster_raw_delta_slots_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
                                                                     const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
                                                                     uint4 *__restrict__ obs, int64_t n) {
     static_assert((L == 16 || L == 32 || L == 64) && (G == 1 || G == 2 || G == 4) && (VIEWS == 1 || VIEWS == 2), "");
@@ -292,6 +421,8 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
     }
 }
 
+#endif  // CRL_ABLATION
+
 #ifdef CRL_ABLATION  // superseded mapping (one lane per env, one wavefront per (view, object) of 64 envs): profiling build only, CRL_RAW_DELTA_LANES=1
 __device__ __forceinline__ void delta_store(uint4 *__restrict__ out, const Frame &f, const DeltaRect &r, int view, const uint4 *__restrict__ atlas_rgb,
                                             int ink_row0, int ink_row1) {
@@ -354,22 +485,20 @@ __global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_lanes_ke
 }
 #endif  // CRL_ABLATION
 
-static constexpr int kDeltaL = 32, kDeltaG = 4;  // production: lanes per (env, view); chunks per block (4: whole 64-byte memory requests)
-
 void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
                                   uint8_t *obs, int views, hipStream_t st) {
     if (n <= 0 || (views != 1 && views != 2)) return;
     const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
     uint4 *ob = reinterpret_cast<uint4 *>(obs);
-#define CRL_LAUNCH_DELTA(V, L, G)                                                                                                       \
-    hipLaunchKernelGGL((pong_raster_raw_delta_kernel<V, L, G>), dim3((unsigned)((n * V * L + 255) / 256)), dim3(256), 0, st, frames, drawn, at, \
-                       ink_row0, ink_row1, ob, n)
+#define CRL_LAUNCH_DELTA(KERNEL, V, L)                                                                                                     \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)((n * V * L + 255) / 256)), dim3(256), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n)
 #ifdef CRL_ABLATION
-    // (profiling build only: CRL_RAW_DELTA_L / CRL_RAW_DELTA_G select the lanes per (env, view) and the chunks per block that lost the
-    // measurement, CRL_RAW_DELTA_LANES=1 the superseded lane-per-env mapping)
+    // (profiling build only: CRL_RAW_DELTA_SLOTS=1 selects the superseded running-sum mapping, CRL_RAW_DELTA_L / CRL_RAW_DELTA_G
+    // its lanes per (env, view) and its chunks per block; CRL_RAW_DELTA_LANES=1 the lane-per-env mapping before it)
     static const int abl_lanes = getenv("CRL_RAW_DELTA_LANES") ? atoi(getenv("CRL_RAW_DELTA_LANES")) : 0;
     static const int abl_l = getenv("CRL_RAW_DELTA_L") ? atoi(getenv("CRL_RAW_DELTA_L")) : kDeltaL;
     static const int abl_g = getenv("CRL_RAW_DELTA_G") ? atoi(getenv("CRL_RAW_DELTA_G")) : kDeltaG;
+    static const int abl_slots = getenv("CRL_RAW_DELTA_SLOTS") ? atoi(getenv("CRL_RAW_DELTA_SLOTS")) : 0;
     if (abl_lanes) {
         const unsigned blocks = (unsigned)((n + 63) / 64);
         if (views == 2)
@@ -378,13 +507,13 @@ void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64
             hipLaunchKernelGGL((pong_raster_raw_delta_lanes_kernel<1>), dim3(blocks), dim3(192), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
         return;
     }
-    if (abl_l != kDeltaL || abl_g != kDeltaG) {
+    if (abl_slots || abl_l != kDeltaL || abl_g != kDeltaG) {
         const int g = (uintptr_t)obs % (16 * abl_g) ? 1 : abl_g;
-#define CRL_DELTA_CASE(L, G)                \
-    if (abl_l == L && g == G) {             \
-        if (views == 2) CRL_LAUNCH_DELTA(2, L, G); \
-        else CRL_LAUNCH_DELTA(1, L, G);     \
-        return;                             \
+#define CRL_DELTA_CASE(L, G)                                                                      \
+    if (abl_l == L && g == G) {                                                                   \
+        if (views == 2) CRL_LAUNCH_DELTA((pong_raster_raw_delta_slots_kernel<2, L, G>), 2, L);    \
+        else CRL_LAUNCH_DELTA((pong_raster_raw_delta_slots_kernel<1, L, G>), 1, L);               \
+        return;                                                                                   \
     }
         CRL_DELTA_CASE(16, 1) CRL_DELTA_CASE(16, 2) CRL_DELTA_CASE(16, 4) CRL_DELTA_CASE(32, 1) CRL_DELTA_CASE(32, 2) CRL_DELTA_CASE(32, 4)
         CRL_DELTA_CASE(64, 1) CRL_DELTA_CASE(64, 2) CRL_DELTA_CASE(64, 4)
@@ -392,14 +521,14 @@ void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64
         return;  // (no such variant: nothing is drawn, which the tests see)
     }
 #endif
-    // a block is a whole sector only in a buffer aligned to it; crl_draw_raw_delta admits any 16-byte-aligned one: single chunks there
+    // a block is a whole memory request only in a buffer aligned to it; crl_draw_raw_delta admits any 16-byte-aligned one: single chunks there
     const bool blocks_ok = (uintptr_t)obs % (16 * kDeltaG) == 0;
     if (views == 2) {
-        if (blocks_ok) CRL_LAUNCH_DELTA(2, kDeltaL, kDeltaG);
-        else CRL_LAUNCH_DELTA(2, kDeltaL, 1);
+        if (blocks_ok) CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<2, kDeltaG>), 2, kDeltaL);
+        else CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<2, 1>), 2, kDeltaL);
     } else {
-        if (blocks_ok) CRL_LAUNCH_DELTA(1, kDeltaL, kDeltaG);
-        else CRL_LAUNCH_DELTA(1, kDeltaL, 1);
+        if (blocks_ok) CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<1, kDeltaG>), 1, kDeltaL);
+        else CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<1, 1>), 1, kDeltaL);
     }
 #undef CRL_LAUNCH_DELTA
 }
