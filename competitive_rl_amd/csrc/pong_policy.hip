@@ -904,6 +904,9 @@ int crl_policy_create(int32_t device, int64_t num_envs, const float *conv1_w, co
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+#ifdef CRL_ABLATION
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_policy_mfma_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+#endif
         if (e != hipSuccess) {
             crl_policy_destroy(p);
             return crl_fail(CRL_EHIP, "crl_policy_create (mfma weights): %s", hipGetErrorString(e));
@@ -982,7 +985,10 @@ int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride
         const int64_t mgroups = (p->n + kME - 1) / kME;
         const unsigned mgrid = (unsigned)(mgroups < p->cus ? mgroups : p->cus);  // persistent: one workgroup per CU
 #ifdef CRL_ABLATION
-        if (use_mfma != 3)
+        if (use_mfma != 3 && p->sampling)  // (set_sampling holds for the profiling kernels too)
+            hipLaunchKernelGGL((pong_policy_mfma_kernel<false, false, true>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
+                               frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr, S);
+        else if (use_mfma != 3)
             hipLaunchKernelGGL((pong_policy_mfma_kernel<false, false, false>), dim3(mgrid), dim3(kMThreads), kMLds, main_st, p->WM, p->ring, p->head, frame_dev,
                                frame_stride, actions_dev, action_stride, logits_dev, p->n, p->ticket, mdbg, (const int32_t *)nullptr, (const unsigned *)nullptr, S);
         else

@@ -179,18 +179,7 @@ def test_policy_abi_rejects_bad_arguments():
     pol.close()  # idempotent
 
 
-@pytest.mark.parametrize("mode", ["0", "1"])
-def test_mfma_and_hybrid_policy_kernels_match_the_oracle(mode):
-    """The non-default opponent kernels -- packed-FMA (CRL_POLICY_MFMA=0) and fp32-MFMA conv1 (=1); the default, conv1 as three
-    exact bf16 products per tap on the matrix pipe, is what every other test in this file runs -- give the same logits within
-    1e-4 and the same actions as the numpy oracle, over ring wrap-around and ragged group sizes; a child process, the switch is
-    read once."""
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    import subprocess
-    import sys
-
-    code = r"""
+_SWITCH_CHILD = r"""
 import os, sys, numpy as np, torch
 sys.path.insert(0, %r)
 from competitive_rl_amd.tournament import get_compute_action_function
@@ -209,10 +198,71 @@ for n in (5000, 8, 13):
         clear = (srt[:, 2] - srt[:, 1]) > 1e-3
         assert np.array_equal(a[clear], ao[clear]), (n, t)
     pol.close()
+# the witness batch: dense frames, the logits of the last call go to the parent
+n = 13
+pol = get_compute_action_function("MEDIUM", n)
+rs = np.random.RandomState(77)
+for t in range(4):
+    pol.act_device(torch.from_numpy(rs.randint(0, 256, (n, 1, 42, 42)).astype(np.uint8)).cuda(), want_logits=True)
+np.save(sys.argv[1], pol.logits().cpu().numpy())
+pol.close()
+# the sampled epilogue of whichever kernel the switch selects: 780 draws against the written rule fed the device's own logits
+from tests.test_hip_league_sampling import T, _compare
+n, seed, base, eps = 65, (1 << 40) + 9, (1 << 33) + 3, 0.1
+pol = get_compute_action_function("MEDIUM", n)
+pol.set_sampling(T, eps, seed=seed, env_id_base=base)
+got, logits = [], []
+for t in range(12):
+    f = (rs.random_sample((n, 1, 42, 42)) > 0.7).astype(np.uint8) * rs.randint(0, 256, (n, 1, 42, 42)).astype(np.uint8)
+    got.append(pol.act_device(torch.from_numpy(f).cuda(), want_logits=True).cpu().numpy().astype(np.int64))
+    logits.append(pol.logits().cpu().numpy().copy())
+tally = [0, 0, 0, 0]
+_compare(np.stack(got), seed, base + np.arange(n)[None, :], np.arange(12)[:, None], np.stack(logits), T, eps, tally)
+print("sampled, left out, off the argmax, explored", tally)
+assert tally[0] + tally[3] == 12 * n and tally[1] <= 1e-3 * tally[0] and tally[2] >= 0.10 * tally[0] and tally[3] > 0, tally
+pol.close()
 print("policy ok")
 """ % (ROOT, ROOT)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CRL_POLICY_MFMA=mode), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "policy ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+_switch_logits = {}
+
+
+def _switch_child(mode):
+    """The child above under the profiling library with CRL_POLICY_MFMA=`mode` (None: unset); returns its witness logits.  One
+    process per mode and session: library and switch are chosen once per process."""
+    if mode not in _switch_logits:
+        import subprocess
+        import sys
+        import tempfile
+
+        from tests.policy_f64_child import abl_library
+
+        abl_library()
+        env = dict(os.environ, CRL_LIB_VARIANT="abl")
+        env.pop("CRL_POLICY_MFMA", None)
+        if mode is not None:
+            env["CRL_POLICY_MFMA"] = mode
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "witness.npy")
+            r = subprocess.run([sys.executable, "-c", _SWITCH_CHILD, out], env=env, capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0 and "policy ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+            _switch_logits[mode] = np.load(out)
+    return _switch_logits[mode]
+
+
+@pytest.mark.parametrize("mode", ["0", "1"])
+def test_mfma_and_hybrid_policy_kernels_match_the_oracle(mode):
+    """The non-default opponent kernels -- packed-FMA (CRL_POLICY_MFMA=0) and fp32-MFMA conv1 (=1); the default, conv1 as three
+    exact bf16 products per tap on the matrix pipe, is what every other test in this file runs -- give the same logits within
+    1e-4 and the same actions as the numpy oracle, over ring wrap-around and ragged group sizes; a child process, the switch is
+    read once -- and only by the profiling library (CRL_LIB_VARIANT=abl), which the child therefore loads.  Witness that the switch
+    took effect: on a dense batch the logits differ in at least one bit from those of a second child that leaves it unset.  The
+    same child checks the selected kernel's sampled epilogue (set_sampling) against league_sample_reference, with the margin and
+    the left-out cap of tests/test_hip_league_sampling.py."""
+    if not torch.cuda.is_available():
+        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
+    got, default = _switch_child(mode), _switch_child(None)
+    assert got.shape == default.shape == (13, 3) and np.abs(got - default).max() < 2e-4
+    assert not np.array_equal(got.view(np.int32), default.view(np.int32)), "CRL_POLICY_MFMA=%s ran the default kernel" % mode
 
 
 @pytest.mark.gpu
