@@ -20,6 +20,7 @@ ATLAS_BYTES = 22 * 22 * 34 * 160
 
 CRL_LEAGUE_MAX_AGENTS = 16
 CRL_LEAGUE_RANDOM, CRL_LEAGUE_RULE_BASED, CRL_LEAGUE_LIGHT = 0, 1, 2
+CRL_POOL_KIND_FULL = 3  # a full-size ActorCritic agent (crl_pool_add_full); a #define beside enum crl_league_kind
 CRL_LEAGUE_DOMAIN_OPPONENT, CRL_LEAGUE_DOMAIN_ACTION, CRL_LEAGUE_DOMAIN_SAMPLE = 0x4C47554F, 0x4C475541, 0x4C475553
 CRL_LEDGER_DOMAIN_OPPONENT = 0x4C475557
 CRL_LEDGER_COUNTERS = 6  # rows of the counters tensor, in this order (enum crl_ledger_counter)
@@ -128,6 +129,7 @@ SIGNATURES = {
     "crl_league_destroy": (None, [vp]),
     "crl_league_add_builtin": (i32, [vp, i32]),
     "crl_league_add_light": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "crl_pool_add_full": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "crl_sampling_set_agent": (i32, [vp, i32, f32, f32]),
     "crl_sampling_get_agent": (i32, [vp, i32, P(f32), P(f32)]),
     "crl_league_seed": (i32, [vp, u64, vp]),

@@ -8,7 +8,8 @@ each env holds a pair, the whole round-robin runs side by side, and the env's ne
 * both seats are served by ONE ``crl_league`` of ``2 * num_envs`` virtual envs: virtual env ``2 * i + seat`` reads view ``seat`` of env
   ``i`` out of the env's ``(N, 2, K, 42, 42)`` observation buffer and writes ``actions[i, seat]``; its int32 ``[2N]`` assignment is the
   array of (left, right) pairs.  The launches are the league's own (one partition, one fill, one list launch per CNN agent for both
-  seats together).  That league is created with ``env_id_base = 2 * (the env's)``, so RANDOM's action stream is keyed by
+  seats together; three per pass for a full-size ActorCritic agent, ``add_full_agent``, whose snapshots enter the payoff matrix like
+  any other agent).  That league is created with ``env_id_base = 2 * (the env's)``, so RANDOM's action stream is keyed by
   ``2 * gid + seat`` (``league_draw_reference(seed, 2 * gid + seat, step, CRL_LEAGUE_DOMAIN_ACTION, 3)``), and so is the stream of
   the agents' sampled and explored actions (``set_sampling``; ``league_sample_reference(seed, 2 * gid + seat, step, ...)``);
 * the books and the pair draws are ``crl_arena_*`` (csrc/pong_arena.hip), an object beside the league as ``crl_ledger`` is:
@@ -25,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .league import _BUILTIN_KINDS, _get_sampling, _light_weights, _set_sampling, check_sampling, league_draw_reference
+from .league import (_BUILTIN_KINDS, _add_full, _full_weights, _get_sampling, _light_weights, _set_sampling, check_sampling,
+                     league_draw_reference)
 from .policy_serving import _KEYS, BUILTIN_CHECKPOINTS, load_light_weights
 from .tournament import get_builtin_agent_names
 
@@ -212,7 +214,8 @@ class ArenaBooks:
 class LeagueArena:
     """The round-robin of a pool on one ``cPongDouble-v0`` batch.  ``env``: a ``HipPongVecEnv`` in wrapped mode with ``resized_dim=42``
     and uint8 observations (``make_envs("cPongDouble-v0", ..., resized_dim=42, frame_stack=None)``).  ``agent_names``: any of RANDOM,
-    RULE_BASED, WEAK, MEDIUM (default: all four); ``add_agent`` adds LightActorCritic weight sets of the caller's own.
+    RULE_BASED, WEAK, MEDIUM (default: all four); ``add_agent`` adds LightActorCritic weight sets of the caller's own, ``add_full_agent``
+    full-size ActorCritic ones.
     ``env_id_base``: the global id of env 0 (default: the env's); the pair draws are keyed by that REAL id, the league that serves the
     bats is created with twice it, so RANDOM's action stream and the sample stream of ``set_sampling`` are keyed by ``2 * gid + seat``.
     ``include_mirror``: schedule an agent
@@ -284,10 +287,21 @@ class LeagueArena:
 
     def add_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0):
         """A LightActorCritic agent of one's own -- a checkpoint path, a dict of the six arrays in torch layout or a light ``Policy``
-        (a trainer's snapshot).  Its cells enter the draw table with weight 1; the pairs in force stay.  Full-size networks are refused.
+        (a trainer's snapshot).  Its cells enter the draw table with weight 1; the pairs in force stay.  Full-size networks are refused
+        here: ``add_full_agent`` takes them.
         ``temperature`` / ``epsilon``: its play style (``set_sampling``); the default is greedy."""
         check_sampling(temperature, epsilon)  # (before the agent enters the pool)
         self._add(name, N.CRL_LEAGUE_LIGHT, _light_weights(name, weights_or_checkpoint))
+        if temperature or epsilon:
+            self.set_sampling(name, temperature, epsilon)
+        self.books.set_agents(len(self.agent_names))
+
+    def add_full_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0, scratch_rows=None):
+        """A full-size ActorCritic agent of one's own (``LeagueEnvWrapper.add_full_agent``: a checkpoint path, a dict of the eight arrays
+        in torch layout or a full-size ``Policy``), served in both seats.  Its cells enter the draw table with weight 1; the pairs in
+        force stay.  ``scratch_rows``: rows of the one activation scratch (None: min(2 * num_envs, 65 536) -- the seats are the rows)."""
+        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
+        _add_full(self, name, _full_weights(name, weights_or_checkpoint), scratch_rows)
         if temperature or epsilon:
             self.set_sampling(name, temperature, epsilon)
         self.books.set_agents(len(self.agent_names))

@@ -13,6 +13,10 @@
 // is assigned (one `head` for all envs), so an env that changes hands is judged on the frames it really showed.  Exactly one
 // writer per env and step for the ring slot and for the action: the fill kernel for envs of RANDOM / RULE_BASED, the env's own
 // agent's list launch otherwise.
+//
+// Full-size agents (CRL_POOL_KIND_FULL, crl_pool_add_full): the ActorCritic of pong_policy_full.hip on the agent's list, three
+// launches per pass (policy_full_act_list).  Each has its own weight blob and list; the activation scratch (act2, feat) is ONE per
+// league, shared by all of them -- their launches are ordered on the stream -- and allocated by the first add.
 #include <string.h>
 
 #include <vector>
@@ -43,7 +47,7 @@ struct LeagueExplore {
 };
 
 struct LeagueLists {
-    int32_t *list[kMaxAgents];  // CNN agents: env indices of the agent (order free); nullptr for RANDOM / RULE_BASED
+    int32_t *list[kMaxAgents];  // CNN agents (light and full-size): env indices of the agent (order free); nullptr for RANDOM / RULE_BASED
 };
 
 // Re-draws the opponent of every env (redraw_all) or of the envs whose flag in `done` is set, then rebuilds the per-agent counts and
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(kLThreads) void league_fill_kernel(const int32_t *_
     if (i < n) {
         const int a = assign[i];
         const int kind = (a >= 0 && a < agents) ? kinds[a] : CRL_LEAGUE_RULE_BASED;
-        mine = kind != CRL_LEAGUE_LIGHT;
+        mine = kind < CRL_LEAGUE_LIGHT;  // CRL_LEAGUE_LIGHT and CRL_POOL_KIND_FULL: a list launch visits the env (action and frame push)
         if (kind == CRL_LEAGUE_RANDOM) actions[i * action_stride] = (int32_t)league_draw(seed, (uint64_t)(env_id_base + i), step, CRL_LEAGUE_DOMAIN_ACTION, 3u);
         else if (mine) {
             int act = CRL_PONG_CHEAT;
@@ -133,7 +137,9 @@ struct crl_league {
     uint32_t step = 0;   // crl_league_act calls since create / seed: the counter of RANDOM's action draws
     int agents = 0;
     int kind[kMaxAgents] = {};
-    float *raw[kMaxAgents] = {};  // CNN agents: the checkpoint tensors (pong_league.h kLightRawFloats)
+    float *raw[kMaxAgents] = {};  // CNN agents: the checkpoint tensors (pong_league.h kLightRawFloats; full-size: policy_full_pack's blob)
+    int64_t scratch_rows = 0;     // full-size agents: rows of the shared scratch, fixed by the first crl_pool_add_full (0: none yet)
+    float *act2 = nullptr, *feat = nullptr;  // ... [scratch_rows][3872] and [scratch_rows][256]
     float temperature[kMaxAgents] = {}, epsilon[kMaxAgents] = {};  // crl_sampling_set_agent, as given
     SampleArgs sample[kMaxAgents] = {};                            // ... and as the launches take it (inv_t, eps_q)
     LeagueLists T{};
@@ -155,10 +161,25 @@ static int league_partition(crl_league *l, const uint8_t *done_dev, int redraw_a
     return CRL_OK;
 }
 
-static int league_add(crl_league *l, int kind, const float *raw_host) {
+static int league_add(crl_league *l, int kind, const float *raw_host, int64_t scratch_rows = 0) {
     if (l->agents >= kMaxAgents) return crl_fail(CRL_EINVAL, "crl_league: at most %d agents in a pool", kMaxAgents);
     HIP_TRY(hipSetDevice(l->device));
     const int a = l->agents;
+    if (kind == CRL_POOL_KIND_FULL) {
+        const size_t blob = (size_t)policy_full_blob_floats() * sizeof(float);
+        if (!l->scratch_rows) {  // the first full-size agent: the league's one scratch
+            if (int rc = crl_dev_zalloc(&l->act2, (size_t)scratch_rows * policy_full_act2_floats() * sizeof(float), "crl_pool_add_full")) return rc;
+            if (int rc = crl_dev_zalloc(&l->feat, (size_t)scratch_rows * policy_full_feat_floats() * sizeof(float), "crl_pool_add_full")) {
+                (void)hipFree(l->act2), l->act2 = nullptr;
+                return rc;
+            }
+            l->scratch_rows = scratch_rows;
+        }
+        if (!l->raw[a]) HIP_TRY(hipMalloc(&l->raw[a], blob));  // (a slot whose add failed half way keeps what it got: destroy frees it)
+        HIP_TRY(hipMemcpy(l->raw[a], raw_host, blob, hipMemcpyHostToDevice));
+        if (!l->T.list[a])
+            if (int rc = crl_dev_zalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t), "crl_pool_add_full")) return rc;
+    }
     if (kind == CRL_LEAGUE_LIGHT) {
         HIP_TRY(hipMalloc(&l->raw[a], kLightRawFloats * sizeof(float)));
         HIP_TRY(hipMemcpy(l->raw[a], raw_host, kLightRawFloats * sizeof(float), hipMemcpyHostToDevice));
@@ -207,6 +228,8 @@ void crl_league_destroy(crl_league *l) {
         if (l->raw[a]) (void)hipFree(l->raw[a]);
         if (l->T.list[a]) (void)hipFree(l->T.list[a]);
     }
+    if (l->act2) (void)hipFree(l->act2);
+    if (l->feat) (void)hipFree(l->feat);
     if (l->ring) (void)hipFree(l->ring);
     if (l->assign) (void)hipFree(l->assign);
     if (l->draw_ctr) (void)hipFree(l->draw_ctr);
@@ -229,6 +252,26 @@ int crl_league_add_light(crl_league *l, const float *conv1_w, const float *conv1
     memcpy(raw.data(), conv1_w, 1024 * 4), memcpy(raw.data() + 1024, conv1_b, 16 * 4), memcpy(raw.data() + 1040, conv2_w, 1024 * 4);
     memcpy(raw.data() + 2064, conv2_b, 16 * 4), memcpy(raw.data() + 2080, actor_w, 4800 * 4), memcpy(raw.data() + 6880, actor_b, 3 * 4);
     return league_add(l, CRL_LEAGUE_LIGHT, raw.data());
+}
+
+int crl_pool_add_full(crl_league *l, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *conv3_w,
+                      const float *conv3_b, const float *actor_w, const float *actor_b, int64_t scratch_rows) {
+    crl_fail_no_ctx();
+    if (!l || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !conv3_w || !conv3_b || !actor_w || !actor_b)
+        return crl_fail(CRL_EINVAL, "crl_pool_add_full: null argument");
+    if (scratch_rows < 0) return crl_fail(CRL_EINVAL, "crl_pool_add_full: scratch_rows must be >= 0 (0: min(num_envs, 65536)), not %lld", (long long)scratch_rows);
+    if (l->agents >= kMaxAgents) return crl_fail(CRL_EINVAL, "crl_pool_add_full: at most %d agents in a pool", kMaxAgents);
+    if (l->scratch_rows) {
+        if (scratch_rows && scratch_rows != l->scratch_rows)
+            return crl_fail(CRL_EINVAL, "crl_pool_add_full: scratch_rows %lld, but the league's scratch holds %lld rows (the first full-size agent fixed it; pass 0 or that value)",
+                            (long long)scratch_rows, (long long)l->scratch_rows);
+        scratch_rows = l->scratch_rows;
+    } else if (!scratch_rows) {
+        scratch_rows = l->n < 65536 ? l->n : 65536;
+    }
+    std::vector<float> blob((size_t)policy_full_blob_floats(), 0.f);
+    policy_full_pack(blob.data(), conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
+    return league_add(l, CRL_POOL_KIND_FULL, blob.data(), scratch_rows);
 }
 
 int crl_sampling_set_agent(crl_league *l, int32_t agent, float temperature, float epsilon) {
@@ -318,6 +361,12 @@ int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride
             S.seed = l->seed, S.id_base = l->env_id_base, S.n = l->step;
             HIP_TRY(policy_light_act_list(l->raw[a], l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, l->T.list[a],
                                           league_counts(l) + a, l->n, l->cus, l->ctrl + a, sampled ? &S : nullptr, st));
+        } else if (l->kind[a] == CRL_POOL_KIND_FULL) {
+            SampleArgs S = l->sample[a];
+            const bool sampled = S.inv_t != 0.f || S.eps_q != 0;
+            S.seed = l->seed, S.id_base = l->env_id_base, S.n = l->step;
+            HIP_TRY(policy_full_act_list(l->raw[a], l->act2, l->feat, l->scratch_rows, l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride,
+                                         logits_dev, l->T.list[a], league_counts(l) + a, l->n, l->cus, sampled ? &S : nullptr, st));
         }
     l->head = (l->head + 1) & 3;
     l->step++;

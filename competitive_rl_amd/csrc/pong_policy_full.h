@@ -21,4 +21,23 @@ void policy_full_destroy(PolicyFull *f);
 hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
                            int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, hipStream_t st);
 
+
+// ---- the list form: a league's full-size agents (pong_league.hip).  The league owns the weight blobs and ONE activation scratch.
+int64_t policy_full_blob_floats();  // floats of a packed weight blob (w1 | b1 | w2 | b2 | w3 | b3 | wa | ba)
+int64_t policy_full_act2_floats();  // scratch floats per row: act2 [rows][3872] ...
+int64_t policy_full_feat_floats();  // ... and feat [rows][256]
+// host: packs the eight tensors (torch layouts, as policy_full_create takes them) into blob[policy_full_blob_floats()]
+void policy_full_pack(float *blob, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *conv3_w,
+                      const float *conv3_b, const float *actor_w, const float *actor_b);
+// The three kernels for the envs env_list[0 .. *count_dev): row r of the compact scratch (act2 [scratch_rows][3872], feat
+// [scratch_rows][256]) belongs to env env_list[r]; ring planes, frames, actions and logits are addressed through the list, and the
+// frame of each listed env is pushed into its ring plane `head`.  The count is known on the device only: ceil(max_envs /
+// scratch_rows) passes are launched, pass p serves list positions [p * scratch_rows, min(count, (p + 1) * scratch_rows)), a pass
+// past the count is three launches that return at once.  Grids are persistent and sized from max_envs (an upper bound of the
+// count) and `cus`.  `w_blob`: a device copy of policy_full_pack's blob; `sample`: null = argmax, else include/crl.h "sampled
+// actions" with these parameters, drawn with the ENV's id (id_base: the global id of env 0 of the arrays the list indexes).
+hipError_t policy_full_act_list(const float *w_blob, float *act2, float *feat, int64_t scratch_rows, uint8_t *ring, int head, const uint8_t *frame,
+                                int64_t frame_stride, int32_t *actions, int64_t action_stride, float *logits, const int32_t *env_list,
+                                const unsigned *count_dev, int64_t max_envs, int cus, const SampleArgs *sample, hipStream_t st);
+
 }  // namespace crl

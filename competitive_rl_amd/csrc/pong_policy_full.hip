@@ -20,6 +20,12 @@
 // compute bound on the 157 TFLOP/s fp32 matrix pipe.  Measured at 65 536 envs (profiles/r04_policy_full_stats.csv): front
 // 1.34 ms (ideal 0.94), conv3 1.00 ms (ideal 0.83), actor 0.017 ms = 2.36 ms per call; the first version (conv1 and conv2
 // as separate kernels through HBM, byte / 255 divisions on the vector pipe) took 4.4.
+//
+// LIST form (template parameter LIST of the three kernels; the dense instantiations are the code they were): the same kernels on
+// the env-index list of a league's full-size agent, whose count is known on the device only (ListArgs).  Row r of the compact
+// scratch belongs to env env_list[r]; ring, frame, action and logits are addressed by the env, act2 and feat by the row.  All three
+// grids are persistent and sized from an upper bound of the count; a workgroup without a row returns before it touches LDS or
+// reaches a barrier.  The arithmetic of a row is the dense kernels', operation for operation, and does not depend on the row's place.
 #include "pong_policy_full.h"
 
 #include <string.h>
@@ -53,6 +59,17 @@ struct PolicyFull {
     float *feat = nullptr;  // [chunk][256] after ReLU
 };
 
+// LIST launches: the rows of this pass are the list positions [row0, min(*count_dev, row0 + rows)); env_list points at position row0.
+struct ListArgs {
+    const int32_t *env_list;
+    const unsigned *count_dev;
+    int64_t row0;
+};
+__device__ inline int64_t list_rows(const ListArgs &L, int64_t rows) {
+    const int64_t left = (int64_t)*L.count_dev - L.row0;
+    return left < rows ? (left > 0 ? left : 0) : rows;
+}
+
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // conv1 + ReLU + conv2 + ReLU of one env per workgroup pass, act1 never leaves the CU.
@@ -74,12 +91,22 @@ __device__ inline uint32_t pk_bytes_bf16(uint32_t two) {  // the two low bytes o
 }
 static constexpr int kS1Rows = 24, kS1Pitch = 580;  // padded plane 24 x 24 = 576 floats + 4: channels start 4 banks apart
 static constexpr int kW2Pitch = 260;  // floats per output channel in LDS: 65 x 16 bytes, odd -> the 16 lanes of a read phase hit 16 bank groups
+// LIST: row r of act2 is env L.env_list[r]; n comes in as the pass's row capacity and becomes its row count.
+template <bool LIST>
 __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restrict__ ring, int head, const uint8_t *__restrict__ frame,
                                                                 int64_t frame_stride, const float *__restrict__ w1,
                                                                 const float *__restrict__ b1, const float *__restrict__ w2,
-                                                                const float *__restrict__ b2, float *__restrict__ act2, int64_t n) {
+                                                                const float *__restrict__ b2, float *__restrict__ act2, int64_t n, ListArgs L) {
     __shared__ __attribute__((aligned(16))) float sw[kC2 * kW2Pitch];
     __shared__ __attribute__((aligned(16))) float s1[kC1 * kS1Pitch];
+    if constexpr (LIST) {
+        n = list_rows(L, n);
+        if ((int64_t)blockIdx.x >= n) return;  // (the whole workgroup, before LDS and barriers)
+    }
+    auto env_of = [&](int64_t r) -> int64_t {
+        if constexpr (LIST) return L.env_list[r];
+        else return r;
+    };
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
     for (int i = tid; i < kC2 * 64; i += 256) {
         const int r = i >> 6, c = i & 63;
@@ -129,8 +156,9 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
         }
     };
     __syncthreads();
-    if ((int64_t)blockIdx.x < n) prefetch(blockIdx.x);
-    for (int64_t env = blockIdx.x; env < n; env += gridDim.x) {
+    if ((int64_t)blockIdx.x < n) prefetch(env_of(blockIdx.x));
+    for (int64_t r = blockIdx.x; r < n; r += gridDim.x) {
+        const int64_t env = env_of(r);
 #pragma unroll
         for (int it = 0; it < 7; it++) {
             const int tl = min(wave + 4 * it, kP1 / 16 - 1);
@@ -152,7 +180,7 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
             for (int r = 0; r < 4; r++) o[r * kS1Pitch] = fmaxf(acc[r] + bias1[r], 0.f);
         }
         __syncthreads();
-        if (env + gridDim.x < n) prefetch(env + gridDim.x);
+        if (r + gridDim.x < n) prefetch(env_of(r + gridDim.x));
         f4 acc[2][2];
 #pragma unroll
         for (int u = 0; u < 2; u++) acc[u][0] = f4{0.f, 0.f, 0.f, 0.f}, acc[u][1] = f4{0.f, 0.f, 0.f, 0.f};
@@ -173,7 +201,7 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
         for (int u = 0; u < 2; u++) {  // D: channels 16 nb + 4 lk + r x position li: the 16 lanes of a row store 64 consecutive bytes
             const int pos = 32 * wave + 16 * u + li;
             if (pos < kP2) {
-                float *o = act2 + env * kK3 + 4 * lk * kP2 + pos;
+                float *o = act2 + r * kK3 + 4 * lk * kP2 + pos;
 #pragma unroll
                 for (int nb = 0; nb < 2; nb++)
 #pragma unroll
@@ -193,13 +221,18 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
 // x 128 channels, 2 x 2 wavefronts of 64 x 64 (16 accumulators), K in slabs of 16 through two LDS buffers; a wavefront reads
 // each operand of a slab with one 16-byte LDS read per 16-row block (4 + 4 reads for 64 matrix instructions).
 static constexpr int kGM = 128, kGN = 128, kGPitch = 20;  // pitch 20 floats = 5 x 16 bytes, odd: conflict-free 16-lane read phases
-__global__ __launch_bounds__(256, 4) void policy_full_conv3_kernel(const float *__restrict__ act2, const float *__restrict__ w3,
-                                                                const float *__restrict__ b3, float *__restrict__ feat, int64_t n) {
+// One 128 x 128 tile: rows m0 .. m0 + 127 of act2 (n rows in all, m0 < n) against channels n0 .. n0 + 127.  LOOPED: called from a
+// loop over tiles; the thread id then passes through an empty asm statement, so that what is derived from it (loader and fragment
+// offsets, a dozen registers) is formed again per tile and not kept alive beside the 64 accumulators of the epilogue -- hoisted
+// out of the loop it cost 17 spilled registers at the 128 that four workgroups per CU allow.
+template <bool LOOPED>
+__device__ __forceinline__ void policy_full_conv3_tile(const float *__restrict__ act2, const float *__restrict__ w3, const float *__restrict__ b3,
+                                                       float *__restrict__ feat, int64_t n, const int64_t m0, const int n0) {
     __shared__ __attribute__((aligned(16))) float sA[2][kGM * kGPitch];
     __shared__ __attribute__((aligned(16))) float sB[2][kGN * kGPitch];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4, wm = wave >> 1, wn = wave & 1;
-    const int64_t m0 = (int64_t)blockIdx.x * kGM;
-    const int n0 = blockIdx.y * kGN;
+    int tid = threadIdx.x;
+    if constexpr (LOOPED) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4, wm = wave >> 1, wn = wave & 1;
     const int lr = tid >> 2, lc = tid & 3;  // loader: rows lr and lr + 64, 16-byte column lc of the slab
     const float *pa0 = act2 + std::min<int64_t>(m0 + lr, n - 1) * kK3 + 4 * lc;  // rows past the last env repeat it (not stored)
     const float *pa1 = act2 + std::min<int64_t>(m0 + lr + 64, n - 1) * kK3 + 4 * lc;
@@ -256,17 +289,37 @@ __global__ __launch_bounds__(256, 4) void policy_full_conv3_kernel(const float *
     }
 }
 
+// LIST: n comes in as the pass's row capacity and becomes its row count, read once; the grid is persistent over the row tiles.  A
+// workgroup whose first tile lies past the count returns before it forms an address (with a count of 0 the clamp min(m0 + lr, n - 1)
+// would be row -1) or reaches a barrier.  Between two tiles of a workgroup no barrier is needed: the K loop's last two barriers
+// stand between the last reads of buffer 0 and the next tile's first writes to it.
+template <bool LIST>
+__global__ __launch_bounds__(256, 4) void policy_full_conv3_kernel(const float *__restrict__ act2, const float *__restrict__ w3,
+                                                                const float *__restrict__ b3, float *__restrict__ feat, int64_t n, ListArgs L) {
+    if constexpr (LIST) {
+        n = list_rows(L, n);
+        // a one-dimensional grid over (tile, channel half) items, the half fastest: the workgroups that have work are the FIRST ones
+        // of the grid, as in a dense launch of that many rows (with x over the tiles of the row capacity and y the half, a list
+        // shorter than the capacity put its two halves on the same CUs and left others idle)
+        for (int64_t m0 = (int64_t)(blockIdx.x >> 1) * kGM; m0 < n; m0 += (int64_t)(gridDim.x >> 1) * kGM) {
+            const float *a = act2, *w = w3;  // (scalars; through an empty asm per tile, or vector copies of them live across the loop and spill)
+            int64_t rows = n;
+            asm volatile("" : "+s"(a), "+s"(w), "+s"(rows));
+            policy_full_conv3_tile<true>(a, w, b3, feat, rows, m0, (blockIdx.x & 1) * kGN);
+        }
+    } else {
+        policy_full_conv3_tile<false>(act2, w3, b3, feat, n, (int64_t)blockIdx.x * kGM, blockIdx.y * kGN);
+    }
+}
+
 // actor_linear + argmax (first maximum, like torch.argmax / numpy): one wavefront per env, a fixed-shape butterfly sum.
 // SAMPLE: lane 0 draws the action by include/crl.h "sampled actions" instead (a template parameter, as in pong_policy.hip: the
 // greedy kernel is the code it was); S.id_base is the global id of this launch's env 0.
 template <bool SAMPLE>
-__global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__restrict__ feat, const float *__restrict__ wa,
-                                                                const float *__restrict__ ba, int32_t *__restrict__ actions,
-                                                                int64_t action_stride, float *__restrict__ logits, int64_t n, SampleArgs S) {
-    const int lane = threadIdx.x & 63;
-    const int64_t env = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (env >= n) return;
-    const f4 f = *reinterpret_cast<const f4 *>(feat + env * kC3 + 4 * lane);
+__device__ __forceinline__ void policy_full_actor_row(const float *__restrict__ feat, const float *__restrict__ wa, const float *__restrict__ ba,
+                                                      int32_t *__restrict__ actions, int64_t action_stride, float *__restrict__ logits,
+                                                      const int64_t row, const int64_t env, const int lane, const SampleArgs &S) {
+    const f4 f = *reinterpret_cast<const f4 *>(feat + row * kC3 + 4 * lane);
     float s[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -286,6 +339,37 @@ __global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__r
     }
 }
 
+// LIST: a persistent grid, a wavefront walks the rows row, row + 4 gridDim.x, ... below the count; feat is read by the row, the
+// action and the logits are written, and the sample drawn, by the row's env (S.id_base: the global id of env 0 of `actions`).
+template <bool SAMPLE, bool LIST>
+__global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__restrict__ feat, const float *__restrict__ wa,
+                                                                const float *__restrict__ ba, int32_t *__restrict__ actions,
+                                                                int64_t action_stride, float *__restrict__ logits, int64_t n, SampleArgs S,
+                                                                ListArgs L) {
+    const int lane = threadIdx.x & 63;
+    const int64_t env = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if constexpr (LIST) {
+        n = list_rows(L, n);
+        for (int64_t row = env; row < n; row += (int64_t)gridDim.x * 4)  // (the same trip count in every lane of a wavefront)
+            policy_full_actor_row<SAMPLE>(feat, wa, ba, actions, action_stride, logits, row, L.env_list[row], lane, S);
+    } else {
+        if (env >= n) return;
+        policy_full_actor_row<SAMPLE>(feat, wa, ba, actions, action_stride, logits, env, env, lane, S);
+    }
+}
+
+int64_t policy_full_blob_floats() { return kBlob; }
+int64_t policy_full_act2_floats() { return kK3; }
+int64_t policy_full_feat_floats() { return kC3; }
+
+void policy_full_pack(float *blob, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *conv3_w,
+                      const float *conv3_b, const float *actor_w, const float *actor_b) {
+    memcpy(blob + kOffW1, conv1_w, 1024 * sizeof(float)), memcpy(blob + kOffB1, conv1_b, 16 * sizeof(float));
+    memcpy(blob + kOffW2, conv2_w, (size_t)kC2 * 256 * sizeof(float)), memcpy(blob + kOffB2, conv2_b, kC2 * sizeof(float));
+    memcpy(blob + kOffW3, conv3_w, (size_t)kC3 * kK3 * sizeof(float)), memcpy(blob + kOffB3, conv3_b, kC3 * sizeof(float));
+    memcpy(blob + kOffWa, actor_w, (size_t)3 * kC3 * sizeof(float)), memcpy(blob + kOffBa, actor_b, 3 * sizeof(float));
+}
+
 hipError_t policy_full_create(PolicyFull **out, int64_t num_envs, const float *conv1_w, const float *conv1_b, const float *conv2_w,
                               const float *conv2_b, const float *conv3_w, const float *conv3_b, const float *actor_w,
                               const float *actor_b) {
@@ -296,10 +380,7 @@ hipError_t policy_full_create(PolicyFull **out, int64_t num_envs, const float *c
         f->cus <= 0)
         f->cus = 256;
     std::vector<float> blob(kBlob, 0.f);
-    memcpy(blob.data() + kOffW1, conv1_w, 1024 * sizeof(float)), memcpy(blob.data() + kOffB1, conv1_b, 16 * sizeof(float));
-    memcpy(blob.data() + kOffW2, conv2_w, (size_t)kC2 * 256 * sizeof(float)), memcpy(blob.data() + kOffB2, conv2_b, kC2 * sizeof(float));
-    memcpy(blob.data() + kOffW3, conv3_w, (size_t)kC3 * kK3 * sizeof(float)), memcpy(blob.data() + kOffB3, conv3_b, kC3 * sizeof(float));
-    memcpy(blob.data() + kOffWa, actor_w, (size_t)3 * kC3 * sizeof(float)), memcpy(blob.data() + kOffBa, actor_b, 3 * sizeof(float));
+    policy_full_pack(blob.data(), conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
     hipError_t e = hipMalloc(&f->w, blob.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(f->w, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&f->act2, (size_t)f->chunk * kK3 * sizeof(float));
@@ -324,20 +405,44 @@ hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, co
                            int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, hipStream_t st) {
     for (int64_t e0 = 0; e0 < n; e0 += f->chunk) {
         const int64_t c = std::min<int64_t>(f->chunk, n - e0);
-        hipLaunchKernelGGL(policy_full_front_kernel, dim3((unsigned)std::min<int64_t>(c, (int64_t)f->cus * 2)), dim3(256), 0, st,
+        hipLaunchKernelGGL(policy_full_front_kernel<false>, dim3((unsigned)std::min<int64_t>(c, (int64_t)f->cus * 2)), dim3(256), 0, st,
                            ring + e0 * kFRingBytes, head, frame_dev + e0 * frame_stride, frame_stride, f->w + kOffW1, f->w + kOffB1,
-                           f->w + kOffW2, f->w + kOffB2, f->act2, c);
-        hipLaunchKernelGGL(policy_full_conv3_kernel, dim3((unsigned)((c + kGM - 1) / kGM), kC3 / kGN), dim3(256), 0, st, f->act2,
-                           f->w + kOffW3, f->w + kOffB3, f->feat, c);
+                           f->w + kOffW2, f->w + kOffB2, f->act2, c, ListArgs{});
+        hipLaunchKernelGGL(policy_full_conv3_kernel<false>, dim3((unsigned)((c + kGM - 1) / kGM), kC3 / kGN), dim3(256), 0, st, f->act2,
+                           f->w + kOffW3, f->w + kOffB3, f->feat, c, ListArgs{});
         if (sample) {
             SampleArgs S = *sample;
             S.id_base += e0;
-            hipLaunchKernelGGL(policy_full_actor_kernel<true>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
-                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, S);
+            hipLaunchKernelGGL((policy_full_actor_kernel<true, false>), dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
+                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, S, ListArgs{});
         } else {
-            hipLaunchKernelGGL(policy_full_actor_kernel<false>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
-                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, SampleArgs{});
+            hipLaunchKernelGGL((policy_full_actor_kernel<false, false>), dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
+                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, SampleArgs{}, ListArgs{});
         }
+    }
+    return hipGetLastError();
+}
+
+hipError_t policy_full_act_list(const float *w_blob, float *act2, float *feat, int64_t scratch_rows, uint8_t *ring, int head, const uint8_t *frame,
+                                int64_t frame_stride, int32_t *actions, int64_t action_stride, float *logits, const int32_t *env_list,
+                                const unsigned *count_dev, int64_t max_envs, int cus, const SampleArgs *sample, hipStream_t st) {
+    if (scratch_rows <= 0 || max_envs <= 0 || cus <= 0) return hipErrorInvalidValue;
+    for (int64_t r0 = 0; r0 < max_envs; r0 += scratch_rows) {  // the count is on the device: a pass past it is three launches that return at once
+        const int64_t rows = std::min<int64_t>(scratch_rows, max_envs - r0);
+        const ListArgs L{env_list + r0, count_dev, r0};
+        const int64_t tiles = (rows + kGM - 1) / kGM;
+        hipLaunchKernelGGL(policy_full_front_kernel<true>, dim3((unsigned)std::min<int64_t>(rows, (int64_t)cus * 2)), dim3(256), 0, st, ring, head,
+                           frame, frame_stride, w_blob + kOffW1, w_blob + kOffB1, w_blob + kOffW2, w_blob + kOffB2, act2, rows, L);
+        // four workgroups of conv3 per CU are resident: 2 x cus tiles x two channel halves, (tile, half) items in a one-dimensional grid
+        hipLaunchKernelGGL(policy_full_conv3_kernel<true>, dim3((unsigned)(2 * std::min<int64_t>(tiles, (int64_t)cus * 2))), dim3(256), 0, st, act2,
+                           w_blob + kOffW3, w_blob + kOffB3, feat, rows, L);
+        const dim3 ag((unsigned)std::min<int64_t>((rows + 3) / 4, (int64_t)cus * 8));
+        if (sample)
+            hipLaunchKernelGGL((policy_full_actor_kernel<true, true>), ag, dim3(256), 0, st, feat, w_blob + kOffWa, w_blob + kOffBa, actions,
+                               action_stride, logits, rows, *sample, L);
+        else
+            hipLaunchKernelGGL((policy_full_actor_kernel<false, true>), ag, dim3(256), 0, st, feat, w_blob + kOffWa, w_blob + kOffBa, actions,
+                               action_stride, logits, rows, SampleArgs{}, L);
     }
     return hipGetLastError();
 }

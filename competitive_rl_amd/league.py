@@ -5,8 +5,11 @@ a trainer gets a mixed population of opponents because it runs many worker proce
 (``reset_opponent`` -> ``random.choice(agent_names)``, :27-33).  On this backend one batch is the population, so the league keeps an
 int32 ``assignment`` per env on the device (index into ``agent_names``) and serves every env's opponent in the step:
 
-* pool: any of RANDOM, RULE_BASED, WEAK, MEDIUM, plus LightActorCritic weight sets of the caller's own (``add_agent``); the full-size
-  ActorCritic is not served inside the league (use ``TournamentEnvWrapper.add_agent`` for a whole batch against one);
+* pool: any of RANDOM, RULE_BASED, WEAK, MEDIUM, plus LightActorCritic weight sets of the caller's own (``add_agent``) and full-size
+  ActorCritic weight sets -- the network of the reference's STRONG / ALPHA_PONG and of ``Policy(..., use_light_model=False)``
+  (utils/network.py:14-56) -- through ``add_full_agent``: a trainer's own snapshots, served per env like every other agent.  Their
+  three kernels run on the agent's env list; the activations between them live in one scratch per league (16.5 KB per row, about
+  1.1 GB at 65 536 rows; ``scratch_rows`` trades memory for passes);
 * every pool entry carries a play style, ``(temperature, epsilon)`` (``set_sampling`` / ``sampling``; default (0, 0) = greedy, today's
   behaviour): a CNN agent at temperature T samples from the softmax of logits / T as the reference's
   ``Policy.compute_action(obs, deterministic=False)`` does at T = 1 (utils/policy_serving.py:48-56), any agent but RANDOM plays a
@@ -25,8 +28,8 @@ int32 ``assignment`` per env on the device (index into ``agent_names``) and serv
   with ``resample_on_done`` the next opponent is then the LEDGER's weighted draw (``LeagueLedger.set_weights`` / ``pfsp_weights``)
   instead of the uniform one.  Without a ledger the wrapper runs the launches it always ran.
 
-The forward pass, the draws and the partition of the envs by agent are HIP behind ``crl_league_*`` (csrc/pong_league.hip,
-csrc/pong_policy.hip); there is no torch model and no CPU path in this module.
+The forward pass, the draws and the partition of the envs by agent are HIP behind ``crl_league_*`` / ``crl_pool_add_full``
+(csrc/pong_league.hip, csrc/pong_policy.hip, csrc/pong_policy_full.hip); there is no torch model and no CPU path in this module.
 """
 import ctypes as C
 
@@ -34,7 +37,8 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .policy_serving import _KEYS, _SHAPES, BUILTIN_CHECKPOINTS, Policy, load_light_weights
+from .policy_serving import (_FULL_KEYS, _FULL_SHAPES, _KEYS, _SHAPES, BUILTIN_CHECKPOINTS, Policy, check_full_weights, load_full_weights,
+                             load_light_weights)
 from .tournament import get_builtin_agent_names
 from .vec_env import CHEAT_CODES  # noqa: F401  (RULE_BASED's action, written by the fill kernel)
 
@@ -45,20 +49,60 @@ def _light_weights(name, source):
     """A LightActorCritic weight set from a checkpoint path, a dict of arrays in torch layout or a light ``Policy``."""
     if isinstance(source, Policy):
         if not source.use_light_model:
-            raise ValueError(f"{name}: the full-size ActorCritic is not served inside the league (LightActorCritic weight sets only); "
-                             "TournamentEnvWrapper.add_agent takes such a policy for a whole batch")
+            raise ValueError(f"{name}: the full-size ActorCritic is not a LightActorCritic weight set, which is what add_agent takes; "
+                             "add_full_agent serves such a policy")
         source = source.weights
     if isinstance(source, str):
         return load_light_weights(source)
     if not isinstance(source, dict):
         raise TypeError(f"{name}: pass a checkpoint path, a dict of LightActorCritic arrays or a light Policy, not {type(source).__name__}")
     if "conv3_w" in source:
-        raise ValueError(f"{name}: the full-size ActorCritic is not served inside the league (LightActorCritic weight sets only)")
+        raise ValueError(f"{name}: the full-size ActorCritic is not a LightActorCritic weight set, which is what add_agent takes; "
+                         "add_full_agent serves such weights")
     w = {k: np.ascontiguousarray(source[k], np.float32) for k in _KEYS}
     for k in _KEYS:
         if w[k].shape != _SHAPES[k]:
             raise ValueError(f"{name}: {k} has shape {w[k].shape}, LightActorCritic on (4, 42, 42) needs {_SHAPES[k]}")
     return w
+
+
+def _full_weights(name, source):
+    """A full-size ActorCritic weight set (the eight arrays of ``policy_serving._FULL_KEYS``, float32, torch layout) from a checkpoint
+    path (``.npz`` or a reference checkpoint), a dict of arrays (further keys, such as the critic's, are ignored) or a full-size
+    ``Policy``.  Light weight sets are refused with a pointer to ``add_agent``."""
+    if isinstance(source, Policy):
+        if source.use_light_model:
+            raise ValueError(f"{name}: a LightActorCritic policy is not a full-size ActorCritic; add_agent takes it")
+        source = source.weights
+    if isinstance(source, str):
+        return load_full_weights(source)
+    if not isinstance(source, dict):
+        raise TypeError(f"{name}: pass a checkpoint path, a dict of ActorCritic arrays or a full-size Policy, not {type(source).__name__}")
+    missing = [k for k in _FULL_KEYS if k not in source]
+    if missing:
+        if "conv3_w" in missing and all(k in source for k in _KEYS):
+            raise ValueError(f"{name}: a LightActorCritic weight set (no conv3_w) is not a full-size ActorCritic; add_agent takes it")
+        raise ValueError(f"{name}: the full-size ActorCritic needs {list(_FULL_KEYS)}; {missing} are missing")
+    for k in _FULL_KEYS:
+        if tuple(np.shape(source[k])) != _FULL_SHAPES[k]:
+            hint = "; add_agent takes LightActorCritic weight sets" if tuple(np.shape(source[k])) == _SHAPES.get(k) else ""
+            raise ValueError(f"{name}: {k} has shape {tuple(np.shape(source[k]))}, ActorCritic on (4, 42, 42) needs {_FULL_SHAPES[k]}{hint}")
+    return check_full_weights(source, name)
+
+
+def _add_full(self, name, weights, scratch_rows):
+    """``crl_pool_add_full`` for ``LeagueEnvWrapper`` / ``LeagueArena``: what both refuse is looked at before the library is called."""
+    if name in self.agent_names:
+        raise ValueError(f"{name} is in the pool already")
+    if len(self.agent_names) >= N.CRL_LEAGUE_MAX_AGENTS:
+        raise ValueError(f"a pool holds at most {N.CRL_LEAGUE_MAX_AGENTS} agents")
+    rows = 0 if scratch_rows is None else int(scratch_rows)
+    if scratch_rows is not None and rows <= 0:
+        raise ValueError(f"scratch_rows must be positive (None: min(envs, 65536)), not {scratch_rows}")
+    with torch.cuda.device(self.device):
+        N.check(self._L.crl_pool_add_full(self._h, *[weights[k].ctypes.data_as(C.c_void_p) for k in _FULL_KEYS], rows))
+    self.agent_names.append(name)
+    self._kinds.append(N.CRL_POOL_KIND_FULL)
 
 
 class LeagueEnvWrapper:
@@ -144,6 +188,22 @@ class LeagueEnvWrapper:
         if self.ledger is not None:
             self.ledger.set_agents(len(self.agent_names))
 
+    def add_full_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0, scratch_rows=None):
+        """A full-size ActorCritic opponent of one's own (utils/network.py:14-56; ``Policy(..., use_light_model=False)``) -- a checkpoint
+        path (``.npz`` or a reference checkpoint), a dict of the eight arrays in torch layout, or a full-size ``Policy``.  Future draws
+        include it; the assignment in force stays.  Its envs see exactly what a dense ``Policy`` of these weights computes on the same
+        frames.  ``temperature`` / ``epsilon``: its play style (``set_sampling``).  ``scratch_rows``: rows of the league's one activation
+        scratch (16.5 KB each), shared by all full-size agents and fixed by the first of them; None = min(num_envs, 65 536), about
+        1.1 GB at 65 536 envs.  Fewer rows cost more passes over the agent's list in every step."""
+        if getattr(self.env, "R", 42) != 42:
+            raise ValueError("ActorCritic opponents act on 42x42 frames: make the env with resized_dim=42 (add_agent's rule as well)")
+        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
+        _add_full(self, name, _full_weights(name, weights_or_checkpoint), scratch_rows)
+        if temperature or epsilon:
+            self.set_sampling(name, temperature, epsilon)
+        if self.ledger is not None:
+            self.ledger.set_agents(len(self.agent_names))
+
     def set_sampling(self, agent, temperature=1.0, epsilon=0.0):
         """The play style of ``agent`` (a name or an index) from the next step on: see ``_set_sampling``."""
         _set_sampling(self, agent, temperature, epsilon)
@@ -202,7 +262,8 @@ class LeagueEnvWrapper:
         """Debug: {name: env indices the kernels visit for that CNN agent} (sorted host arrays; synchronises)."""
         counts, lists = self._lists(True)
         lists = lists.cpu().numpy()
-        return {n: np.sort(lists[a, :counts[a]]) for a, n in enumerate(self.agent_names) if self._kinds[a] == N.CRL_LEAGUE_LIGHT}
+        return {n: np.sort(lists[a, :counts[a]]) for a, n in enumerate(self.agent_names)
+                if self._kinds[a] in (N.CRL_LEAGUE_LIGHT, N.CRL_POOL_KIND_FULL)}
 
     # ---- the shared history
     def reset_history(self):

@@ -467,7 +467,7 @@ int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uin
  *
  * History: the league owns ONE ring of the last four 42x42 opponent-view frames per env, in crl_policy's layout and with its rule
  * (never cleared at episode ends, one head for all envs).  Every crl_league_act pushes every env's frame, whichever agent the env
- * is assigned to; every LightActorCritic agent reads that ring.  With an assignment that never changes, an env's actions are
+ * is assigned to; every CNN agent reads that ring.  With an assignment that never changes, an env's actions are
  * those of a crl_policy of that agent fed the same frames.
  *
  * League draws (tests restate this in numpy; it does not depend on how a batch is cut into shards):
@@ -495,12 +495,29 @@ int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uin
  *                once on the host), m = max z, e_a = exp(z_a - m), S = (e0 + e1) + e2, r = float(x0 >> 8) * 2^-24 (exact, in
  *                [0, 1)); action 0 if r * S < e0, 1 if r * S < e0 + e1, else 2.  (`exp` is the device library's expf; a draw whose r
  *                lies within its error of a boundary may fall on either side.)
- * The logits written to logits_dev are the raw l_a whatever the style. */
+ * The logits written to logits_dev are the raw l_a whatever the style.
+ *
+ * Full-size agents.  A pool also holds agents of kind CRL_POOL_KIND_FULL: the full-size ActorCritic (utils/network.py:14-56, the
+ * network of crl_policy_create_full; what Policy(..., use_light_model=False) serves), added with crl_pool_add_full.  Such an agent
+ * reads the league's shared ring like every CNN agent, has a list of its envs, takes its play style from crl_sampling_set_agent,
+ * and its rows of logits_dev are written.  Its forward pass is crl_policy_act's for the same frames, bit for bit, whatever envs the
+ * list holds and in whatever order.
+ *   scratch: the activations between its three kernels (15 488 + 1 024 bytes per row, 16.5 KB) live in ONE scratch per league of
+ *            scratch_rows rows, shared by all full-size agents of the pool (their launches are ordered on the stream) and allocated
+ *            by the first crl_pool_add_full.  scratch_rows = 0 means min(num_envs, 65 536): at 65 536 rows that is about 1.1 GB.
+ *            Each agent's weights take 3.96 MB more.
+ *   passes:  the agent's env count is known on the device only, so every crl_league_act enqueues ceil(num_envs / scratch_rows)
+ *            passes of three launches per full-size agent; pass p serves positions [p * scratch_rows, min(count, (p + 1) *
+ *            scratch_rows)) of the list, a pass past the count returns at once.
+ *   sampled actions: drawn with gid = env_id_base + i of the ENV i the row belongs to, not with the row's place in the list.
+ * (The kind is a #define and the entry point is named crl_pool_*: the kind enum and the thirteen crl_league_* entry points stay
+ * what they were.) */
 #define CRL_LEAGUE_MAX_AGENTS 16
 #define CRL_LEAGUE_DOMAIN_OPPONENT 0x4C47554Fu /* "LGUO" */
 #define CRL_LEAGUE_DOMAIN_ACTION 0x4C475541u   /* "LGUA" */
 #define CRL_LEAGUE_DOMAIN_SAMPLE 0x4C475553u   /* "LGUS" */
 enum crl_league_kind { CRL_LEAGUE_RANDOM = 0, CRL_LEAGUE_RULE_BASED = 1, CRL_LEAGUE_LIGHT = 2 };
+#define CRL_POOL_KIND_FULL 3 /* a full-size ActorCritic agent ("full-size agents" above); not a value crl_league_add_builtin takes */
 typedef struct crl_league crl_league;
 /* TournamentEnvWrapper.__init__ (competitive_pong_env.py:10-25) for num_envs envs whose global ids start at env_id_base; the pool is
  * empty, every env is assigned agent 0. */
@@ -513,6 +530,14 @@ int crl_league_add_builtin(crl_league *l, int32_t kind);
 int crl_league_add_light(crl_league *l, const float *conv1_w_host /*[16,4,4,4]*/, const float *conv1_b_host /*[16]*/,
                          const float *conv2_w_host /*[16,16,2,2]*/, const float *conv2_b_host /*[16]*/,
                          const float *actor_w_host /*[3,1600]*/, const float *actor_b_host /*[3]*/);
+/* A full-size ActorCritic checkpoint of the caller's ("full-size agents" above): appends the agent with kind CRL_POOL_KIND_FULL; weights
+ * (host pointers, torch layouts) as for crl_policy_create_full.  scratch_rows: rows of the league's shared activation scratch, 0 =
+ * min(num_envs, 65 536); the first full-size agent fixes it, a later one passes 0 or the same value.  Refuses (CRL_EINVAL, before
+ * any GPU call) a null league or weight pointer, a negative scratch_rows, a full pool and a scratch_rows other than the league's. */
+int crl_pool_add_full(crl_league *l, const float *conv1_w_host /*[16,4,4,4]*/, const float *conv1_b_host /*[16]*/,
+                      const float *conv2_w_host /*[32,16,4,4]*/, const float *conv2_b_host /*[32]*/,
+                      const float *conv3_w_host /*[256,32,11,11]*/, const float *conv3_b_host /*[256]*/,
+                      const float *actor_w_host /*[3,256]*/, const float *actor_b_host /*[3]*/, int64_t scratch_rows);
 /* The play style of agent `agent` of the pool ("sampled actions" above), from the next crl_league_act on; host values, no GPU call.
  * Refuses (CRL_EINVAL) an agent outside the pool, a negative or non-finite temperature (or one so small that 1 / temperature is no
  * float32) and an epsilon outside [0, 1].  An agent at (0, 0) is served by the launch it always had.  (Named crl_sampling_*: the
@@ -529,8 +554,8 @@ int crl_league_get_assignment(crl_league *l, int32_t *ids_out_dev, void *stream)
  * done_dev [N] is non-zero, or for every env when done_dev is NULL.  Rebuilds counts and lists.  No host synchronisation. */
 int crl_league_resample(crl_league *l, const uint8_t *done_dev, void *stream);
 /* Debug / tests: counts_out_dev int32 [CRL_LEAGUE_MAX_AGENTS] (envs per agent); lists_out_dev optional int32 [agents][N]: row a
- * holds the env indices of LightActorCritic agent a in its first counts[a] entries (in no particular order), other rows are
- * left as they are. */
+ * holds the env indices of CNN agent a (LightActorCritic or full-size) in its first counts[a] entries (in no particular order),
+ * other rows are left as they are. */
 int crl_league_get_lists(crl_league *l, int32_t *counts_out_dev, int32_t *lists_out_dev, void *stream);
 /* TournamentEnvWrapper.step's opponent half (competitive_pong_env.py:35-41 `self.current_agent(self.prev_opponent_obs)`), per env:
  * pushes env i's frame (frame_dev + i * frame_stride, as crl_policy_act) onto the shared ring and writes the action of the env's
