@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "crl_internal.h"
+#include "pong_band_span.h"
 #include "pong_device.h"
 
 using namespace crl;
@@ -72,6 +73,7 @@ struct crl_ctx {
     std::vector<void *> allocs;
     // raw mode
     uint8_t *atlas_rgb = nullptr;
+    uint8_t *band_span = nullptr;  // pong_band_span.h: the chunk columns a single point changes, per pair and kind
     int ink_row0 = 0, ink_row1 = 0;
     // gray mode
     GrayTables gray{};
@@ -382,6 +384,10 @@ int crl_create(const crl_opts *opts, const uint8_t *score_atlas_host, crl_ctx **
         std::vector<uint8_t> rgb((size_t)CRL_PONG_ATLAS_BYTES * 3);
         for (size_t i = 0; i < (size_t)CRL_PONG_ATLAS_BYTES; i++) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = c->atlas_host[i];
         rc = dev_upload(c, &c->atlas_rgb, rgb);
+        std::vector<uint8_t> span(pong_band_span_bytes(22));
+        const int bad = pong_band_span_table(c->atlas_host.data(), 22, CRL_PONG_TOP, CRL_PONG_W, r0, r1, span.data());
+        if (!rc && bad) rc = crl_fail(CRL_ESTATE, "score atlas: transition %d changes a pixel outside the ink rows [%d, %d)", bad - 1, r0, r1);
+        if (!rc) rc = dev_upload(c, &c->band_span, span);
     } else {
         rc = setup_gray(c);
     }
@@ -549,7 +555,7 @@ int crl_draw_raw_delta(crl_ctx *c, uint8_t *obs_dev, uint64_t *drawn_dev, int32_
     hipStream_t st = (hipStream_t)stream;
     begin_timed(c, 1, st);
     if (drawn_valid) {
-        launch_pong_raster_raw_delta(c->s.obs_frames, drawn_dev, c->n, c->atlas_rgb, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
+        launch_pong_raster_raw_delta(c->s.obs_frames, drawn_dev, c->n, c->atlas_rgb, c->band_span, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
     } else {
         launch_pong_raster_raw(c->s.obs_frames, c->n, c->atlas_rgb, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
         HIP_TRY(hipMemcpyAsync(drawn_dev, c->s.obs_frames, (size_t)c->n * 8, hipMemcpyDeviceToDevice, st));

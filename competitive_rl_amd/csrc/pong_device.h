@@ -214,9 +214,10 @@ void launch_pong_gather_frames(const uint64_t *frames, const int64_t *idx_dev, i
                                hipStream_t st);
 void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
                             uint8_t *obs, int views, hipStream_t st);
-// stores only the chunks that differ between drawn[i] (what obs holds now) and frames[i], then drawn[i] = frames[i]
-void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
-                                  uint8_t *obs, int views, hipStream_t st);
+// stores only the chunks that differ between drawn[i] (what obs holds now) and frames[i], then drawn[i] = frames[i].  band_span: the
+// device copy of pong_band_span_table()'s table for this atlas (22 x 22 pairs x 2 kinds x {first, last} bytes)
+void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, const uint8_t *band_span,
+                                  int ink_row0, int ink_row1, uint8_t *obs, int views, hipStream_t st);
 
 // Byte offsets of the dense INTER_AREA tables inside the blob the gray kernel stages into
 // LDS: xa/ya = float[5][R] weights (tap k of output index d at [k*R + d]); xs0/xn, ys0/yn =

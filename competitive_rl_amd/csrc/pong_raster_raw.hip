@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "crl_internal.h"
+#include "pong_band_span.h"
 #include "pong_device.h"
 
 namespace crl {
@@ -192,7 +193,12 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 // superset of the differing chunks for ANY pair of descriptors):
 //   exactly one descriptor blank ..................... the whole frame;
 //   both blank ....................................... nothing;
-//   otherwise (sl, sr) differ ........................ every chunk of the score-band ink rows [ink_row0, ink_row1);
+//   otherwise a single point (sl + 1 or sr + 1) ...... in the score-band ink rows [ink_row0, ink_row1), the chunk columns from the
+//                                                      first to the last one in which the band images of the old and the new pair
+//                                                      differ (pong_band_span.h: a table made from the atlas in crl_create; 2-3
+//                                                      columns for most pairs of the shipped atlas, up to 12 where a number gains
+//                                                      a digit), mirrored in the second view's rows >= CRL_PONG_MIRROR_ROW;
+//            (sl, sr) differ in any other way ........ every chunk of the ink rows (a game's end, set_state, scores outside the atlas);
 //            and in rows TOP..BOTTOM-1, per object:   ball: the chunks of both 4 x 4 rectangles;
 //                                                     bat:  its chunk column in the rows of the symmetric difference of its old
 //                                                           and new 15-row spans (<= 8 rows for a 4-px move).
@@ -209,9 +215,14 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 // chunks into a block, so a ball's block can reach two chunks into the neighbouring row, which is a court row too.  Every chunk
 // stored is built from the NEW descriptor by court_chunk(): the chunks of a block that are not dirty are rewritten with the bytes
 // they hold.  Blocks of the old ball's rectangle that the new one covers are stored once.  Two lanes may still store the same
-// block (the ball over a bat's column): both write the new frame's bytes, so the race is benign.  Whole frames and score bands (a
-// few envs per step) are strided over by the same lanes through raw_chunk().  The record is read and then written by the env's
-// own wavefront.  A buffer that is not 64-byte aligned takes G = 1: single chunks, exactly the dirty set.
+// block (the ball over a bat's column): both write the new frame's bytes, so the race is benign.  A point's span is laid out the
+// same way -- chunk of the block, block of the row (per lane `blk <= the row's last block`: a row starts 0 or 2 chunks into a block),
+// ink row -- with every chunk, a block's clean ones and those it holds of the neighbouring row included, built from the new descriptor
+// by raw_chunk() from its absolute index.  Whole frames and whole score bands are strided over by the same lanes through raw_chunk().
+// The record is read and then written by the env's own wavefront.  A buffer that is not 64-byte aligned takes G = 1: single chunks,
+// exactly the dirty set.
+// After a synchronous reset the envs score in step with one another: a launch in which 80-94 % of the envs redraw a band (every
+// ~20th step and the one after it: each of the two buffers sees the point once) is what the spread between launches consists of.
 // Measured on MI355X at 65 536 envs, two views, the launch inside the bench's event brackets (profiles/r08_raw_summary.txt):
 //   one lane per env, 16-byte chunks (round 7) ........ 164 us   3.5 M memory write requests, 95 % of them 32-byte with a mask
 //   L = 32, G = 1 / G = 2 (whole 32-byte sectors) ..... 168 / 164 us   (the requests neither merge nor get cheaper)
@@ -223,6 +234,10 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 //   vector / scalar instructions per wavefront ........ 516 / 295 -> 272 / 148 (SQ counters); no load and no vmcnt wait in the court code
 //   the launch inside the bench's event brackets ....... 96.4 -> 91.3 us; the step 0.1103 -> 0.1051 ms; same requests, same bytes
 // Half the instructions bought a twentieth of the time: the launch is bound by its 3.1 M scattered 64-byte requests, not by issue.
+// Round 10 (profiles/r10_raw_summary.txt): a launch in which 94 % of the envs redraw the whole band holds 20.9 M requests against a
+// court-only launch's 3.1 M and takes 6 x as long; with a point's span it holds 8.7 M (48 per env for the band, the rest because the
+// serve after a point moves the ball and both bats in the same step).  Alternating runs on one box:
+//   the launch inside the bench's event brackets ....... 91.4 -> 66.6 us; the step 0.1052 -> 0.0803 ms; the longest launch 436 -> 171 us
 static constexpr int kDeltaL = 32, kDeltaG = 4;  // lanes per (env, view); chunks per block (4: whole 64-byte memory requests)
 static_assert(kFrameChunks % kDeltaG == 0, "a view starts on a block boundary");
 
@@ -252,8 +267,8 @@ __device__ __forceinline__ BallCols ball_cols(int x) {
 
 template <int VIEWS, int G>
 __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
-                                                                    const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
-                                                                    uint4 *__restrict__ obs, int64_t n) {
+                                                                    const uint4 *__restrict__ atlas_rgb, const uint8_t *__restrict__ band_span,
+                                                                    int ink_row0, int ink_row1, uint4 *__restrict__ obs, int64_t n) {
     static_assert((G == 1 || G == 4) && (VIEWS == 1 || VIEWS == 2), "");
     constexpr int L = kDeltaL, per_env = VIEWS * kFrameChunks, SH = G == 4 ? 2 : 0;
     constexpr int E = 64 / L / VIEWS;  // whole envs per wavefront: one with two views -> uniform descriptor loads
@@ -273,13 +288,39 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
         for (int c = lane; c < kFrameChunks; c += L) out[q_view + c] = raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0);
         return;
     }
+    const int j = lane & (G - 1), u = lane >> SH;  // this lane's chunk of a block; its (row, block) place within an object
     if ((f.sl != g.sl || f.sr != g.sr) && ink_row1 > ink_row0) {  // the score band's ink rows
-        const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
-        for (int c = lane; c < cn; c += L) out[c0 + c] = raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
+        // a single point: the source chunk columns [s0, s1] in which the two band images differ, from the table of the old pair
+        const int kind = f.sl == g.sl;  // 0: left + 1, 1: right + 1
+        int s0 = kBandWholeFirst, s1 = kBandWholeLast;
+        if (band_span && g.sl < 22 && g.sr < 22 && f.sl == g.sl + 1 - kind && f.sr == g.sr + kind) {
+            // (a pair's two entries are one dword: a scalar load where the descriptors are wave-uniform)
+            const uint32_t e = reinterpret_cast<const uint32_t *>(band_span)[g.sl * 22 + g.sr] >> (16 * kind);
+            s0 = e & 255, s1 = (e >> 8) & 255;
+        }
+        if (s1 >= kRowChunks) {  // every other pair (a game's end, set_state, a successor outside the atlas): every chunk of the ink rows
+            const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
+            for (int c = lane; c < cn; c += L) out[c0 + c] = raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
+        } else if (s0 <= s1) {
+            // place = (ink row, block of the row): a row's span touches at most nb blocks (it starts anywhere within its first
+            // block), 1 << bs >= nb of them are a row's share of a trip's L / G places, and a trip takes (L / G) >> bs rows
+            const int w = s1 - s0 + 1, nb = G == 1 ? w : (w + 2 * G - 2) >> SH;
+            int bs = 0;
+            while ((1 << bs) < nb && (1 << bs) < (L >> SH)) bs++;
+            const int dr = u >> bs, bu = u & ((1 << bs) - 1);
+            for (int r0 = ink_row0; r0 < ink_row1; r0 += (L >> SH) >> bs) {
+                const int row = r0 + dr, q_row = q_view + row * kRowChunks;
+                const bool mir = view != 0 && row >= CRL_PONG_MIRROR_ROW;
+                const int first = (q_row + (mir ? kRowChunks - 1 - s1 : s0)) >> SH, last = (q_row + (mir ? kRowChunks - 1 - s0 : s1)) >> SH;
+                for (int b0 = 0; b0 < nb; b0 += 1 << bs) {
+                    const int blk = first + b0 + bu, q = (blk << SH) + j;  // (a block may reach into the neighbouring row: raw_chunk() draws that row's chunk)
+                    if (row < ink_row1 && blk <= last) out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
+                }
+            }
+        }
     }
 
     const bool mirror = view != 0;  // (court rows are all >= CRL_PONG_MIRROR_ROW)
-    const int j = lane & (G - 1), u = lane >> SH;  // this lane's chunk of a block; its (row, block) place within an object
     auto in_court = [](int row) { return (unsigned)(row - CRL_PONG_TOP) < (unsigned)(CRL_PONG_BOTTOM - CRL_PONG_TOP); };
 
     if (f.x != g.x || f.y != g.y) {  // the two balls: place u = (row of the ball, first or second block of the row)
@@ -485,8 +526,8 @@ __global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_lanes_ke
 }
 #endif  // CRL_ABLATION
 
-void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
-                                  uint8_t *obs, int views, hipStream_t st) {
+void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, const uint8_t *band_span,
+                                  int ink_row0, int ink_row1, uint8_t *obs, int views, hipStream_t st) {
     if (n <= 0 || (views != 1 && views != 2)) return;
     const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
     uint4 *ob = reinterpret_cast<uint4 *>(obs);
@@ -523,13 +564,20 @@ void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64
 #endif
     // a block is a whole memory request only in a buffer aligned to it; crl_draw_raw_delta admits any 16-byte-aligned one: single chunks there
     const bool blocks_ok = (uintptr_t)obs % (16 * kDeltaG) == 0;
+    // (profiling build only: CRL_RAW_BAND_WHOLE=1 stores every chunk of the ink rows at any score change, as before the span table)
+    static const bool band_whole = CRL_ABL(getenv("CRL_RAW_BAND_WHOLE") && atoi(getenv("CRL_RAW_BAND_WHOLE")));
+    const uint8_t *span = band_whole ? nullptr : band_span;
+#define CRL_LAUNCH_DELTA_SPAN(V, G)                                                                                                      \
+    hipLaunchKernelGGL((pong_raster_raw_delta_kernel<V, G>), dim3((unsigned)((n * V * kDeltaL + 255) / 256)), dim3(256), 0, st, frames, drawn, at, \
+                       span, ink_row0, ink_row1, ob, n)
     if (views == 2) {
-        if (blocks_ok) CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<2, kDeltaG>), 2, kDeltaL);
-        else CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<2, 1>), 2, kDeltaL);
+        if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(2, kDeltaG);
+        else CRL_LAUNCH_DELTA_SPAN(2, 1);
     } else {
-        if (blocks_ok) CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<1, kDeltaG>), 1, kDeltaL);
-        else CRL_LAUNCH_DELTA((pong_raster_raw_delta_kernel<1, 1>), 1, kDeltaL);
+        if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(1, kDeltaG);
+        else CRL_LAUNCH_DELTA_SPAN(1, 1);
     }
+#undef CRL_LAUNCH_DELTA_SPAN
 #undef CRL_LAUNCH_DELTA
 }
 
