@@ -83,6 +83,13 @@ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
     }
 }
 
+// include/crl.h "league draws": value = floor(x0 * m / 2^32) of Philox4x32-10, counter (gid lo, gid hi, n, domain), key = seed
+__device__ inline uint32_t league_draw(uint64_t seed, uint64_t gid, uint32_t n, uint32_t domain, uint32_t m) {
+    uint32_t c[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), n, domain};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (uint32_t)(((uint64_t)c[0] * m) >> 32);
+}
+
 __device__ inline void serve(PongEnv &e, const ServeSrc &s, int64_t env) {
     double u;
     int bx, by;

@@ -35,13 +35,6 @@ static constexpr int kLRingBytes = CRL_POLICY_STACK * kRingPlanePad;   // 7104 p
 static constexpr int kLThreads = 256;
 static constexpr int kMaxAgents = CRL_LEAGUE_MAX_AGENTS;
 
-// include/crl.h "league draws": value = floor(x0 * m / 2^32) of Philox4x32-10, counter (gid lo, gid hi, n, domain), key = seed
-__device__ inline uint32_t league_draw(uint64_t seed, uint64_t gid, uint32_t n, uint32_t domain, uint32_t m) {
-    uint32_t c[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), n, domain};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    return (uint32_t)(((uint64_t)c[0] * m) >> 32);
-}
-
 struct LeagueExplore {
     uint32_t eps_q[kMaxAgents];  // RULE_BASED agents: the explore threshold of "sampled actions" (0: always the cheat code); 0 for every other kind
 };

@@ -37,8 +37,10 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .ledger import LeagueLedger
 from .policy_serving import (_FULL_KEYS, _FULL_SHAPES, _KEYS, _SHAPES, BUILTIN_CHECKPOINTS, Policy, check_full_weights, load_full_weights,
                              load_light_weights)
+from .rules import check_sampling, league_draw_reference, league_sample_reference, sample_eps_q  # noqa: F401  (re-exported)
 from .tournament import get_builtin_agent_names
 from .vec_env import CHEAT_CODES  # noqa: F401  (RULE_BASED's action, written by the fill kernel)
 
@@ -90,22 +92,150 @@ def _full_weights(name, source):
     return check_full_weights(source, name)
 
 
-def _add_full(self, name, weights, scratch_rows):
-    """``crl_pool_add_full`` for ``LeagueEnvWrapper`` / ``LeagueArena``: what both refuse is looked at before the library is called."""
-    if name in self.agent_names:
-        raise ValueError(f"{name} is in the pool already")
-    if len(self.agent_names) >= N.CRL_LEAGUE_MAX_AGENTS:
-        raise ValueError(f"a pool holds at most {N.CRL_LEAGUE_MAX_AGENTS} agents")
-    rows = 0 if scratch_rows is None else int(scratch_rows)
-    if scratch_rows is not None and rows <= 0:
-        raise ValueError(f"scratch_rows must be positive (None: min(envs, 65536)), not {scratch_rows}")
-    with torch.cuda.device(self.device):
-        N.check(self._L.crl_pool_add_full(self._h, *[weights[k].ctypes.data_as(C.c_void_p) for k in _FULL_KEYS], rows))
-    self.agent_names.append(name)
-    self._kinds.append(N.CRL_POOL_KIND_FULL)
+class AgentPool:
+    """What ``LeagueEnvWrapper`` and ``LeagueArena`` (arena.py) both are: a ``crl_league`` handle serving ``rows`` virtual envs, and the
+    pool of agents behind it -- names, kinds, play styles, the shared frame rings.  A subclass sets ``device`` and calls ``_open_pool``
+    from its constructor; ``_check_new_agent`` and ``_pool_grew`` are its hooks around ``add_agent`` / ``add_full_agent``."""
+
+    def _open_pool(self, rows, env_id_base, seed, agent_names):
+        self._rows = int(rows)
+        self._L = N.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_league_create(self.device.index or 0, self._rows, int(env_id_base), int(seed) & (2 ** 64 - 1), C.byref(h)))
+        self._h = h
+        self.agent_names, self._kinds = [], []
+        for name in get_builtin_agent_names() if agent_names is None else list(agent_names):
+            if name in _BUILTIN_KINDS:
+                self._add(name, _BUILTIN_KINDS[name])
+            elif name in BUILTIN_CHECKPOINTS:
+                self._add(name, N.CRL_LEAGUE_LIGHT, load_light_weights(BUILTIN_CHECKPOINTS[name]))
+            else:
+                raise ValueError("Unknown agent name: {}".format(name))
+        if not self.agent_names:
+            raise ValueError("the pool is empty")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _add(self, name, kind, weights=None, scratch_rows=None):
+        """A builtin, a LightActorCritic or a full-size agent: what the pool refuses is looked at before the library is called."""
+        if name in self.agent_names:
+            raise ValueError(f"{name} is in the pool already")
+        if len(self.agent_names) >= N.CRL_LEAGUE_MAX_AGENTS:
+            raise ValueError(f"a pool holds at most {N.CRL_LEAGUE_MAX_AGENTS} agents")
+        rows = 0 if scratch_rows is None else int(scratch_rows)
+        if scratch_rows is not None and rows <= 0:
+            raise ValueError(f"scratch_rows must be positive (None: min(envs, 65536)), not {scratch_rows}")
+        with torch.cuda.device(self.device):
+            if kind == N.CRL_POOL_KIND_FULL:
+                N.check(self._L.crl_pool_add_full(self._h, *[weights[k].ctypes.data_as(C.c_void_p) for k in _FULL_KEYS], rows))
+            elif kind == N.CRL_LEAGUE_LIGHT:
+                N.check(self._L.crl_league_add_light(self._h, *[weights[k].ctypes.data_as(C.c_void_p) for k in _KEYS]))
+            else:
+                N.check(self._L.crl_league_add_builtin(self._h, kind))
+        self.agent_names.append(name)
+        self._kinds.append(kind)
+
+    def _check_new_agent(self, what):
+        """Hook: raise if the env cannot take a CNN agent (``what``: its network, for the message)."""
+
+    def _pool_grew(self):
+        """Hook: the pool holds one agent more."""
+
+    def _add_cnn(self, name, kind, what, weights_of, source, temperature, epsilon, scratch_rows=None):
+        self._check_new_agent(what)
+        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
+        self._add(name, kind, weights_of(name, source), scratch_rows)
+        if temperature or epsilon:
+            self.set_sampling(name, temperature, epsilon)
+        self._pool_grew()
+
+    def add_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0):
+        """Beyond the reference: a LightActorCritic agent of one's own -- a checkpoint path (``.npz`` or a reference checkpoint), a
+        dict of the six arrays in torch layout, or a light ``Policy`` (a trainer's snapshot).  Future draws include it (in the arena its
+        cells enter the draw table with weight 1); the assignment / the pairs in force stay.  Full-size networks are refused here:
+        ``add_full_agent`` takes them.  ``temperature`` / ``epsilon``: its play style (``set_sampling``); the default is greedy."""
+        self._add_cnn(name, N.CRL_LEAGUE_LIGHT, "LightActorCritic", _light_weights, weights_or_checkpoint, temperature, epsilon)
+
+    def add_full_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0, scratch_rows=None):
+        """A full-size ActorCritic agent of one's own (utils/network.py:14-56; ``Policy(..., use_light_model=False)``) -- a checkpoint
+        path (``.npz`` or a reference checkpoint), a dict of the eight arrays in torch layout, or a full-size ``Policy``.  Future draws
+        include it; the assignment / the pairs in force stay.  Its envs see exactly what a dense ``Policy`` of these weights computes on
+        the same frames.  ``temperature`` / ``epsilon``: its play style (``set_sampling``).  ``scratch_rows``: rows of the pool's one
+        activation scratch (16.5 KB each), shared by all full-size agents and fixed by the first of them; None = min(rows, 65 536) with
+        rows the envs of a league and the 2 * num_envs seats of an arena, about 1.1 GB at 65 536.  Fewer rows cost more passes over the
+        agent's list in every step."""
+        self._add_cnn(name, N.CRL_POOL_KIND_FULL, "ActorCritic", _full_weights, weights_or_checkpoint, temperature, epsilon, scratch_rows)
+
+    def _agent_index(self, agent):
+        if isinstance(agent, str):
+            if agent not in self.agent_names:
+                raise ValueError(f"{agent} is not in the pool {self.agent_names}")
+            return self.agent_names.index(agent)
+        if not 0 <= int(agent) < len(self.agent_names):
+            raise ValueError(f"agent {agent} is not in the pool of {len(self.agent_names)}")
+        return int(agent)
+
+    def set_sampling(self, agent, temperature=1.0, epsilon=0.0):
+        """The play style of ``agent`` (a name or an index; in the arena: in either seat) from the next step on: ``temperature`` 0 plays
+        the argmax, T > 0 samples from softmax(logits / T); ``epsilon``: the share of steps with a uniform action instead (RULE_BASED:
+        instead of the cheat code).  Neither has an effect on RANDOM, the temperature none on RULE_BASED.  Host values that travel with
+        the next launches: no synchronisation."""
+        t, e = check_sampling(temperature, epsilon)
+        N.check(self._L.crl_sampling_set_agent(self._h, self._agent_index(agent), t, e))
+
+    def sampling(self):
+        """Host dict ``name -> (temperature, epsilon)`` of the whole pool (no GPU work)."""
+        out = {}
+        for a, name in enumerate(self.agent_names):
+            t, e = C.c_float(), C.c_float()
+            N.check(self._L.crl_sampling_get_agent(self._h, a, C.byref(t), C.byref(e)))
+            out[name] = (t.value, e.value)
+        return out
+
+    def get_agent_names(self):
+        return self.agent_names
+
+    # ---- the shared history
+    def reset_history(self):
+        """Zeroes the frame rings (``Policy.reset``)."""
+        N.check(self._L.crl_league_reset(self._h, self._stream()))
+
+    def get_stack(self):
+        out = torch.empty((self._rows, 4, 42, 42), dtype=torch.uint8, device=self.device)
+        N.check(self._L.crl_league_get_stack(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def set_stack(self, stack):
+        s = torch.as_tensor(stack).to(self.device, torch.uint8).contiguous()
+        assert tuple(s.shape) == (self._rows, 4, 42, 42)
+        N.check(self._L.crl_league_set_stack(self._h, C.c_void_p(s.data_ptr()), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()
+
+    # ---- lifetime: the handle's part
+    def _seed_pool(self, seed):
+        N.check(self._L.crl_league_seed(self._h, int(seed or 0) & (2 ** 64 - 1), self._stream()))
+
+    def _close_pool(self):
+        """Destroys the handle; False if it was closed before."""
+        if not getattr(self, "_h", None):
+            return False
+        torch.cuda.synchronize(self.device)
+        self._L.crl_league_destroy(self._h)
+        self._h = None
+        return True
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._L.crl_league_destroy(self._h)
+                self._h = None
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
 
 
-class LeagueEnvWrapper:
+class LeagueEnvWrapper(AgentPool):
     """Same single-agent protocol as ``TournamentEnvWrapper`` (step / step_device / reset / reset_opponent / get_agent_names / seed /
     close); see the module docstring for what differs.  ``env_id_base``: the global id of env 0 (default: the wrapped env's).
     ``ledger``: None (no books), True (the wrapper builds a ``LeagueLedger`` with its own seed and id base, and closes it) or a
@@ -127,28 +257,12 @@ class LeagueEnvWrapper:
         self.observation_space, self.action_space = env.observation_space[0], env.action_space[0]
         self.prev_opponent_obs = None  # what the opponents act on: the right-hand view of the previous step / reset
         self.record_logits = False     # tests: keep the CNN agents' logits of every step (``logits()``)
-        self._L = N.load()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(self._L.crl_league_create(self.device.index or 0, self.num_envs, self.env_id_base, int(seed) & (2 ** 64 - 1), C.byref(h)))
-        self._h = h
-        self.agent_names, self._kinds = [], []
         self._act = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
         self._logits = torch.zeros((self.num_envs, 3), dtype=torch.float32, device=self.device)
-        for name in names:
-            if name in _BUILTIN_KINDS:
-                self._add(name, _BUILTIN_KINDS[name], None)
-            elif name in BUILTIN_CHECKPOINTS:
-                self._add(name, N.CRL_LEAGUE_LIGHT, load_light_weights(BUILTIN_CHECKPOINTS[name]))
-            else:
-                raise ValueError("Unknown agent name: {}".format(name))
-        if not self.agent_names:
-            raise ValueError("the pool is empty")
+        self._open_pool(self.num_envs, self.env_id_base, seed, names)
         self.set_opponents("RULE_BASED" if "RULE_BASED" in self.agent_names else 0)  # the reference starts with RULE_BASED
         self.ledger, self._own_ledger = None, ledger is True
         if ledger is not None and ledger is not False:
-            from .ledger import LeagueLedger
-
             if ledger is True:
                 ledger = LeagueLedger(self.num_envs, len(self.agent_names), self.device, seed=seed, env_id_base=self.env_id_base)
             if not isinstance(ledger, LeagueLedger):
@@ -159,61 +273,14 @@ class LeagueEnvWrapper:
             self.ledger = ledger
             self._ids = [torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device) for _ in range(2)]  # played / next
 
-    # ---- pool
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _add(self, name, kind, weights):
-        assert name not in self.agent_names, name
-        if len(self.agent_names) >= N.CRL_LEAGUE_MAX_AGENTS:
-            raise ValueError(f"a league holds at most {N.CRL_LEAGUE_MAX_AGENTS} agents")
-        with torch.cuda.device(self.device):
-            if kind == N.CRL_LEAGUE_LIGHT:
-                N.check(self._L.crl_league_add_light(self._h, *[weights[k].ctypes.data_as(C.c_void_p) for k in _KEYS]))
-            else:
-                N.check(self._L.crl_league_add_builtin(self._h, kind))
-        self.agent_names.append(name)
-        self._kinds.append(kind)
-
-    def add_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0):
-        """Beyond the reference: a LightActorCritic opponent of one's own -- a checkpoint path (``.npz`` or a reference checkpoint), a
-        dict of the six arrays in torch layout, or a light ``Policy``.  Future draws include it; the assignment in force stays.
-        ``temperature`` / ``epsilon``: its play style (``set_sampling``); the default is greedy."""
+    # ---- pool: the hooks
+    def _check_new_agent(self, what):
         if getattr(self.env, "R", 42) != 42:
-            raise ValueError("LightActorCritic opponents act on 42x42 frames: make the env with resized_dim=42")
-        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
-        self._add(name, N.CRL_LEAGUE_LIGHT, _light_weights(name, weights_or_checkpoint))
-        if temperature or epsilon:
-            self.set_sampling(name, temperature, epsilon)
+            raise ValueError(f"{what} opponents act on 42x42 frames: make the env with resized_dim=42")
+
+    def _pool_grew(self):
         if self.ledger is not None:
             self.ledger.set_agents(len(self.agent_names))
-
-    def add_full_agent(self, name, weights_or_checkpoint, temperature=0.0, epsilon=0.0, scratch_rows=None):
-        """A full-size ActorCritic opponent of one's own (utils/network.py:14-56; ``Policy(..., use_light_model=False)``) -- a checkpoint
-        path (``.npz`` or a reference checkpoint), a dict of the eight arrays in torch layout, or a full-size ``Policy``.  Future draws
-        include it; the assignment in force stays.  Its envs see exactly what a dense ``Policy`` of these weights computes on the same
-        frames.  ``temperature`` / ``epsilon``: its play style (``set_sampling``).  ``scratch_rows``: rows of the league's one activation
-        scratch (16.5 KB each), shared by all full-size agents and fixed by the first of them; None = min(num_envs, 65 536), about
-        1.1 GB at 65 536 envs.  Fewer rows cost more passes over the agent's list in every step."""
-        if getattr(self.env, "R", 42) != 42:
-            raise ValueError("ActorCritic opponents act on 42x42 frames: make the env with resized_dim=42 (add_agent's rule as well)")
-        check_sampling(temperature, epsilon)  # (before the agent enters the pool)
-        _add_full(self, name, _full_weights(name, weights_or_checkpoint), scratch_rows)
-        if temperature or epsilon:
-            self.set_sampling(name, temperature, epsilon)
-        if self.ledger is not None:
-            self.ledger.set_agents(len(self.agent_names))
-
-    def set_sampling(self, agent, temperature=1.0, epsilon=0.0):
-        """The play style of ``agent`` (a name or an index) from the next step on: see ``_set_sampling``."""
-        _set_sampling(self, agent, temperature, epsilon)
-
-    def sampling(self):
-        """Host dict ``name -> (temperature, epsilon)`` of the whole pool (no GPU work)."""
-        return _get_sampling(self)
-
-    def get_agent_names(self):
-        return self.agent_names
 
     # ---- assignment
     def set_opponents(self, ids):
@@ -264,22 +331,6 @@ class LeagueEnvWrapper:
         lists = lists.cpu().numpy()
         return {n: np.sort(lists[a, :counts[a]]) for a, n in enumerate(self.agent_names)
                 if self._kinds[a] in (N.CRL_LEAGUE_LIGHT, N.CRL_POOL_KIND_FULL)}
-
-    # ---- the shared history
-    def reset_history(self):
-        """Zeroes the shared frame ring (``Policy.reset``)."""
-        N.check(self._L.crl_league_reset(self._h, self._stream()))
-
-    def get_stack(self):
-        out = torch.empty((self.num_envs, 4, 42, 42), dtype=torch.uint8, device=self.device)
-        N.check(self._L.crl_league_get_stack(self._h, C.c_void_p(out.data_ptr()), self._stream()))
-        return out
-
-    def set_stack(self, stack):
-        s = torch.as_tensor(stack).to(self.device, torch.uint8).contiguous()
-        assert tuple(s.shape) == (self.num_envs, 4, 42, 42)
-        N.check(self._L.crl_league_set_stack(self._h, C.c_void_p(s.data_ptr()), self._stream()))
-        torch.cuda.current_stream(self.device).synchronize()
 
     def logits(self):
         """float32 (N, 3): with ``record_logits`` set, the logits of the last step for envs on a CNN agent (other rows keep what they held)."""
@@ -365,124 +416,12 @@ class LeagueEnvWrapper:
         """Seeds the wrapped env and re-keys the league's draws (sampled and explored actions included) and its ledger's (all draw
         counters start over)."""
         self.env.seed(s)
-        N.check(self._L.crl_league_seed(self._h, int(s or 0) & (2 ** 64 - 1), self._stream()))
+        self._seed_pool(s)
         if self.ledger is not None:
             self.ledger.seed(s)
 
     def close(self):
-        if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
-            self._L.crl_league_destroy(self._h)
-            self._h = None
+        if self._close_pool():
             if self._own_ledger and self.ledger is not None:
                 self.ledger.close()
             self.env.close()
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._L.crl_league_destroy(self._h)
-                self._h = None
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass
-
-
-def check_sampling(temperature, epsilon):
-    """What ``crl_sampling_set_agent`` / ``crl_policy_set_sampling`` accept, as float32 values: a finite temperature >= 0 (whose
-    reciprocal is a float32) and an epsilon in [0, 1]."""
-    with np.errstate(over="ignore", divide="ignore"):
-        t, e = np.float32(temperature), np.float32(epsilon)
-        if not (np.isfinite(t) and t >= 0) or (t > 0 and not np.isfinite(np.float32(1) / t)):
-            raise ValueError(f"temperature must be finite and >= 0 (and 1 / temperature a float32), not {temperature}")
-    if not 0 <= e <= 1:
-        raise ValueError(f"epsilon must lie in [0, 1], not {epsilon}")
-    return float(t), float(e)
-
-
-def _agent_index(self, agent):
-    if isinstance(agent, str):
-        if agent not in self.agent_names:
-            raise ValueError(f"{agent} is not in the pool {self.agent_names}")
-        return self.agent_names.index(agent)
-    if not 0 <= int(agent) < len(self.agent_names):
-        raise ValueError(f"agent {agent} is not in the pool of {len(self.agent_names)}")
-    return int(agent)
-
-
-def _set_sampling(self, agent, temperature, epsilon):
-    """``LeagueEnvWrapper.set_sampling`` / ``LeagueArena.set_sampling``: ``temperature`` 0 plays the argmax, T > 0 samples from
-    softmax(logits / T); ``epsilon``: the share of steps with a uniform action instead (RULE_BASED: instead of the cheat code).  Neither
-    has an effect on RANDOM, the temperature none on RULE_BASED.  Host values that travel with the next launches: no synchronisation."""
-    t, e = check_sampling(temperature, epsilon)
-    N.check(self._L.crl_sampling_set_agent(self._h, _agent_index(self, agent), t, e))
-
-
-def _get_sampling(self):
-    out = {}
-    for a, name in enumerate(self.agent_names):
-        t, e = C.c_float(), C.c_float()
-        N.check(self._L.crl_sampling_get_agent(self._h, a, C.byref(t), C.byref(e)))
-        out[name] = (t.value, e.value)
-    return out
-
-
-def sample_eps_q(epsilon):
-    """The explore threshold of "sampled actions": min(floor(epsilon * 2^32), 0xFFFFFFFF), in double from the float32 epsilon."""
-    return min(int(np.floor(float(np.float32(epsilon)) * 4294967296.0)), 0xFFFFFFFF)
-
-
-def _philox4x32_10(gid, counter, domain, seed):
-    """The four result words (uint64 arrays holding 32 bits) of counter (gid lo, gid hi, counter, domain) under key (seed lo, seed hi)."""
-    gid = np.asarray(gid, np.uint64)
-    counter = np.asarray(counter, np.uint64)
-    shape = np.broadcast(gid, counter).shape
-    mask = np.uint64(0xFFFFFFFF)
-    c = [np.broadcast_to(gid & mask, shape).copy(), np.broadcast_to(gid >> np.uint64(32), shape).copy(),
-         np.broadcast_to(counter & mask, shape).copy(), np.full(shape, int(domain) & 0xFFFFFFFF, np.uint64)]
-    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c
-
-
-def league_sample_reference(seed, gid, n, logits, temperature, epsilon):
-    """The rule of include/crl.h "sampled actions" in numpy: one Philox4x32-10 call with counter (gid lo, gid hi, n,
-    CRL_LEAGUE_DOMAIN_SAMPLE) under the seed gives x0, x1, x2; if x1 < eps_q the action is (x2 * 3) >> 32 (explored); otherwise the
-    first-index argmax for ``temperature`` 0; otherwise the inverse-CDF draw of softmax(logits * inv_t) at r = (x0 >> 8) * 2^-24, with
-    inv_t = float32(1 / temperature) as the kernels receive it -- computed HERE in float64, so ``margin`` says how far r lay from the
-    nearer boundary: min(|r - e0 / S|, |r - (e0 + e1) / S|), inf for greedy and explored draws.  A kernel's float32 ``exp`` may decide a
-    draw of tiny margin the other way.  ``gid``, ``n`` broadcast against ``logits[..., 3]``; ``temperature`` / ``epsilon`` are scalars.
-    Returns (action int64, explored bool, margin float64).  Host code for tests and for callers that want to predict a draw; the
-    kernels do not use it."""
-    t, _ = check_sampling(temperature, epsilon)
-    lg = np.asarray(logits, np.float64)
-    if lg.shape[-1] != 3:
-        raise ValueError("logits[..., 3]")
-    shape = np.broadcast(np.asarray(gid), np.asarray(n), lg[..., 0]).shape
-    x = _philox4x32_10(np.broadcast_to(np.asarray(gid, np.uint64), shape), np.broadcast_to(np.asarray(n, np.uint64), shape),
-                       N.CRL_LEAGUE_DOMAIN_SAMPLE, seed)
-    lg = np.broadcast_to(lg, shape + (3,))
-    explored = x[1] < np.uint64(sample_eps_q(epsilon))
-    action = ((x[2] * np.uint64(3)) >> np.uint64(32)).astype(np.int64)
-    margin = np.full(shape, np.inf)
-    greedy = np.argmax(lg, axis=-1).astype(np.int64)  # (first index on ties)
-    if t == 0:
-        return np.where(explored, action, greedy), explored, margin
-    z = lg * np.float64(np.float32(1) / np.float32(t))
-    e = np.exp(z - z.max(axis=-1, keepdims=True))
-    s = e.sum(axis=-1)
-    b0, b1 = e[..., 0] / s, (e[..., 0] + e[..., 1]) / s
-    r = (x[0] >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
-    sampled = np.where(r < b0, 0, np.where(r < b1, 1, 2)).astype(np.int64)
-    margin = np.where(explored, np.inf, np.minimum(np.abs(r - b0), np.abs(r - b1)))
-    return np.where(explored, action, sampled), explored, margin
-
-
-def league_draw_reference(seed, gid, counter, domain, m):
-    """The league's draw rule in numpy (include/crl.h "league draws"): Philox4x32-10 word 0 of counter (gid lo, gid hi, counter,
-    domain) under key (seed lo, seed hi), scaled to [0, m) by a multiply-high.  Arrays broadcast; returns int64.  Host code for
-    tests and for callers that want to predict an assignment; the kernels do not use it."""
-    c = _philox4x32_10(gid, counter, domain, seed)
-    return ((c[0] * np.uint64(m)) >> np.uint64(32)).astype(np.int64)

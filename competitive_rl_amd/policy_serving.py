@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .rules import check_sampling
 
 ASSETS = os.path.join(N.PKG, "assets")
 BUILTIN_CHECKPOINTS = {"WEAK": os.path.join(ASSETS, "pong_policy_weak.npz"),
@@ -170,8 +171,6 @@ class Policy:
         softmax(logits / T) -- the reference's ``compute_action(obs, deterministic=False)`` at T = 1 --, ``epsilon`` is the share of
         uniform actions.  ``seed`` keys the draws, env i draws as global id ``env_id_base + i``, and the call counter starts over.
         ``set_sampling(0, 0)`` is greedy again; ``compute_action`` keeps its own (host-side) sampling."""
-        from .league import check_sampling
-
         t, e = check_sampling(temperature, epsilon)
         N.check(self._L.crl_policy_set_sampling(self._h, t, e, int(seed) & (2 ** 64 - 1), int(env_id_base)))
 

@@ -1,0 +1,81 @@
+"""The host-side rules of the league, the ledger and the arena that need no GPU and no other module of the package: what a play style
+may be (``check_sampling``) and the numpy restatements of the device draws (include/crl.h "league draws", "sampled actions").  A leaf:
+``league``, ``ledger``, ``arena`` and ``policy_serving`` import it, it imports none of them.
+"""
+import numpy as np
+
+from . import _native as N
+
+
+def check_sampling(temperature, epsilon):
+    """What ``crl_sampling_set_agent`` / ``crl_policy_set_sampling`` accept, as float32 values: a finite temperature >= 0 (whose
+    reciprocal is a float32) and an epsilon in [0, 1]."""
+    with np.errstate(over="ignore", divide="ignore"):
+        t, e = np.float32(temperature), np.float32(epsilon)
+        if not (np.isfinite(t) and t >= 0) or (t > 0 and not np.isfinite(np.float32(1) / t)):
+            raise ValueError(f"temperature must be finite and >= 0 (and 1 / temperature a float32), not {temperature}")
+    if not 0 <= e <= 1:
+        raise ValueError(f"epsilon must lie in [0, 1], not {epsilon}")
+    return float(t), float(e)
+
+
+def sample_eps_q(epsilon):
+    """The explore threshold of "sampled actions": min(floor(epsilon * 2^32), 0xFFFFFFFF), in double from the float32 epsilon."""
+    return min(int(np.floor(float(np.float32(epsilon)) * 4294967296.0)), 0xFFFFFFFF)
+
+
+def _philox4x32_10(gid, counter, domain, seed):
+    """The four result words (uint64 arrays holding 32 bits) of counter (gid lo, gid hi, counter, domain) under key (seed lo, seed hi)."""
+    gid = np.asarray(gid, np.uint64)
+    counter = np.asarray(counter, np.uint64)
+    shape = np.broadcast(gid, counter).shape
+    mask = np.uint64(0xFFFFFFFF)
+    c = [np.broadcast_to(gid & mask, shape).copy(), np.broadcast_to(gid >> np.uint64(32), shape).copy(),
+         np.broadcast_to(counter & mask, shape).copy(), np.full(shape, int(domain) & 0xFFFFFFFF, np.uint64)]
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c
+
+
+def league_sample_reference(seed, gid, n, logits, temperature, epsilon):
+    """The rule of include/crl.h "sampled actions" in numpy: one Philox4x32-10 call with counter (gid lo, gid hi, n,
+    CRL_LEAGUE_DOMAIN_SAMPLE) under the seed gives x0, x1, x2; if x1 < eps_q the action is (x2 * 3) >> 32 (explored); otherwise the
+    first-index argmax for ``temperature`` 0; otherwise the inverse-CDF draw of softmax(logits * inv_t) at r = (x0 >> 8) * 2^-24, with
+    inv_t = float32(1 / temperature) as the kernels receive it -- computed HERE in float64, so ``margin`` says how far r lay from the
+    nearer boundary: min(|r - e0 / S|, |r - (e0 + e1) / S|), inf for greedy and explored draws.  A kernel's float32 ``exp`` may decide a
+    draw of tiny margin the other way.  ``gid``, ``n`` broadcast against ``logits[..., 3]``; ``temperature`` / ``epsilon`` are scalars.
+    Returns (action int64, explored bool, margin float64).  Host code for tests and for callers that want to predict a draw; the
+    kernels do not use it."""
+    t, _ = check_sampling(temperature, epsilon)
+    lg = np.asarray(logits, np.float64)
+    if lg.shape[-1] != 3:
+        raise ValueError("logits[..., 3]")
+    shape = np.broadcast(np.asarray(gid), np.asarray(n), lg[..., 0]).shape
+    x = _philox4x32_10(np.broadcast_to(np.asarray(gid, np.uint64), shape), np.broadcast_to(np.asarray(n, np.uint64), shape),
+                       N.CRL_LEAGUE_DOMAIN_SAMPLE, seed)
+    lg = np.broadcast_to(lg, shape + (3,))
+    explored = x[1] < np.uint64(sample_eps_q(epsilon))
+    action = ((x[2] * np.uint64(3)) >> np.uint64(32)).astype(np.int64)
+    margin = np.full(shape, np.inf)
+    greedy = np.argmax(lg, axis=-1).astype(np.int64)  # (first index on ties)
+    if t == 0:
+        return np.where(explored, action, greedy), explored, margin
+    z = lg * np.float64(np.float32(1) / np.float32(t))
+    e = np.exp(z - z.max(axis=-1, keepdims=True))
+    s = e.sum(axis=-1)
+    b0, b1 = e[..., 0] / s, (e[..., 0] + e[..., 1]) / s
+    r = (x[0] >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+    sampled = np.where(r < b0, 0, np.where(r < b1, 1, 2)).astype(np.int64)
+    margin = np.where(explored, np.inf, np.minimum(np.abs(r - b0), np.abs(r - b1)))
+    return np.where(explored, action, sampled), explored, margin
+
+
+def league_draw_reference(seed, gid, counter, domain, m):
+    """The league's draw rule in numpy (include/crl.h "league draws"): Philox4x32-10 word 0 of counter (gid lo, gid hi, counter,
+    domain) under key (seed lo, seed hi), scaled to [0, m) by a multiply-high.  Arrays broadcast; returns int64.  Host code for
+    tests and for callers that want to predict an assignment; the kernels do not use it."""
+    c = _philox4x32_10(gid, counter, domain, seed)
+    return ((c[0] * np.uint64(m)) >> np.uint64(32)).astype(np.int64)

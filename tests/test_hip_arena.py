@@ -161,6 +161,31 @@ def test_every_redraw_follows_the_written_rule():
     books.close()
 
 
+def test_a_refused_load_leaves_the_books_as_they_were():
+    """Counters of the wrong size and an all-zero weight table are refused before anything is written."""
+    _need_gpu()
+    n, agents, steps = 65, 3, 12
+    g = torch.Generator(device="cuda").manual_seed(2)
+    books = ArenaBooks(n, agents, "cuda:0", seed=9, env_id_base=40)
+    pairs = torch.randint(0, agents, (n, 2), generator=g, device="cuda", dtype=torch.int32)
+    for t in range(steps):
+        reward = torch.randint(-1, 2, (n,), generator=g, device="cuda").float()
+        done = (torch.randint(0, 4, (n,), generator=g, device="cuda") == 0).to(torch.uint8)
+        books.update(pairs, reward, done, redraw=True, out=pairs)
+    before = books.state_dict()
+    assert before["counters"][0].sum() > 0 and before["draw_ctr"].any() and before["ret"].any()
+    other = {"agents": agents, "seed": 1234, "counters": before["counters"] + 5, "ignored": before["ignored"] + 1, "ret": before["ret"] + 1,
+             "len": before["len"] + 1, "draw_ctr": before["draw_ctr"] + np.uint32(1), "weights": np.arange(9, dtype=np.uint32).reshape(3, 3)}
+    for bad in (dict(other, counters=np.zeros((N.CRL_ARENA_COUNTERS, 16, 15), np.int64)), dict(other, weights=np.zeros((3, 3), np.uint32))):
+        with pytest.raises(ValueError, match="load_state_dict"):
+            books.load_state_dict(bad)
+        after = books.state_dict()
+        assert sorted(after) == sorted(before)
+        for k in before:
+            assert np.array_equal(after[k], before[k]), k
+    books.close()
+
+
 def _random_books(rs):
     c = rs.randint(-10 ** 9, 10 ** 9, (N.CRL_ARENA_COUNTERS, 16, 16)).astype(np.int64)
     e = rs.randint(0, 10 ** rs.randint(1, 13, (16, 16)), dtype=np.int64)

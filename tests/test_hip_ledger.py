@@ -213,16 +213,21 @@ def _synthetic(n, agents, steps, seed, lo=-1, hi=None):
     return assign, reward, done
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 1003])
-def test_made_up_steps_with_losses_draws_and_ids_outside_the_pool(n):
+@pytest.mark.parametrize("n, agents", [pytest.param(n, 5, id=str(n)) for n in (1, 63, 64, 65, 257, 1003)]
+                         + [pytest.param(n, 16, id=f"{n}-full-pool") for n in (65, 257)])
+def test_made_up_steps_with_losses_draws_and_ids_outside_the_pool(n, agents):
     """What Pong cannot show: drawn episodes (return 0), ids outside the pool (-> `ignored`), the reward's column stride; at sizes
-    around the wavefront and the block.  Every second step asks for redraws and takes the ids in place."""
+    around the wavefront and the block.  Every second step asks for redraws and takes the ids in place.  At step 20 EVERY env is done
+    and env i holds id (i mod (agents + 2)) - 1: a wavefront then carries every key of the pool plus -1 and `agents`, the last one the
+    lanes beyond n as well -- with the full pool of 16 the most rounds the step's grouping loop can run."""
     _need_gpu()
-    agents, steps = 5, 60
+    steps = 60
     led = LeagueLedger(n, agents, "cuda:0", seed=31, env_id_base=(1 << 33) + 5)
-    table = [2, 0, 1, 4, 1]
+    table = [2, 0, 1, 4, 1] if agents == 5 else [(3 * k) % 5 for k in range(agents)]
     led.set_weights(table)
     assign, reward, done = _synthetic(n, agents, steps, n)
+    done[20] = 1
+    assign[20] = torch.arange(n, device="cuda", dtype=torch.int32) % (agents + 2) - 1
     replay, ctr, gid = Replay(n, agents), np.zeros(n, np.int64), (1 << 33) + 5 + np.arange(n)
     for t in range(steps):
         a, r, d = assign[t].cpu().numpy(), reward[t, :, 0].cpu().numpy(), done[t].cpu().numpy().astype(bool)
@@ -299,6 +304,50 @@ def test_a_fresh_ledger_continues_from_a_state_dict():
     for k in sa:
         assert np.array_equal(sa[k], sb[k]), k
     a.close(), b.close()
+
+
+def _same_state(a, b):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_a_refused_load_leaves_the_ledger_as_it_was():
+    """An all-zero weight table and counters of the wrong size are refused BEFORE anything is written (the library would refuse the
+    table only after the counters and the per-env state had been replaced)."""
+    _need_gpu()
+    n, agents, steps = 65, 3, 12
+    assign, reward, done = _synthetic(n, agents, steps, 4)
+    led = LeagueLedger(n, agents, "cuda:0", seed=9, env_id_base=40)
+    led.set_weights([4, 0, 3])
+    for t in range(steps):
+        led.update(assign[t], reward[t], done[t], redraw=True)
+    before = led.state_dict()
+    assert before["counters"][0].sum() > 0 and before["draw_ctr"].any() and before["ret"].any()
+    other = {"agents": agents, "seed": 1234, "counters": before["counters"] + 5, "ignored": before["ignored"] + 1, "ret": before["ret"] + 1,
+             "len": before["len"] + 1, "draw_ctr": before["draw_ctr"] + np.uint32(1), "weights": np.array([1, 2, 3], np.uint32)}
+    for bad in (dict(other, weights=np.zeros(agents, np.uint32)), dict(other, counters=np.zeros((N.CRL_LEDGER_COUNTERS, 15), np.int64))):
+        with pytest.raises(ValueError, match="load_state_dict"):
+            led.load_state_dict(bad)
+        _same_state(led.state_dict(), before)
+    led.load_state_dict(other)  # (what was refused differs from a good one in that entry alone)
+    _same_state(led.state_dict(), other)
+    led.close()
+
+
+def test_a_duplicate_name_is_refused_and_the_pool_stays():
+    _need_gpu()
+    from competitive_rl_amd.policy_serving import BUILTIN_CHECKPOINTS
+
+    lg = LeagueEnvWrapper(_env(1, 3), 1, NAMES4, ledger=True)
+    lg.add_agent("MINE", BUILTIN_CHECKPOINTS["WEAK"])
+    names, kinds, styles, weights = list(lg.agent_names), list(lg._kinds), lg.sampling(), lg.ledger.weights()
+    for name in ("MINE", "RANDOM"):
+        with pytest.raises(ValueError, match="is in the pool already"):
+            lg.add_agent(name, BUILTIN_CHECKPOINTS["MEDIUM"], temperature=1.0)
+    assert lg.agent_names == names and lg._kinds == kinds and lg.sampling() == styles and lg.counts().tolist() == [0, 0, 0, 1, 0]
+    assert lg.ledger.agents == 5 and np.array_equal(lg.ledger.weights(), weights) and weights.tolist() == [1] * 5
+    lg.close()
 
 
 def test_step_device_with_a_ledger_does_no_host_work():

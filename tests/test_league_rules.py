@@ -1,7 +1,11 @@
 """The league's draw rule (include/crl.h "league draws"), restated in plain numpy here -- tests/test_hip_league.py compares the kernels
 with THIS restatement -- and the agreement of header, ctypes binding and package for the new entry points.  No GPU."""
+import ast
+import itertools
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -136,3 +140,29 @@ def test_the_league_refuses_the_full_size_network_and_malformed_weights():
 
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         LeagueEnvWrapper(NoDevice(), 4)
+
+
+_MODULES = ("ledger", "arena", "league", "policy_serving")
+
+
+def test_the_league_modules_import_in_any_order():
+    """Each of the 24 orders in an interpreter of its own (eight at a time): no module needs another to have been imported first."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    orders = list(itertools.permutations(_MODULES))
+    for k in range(0, len(orders), 8):
+        procs = [(o, subprocess.Popen([sys.executable, "-c", "; ".join(f"import competitive_rl_amd.{m}" for m in o)], cwd=root,
+                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for o in orders[k:k + 8]]
+        for o, p in procs:
+            out, _ = p.communicate()
+            assert p.returncode == 0, (o, out[-2000:])
+
+
+@pytest.mark.parametrize("module", ["league", "policy_serving"])
+def test_no_import_statement_inside_a_function(module):
+    """league.py took LeagueLedger and policy_serving.py took check_sampling through imports inside a function, around an import cycle;
+    the rules now live in a leaf module (rules.py) and every import is at the top."""
+    path = os.path.join(os.path.dirname(N.__file__), module + ".py")
+    tree = ast.parse(open(path).read())
+    inside = [(f.name, n.lineno) for f in ast.walk(tree) if isinstance(f, (ast.FunctionDef, ast.AsyncFunctionDef, ast.Lambda))
+              for n in ast.walk(f) if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert not inside, inside
