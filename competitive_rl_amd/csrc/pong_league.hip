@@ -25,13 +25,11 @@
 #include "pong_device.h"
 #include "pong_league.h"
 #include "pong_policy_full.h"
+#include "pong_ring.h"
 #include "pong_sample.h"
 
 namespace crl {
 
-static constexpr int kLPlane = CRL_POLICY_DIM * CRL_POLICY_DIM;       // 1764 bytes
-static constexpr int kLPlaneWords = kLPlane / 4;                       // 441
-static constexpr int kLRingBytes = CRL_POLICY_STACK * kRingPlanePad;   // 7104 per env
 static constexpr int kLThreads = 256;
 static constexpr int kMaxAgents = CRL_LEAGUE_MAX_AGENTS;
 
@@ -103,11 +101,11 @@ __global__ __launch_bounds__(kLThreads) void league_fill_kernel(const int32_t *_
         m &= m - 1;
         const int64_t e = w0 + b;
         const uint32_t *src = reinterpret_cast<const uint32_t *>(frame + e * frame_stride);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(ring + e * (int64_t)kLRingBytes + head * kRingPlanePad);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(ring + e * (int64_t)kRingBytes + head * kPlanePad);
 #pragma unroll
         for (int q = 0; q < 7; q++) {
             const int d = q * 64 + lane;
-            if (d < kLPlaneWords) dst[d] = src[d];
+            if (d < kPlaneWords) dst[d] = src[d];
         }
     }
 }
@@ -158,27 +156,21 @@ static int league_add(crl_league *l, int kind, const float *raw_host, int64_t sc
     if (l->agents >= kMaxAgents) return crl_fail(CRL_EINVAL, "crl_league: at most %d agents in a pool", kMaxAgents);
     HIP_TRY(hipSetDevice(l->device));
     const int a = l->agents;
-    if (kind == CRL_POOL_KIND_FULL) {
-        const size_t blob = (size_t)policy_full_blob_floats() * sizeof(float);
-        if (!l->scratch_rows) {  // the first full-size agent: the league's one scratch
-            if (int rc = crl_dev_zalloc(&l->act2, (size_t)scratch_rows * policy_full_act2_floats() * sizeof(float), "crl_pool_add_full")) return rc;
-            if (int rc = crl_dev_zalloc(&l->feat, (size_t)scratch_rows * policy_full_feat_floats() * sizeof(float), "crl_pool_add_full")) {
-                (void)hipFree(l->act2), l->act2 = nullptr;
-                return rc;
-            }
-            l->scratch_rows = scratch_rows;
+    if (kind == CRL_POOL_KIND_FULL && !l->scratch_rows) {  // the first full-size agent: the league's one scratch
+        if (int rc = crl_dev_zalloc(&l->act2, (size_t)scratch_rows * policy_full_act2_floats() * sizeof(float), "crl_pool_add_full")) return rc;
+        if (int rc = crl_dev_zalloc(&l->feat, (size_t)scratch_rows * policy_full_feat_floats() * sizeof(float), "crl_pool_add_full")) {
+            (void)hipFree(l->act2), l->act2 = nullptr;
+            return rc;
         }
-        if (!l->raw[a]) HIP_TRY(hipMalloc(&l->raw[a], blob));  // (a slot whose add failed half way keeps what it got: destroy frees it)
-        HIP_TRY(hipMemcpy(l->raw[a], raw_host, blob, hipMemcpyHostToDevice));
-        if (!l->T.list[a])
-            if (int rc = crl_dev_zalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t), "crl_pool_add_full")) return rc;
+        l->scratch_rows = scratch_rows;
     }
-    if (kind == CRL_LEAGUE_LIGHT) {
-        HIP_TRY(hipMalloc(&l->raw[a], kLightRawFloats * sizeof(float)));
-        HIP_TRY(hipMemcpy(l->raw[a], raw_host, kLightRawFloats * sizeof(float), hipMemcpyHostToDevice));
-        // (entries past the count are read, never used)
-        if (int rc = crl_dev_zalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t), "crl_league_add_light")) return rc;
-        HIP_TRY(policy_light_list_prepare());
+    if (kind == CRL_POOL_KIND_FULL || kind == CRL_LEAGUE_LIGHT) {  // the CNN agents: the weights and the env list
+        const size_t bytes = (kind == CRL_LEAGUE_LIGHT ? (size_t)kLightRawFloats : (size_t)policy_full_blob_floats()) * sizeof(float);
+        if (!l->raw[a]) HIP_TRY(hipMalloc(&l->raw[a], bytes));  // (a slot whose add failed half way keeps what it got: destroy frees it)
+        HIP_TRY(hipMemcpy(l->raw[a], raw_host, bytes, hipMemcpyHostToDevice));
+        if (!l->T.list[a])  // (entries past the count are read, never used)
+            if (int rc = crl_dev_zalloc(&l->T.list[a], (size_t)(l->n_pad + 8) * sizeof(int32_t), "crl_league: an agent's env list")) return rc;
+        if (kind == CRL_LEAGUE_LIGHT) HIP_TRY(policy_light_prepare());
     }
     l->kind[a] = kind;
     const int32_t k32 = kind;
@@ -202,7 +194,7 @@ int crl_league_create(int32_t device, int64_t num_envs, int64_t env_id_base, uin
     l->device = device, l->n = num_envs, l->n_pad = (num_envs + 7) / 8 * 8, l->env_id_base = env_id_base, l->seed = seed;
     if (hipDeviceGetAttribute(&l->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || l->cus <= 0) l->cus = 256;
     const char *what = "crl_league_create";
-    int rc = crl_dev_zalloc(&l->ring, (size_t)num_envs * kLRingBytes, what);
+    int rc = crl_dev_zalloc(&l->ring, (size_t)num_envs * kRingBytes, what);
     if (!rc) rc = crl_dev_zalloc(&l->assign, (size_t)num_envs * sizeof(int32_t), what);
     if (!rc) rc = crl_dev_zalloc(&l->draw_ctr, (size_t)num_envs * sizeof(uint32_t), what);
     if (!rc) rc = crl_dev_zalloc(&l->ctrl, 3 * kMaxAgents * sizeof(unsigned), what);
@@ -242,8 +234,7 @@ int crl_league_add_light(crl_league *l, const float *conv1_w, const float *conv1
     crl_fail_no_ctx();
     if (!l || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b) return crl_fail(CRL_EINVAL, "crl_league_add_light: null argument");
     std::vector<float> raw(kLightRawFloats, 0.f);
-    memcpy(raw.data(), conv1_w, 1024 * 4), memcpy(raw.data() + 1024, conv1_b, 16 * 4), memcpy(raw.data() + 1040, conv2_w, 1024 * 4);
-    memcpy(raw.data() + 2064, conv2_b, 16 * 4), memcpy(raw.data() + 2080, actor_w, 4800 * 4), memcpy(raw.data() + 6880, actor_b, 3 * 4);
+    policy_light_pack(raw.data(), conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b);
     return league_add(l, CRL_LEAGUE_LIGHT, raw.data());
 }
 
@@ -336,8 +327,7 @@ int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride
                    void *stream) {
     crl_fail_no_ctx();
     if (!l || !frame_dev || !actions_dev) return crl_fail(CRL_EINVAL, "crl_league_act: null argument");
-    if (frame_stride < kLPlane || (frame_stride & 3) || ((uintptr_t)frame_dev & 3) || action_stride < 1)
-        return crl_fail(CRL_EINVAL, "crl_league_act: frame_stride must be a multiple of 4 and >= 1764, frames 4-byte aligned");
+    if (int rc = ring_check_act("crl_league_act", frame_dev, frame_stride, action_stride)) return rc;
     if (l->agents <= 0) return crl_fail(CRL_ESTATE, "crl_league_act: the pool is empty");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(l->ctrl, 0, kMaxAgents * sizeof(unsigned), st));  // the tickets
@@ -347,20 +337,18 @@ int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride
     hipLaunchKernelGGL(league_fill_kernel, dim3((unsigned)((l->n + kLThreads - 1) / kLThreads)), dim3(kLThreads), 0, st, league_kinds(l), l->agents,
                        l->assign, l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, l->seed, l->env_id_base, l->step, l->n, E);
     HIP_TRY(hipGetLastError());
-    for (int a = 0; a < l->agents; a++)
-        if (l->kind[a] == CRL_LEAGUE_LIGHT) {
-            SampleArgs S = l->sample[a];  // an agent at (0, 0) -- every agent, until crl_sampling_set_agent -- keeps the greedy launch
-            const bool sampled = S.inv_t != 0.f || S.eps_q != 0;
-            S.seed = l->seed, S.id_base = l->env_id_base, S.n = l->step;
+    for (int a = 0; a < l->agents; a++) {
+        if (l->kind[a] != CRL_LEAGUE_LIGHT && l->kind[a] != CRL_POOL_KIND_FULL) continue;
+        SampleArgs S = l->sample[a];  // an agent at (0, 0) -- every agent, until crl_sampling_set_agent -- keeps the greedy launch
+        const SampleArgs *sample = sample_active(S) ? &S : nullptr;
+        S.seed = l->seed, S.id_base = l->env_id_base, S.n = l->step;
+        if (l->kind[a] == CRL_LEAGUE_LIGHT)
             HIP_TRY(policy_light_act_list(l->raw[a], l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, l->T.list[a],
-                                          league_counts(l) + a, l->n, l->cus, l->ctrl + a, sampled ? &S : nullptr, st));
-        } else if (l->kind[a] == CRL_POOL_KIND_FULL) {
-            SampleArgs S = l->sample[a];
-            const bool sampled = S.inv_t != 0.f || S.eps_q != 0;
-            S.seed = l->seed, S.id_base = l->env_id_base, S.n = l->step;
+                                          league_counts(l) + a, l->n, l->cus, l->ctrl + a, sample, st));
+        else
             HIP_TRY(policy_full_act_list(l->raw[a], l->act2, l->feat, l->scratch_rows, l->ring, l->head, frame_dev, frame_stride, actions_dev, action_stride,
-                                         logits_dev, l->T.list[a], league_counts(l) + a, l->n, l->cus, sampled ? &S : nullptr, st));
-        }
+                                         logits_dev, l->T.list[a], league_counts(l) + a, l->n, l->cus, sample, st));
+    }
     l->head = (l->head + 1) & 3;
     l->step++;
     return CRL_OK;
@@ -369,23 +357,12 @@ int crl_league_act(crl_league *l, const uint8_t *frame_dev, int64_t frame_stride
 int crl_league_reset(crl_league *l, void *stream) {
     crl_fail_no_ctx();
     if (!l) return crl_fail(CRL_EINVAL, "crl_league_reset: null league");
-    HIP_TRY(hipMemsetAsync(l->ring, 0, (size_t)l->n * kLRingBytes, (hipStream_t)stream));
+    HIP_TRY(ring_reset(l->ring, l->n, (hipStream_t)stream));
     l->head = 0;
     return CRL_OK;
 }
 
-int crl_league_get_stack(crl_league *l, uint8_t *stack_out_dev, void *stream) {
-    crl_fail_no_ctx();
-    if (!l || !stack_out_dev) return crl_fail(CRL_EINVAL, "crl_league_get_stack: null argument");
-    HIP_TRY(policy_copy_stack(l->ring, stack_out_dev, l->head, l->n, 0, (hipStream_t)stream));
-    return CRL_OK;
-}
-
-int crl_league_set_stack(crl_league *l, const uint8_t *stack_in_dev, void *stream) {
-    crl_fail_no_ctx();
-    if (!l || !stack_in_dev) return crl_fail(CRL_EINVAL, "crl_league_set_stack: null argument");
-    HIP_TRY(policy_copy_stack(l->ring, const_cast<uint8_t *>(stack_in_dev), l->head, l->n, 1, (hipStream_t)stream));
-    return CRL_OK;
-}
+int crl_league_get_stack(crl_league *l, uint8_t *stack_out_dev, void *stream) { return ring_copy_stack("crl_league_get_stack", l, stack_out_dev, 0, stream); }
+int crl_league_set_stack(crl_league *l, const uint8_t *stack_in_dev, void *stream) { return ring_copy_stack("crl_league_set_stack", l, stack_in_dev, 1, stream); }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // pong_policy_full.hip -- the full-size ActorCritic opponent of cPongTournament-v0 (STRONG / ALPHA_PONG's model) on device.
 //
 // Restates Policy.__call__ (reference utils/policy_serving.py:46-66) with use_light_model=False: the same four-frame
-// stack as the light opponents (pong_policy.hip owns the ring), then ActorCritic.forward (utils/network.py:14-50):
+// stack as the light opponents (the ring of pong_ring.h), then ActorCritic.forward (utils/network.py:14-50):
 //   x / 255 -> conv1 4->16 k4 s2 (20x20) -> ReLU -> conv2 16->32 k4 s2 pad 2 (11x11) -> ReLU -> conv3 32->256 k11 (1x1) -> ReLU
 //   -> actor_linear 256->3, argmax.        4.79 MFLOP per env: conv1 0.82, conv2 1.98, conv3 1.98.
 //
@@ -34,14 +34,12 @@
 #include <vector>
 
 #include "crl_internal.h"
+#include "pong_net.h"
+#include "pong_ring.h"
 #include "pong_sample.h"
 
 namespace crl {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-static constexpr int kFDim = 42, kFPlanePad = kRingPlanePad, kFRingBytes = 4 * kFPlanePad;  // the ring of pong_policy.hip
 static constexpr int kC1 = 16, kP1 = 400;        // conv1: 16 channels x 20 x 20
 static constexpr int kC2 = 32, kP2 = 121;        // conv2: 32 channels x 11 x 11
 static constexpr int kK3 = kC2 * kP2;            // 3872 = conv3's receptive field: the whole of act2
@@ -82,13 +80,6 @@ __device__ inline int64_t list_rows(const ListArgs &L, int64_t rows) {
 //   conv2: a wavefront owns two tiles of 16 positions (121 = 8 tiles, the last one ragged): per input channel four 8-byte LDS
 //   reads of the window rows (A) and two 16-byte reads of the weights (B) feed 16 fp32 matrix instructions on four accumulators.
 // The new frame is read straight from the caller's buffer (plane 3 of the stack) and copied over the oldest ring plane here.
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ inline uint32_t pk_bytes_bf16(uint32_t two) {  // the two low bytes of `two` as a pair of bf16
-    const bf2 v = {(__bf16)(float)(two & 255u), (__bf16)(float)((two >> 8) & 255u)};
-    return __builtin_bit_cast(uint32_t, v);
-}
 static constexpr int kS1Rows = 24, kS1Pitch = 580;  // padded plane 24 x 24 = 576 floats + 4: channels start 4 banks apart
 static constexpr int kW2Pitch = 260;  // floats per output channel in LDS: 65 x 16 bytes, odd -> the 16 lanes of a read phase hit 16 bank groups
 // LIST: row r of act2 is env L.env_list[r]; n comes in as the pass's row capacity and becomes its row count.
@@ -118,12 +109,9 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const float w = w1[li * 64 + 32 * h + 8 * lk + j] / 255.0f;
-            const __bf16 t0 = (__bf16)w;
-            const float r1 = w - (float)t0;  // exact
-            const __bf16 t1 = (__bf16)r1;
-            const float r2 = r1 - (float)t1;  // exact
-            wB[0][h][j] = t0, wB[1][h][j] = t1, wB[2][h][j] = (__bf16)r2;
+            __bf16 t0, t1, t2;
+            split_bf16x3(w1[li * 64 + 32 * h + 8 * lk + j] / 255.0f, t0, t1, t2);
+            wB[0][h][j] = t0, wB[1][h][j] = t1, wB[2][h][j] = t2;
         }
     f4 bias1, bias2[2];  // D rows = channels 4 lk + r
 #pragma unroll
@@ -140,18 +128,18 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
     // its own loads, cost 0.86 ms of the kernel's 1.63 at 65 536 envs)
     uint32_t raw[7][2][2];
     auto prefetch = [&](int64_t env) {
-        const uint8_t *fr = frame + env * frame_stride, *rg = ring + env * kFRingBytes;
-        const int win = (2 * (lk & 1)) * kFDim;
-        const uint8_t *pl[2] = {rg + ((head + 1 + (lk >> 1)) & 3) * kFPlanePad + win,                 // plane lk >> 1
-                                ((lk >> 1) ? fr : rg + ((head + 3) & 3) * kFPlanePad) + win};          // plane 2 + (lk >> 1); 3 = the new frame
+        const uint8_t *fr = frame + env * frame_stride, *rg = ring + env * kRingBytes;
+        const int win = (2 * (lk & 1)) * kDim;
+        const uint8_t *pl[2] = {rg + ((head + 1 + (lk >> 1)) & 3) * kPlanePad + win,                 // plane lk >> 1
+                                ((lk >> 1) ? fr : rg + ((head + 3) & 3) * kPlanePad) + win};          // plane 2 + (lk >> 1); 3 = the new frame
 #pragma unroll
         for (int it = 0; it < 7; it++) {  // 25 tiles over 4 wavefronts: the spare turns repeat tile 24 (same values, same addresses)
             const int tl = min(wave + 4 * it, kP1 / 16 - 1);
-            const int p = tl * 16 + li, y = p / 20, x = p - y * 20, off = 2 * y * kFDim + 2 * x;
+            const int p = tl * 16 + li, y = p / 20, x = p - y * 20, off = 2 * y * kDim + 2 * x;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 __builtin_memcpy(&raw[it][h][0], pl[h] + off, 4);
-                __builtin_memcpy(&raw[it][h][1], pl[h] + off + kFDim, 4);
+                __builtin_memcpy(&raw[it][h][1], pl[h] + off + kDim, 4);
             }
         }
     };
@@ -210,8 +198,8 @@ __global__ __launch_bounds__(256) void policy_full_front_kernel(uint8_t *__restr
         }
         {  // the new frame replaces the oldest plane of the ring (FrameStackTensor.update without a mask, utils/utils.py:159-170)
             const uint32_t *src = reinterpret_cast<const uint32_t *>(frame + env * frame_stride);
-            uint32_t *dst = reinterpret_cast<uint32_t *>(ring + env * kFRingBytes + head * kFPlanePad);
-            for (int i = tid; i < kFDim * kFDim / 4; i += 256) dst[i] = src[i];
+            uint32_t *dst = reinterpret_cast<uint32_t *>(ring + env * kRingBytes + head * kPlanePad);
+            for (int i = tid; i < kPlaneWords; i += 256) dst[i] = src[i];
         }
         __syncthreads();  // s1 is rewritten by the next env's conv1
     }
@@ -329,14 +317,7 @@ __device__ __forceinline__ void policy_full_actor_row(const float *__restrict__ 
         for (int off = 32; off >= 1; off >>= 1) s[c] += __shfl_xor(s[c], off);
         s[c] += ba[c];
     }
-    if (lane == 0) {
-        int a = 0;
-        if (s[1] > s[0]) a = 1;
-        if (s[2] > fmaxf(s[0], s[1])) a = 2;
-        if constexpr (SAMPLE) a = sample_action(S, env, s[0], s[1], s[2], a);
-        actions[env * action_stride] = a;
-        if (logits) logits[env * 3] = s[0], logits[env * 3 + 1] = s[1], logits[env * 3 + 2] = s[2];
-    }
+    if (lane == 0) action_epilogue<SAMPLE>(S, env, s[0], s[1], s[2], actions, action_stride, logits);
 }
 
 // LIST: a persistent grid, a wavefront walks the rows row, row + 4 gridDim.x, ... below the count; feat is read by the row, the
@@ -406,19 +387,15 @@ hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, co
     for (int64_t e0 = 0; e0 < n; e0 += f->chunk) {
         const int64_t c = std::min<int64_t>(f->chunk, n - e0);
         hipLaunchKernelGGL(policy_full_front_kernel<false>, dim3((unsigned)std::min<int64_t>(c, (int64_t)f->cus * 2)), dim3(256), 0, st,
-                           ring + e0 * kFRingBytes, head, frame_dev + e0 * frame_stride, frame_stride, f->w + kOffW1, f->w + kOffB1,
+                           ring + e0 * kRingBytes, head, frame_dev + e0 * frame_stride, frame_stride, f->w + kOffW1, f->w + kOffB1,
                            f->w + kOffW2, f->w + kOffB2, f->act2, c, ListArgs{});
         hipLaunchKernelGGL(policy_full_conv3_kernel<false>, dim3((unsigned)((c + kGM - 1) / kGM), kC3 / kGN), dim3(256), 0, st, f->act2,
                            f->w + kOffW3, f->w + kOffB3, f->feat, c, ListArgs{});
-        if (sample) {
-            SampleArgs S = *sample;
-            S.id_base += e0;
-            hipLaunchKernelGGL((policy_full_actor_kernel<true, false>), dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
-                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, S, ListArgs{});
-        } else {
-            hipLaunchKernelGGL((policy_full_actor_kernel<false, false>), dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st, f->feat, f->w + kOffWa, f->w + kOffBa,
-                               actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c, SampleArgs{}, ListArgs{});
-        }
+        SampleArgs S = sample ? *sample : SampleArgs{};
+        S.id_base += e0;
+        hipLaunchKernelGGL((sample ? policy_full_actor_kernel<true, false> : policy_full_actor_kernel<false, false>), dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
+                           f->feat, f->w + kOffWa, f->w + kOffBa, actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c,
+                           S, ListArgs{});
     }
     return hipGetLastError();
 }
@@ -437,12 +414,8 @@ hipError_t policy_full_act_list(const float *w_blob, float *act2, float *feat, i
         hipLaunchKernelGGL(policy_full_conv3_kernel<true>, dim3((unsigned)(2 * std::min<int64_t>(tiles, (int64_t)cus * 2))), dim3(256), 0, st, act2,
                            w_blob + kOffW3, w_blob + kOffB3, feat, rows, L);
         const dim3 ag((unsigned)std::min<int64_t>((rows + 3) / 4, (int64_t)cus * 8));
-        if (sample)
-            hipLaunchKernelGGL((policy_full_actor_kernel<true, true>), ag, dim3(256), 0, st, feat, w_blob + kOffWa, w_blob + kOffBa, actions,
-                               action_stride, logits, rows, *sample, L);
-        else
-            hipLaunchKernelGGL((policy_full_actor_kernel<false, true>), ag, dim3(256), 0, st, feat, w_blob + kOffWa, w_blob + kOffBa, actions,
-                               action_stride, logits, rows, SampleArgs{}, L);
+        hipLaunchKernelGGL((sample ? policy_full_actor_kernel<true, true> : policy_full_actor_kernel<false, true>), ag, dim3(256), 0, st, feat, w_blob + kOffWa,
+                           w_blob + kOffBa, actions, action_stride, logits, rows, sample ? *sample : SampleArgs{}, L);
     }
     return hipGetLastError();
 }

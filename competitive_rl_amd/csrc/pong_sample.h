@@ -1,6 +1,7 @@
-// pong_sample.h -- include/crl.h "sampled actions": the action epilogue of a served agent that does not play greedy.  One Philox
-// call by the lane that writes the action; shared by the LightActorCritic kernels (pong_policy.hip), the full-size actor
-// (pong_policy_full.hip) and RULE_BASED's explore branch (pong_league.hip).
+// pong_sample.h -- the action epilogue of a served agent (action_epilogue: argmax or draw, and the stores) and include/crl.h
+// "sampled actions" for one that does not play greedy: one Philox call by the lane that writes the action.  Shared by the
+// LightActorCritic kernels (pong_policy.hip), the full-size actor (pong_policy_full.hip) and RULE_BASED's explore branch
+// (pong_league.hip).
 #pragma once
 #include <math.h>
 
@@ -50,6 +51,27 @@ __device__ inline int sample_action(const SampleArgs &S, int64_t env, float l0, 
     const float e01 = e0 + e1, sum = e01 + e2;
     const float rs = ((float)(x0 >> 8) * 0x1p-24f) * sum;
     return rs < e0 ? 0 : rs < e01 ? 1 : 2;
+}
+
+// host: does an agent with these parameters need the SAMPLE kernels?  (0, 0) -- every agent, until it is set -- keeps the greedy ones
+inline bool sample_active(const SampleArgs &S) { return S.inv_t != 0.f || S.eps_q != 0; }
+
+// What the lane that holds an env's three logits does with them: the first-index argmax (torch.argmax; a NaN logit is no supported
+// input and is not guarded), SAMPLE: the draw instead, then the action and, where asked for, the logits.  SAMPLE is a template
+// parameter, not a branch on a kernel argument: the greedy kernels are the code they were, whatever the compiler makes of the draw.
+template <bool SAMPLE>
+__device__ __forceinline__ void action_epilogue(const SampleArgs &S, int64_t env, float a0, float a1, float a2, int32_t *__restrict__ actions,
+                                                int64_t action_stride, float *__restrict__ logits) {
+    int best = 0;
+    float bv = a0;
+    if (a1 > bv) best = 1, bv = a1;
+    if (a2 > bv) best = 2;
+    if constexpr (SAMPLE) best = sample_action(S, env, a0, a1, a2, best);
+    actions[env * action_stride] = best;
+    if (logits) {
+        float *lo = logits + env * 3;
+        lo[0] = a0, lo[1] = a1, lo[2] = a2;
+    }
 }
 
 }  // namespace crl
