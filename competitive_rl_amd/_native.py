@@ -108,6 +108,9 @@ SIGNATURES = {
     "crl_policy_get_stack": (i32, [vp, vp, vp]),
     "crl_policy_set_stack": (i32, [vp, vp, vp]),
     "crl_policy_set_sampling": (i32, [vp, f32, f32, u64, i64]),
+    "crl_policy_set_critic": (i32, [vp, vp, vp]),
+    "crl_policy_act_rollout": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
+    "crl_policy_load_weights": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "crl_terminal_observation_dev": (i32, [vp, vp, i64, vp, vp]),
     "crl_check": (i32, [vp, vp]),
     "crl_car_info": (i32, [vp, P(vp), P(vp)]),
@@ -130,6 +133,8 @@ SIGNATURES = {
     "crl_league_add_builtin": (i32, [vp, i32]),
     "crl_league_add_light": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "crl_pool_add_full": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "crl_pool_load_light": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_pool_load_full": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "crl_sampling_set_agent": (i32, [vp, i32, f32, f32]),
     "crl_sampling_get_agent": (i32, [vp, i32, P(f32), P(f32)]),
     "crl_league_seed": (i32, [vp, u64, vp]),

@@ -138,6 +138,7 @@ struct crl_league {
     int32_t *assign = nullptr;
     uint32_t *draw_ctr = nullptr;
     unsigned *ctrl = nullptr;  // [0, 16): tickets of the list launches, [16, 32): counts, [32, 48): kinds (int32)
+    WeightStage stage{};       // crl_pool_load_light / _load_full: the pinned host copy of the blob on its way (pong_league.h)
 };
 
 static unsigned *league_counts(crl_league *l) { return l->ctrl + kMaxAgents; }
@@ -209,6 +210,7 @@ int crl_league_create(int32_t device, int64_t num_envs, int64_t env_id_base, uin
 void crl_league_destroy(crl_league *l) {
     if (!l) return;
     (void)hipSetDevice(l->device);
+    weight_stage_free(l->stage);
     for (int a = 0; a < kMaxAgents; a++) {
         if (l->raw[a]) (void)hipFree(l->raw[a]);
         if (l->T.list[a]) (void)hipFree(l->T.list[a]);
@@ -256,6 +258,44 @@ int crl_pool_add_full(crl_league *l, const float *conv1_w, const float *conv1_b,
     std::vector<float> blob((size_t)policy_full_blob_floats(), 0.f);
     policy_full_pack(blob.data(), conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
     return league_add(l, CRL_POOL_KIND_FULL, blob.data(), scratch_rows);
+}
+
+// the slot of a reload (`who`): in the pool, and of kind `kind`
+static int pool_load_slot(const char *who, crl_league *l, int32_t agent, int kind) {
+    if (agent < 0 || agent >= l->agents) return crl_fail(CRL_EINVAL, "%s: agent %d is not in the pool of %d", who, agent, l->agents);
+    if (l->kind[agent] != kind)
+        return crl_fail(CRL_EINVAL, "%s: agent %d is %s", who, agent,
+                        l->kind[agent] == CRL_LEAGUE_LIGHT ? "a LightActorCritic slot (crl_pool_load_light)"
+                        : l->kind[agent] == CRL_POOL_KIND_FULL ? "a full-size slot (crl_pool_load_full)" : "a built-in agent without weights");
+    return CRL_OK;
+}
+
+int crl_pool_load_light(crl_league *l, int32_t agent, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b,
+                        const float *actor_w, const float *actor_b, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b) return crl_fail(CRL_EINVAL, "crl_pool_load_light: null argument");
+    if (int rc = pool_load_slot("crl_pool_load_light", l, agent, CRL_LEAGUE_LIGHT)) return rc;
+    HIP_TRY(hipSetDevice(l->device));
+    HIP_TRY(weight_stage_begin(l->stage, kLightRawFloats));
+    l->stage.host[kLightRawFloats - 1] = 0.f;  // (the pad behind the actor's bias)
+    policy_light_pack(l->stage.host, conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b);
+    HIP_TRY(weight_stage_send(l->stage, l->raw[agent], kLightRawFloats, (hipStream_t)stream));
+    return CRL_OK;
+}
+
+int crl_pool_load_full(crl_league *l, int32_t agent, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b,
+                       const float *conv3_w, const float *conv3_b, const float *actor_w, const float *actor_b, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !conv3_w || !conv3_b || !actor_w || !actor_b)
+        return crl_fail(CRL_EINVAL, "crl_pool_load_full: null argument");
+    if (int rc = pool_load_slot("crl_pool_load_full", l, agent, CRL_POOL_KIND_FULL)) return rc;
+    const size_t floats = (size_t)policy_full_blob_floats();
+    HIP_TRY(hipSetDevice(l->device));
+    HIP_TRY(weight_stage_begin(l->stage, floats));
+    l->stage.host[floats - 1] = 0.f;  // (the pad behind the actor's bias)
+    policy_full_pack(l->stage.host, conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
+    HIP_TRY(weight_stage_send(l->stage, l->raw[agent], floats, (hipStream_t)stream));
+    return CRL_OK;
 }
 
 int crl_sampling_set_agent(crl_league *l, int32_t agent, float temperature, float epsilon) {

@@ -83,6 +83,14 @@ static constexpr int kMThreads = 64 * kMWaves;
 static constexpr int kMBuf = kME * CRL_POLICY_STACK * kPlanePad;  // 56 832 bytes per staging buffer
 static constexpr int kMLdsRest = (3 * 1600 + 2 * kME * kPos * 3 + 4) * 4;
 static constexpr int kMLds = 2 * kMBuf + kMLdsRest;
+// VALUE instantiations: the critic is a fourth row of sh_wa.  A fourth column of sh_part beside it would need 164 880 bytes, 1 040 over
+// the CU's 160 KiB, so the value's partials are reduced further inside the wavefront before they go to LDS: over the four positions
+// 4 b .. 4 b + 3 of a BLOCK b.  Tiles (16 positions) and envs (100) both start at multiples of 4, so a block never straddles either
+// and is the same four positions of the same env wherever the env sits in its group -- which a reduction over the whole tile,
+// cut by the env's boundary, would not be.  25 floats per env instead of 100: 160 080 bytes in all.
+static constexpr int kVBlocks = kPos / 4;  // 25 blocks per env
+static constexpr int kMLdsValue = kMLds + (1600 + 2 * kME * kVBlocks) * 4;
+static_assert(kMLdsValue <= 160 * 1024, "the VALUE instantiations' LDS must fit a CU");
 
 // LIST: the group's eight envs are entries of an env-index list (the league, pong_league.hip) instead of env0 .. env0 + 7.  The
 // entries sit in SGPRs before the first request of the group is issued (GroupIdx::load / pin): a load that returned between two
@@ -148,24 +156,30 @@ struct PolicyWeightsM {
 // SAMPLE: the lane that writes an env's action draws it by include/crl.h "sampled actions" (sample_action, one Philox call) instead of
 // keeping the argmax.  A template parameter, not a branch on a kernel argument: the greedy instantiations are then the code they were
 // (same registers, same LDS, same schedule around the matrix instructions), whatever the compiler makes of the sampling epilogue.
-template <bool BF, bool LIST, bool SAMPLE>
+// VALUE (crl_policy_act_rollout with values or log-probs; dense only): the critic head beside the actor -- a fourth partial per lane over
+// the same four channels, fmaf by fmaf, summed in a fixed shape of its own (four positions in the wavefront, then 25 blocks in
+// finish_group) -- and the epilogue's value / log-prob stores (H).  A template parameter like SAMPLE, for the same reason.
+template <bool BF, bool LIST, bool SAMPLE, bool VALUE = false>
 __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWeightsM W, uint8_t *__restrict__ ring, int head,
                                                                   const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                   int32_t *__restrict__ actions, int64_t action_stride,
                                                                   float *__restrict__ logits_out, int64_t n_arg, unsigned *__restrict__ ticket, int dbg_arg,
-                                                                  const int32_t *__restrict__ env_list, const unsigned *__restrict__ count_dev, SampleArgs S) {
+                                                                  const int32_t *__restrict__ env_list, const unsigned *__restrict__ count_dev, SampleArgs S, HeadArgs H) {
     const int64_t n = LIST ? (int64_t)*count_dev : n_arg;
     const int dbg = CRL_ABL(dbg_arg);  // timing ablations / phase stamps: profiling build only
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *sh_buf = smem;                                             // [2][kME][4][kPlanePad]
-    float *sh_wa = reinterpret_cast<float *>(smem + 2 * kMBuf);         // [3][1600]
-    float *sh_part = sh_wa + 3 * 1600;                                  // [2][kME * 100][3]: a group's partial logits, double-buffered
-    unsigned *sh_ticket = reinterpret_cast<unsigned *>(sh_part + 2 * kME * kPos * 3);  // [2]
+    float *sh_wa = reinterpret_cast<float *>(smem + 2 * kMBuf);         // [3][1600]; VALUE: [4][1600], the critic last
+    float *sh_part = sh_wa + (VALUE ? 4 : 3) * 1600;                    // [2][kME * 100][3]: a group's partial logits, double-buffered
+    float *sh_vpart = sh_part + 2 * kME * kPos * 3;                     // VALUE: [2][kME * 25]: its partial values, one per block of four positions
+    unsigned *sh_ticket = reinterpret_cast<unsigned *>(sh_vpart + (VALUE ? 2 * kME * kVBlocks : 0));  // [2]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int lj = lane & 15, lk = lane >> 4;
     const int64_t ngroups = (n + kME - 1) / kME;
 
     for (int i = tid; i < 3 * 1600; i += kMThreads) sh_wa[i] = W.wa[i];
+    if constexpr (VALUE)
+        for (int i = tid; i < 1600; i += kMThreads) sh_wa[3 * 1600 + i] = H.wc[i];
     // the wavefront's weights, once: A operands of every MFMA step
     float w1[16], w2[4][4];
     bf8 wA[3][2];  // BF: A[oc = lj][k = 32 i + 8 lk + j], k = ic * 16 + ky * 4 + kx (torch's own order), as three bf16 terms
@@ -192,6 +206,8 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
 #pragma unroll
     for (int r = 0; r < 4; r++) bias1[r] = W.b1[4 * lk + r], bias2[r] = W.b2[4 * lk + r];  // D rows = channels 4 lk + r
     float ba0 = W.ba[0], ba1 = W.ba[1], ba2 = W.ba[2];
+    float bc = 0.f;
+    if constexpr (VALUE) bc = H.bc[0];
     // Every load above must have RETURNED before the first LDS-DMA request is issued: the compiler waits for a load at its
     // first use with a vmcnt(N) that counts only the loads it knows of -- inside the tile loop that wait would also drain
     // the next group's LDS-DMA transfers (inline asm, invisible to it) and serialise staging with the convolutions.
@@ -213,6 +229,7 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
 #pragma unroll
         for (int r = 0; r < 4; r++) asm volatile("" : "+v"(w2[c][r]));
     asm volatile("" : "+v"(bias1), "+v"(bias2), "+v"(ba0), "+v"(ba1), "+v"(ba2));
+    if constexpr (VALUE) asm volatile("" : "+v"(bc));
     __syncthreads();  // sh_wa is staged
 
     // Three groups are in play: g (being computed), g1 (streaming into the other buffer) and the ticket for the one after
@@ -254,7 +271,15 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
             }
 #pragma unroll
             for (int d = 16; d >= 1; d >>= 1) s0 += __shfl_xor(s0, d), s1 += __shfl_xor(s1, d), s2 += __shfl_xor(s2, d);
-            if (lane == 0) action_epilogue<SAMPLE>(S, group_env<LIST>(ixg, e0, pe), ba0 + s0, ba1 + s1, ba2 + s2, actions, action_stride, logits_out);
+            if constexpr (VALUE) {  // the env's 25 block sums: lane j takes block j, the same 32-lane butterfly
+                float sv = j < kVBlocks ? sh_vpart[par * (kME * kVBlocks) + pe * kVBlocks + j] : 0.f;
+#pragma unroll
+                for (int d = 16; d >= 1; d >>= 1) sv += __shfl_xor(sv, d);
+                if (lane == 0)
+                    action_epilogue<SAMPLE, true>(S, group_env<LIST>(ixg, e0, pe), ba0 + s0, ba1 + s1, ba2 + s2, actions, action_stride, logits_out, bc + sv, &H);
+            } else {
+                if (lane == 0) action_epilogue<SAMPLE>(S, group_env<LIST>(ixg, e0, pe), ba0 + s0, ba1 + s1, ba2 + s2, actions, action_stride, logits_out);
+            }
         }
     };
     long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
@@ -411,7 +436,7 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                 continue;
             }
             // ---- actor: lane (position lj, channels 4 lk + r)
-            float l0 = 0.f, l1 = 0.f, l2 = 0.f;
+            float l0 = 0.f, l1 = 0.f, l2 = 0.f, lv = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const float f = fmaxf(d2a[r] + d2b[r], 0.f);
@@ -419,11 +444,17 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                 l0 = __builtin_fmaf(sh_wa[wi], f, l0);
                 l1 = __builtin_fmaf(sh_wa[1600 + wi], f, l1);
                 l2 = __builtin_fmaf(sh_wa[3200 + wi], f, l2);
+                if constexpr (VALUE) lv = __builtin_fmaf(sh_wa[4800 + wi], f, lv);
             }
             // the four channel groups of a position sit 16 lanes apart: (g0 + g1) + (g2 + g3), a fixed order
             l0 += __shfl_xor(l0, 16), l1 += __shfl_xor(l1, 16), l2 += __shfl_xor(l2, 16);
             l0 += __shfl_xor(l0, 32), l1 += __shfl_xor(l1, 32), l2 += __shfl_xor(l2, 32);
             if (lk == 0) part_out[q * 3 + 0] = l0, part_out[q * 3 + 1] = l1, part_out[q * 3 + 2] = l2;
+            if constexpr (VALUE) {  // channel groups as above, then the block's four positions (lanes lj ^ 1, lj ^ 2): one float per block
+                lv += __shfl_xor(lv, 16), lv += __shfl_xor(lv, 32);
+                lv += __shfl_xor(lv, 1), lv += __shfl_xor(lv, 2);
+                if (lk == 0 && (lj & 3) == 0) sh_vpart[cur * (kME * kVBlocks) + (q >> 2)] = lv;
+            }
         }
         MTICK(1)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's share of the next group has landed (and the ticket is back)
@@ -457,6 +488,29 @@ __global__ void pong_policy_copy_stack_kernel(uint8_t *__restrict__ ring, uint8_
     else *ep = *rp;
 }
 
+// pong_ring.h ring_mask_reset: a lane per env flag, a wavefront per flagged env's 444 16-byte chunks
+__global__ __launch_bounds__(256) void pong_ring_mask_reset_kernel(uint8_t *__restrict__ ring, const uint8_t *__restrict__ reset, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    unsigned long long m = __ballot(i < n && reset[i] != 0);
+    const int64_t w0 = i - lane;
+    while (m) {  // (uniform; a wavefront without a flag leaves here)
+        const int b = __ffsll(m) - 1;
+        m &= m - 1;
+        uint4 *dst = reinterpret_cast<uint4 *>(ring + (w0 + b) * (int64_t)kRingBytes);  // (w0 + b < n: the flag was read there)
+#pragma unroll
+        for (int q = 0; q < (kRingBytes / 16 + 63) / 64; q++) {
+            const int c = q * 64 + lane;
+            if (c < kRingBytes / 16) dst[c] = uint4{0u, 0u, 0u, 0u};
+        }
+    }
+}
+
+hipError_t ring_mask_reset(uint8_t *ring, const uint8_t *reset, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(pong_ring_mask_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ring, reset, n);
+    return hipGetLastError();
+}
+
 hipError_t policy_copy_stack(uint8_t *ring, uint8_t *ext, int head, int64_t n, int to_ring, hipStream_t st) {
     const int64_t words = n * CRL_POLICY_STACK * kPlaneWords;
     hipLaunchKernelGGL(pong_policy_copy_stack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ring, ext, head, words, to_ring);
@@ -468,33 +522,40 @@ static PolicyWeightsM light_weights(const float *raw) {  // raw: device floats, 
     return PolicyWeightsM{raw + kLightW1, raw + kLightB1, raw + kLightW2, raw + kLightB2, raw + kLightWa, raw + kLightBa};
 }
 
-// every instantiation this build launches: [list * 2 + sample]; profiling build: [4 + sample] is conv1 on the fp32 matrix instruction
+// every instantiation this build launches, with its dynamic LDS: [list * 2 + sample], [4 + sample] the dense rollout launch (VALUE);
+// profiling build: [6 + sample] is conv1 on the fp32 matrix instruction
 typedef decltype(&pong_policy_mfma_kernel<true, false, false>) MfmaKernel;
-static const MfmaKernel kMfmaKernels[] = {
-    pong_policy_mfma_kernel<true, false, false>, pong_policy_mfma_kernel<true, false, true>,
-    pong_policy_mfma_kernel<true, true, false>,  pong_policy_mfma_kernel<true, true, true>,
+struct MfmaEntry {
+    MfmaKernel kernel;
+    int lds;
+};
+static const MfmaEntry kMfmaKernels[] = {
+    {pong_policy_mfma_kernel<true, false, false>, kMLds},            {pong_policy_mfma_kernel<true, false, true>, kMLds},
+    {pong_policy_mfma_kernel<true, true, false>, kMLds},             {pong_policy_mfma_kernel<true, true, true>, kMLds},
+    {pong_policy_mfma_kernel<true, false, false, true>, kMLdsValue}, {pong_policy_mfma_kernel<true, false, true, true>, kMLdsValue},
 #ifdef CRL_ABLATION
-    pong_policy_mfma_kernel<false, false, false>, pong_policy_mfma_kernel<false, false, true>,
+    {pong_policy_mfma_kernel<false, false, false>, kMLds},           {pong_policy_mfma_kernel<false, false, true>, kMLds},
 #endif
 };
 
 hipError_t policy_light_prepare() {
     hipError_t e = hipSuccess;
-    for (MfmaKernel k : kMfmaKernels)
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kMLds);
+    for (const MfmaEntry &k : kMfmaKernels)
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
     return e;
 }
 
 // One persistent launch, a workgroup per CU at the most.  env_list / count_dev: the LIST form (`n` is then an upper bound of the count,
-// which the kernel reads itself), else null; sample: null = argmax; bf = false: profiling build only, dense only.
+// which the kernel reads itself), else null; sample: null = argmax; bf = false: profiling build only, dense only; heads: the rollout
+// launch (dense, bf only), else null.
 static hipError_t policy_mfma_launch(bool bf, const float *raw, uint8_t *ring, int head, const uint8_t *frame, int64_t frame_stride, int32_t *actions,
                                      int64_t action_stride, float *logits, int64_t n, int cus, unsigned *ticket, int dbg, const int32_t *env_list,
-                                     const unsigned *count_dev, const SampleArgs *sample, hipStream_t st) {
+                                     const unsigned *count_dev, const SampleArgs *sample, const HeadArgs *heads, hipStream_t st) {
     const int64_t groups = (n + kME - 1) / kME;
     const unsigned grid = (unsigned)(groups < cus ? groups : cus);
-    const MfmaKernel kernel = kMfmaKernels[(CRL_ABL(!bf) ? 4 : env_list ? 2 : 0) + (sample ? 1 : 0)];
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kMThreads), kMLds, st, light_weights(raw), ring, head, frame, frame_stride, actions, action_stride, logits,
-                       env_list ? (int64_t)0 : n, ticket, dbg, env_list, count_dev, sample ? *sample : SampleArgs{});
+    const MfmaEntry &k = kMfmaKernels[(heads ? 4 : CRL_ABL(!bf) ? 6 : env_list ? 2 : 0) + (sample ? 1 : 0)];
+    hipLaunchKernelGGL(k.kernel, dim3(grid), dim3(kMThreads), k.lds, st, light_weights(raw), ring, head, frame, frame_stride, actions, action_stride, logits,
+                       env_list ? (int64_t)0 : n, ticket, dbg, env_list, count_dev, sample ? *sample : SampleArgs{}, heads ? *heads : HeadArgs{});
     return hipGetLastError();
 }
 
@@ -502,7 +563,7 @@ hipError_t policy_light_act_list(const float *raw, uint8_t *ring, int head, cons
                                  int64_t action_stride, float *logits, const int32_t *env_list, const unsigned *count_dev, int64_t max_envs, int cus,
                                  unsigned *ticket, const SampleArgs *sample, hipStream_t st) {
     return policy_mfma_launch(true, raw, ring, head, frame, frame_stride, actions, action_stride, logits, max_envs, cus, ticket, 0, env_list, count_dev,
-                              sample, st);
+                              sample, nullptr, st);
 }
 
 #ifdef CRL_ABLATION
@@ -523,7 +584,9 @@ struct crl_policy {
     float *raw = nullptr;        // the checkpoint tensors in torch layout (pong_league.h kLightRawFloats)
     PolicyFull *full = nullptr;  // crl_policy_create_full: ActorCritic instead of LightActorCritic (pong_policy_full.hip)
     bool sampling = false;       // crl_policy_set_sampling with a temperature or an epsilon that is not 0: the SAMPLE kernels
-    SampleArgs S{};              // S.n: crl_policy_act calls since create / crl_policy_set_sampling
+    SampleArgs S{};              // S.n: crl_policy_act / _act_rollout calls since create / crl_policy_set_sampling
+    bool critic = false;         // crl_policy_set_critic / _load_weights gave a critic head (the blob's tail, zero until then)
+    WeightStage stage{};         // crl_policy_load_weights: the pinned host copy of the blob
 #ifdef CRL_ABLATION
     PolicyWeights packed{};      // the packed-FMA kernel's weight stream
 #endif
@@ -540,7 +603,7 @@ int crl_policy_create(int32_t device, int64_t num_envs, const float *conv1_w, co
     crl_policy *p = new crl_policy();
     p->device = device, p->n = num_envs;
     if (hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || p->cus <= 0) p->cus = 256;
-    std::vector<float> raw(kLightRawFloats, 0.f);
+    std::vector<float> raw(kLightRawFloats + kLightCriticFloats, 0.f);  // (the critic part stays zero until crl_policy_set_critic / _load_weights)
     policy_light_pack(raw.data(), conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b);
     hipError_t e = hipMalloc(&p->raw, raw.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->raw, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -582,6 +645,7 @@ int crl_policy_create_full(int32_t device, int64_t num_envs, const float *conv1_
 void crl_policy_destroy(crl_policy *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    weight_stage_free(p->stage);
     policy_full_destroy(p->full);
 #ifdef CRL_ABLATION
     if (p->packed.stream) (void)hipFree(const_cast<float *>(p->packed.stream));
@@ -600,34 +664,101 @@ int crl_policy_reset(crl_policy *p, void *stream) {
     return CRL_OK;
 }
 
-int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride, int32_t *actions_dev, int64_t action_stride,
-                   float *logits_dev, void *stream) {
+// crl_policy_act (`who`; reset, values and logp null) and crl_policy_act_rollout.  Without values and log-probs the launches are
+// crl_policy_act's own; with either, the VALUE instantiations / the full-size actor with the critic row.
+static int policy_act(const char *who, crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride, const uint8_t *reset_dev, int32_t *actions_dev,
+                      int64_t action_stride, float *logits_dev, float *values_dev, float *logp_dev, void *stream) {
     crl_fail_no_ctx();
-    if (!p || !frame_dev || !actions_dev) return crl_fail(CRL_EINVAL, "crl_policy_act: null argument");
-    if (int rc = ring_check_act("crl_policy_act", frame_dev, frame_stride, action_stride)) return rc;
+    if (!p || !frame_dev || !actions_dev) return crl_fail(CRL_EINVAL, "%s: null argument", who);
+    if (int rc = ring_check_act(who, frame_dev, frame_stride, action_stride)) return rc;
+    if (values_dev && !p->critic) return crl_fail(CRL_EINVAL, "%s: values_dev, but the policy has no critic (crl_policy_set_critic / _load_weights)", who);
     hipStream_t st = (hipStream_t)stream;
+    if (reset_dev) HIP_TRY(ring_mask_reset(p->ring, reset_dev, p->n, st));
     const SampleArgs S = p->S;  // this call's counter; the next call's is one further, whichever kernel serves it
     p->S.n++;
     const SampleArgs *sample = p->sampling ? &S : nullptr;
+    const bool heads = values_dev || logp_dev;
     hipError_t e;
     if (p->full) {
-        e = policy_full_act(p->full, p->ring, p->head, p->n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, sample, st);
+        e = heads ? policy_full_act_heads(p->full, p->ring, p->head, p->n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, sample, values_dev,
+                                          logp_dev, st)
+                  : policy_full_act(p->full, p->ring, p->head, p->n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, sample, st);
     } else {
         HIP_TRY(hipMemsetAsync(p->ticket, 0, sizeof(unsigned), st));
         // The matrix-pipe kernel, conv1 as three exact bf16 products per tap (430 us at 65 536 envs).  Profiling build only
         // (CRL_POLICY_MFMA): 1 = the same kernel with conv1 on the fp32 matrix instruction (757 us), 0 = the packed-FMA kernel of
-        // round 1 (725-805 us, pong_policy_packed.inc); CRL_POLICY_MFMA_DEBUG skips phases (wrong outputs).
+        // round 1 (725-805 us, pong_policy_packed.inc); CRL_POLICY_MFMA_DEBUG skips phases (wrong outputs).  The rollout launch has
+        // the one kernel.
         static const int use_mfma = CRL_ABL(getenv("CRL_POLICY_MFMA") != nullptr) ? atoi(getenv("CRL_POLICY_MFMA")) : 3;
         static const int mdbg = CRL_ABL(getenv("CRL_POLICY_MFMA_DEBUG") ? atoi(getenv("CRL_POLICY_MFMA_DEBUG")) : 0);
+        const HeadArgs H{p->raw + kLightWc, p->raw + kLightBc, values_dev, logp_dev};
+        if (heads)
+            e = policy_mfma_launch(true, p->raw, p->ring, p->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, p->cus, p->ticket, 0,
+                                   nullptr, nullptr, sample, &H, st);
+        else
 #ifdef CRL_ABLATION
-        if (!packed_policy_act(p->packed, use_mfma, p->ring, p->head, p->n, p->cus, frame_dev, frame_stride, actions_dev, action_stride, logits_dev,
-                               p->ticket, p->sampling, S, st, &e))
+            if (!packed_policy_act(p->packed, use_mfma, p->ring, p->head, p->n, p->cus, frame_dev, frame_stride, actions_dev, action_stride, logits_dev,
+                                   p->ticket, p->sampling, S, st, &e))
 #endif
             e = policy_mfma_launch(use_mfma == 3, p->raw, p->ring, p->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, p->cus,
-                                   p->ticket, mdbg, nullptr, nullptr, sample, st);
+                                   p->ticket, mdbg, nullptr, nullptr, sample, nullptr, st);
     }
-    if (e != hipSuccess) return crl_fail(CRL_EHIP, "crl_policy_act: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", who, hipGetErrorString(e));
     p->head = (p->head + 1) & 3;
+    return CRL_OK;
+}
+
+int crl_policy_act(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride, int32_t *actions_dev, int64_t action_stride,
+                   float *logits_dev, void *stream) {
+    return policy_act("crl_policy_act", p, frame_dev, frame_stride, nullptr, actions_dev, action_stride, logits_dev, nullptr, nullptr, stream);
+}
+
+int crl_policy_act_rollout(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride, const uint8_t *reset_dev, int32_t *actions_dev,
+                           int64_t action_stride, float *logits_dev, float *values_dev, float *logp_dev, void *stream) {
+    return policy_act("crl_policy_act_rollout", p, frame_dev, frame_stride, reset_dev, actions_dev, action_stride, logits_dev, values_dev, logp_dev,
+                      stream);
+}
+
+int crl_policy_set_critic(crl_policy *p, const float *critic_w, const float *critic_b) {
+    crl_fail_no_ctx();
+    if (!p || !critic_w || !critic_b) return crl_fail(CRL_EINVAL, "crl_policy_set_critic: null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    std::vector<float> c((size_t)(p->full ? policy_full_critic_floats() : kLightCriticFloats), 0.f);
+    float *dev;
+    if (p->full) {
+        policy_full_pack_critic(c.data(), critic_w, critic_b);
+        dev = policy_full_blob(p->full) + policy_full_blob_floats();
+    } else {
+        policy_light_pack_critic(c.data(), critic_w, critic_b);
+        dev = p->raw + kLightRawFloats;
+    }
+    HIP_TRY(hipMemcpy(dev, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
+    p->critic = true;
+    return CRL_OK;
+}
+
+int crl_policy_load_weights(crl_policy *p, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *conv3_w,
+                            const float *conv3_b, const float *actor_w, const float *actor_b, const float *critic_w, const float *critic_b, void *stream) {
+    crl_fail_no_ctx();
+    if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b || !critic_w != !critic_b || !conv3_w != !conv3_b)
+        return crl_fail(CRL_EINVAL, "crl_policy_load_weights: null argument (only the conv3 pair and the critic pair may be null, each as a pair)");
+    if (!p->full != !conv3_w)
+        return crl_fail(CRL_EINVAL, "crl_policy_load_weights: %s", p->full ? "a full-size policy needs conv3" : "a LightActorCritic policy has no conv3: pass null");
+    const size_t actor_floats = p->full ? (size_t)policy_full_blob_floats() : (size_t)kLightRawFloats;
+    const size_t critic_floats = p->full ? (size_t)policy_full_critic_floats() : (size_t)kLightCriticFloats;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(weight_stage_begin(p->stage, actor_floats + critic_floats));
+    p->stage.host[actor_floats - 1] = 0.f;  // (the pads behind the two biases)
+    for (size_t i = critic_floats - 3; i < critic_floats; i++) p->stage.host[actor_floats + i] = 0.f;
+    if (p->full) {
+        policy_full_pack(p->stage.host, conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
+        if (critic_w) policy_full_pack_critic(p->stage.host + actor_floats, critic_w, critic_b);
+    } else {
+        policy_light_pack(p->stage.host, conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b);
+        if (critic_w) policy_light_pack_critic(p->stage.host + actor_floats, critic_w, critic_b);
+    }
+    HIP_TRY(weight_stage_send(p->stage, p->full ? policy_full_blob(p->full) : p->raw, actor_floats + (critic_w ? critic_floats : 0), (hipStream_t)stream));
+    if (critic_w) p->critic = true;
     return CRL_OK;
 }
 

@@ -6,6 +6,7 @@
 namespace crl {
 
 struct SampleArgs;  // pong_sample.h
+struct HeadArgs;    // pong_sample.h
 
 struct PolicyFull;  // device weights + activation scratch of one crl_policy
 
@@ -18,6 +19,15 @@ void policy_full_destroy(PolicyFull *f);
 // sample: null = argmax, else include/crl.h "sampled actions" with these parameters
 hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
                            int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, hipStream_t st);
+// ... with the rollout heads (include/crl.h "rollout heads"): `values` / `logp`, float32 [n] on the device, each optional
+hipError_t policy_full_act_heads(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
+                                 int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, float *values,
+                                 float *logp, hipStream_t st);
+// A crl_policy's blob carries the critic head (critic [1][256] | bc + 3 pad) behind policy_full_pack's: its device copy, the floats of
+// the actor part (policy_full_blob_floats) and of the critic part, and the packing of the latter into critic_part[critic_floats].
+float *policy_full_blob(PolicyFull *f);
+int64_t policy_full_critic_floats();
+void policy_full_pack_critic(float *critic_part, const float *critic_w, const float *critic_b);
 
 
 // ---- the list form: a league's full-size agents (pong_league.hip).  The league owns the weight blobs and ONE activation scratch.

@@ -48,6 +48,7 @@ static constexpr int64_t kChunk = 65536;         // envs per pass (scratch: 42 K
 
 static constexpr int kOffW1 = 0, kOffB1 = kOffW1 + 1024, kOffW2 = kOffB1 + 16, kOffB2 = kOffW2 + kC2 * 256, kOffW3 = kOffB2 + 32;
 static constexpr int kOffB3 = kOffW3 + kC3 * kK3, kOffWa = kOffB3 + kC3, kOffBa = kOffWa + 3 * kC3, kBlob = kOffBa + 4;
+static constexpr int kOffWc = kBlob, kOffBc = kOffWc + kC3, kCritic = kC3 + 4;  // a crl_policy's blob: the critic row and its bias behind the actor
 
 struct PolicyFull {
     int64_t n = 0, chunk = 0;
@@ -303,10 +304,11 @@ __global__ __launch_bounds__(256, 4) void policy_full_conv3_kernel(const float *
 // actor_linear + argmax (first maximum, like torch.argmax / numpy): one wavefront per env, a fixed-shape butterfly sum.
 // SAMPLE: lane 0 draws the action by include/crl.h "sampled actions" instead (a template parameter, as in pong_policy.hip: the
 // greedy kernel is the code it was); S.id_base is the global id of this launch's env 0.
-template <bool SAMPLE>
+// VALUE (the rollout launch): a fourth dot product, the critic row H.wc, in the same shape; lane 0 writes the value and the log-prob.
+template <bool SAMPLE, bool VALUE>
 __device__ __forceinline__ void policy_full_actor_row(const float *__restrict__ feat, const float *__restrict__ wa, const float *__restrict__ ba,
                                                       int32_t *__restrict__ actions, int64_t action_stride, float *__restrict__ logits,
-                                                      const int64_t row, const int64_t env, const int lane, const SampleArgs &S) {
+                                                      const int64_t row, const int64_t env, const int lane, const SampleArgs &S, const HeadArgs &H) {
     const f4 f = *reinterpret_cast<const f4 *>(feat + row * kC3 + 4 * lane);
     float s[3];
 #pragma unroll
@@ -317,31 +319,45 @@ __device__ __forceinline__ void policy_full_actor_row(const float *__restrict__ 
         for (int off = 32; off >= 1; off >>= 1) s[c] += __shfl_xor(s[c], off);
         s[c] += ba[c];
     }
-    if (lane == 0) action_epilogue<SAMPLE>(S, env, s[0], s[1], s[2], actions, action_stride, logits);
+    if constexpr (VALUE) {
+        const f4 w = *reinterpret_cast<const f4 *>(H.wc + 4 * lane);
+        float v = ((f[0] * w[0] + f[1] * w[1]) + f[2] * w[2]) + f[3] * w[3];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+        v += H.bc[0];
+        if (lane == 0) action_epilogue<SAMPLE, true>(S, env, s[0], s[1], s[2], actions, action_stride, logits, v, &H);
+    } else {
+        if (lane == 0) action_epilogue<SAMPLE>(S, env, s[0], s[1], s[2], actions, action_stride, logits);
+    }
 }
 
 // LIST: a persistent grid, a wavefront walks the rows row, row + 4 gridDim.x, ... below the count; feat is read by the row, the
 // action and the logits are written, and the sample drawn, by the row's env (S.id_base: the global id of env 0 of `actions`).
-template <bool SAMPLE, bool LIST>
+template <bool SAMPLE, bool LIST, bool VALUE = false>
 __global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__restrict__ feat, const float *__restrict__ wa,
                                                                 const float *__restrict__ ba, int32_t *__restrict__ actions,
                                                                 int64_t action_stride, float *__restrict__ logits, int64_t n, SampleArgs S,
-                                                                ListArgs L) {
+                                                                ListArgs L, HeadArgs H) {
     const int lane = threadIdx.x & 63;
     const int64_t env = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if constexpr (LIST) {
         n = list_rows(L, n);
         for (int64_t row = env; row < n; row += (int64_t)gridDim.x * 4)  // (the same trip count in every lane of a wavefront)
-            policy_full_actor_row<SAMPLE>(feat, wa, ba, actions, action_stride, logits, row, L.env_list[row], lane, S);
+            policy_full_actor_row<SAMPLE, VALUE>(feat, wa, ba, actions, action_stride, logits, row, L.env_list[row], lane, S, H);
     } else {
         if (env >= n) return;
-        policy_full_actor_row<SAMPLE>(feat, wa, ba, actions, action_stride, logits, env, env, lane, S);
+        policy_full_actor_row<SAMPLE, VALUE>(feat, wa, ba, actions, action_stride, logits, env, env, lane, S, H);
     }
 }
 
 int64_t policy_full_blob_floats() { return kBlob; }
 int64_t policy_full_act2_floats() { return kK3; }
 int64_t policy_full_feat_floats() { return kC3; }
+int64_t policy_full_critic_floats() { return kCritic; }
+float *policy_full_blob(PolicyFull *f) { return f->w; }
+void policy_full_pack_critic(float *critic_part, const float *critic_w, const float *critic_b) {
+    memcpy(critic_part, critic_w, kC3 * sizeof(float)), critic_part[kOffBc - kOffWc] = critic_b[0];
+}
 
 void policy_full_pack(float *blob, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *conv3_w,
                       const float *conv3_b, const float *actor_w, const float *actor_b) {
@@ -360,7 +376,7 @@ hipError_t policy_full_create(PolicyFull **out, int64_t num_envs, const float *c
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         f->cus <= 0)
         f->cus = 256;
-    std::vector<float> blob(kBlob, 0.f);
+    std::vector<float> blob(kBlob + kCritic, 0.f);  // (the critic part stays zero until crl_policy_set_critic / _load_weights)
     policy_full_pack(blob.data(), conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
     hipError_t e = hipMalloc(&f->w, blob.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(f->w, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -382,8 +398,10 @@ void policy_full_destroy(PolicyFull *f) {
     delete f;
 }
 
-hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
-                           int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, hipStream_t st) {
+// `heads`: the rollout launch of the actor (values / logp of the whole batch, each optional), else null
+static hipError_t policy_full_act_any(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
+                                      int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, const HeadArgs *heads,
+                                      hipStream_t st) {
     for (int64_t e0 = 0; e0 < n; e0 += f->chunk) {
         const int64_t c = std::min<int64_t>(f->chunk, n - e0);
         hipLaunchKernelGGL(policy_full_front_kernel<false>, dim3((unsigned)std::min<int64_t>(c, (int64_t)f->cus * 2)), dim3(256), 0, st,
@@ -393,11 +411,27 @@ hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, co
                            f->w + kOffW3, f->w + kOffB3, f->feat, c, ListArgs{});
         SampleArgs S = sample ? *sample : SampleArgs{};
         S.id_base += e0;
-        hipLaunchKernelGGL((sample ? policy_full_actor_kernel<true, false> : policy_full_actor_kernel<false, false>), dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
+        HeadArgs H{};
+        if (heads) H = HeadArgs{heads->wc, heads->bc, heads->values ? heads->values + e0 : nullptr, heads->logp ? heads->logp + e0 : nullptr};
+        const auto actor = heads ? (sample ? policy_full_actor_kernel<true, false, true> : policy_full_actor_kernel<false, false, true>)
+                                 : (sample ? policy_full_actor_kernel<true, false> : policy_full_actor_kernel<false, false>);
+        hipLaunchKernelGGL(actor, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, st,
                            f->feat, f->w + kOffWa, f->w + kOffBa, actions_dev + e0 * action_stride, action_stride, logits_dev ? logits_dev + e0 * 3 : nullptr, c,
-                           S, ListArgs{});
+                           S, ListArgs{}, H);
     }
     return hipGetLastError();
+}
+
+hipError_t policy_full_act(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
+                           int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, hipStream_t st) {
+    return policy_full_act_any(f, ring, head, n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, sample, nullptr, st);
+}
+
+hipError_t policy_full_act_heads(PolicyFull *f, uint8_t *ring, int head, int64_t n, const uint8_t *frame_dev, int64_t frame_stride,
+                                 int32_t *actions_dev, int64_t action_stride, float *logits_dev, const SampleArgs *sample, float *values,
+                                 float *logp, hipStream_t st) {
+    const HeadArgs H{f->w + kOffWc, f->w + kOffBc, values, logp};
+    return policy_full_act_any(f, ring, head, n, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, sample, &H, st);
 }
 
 hipError_t policy_full_act_list(const float *w_blob, float *act2, float *feat, int64_t scratch_rows, uint8_t *ring, int head, const uint8_t *frame,
@@ -415,7 +449,7 @@ hipError_t policy_full_act_list(const float *w_blob, float *act2, float *feat, i
                            w_blob + kOffW3, w_blob + kOffB3, feat, rows, L);
         const dim3 ag((unsigned)std::min<int64_t>((rows + 3) / 4, (int64_t)cus * 8));
         hipLaunchKernelGGL((sample ? policy_full_actor_kernel<true, true> : policy_full_actor_kernel<false, true>), ag, dim3(256), 0, st, feat, w_blob + kOffWa,
-                           w_blob + kOffBa, actions, action_stride, logits, rows, sample ? *sample : SampleArgs{}, L);
+                           w_blob + kOffBa, actions, action_stride, logits, rows, sample ? *sample : SampleArgs{}, L, HeadArgs{});
     }
     return hipGetLastError();
 }

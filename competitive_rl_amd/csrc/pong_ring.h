@@ -25,6 +25,11 @@ inline int ring_check_act(const char *who, const uint8_t *frame_dev, int64_t fra
 
 inline hipError_t ring_reset(uint8_t *ring, int64_t n, hipStream_t st) { return hipMemsetAsync(ring, 0, (size_t)n * kRingBytes, st); }
 
+// FrameStackTensor.update's mask (utils/utils.py:158-170) for a learner's ring: all four planes of every env whose byte in `reset`
+// (u8 [n], device) is not 0 are zeroed, in front of the act launch that pushes the next frame (pong_policy.hip).  Each lane reads one
+// flag, the wavefront ballots and zeroes the flagged envs' 7 104 bytes in 16-byte stores; one without a flag leaves after the ballot.
+hipError_t ring_mask_reset(uint8_t *ring, const uint8_t *reset, int64_t n, hipStream_t st);
+
 // ring <-> the model's stack (u8 [n][4][42][42], oldest first; tests, checkpoints): pong_policy.hip
 hipError_t policy_copy_stack(uint8_t *ring, uint8_t *ext, int head, int64_t n, int to_ring, hipStream_t st);
 // ... as the body of crl_*_get_stack / _set_stack (`who`) of an object T with a ring, its head and n

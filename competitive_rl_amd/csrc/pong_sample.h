@@ -53,20 +53,60 @@ __device__ inline int sample_action(const SampleArgs &S, int64_t env, float l0, 
     return rs < e0 ? 0 : rs < e01 ? 1 : 2;
 }
 
+// What a rollout launch (crl_policy_act_rollout with values or log-probs) carries beside the actor: the critic row and where the two
+// extra heads go.  The other launches pass it zeroed and never read it.
+struct HeadArgs {
+    const float *wc, *bc;  // critic_linear: [1600] (light) / [256] (full-size) and [1], device
+    float *values;         // optional float32 [N]: critic_linear(features)
+    float *logp;           // optional float32 [N]: include/crl.h "rollout heads"
+};
+
+// include/crl.h "rollout heads": step 3 of "sampled actions" with its terms kept -- d_a = z_a - m, e_a = expf(d_a), S = (e0 + e1) + e2
+// are formed ONCE and serve the draw and the log-probability both.  inv_t is 1 where the style has no temperature.
+struct SoftmaxTerms {
+    float d0, d1, d2, e0, e01, sum;
+};
+__device__ inline SoftmaxTerms softmax_terms(float l0, float l1, float l2, float inv_t) {
+    const float z0 = l0 * inv_t, z1 = l1 * inv_t, z2 = l2 * inv_t;
+    const float m = fmaxf(fmaxf(z0, z1), z2);
+    SoftmaxTerms t;
+    t.d0 = z0 - m, t.d1 = z1 - m, t.d2 = z2 - m;
+    const float e0 = expf(t.d0), e1 = expf(t.d1), e2 = expf(t.d2);
+    t.e0 = e0, t.e01 = e0 + e1, t.sum = t.e01 + e2;
+    return t;
+}
+
 // host: does an agent with these parameters need the SAMPLE kernels?  (0, 0) -- every agent, until it is set -- keeps the greedy ones
 inline bool sample_active(const SampleArgs &S) { return S.inv_t != 0.f || S.eps_q != 0; }
 
 // What the lane that holds an env's three logits does with them: the first-index argmax (torch.argmax; a NaN logit is no supported
 // input and is not guarded), SAMPLE: the draw instead, then the action and, where asked for, the logits.  SAMPLE is a template
 // parameter, not a branch on a kernel argument: the greedy kernels are the code they were, whatever the compiler makes of the draw.
-template <bool SAMPLE>
+// HEADS (the rollout launches): the value `v` and the log-probability of the action written, whichever branch chose it, go out as
+// well (H.values / H.logp, each optional); the softmax terms are formed once for the draw and the log-probability.  A template
+// parameter for the same reason: action_epilogue<SAMPLE> is the code it was.
+template <bool SAMPLE, bool HEADS = false>
 __device__ __forceinline__ void action_epilogue(const SampleArgs &S, int64_t env, float a0, float a1, float a2, int32_t *__restrict__ actions,
-                                                int64_t action_stride, float *__restrict__ logits) {
+                                                int64_t action_stride, float *__restrict__ logits, float v = 0.f, const HeadArgs *H = nullptr) {
     int best = 0;
     float bv = a0;
     if (a1 > bv) best = 1, bv = a1;
     if (a2 > bv) best = 2;
-    if constexpr (SAMPLE) best = sample_action(S, env, a0, a1, a2, best);
+    if constexpr (HEADS) {
+        const bool tempered = SAMPLE && S.inv_t != 0.f;
+        const SoftmaxTerms t = softmax_terms(a0, a1, a2, tempered ? S.inv_t : 1.0f);
+        if constexpr (SAMPLE) {
+            uint32_t x0;
+            const int explored = sample_explore(S.seed, (uint64_t)(S.id_base + env), S.n, S.eps_q, x0);
+            if (explored >= 0) best = explored;
+            else if (tempered) {
+                const float rs = ((float)(x0 >> 8) * 0x1p-24f) * t.sum;
+                best = rs < t.e0 ? 0 : rs < t.e01 ? 1 : 2;
+            }
+        }
+        if (H->values) H->values[env] = v;
+        if (H->logp) H->logp[env] = (best == 0 ? t.d0 : best == 1 ? t.d1 : t.d2) - logf(t.sum);
+    } else if constexpr (SAMPLE) best = sample_action(S, env, a0, a1, a2, best);
     actions[env * action_stride] = best;
     if (logits) {
         float *lo = logits + env * 3;

@@ -168,6 +168,23 @@ class AgentPool:
         agent's list in every step."""
         self._add_cnn(name, N.CRL_POOL_KIND_FULL, "ActorCritic", _full_weights, weights_or_checkpoint, temperature, epsilon, scratch_rows)
 
+    def update_agent(self, agent, weights_or_checkpoint):
+        """Replaces the weights of CNN agent ``agent`` (a name or an index) in place -- a learner's newer snapshot into the slot of an older
+        one, so a full pool can follow a learner (``crl_pool_load_light`` / ``crl_pool_load_full``).  Takes what ``add_agent`` /
+        ``add_full_agent`` take, of the slot's own network; a built-in agent and the other network are refused, the pool is then what
+        it was.  Ordered on the current stream, no synchronisation: steps enqueued before play the old weights.  Assignment, lists,
+        play styles and the shared history are untouched."""
+        a = self._agent_index(agent)
+        name, kind = self.agent_names[a], self._kinds[a]
+        if kind == N.CRL_LEAGUE_LIGHT:
+            w, load, keys = _light_weights(name, weights_or_checkpoint), self._L.crl_pool_load_light, _KEYS
+        elif kind == N.CRL_POOL_KIND_FULL:
+            w, load, keys = _full_weights(name, weights_or_checkpoint), self._L.crl_pool_load_full, _FULL_KEYS
+        else:
+            raise ValueError(f"{name} is a built-in agent without weights")
+        with torch.cuda.device(self.device):
+            N.check(load(self._h, a, *[w[k].ctypes.data_as(C.c_void_p) for k in keys], self._stream()))
+
     def _agent_index(self, agent):
         if isinstance(agent, str):
             if agent not in self.agent_names:

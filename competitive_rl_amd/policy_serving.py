@@ -9,6 +9,11 @@ include/crl.h); there is no torch model and no CPU path in this module.
 full-size ActorCritic (network.py:14-50; three fp32 MFMA GEMM kernels, csrc/pong_policy_full.hip) for checkpoints a
 user trained with the reference -- the reference tree itself ships none for it (STRONG / ALPHA_PONG's files
 are missing), so without a checkpoint it starts from the reference's orthogonal initialisation.
+
+A trainer's own network is served by the same kernels: ``act_rollout`` returns ``(values, actions, log_probs)`` of one forward pass
+(the critic head of the checkpoint, the log-probability of the action written, a reset flag per env that masks the frame stack as
+``FrameStackTensor.update(obs, mask)`` does) and ``load_weights`` replaces the weights in place after every update
+(include/crl.h "rollout heads").
 """
 import ctypes as C
 import logging
@@ -18,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .rules import check_sampling
+from .rules import check_sampling, rollout_logp_reference  # noqa: F401  (re-exported)
 
 ASSETS = os.path.join(N.PKG, "assets")
 BUILTIN_CHECKPOINTS = {"WEAK": os.path.join(ASSETS, "pong_policy_weak.npz"),
@@ -45,6 +50,30 @@ def load_light_weights(checkpoint_path):
         if w[k].shape != _SHAPES[k]:
             raise ValueError(f"{checkpoint_path}: {k} has shape {w[k].shape}, LightActorCritic on (4, 42, 42) needs {_SHAPES[k]}")
     return w
+
+
+_CRITIC_KEYS = ("critic_w", "critic_b")
+_CRITIC_SHAPES = {False: {"critic_w": (1, 256), "critic_b": (1,)}, True: {"critic_w": (1, 1600), "critic_b": (1,)}}  # [use_light_model]
+
+
+def critic_of(source, light, origin="weights"):
+    """The critic head (``critic_w``, ``critic_b``: float32, torch layout) that travels BESIDE a weight set -- ``load_light_weights`` /
+    ``load_full_weights`` return the actor's tensors only, as they always did -- or None when ``source`` carries none.  ``source``: an
+    ``.npz`` path, a reference checkpoint's path (``critic_linear.*``) or a dict of arrays."""
+    if isinstance(source, str):
+        if source.endswith(".npz"):
+            z = np.load(source)
+            source = {k: z[k] for k in _CRITIC_KEYS if k in z.files}
+        else:
+            sd = torch.load(source, map_location="cpu", weights_only=False)["model"]
+            source = {k: sd[n].detach().cpu().numpy() for k, n in zip(_CRITIC_KEYS, ("critic_linear.weight", "critic_linear.bias")) if n in sd}
+    if not all(k in source for k in _CRITIC_KEYS):
+        return None
+    c = {k: np.ascontiguousarray(source[k], np.float32) for k in _CRITIC_KEYS}
+    for k in _CRITIC_KEYS:
+        if c[k].shape != _CRITIC_SHAPES[bool(light)][k]:
+            raise ValueError(f"{origin}: {k} has shape {c[k].shape}, this network's critic_linear needs {_CRITIC_SHAPES[bool(light)][k]}")
+    return c
 
 
 _FULL_KEYS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "actor_w", "actor_b")
@@ -106,14 +135,11 @@ class Policy:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.use_light_model = bool(use_light_model)
-        if weights is not None:
-            self.weights = ({k: np.ascontiguousarray(weights[k], np.float32) for k in _KEYS} if use_light_model
-                            else check_full_weights(weights))
-        elif checkpoint_path:
-            self.weights = load_light_weights(checkpoint_path) if use_light_model else load_full_weights(checkpoint_path)
+        if weights is not None or checkpoint_path:
+            self.weights, self.critic = self._weights_of(weights if weights is not None else checkpoint_path)
         else:
             logging.warning("Loading a policy without checkpoint!")
-            self.weights = _random_light_weights() if use_light_model else _random_full_weights()
+            self.weights, self.critic = (_random_light_weights() if use_light_model else _random_full_weights()), None
         self._L = N.load()
         h = C.c_void_p()
         ptr = [self.weights[k].ctypes.data_as(C.c_void_p) for k in (_KEYS if use_light_model else _FULL_KEYS)]
@@ -121,8 +147,31 @@ class Policy:
         with torch.cuda.device(self.device):
             N.check(create(self.device.index or 0, self.num_envs, *ptr, C.byref(h)))
         self._h = h
+        if self.critic is not None:
+            with torch.cuda.device(self.device):
+                N.check(self._L.crl_policy_set_critic(self._h, *[self.critic[k].ctypes.data_as(C.c_void_p) for k in _CRITIC_KEYS]))
         self._actions = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
         self._logits = torch.zeros((self.num_envs, 3), dtype=torch.float32, device=self.device)
+        self._values = torch.zeros((self.num_envs,), dtype=torch.float32, device=self.device)
+        self._logp = torch.zeros((self.num_envs,), dtype=torch.float32, device=self.device)
+
+    def _weights_of(self, source):
+        """(the actor's tensors as ``self.weights`` holds them, the critic head or None) of a dict of arrays or a checkpoint path"""
+        light = self.use_light_model
+        if isinstance(source, Policy):
+            if source.use_light_model != light:
+                raise ValueError("the other policy serves the other network")
+            return source.weights, source.critic
+        if isinstance(source, str):
+            w = load_light_weights(source) if light else load_full_weights(source)
+        elif light:
+            w = {k: np.ascontiguousarray(source[k], np.float32) for k in _KEYS}
+            for k in _KEYS:
+                if w[k].shape != _SHAPES[k]:
+                    raise ValueError(f"weights: {k} has shape {w[k].shape}, LightActorCritic on (4, 42, 42) needs {_SHAPES[k]}")
+        else:
+            w = check_full_weights(source)
+        return w, critic_of(source, light, source if isinstance(source, str) else "weights")
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -162,8 +211,48 @@ class Policy:
         return out
 
     def logits(self):
-        """Logits of the last ``act_device(..., want_logits=True)`` call, float32 (N, 3)."""
+        """Logits of the last ``act_device(..., want_logits=True)`` / ``act_rollout(..., want_logits=True)`` call, float32 (N, 3)."""
         return self._logits
+
+    def act_rollout(self, obs, reset=None, out=None, want_logits=False, want_values=True):
+        """A learner's step (the reference's ``trainer.compute_action(obs, deterministic)`` on a masked ``FrameStackTensor``,
+        utils/utils.py:121-123, :43-58): ``act_device`` that also returns the critic's value and the log-probability of the action it
+        wrote -- ``(values, actions, log_probs)``, float32 (N,), int32 (as ``out`` of ``act_device``), float32 (N,), device tensors
+        (the two float ones are the policy's own buffers, overwritten by the next call), no host synchronisation.  ``reset``: N uint8
+        or bool flags on the device, e.g. the env's ``done`` of the previous step as it is: the stack of every flagged env is zeroed
+        before ``obs`` is pushed, so the network sees [0, 0, 0, frame] there (``FrameStackTensor.update(obs, 1 - reset)``).  The
+        log-probability follows include/crl.h "rollout heads" (``rules.rollout_logp_reference``): of softmax(logits / T) at the
+        policy's temperature (T = 1 when greedy), epsilon not folded in.  Needs a critic (``critic_w`` / ``critic_b`` beside the
+        weights, an ``.npz`` or a reference checkpoint that carries them) unless ``want_values=False``; values are then None."""
+        f = self._frames(obs)
+        out = self._actions if out is None else out
+        assert out.dtype == torch.int32 and out.device == self.device and out.shape[0] == self.num_envs and out.numel() == self.num_envs
+        stride = out.stride(0) if self.num_envs > 1 else 1
+        if reset is not None:
+            assert reset.device == self.device and reset.numel() == self.num_envs and reset.dtype in (torch.uint8, torch.bool), "reset: N uint8 / bool flags on the device"
+            reset = reset.reshape(-1).contiguous()
+            reset = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
+        N.check(self._L.crl_policy_act_rollout(self._h, C.c_void_p(f.data_ptr()), f.stride(0), C.c_void_p(reset.data_ptr()) if reset is not None else None,
+                                               C.c_void_p(out.data_ptr()), stride, C.c_void_p(self._logits.data_ptr()) if want_logits else None,
+                                               C.c_void_p(self._values.data_ptr()) if want_values else None, C.c_void_p(self._logp.data_ptr()),
+                                               self._stream()))
+        return (self._values if want_values else None), out, self._logp
+
+    def load_weights(self, weights_or_checkpoint):
+        """Replaces the network's weights in place (``crl_policy_load_weights``): a dict of arrays in torch layout, a checkpoint path
+        (``.npz`` or a reference checkpoint) or another ``Policy`` of the same network; with ``critic_w`` / ``critic_b`` the critic
+        too, without them the current critic stays.  Ordered on the current stream -- ``act_*`` calls enqueued before use the old
+        weights, calls after it the new ones -- without synchronising the device; the frame stack, its history, the play style and
+        its call counter are untouched.  The arrays are copied before the call returns."""
+        w, critic = self._weights_of(weights_or_checkpoint)
+        k = {k: w[k].ctypes.data_as(C.c_void_p) for k in w}
+        c = [critic[k].ctypes.data_as(C.c_void_p) for k in _CRITIC_KEYS] if critic is not None else [None, None]
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_policy_load_weights(self._h, k["conv1_w"], k["conv1_b"], k["conv2_w"], k["conv2_b"], k.get("conv3_w"), k.get("conv3_b"),
+                                                    k["actor_w"], k["actor_b"], *c, self._stream()))
+        self.weights = w
+        if critic is not None:
+            self.critic = critic
 
     def set_sampling(self, temperature=1.0, epsilon=0.0, seed=0, env_id_base=0):
         """From the next ``act_device`` / ``__call__`` on the actions are drawn on the device, in the kernel's epilogue, by the rule of

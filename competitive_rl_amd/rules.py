@@ -73,6 +73,27 @@ def league_sample_reference(seed, gid, n, logits, temperature, epsilon):
     return np.where(explored, action, sampled), explored, margin
 
 
+def rollout_logp_reference(logits, actions, temperature):
+    """The log-probability rule of include/crl.h "rollout heads" in numpy: z_a = l_a * inv_t, m = max z, d_a = z_a - m in float32 exactly
+    as the kernels form them (inv_t = float32 1 / temperature, 1 at temperature 0); e_a = exp(d_a), S = (e0 + e1) + e2 and
+    logp = d_action - log(S) HERE in float64.  ``actions`` are the actions written, whichever branch chose them: epsilon is not
+    folded into the probability.  ``logits[..., 3]`` float32, ``actions[...]`` integers; returns float64.  Host code for tests and
+    for callers that want to check a log-prob; the kernels do not use it."""
+    t, _ = check_sampling(temperature, 0.0)
+    lg = np.asarray(logits, np.float32)
+    if lg.shape[-1] != 3:
+        raise ValueError("logits[..., 3]")
+    inv_t = np.float32(1) / np.float32(t) if t > 0 else np.float32(1)
+    z = (lg * inv_t).astype(np.float32)
+    d = (z - z.max(axis=-1, keepdims=True)).astype(np.float32)
+    e = np.exp(d.astype(np.float64))
+    s = (e[..., 0] + e[..., 1]) + e[..., 2]
+    a = np.asarray(actions, np.int64)
+    if a.shape != lg.shape[:-1] or a.min(initial=0) < 0 or a.max(initial=0) > 2:
+        raise ValueError("one action in {0, 1, 2} per row of logits")
+    return np.take_along_axis(d, a[..., None], axis=-1)[..., 0].astype(np.float64) - np.log(s)
+
+
 def league_draw_reference(seed, gid, counter, domain, m):
     """The league's draw rule in numpy (include/crl.h "league draws"): Philox4x32-10 word 0 of counter (gid lo, gid hi, counter,
     domain) under key (seed lo, seed hi), scaled to [0, m) by a multiply-high.  Arrays broadcast; returns int64.  Host code for

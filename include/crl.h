@@ -458,6 +458,52 @@ int crl_policy_set_stack(crl_policy *p, const uint8_t *stack_in_dev, void *strea
  * never had this called plays the argmax.  Refuses (CRL_EINVAL, before any GPU call) what crl_sampling_set_agent refuses. */
 int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base);
 
+/* ---- rollout heads: serving a LEARNER ---------------------------------------------------------
+ * The reference's trainers run their own network through trainer.compute_action(obs, deterministic) -> (values, actions, log_probs)
+ * (utils/utils.py:121-123) on a FrameStackTensor that step_envs zeroes for finished envs before the next frame is pushed
+ * (FrameStackTensor.update(obs, mask), utils/utils.py:158-170, :43-58), and the network changes after every update.  A crl_policy
+ * serves such a network with four additions; none of them changes what crl_policy_act computes.
+ *
+ * Critic.  LightActorCritic.forward / ActorCritic.forward return (logits, value) (utils/network.py:40-47, 83-89):
+ * value = critic_linear(features), [1, 1600] + [1] for the light network and [1, 256] + [1] for the full-size one, on the features
+ * the actor reads.  crl_policy_set_critic uploads the head (host pointers, torch layout; synchronous like create).  A policy that
+ * never got one behaves as before.  On the device the light network's value is summed in a fixed shape of its own (the four
+ * channel groups of a position, four neighbouring positions, then the env's 25 such blocks), the full-size one's like a logit: an
+ * env's value does not depend on the batch size or on where the env sits in it. */
+int crl_policy_set_critic(crl_policy *p, const float *critic_w_host /*[1,1600] or [1,256]*/, const float *critic_b_host /*[1]*/);
+/* crl_policy_act plus:
+ *   reset_dev   optional u8 [N]: for every env with a non-zero byte all four planes of the stack are zeroed BEFORE this call's frame
+ *               is pushed -- the network then sees [0, 0, 0, frame], FrameStackTensor.update with mask = 1 - reset.  One more
+ *               launch in front of the act launch on the same stream; with NULL there is none.
+ *   values_dev  optional float32 [N]: critic_linear(features) of the same forward pass.
+ *   logp_dev    optional float32 [N]: the log-probability of the action THIS call writes to actions_dev, by the rule below.
+ * With values_dev and logp_dev both NULL the launches are crl_policy_act's own.  The call advances the same counter as crl_policy_act
+ * (the n of "sampled actions") and pushes the same ring; the two may be mixed call by call, and logits and actions are the same
+ * bits either way.  Refuses (CRL_EINVAL, before any GPU call) what crl_policy_act refuses, and values_dev on a policy without a
+ * critic.
+ *
+ * Log-probability rule (tests restate it in numpy: rules.rollout_logp_reference).  float32, one rounding per operation; the terms are
+ * those of step 3 of "sampled actions" and are formed once for the draw and the log-probability both:
+ *   inv_t = the policy's float32 1 / temperature, and 1.0f at temperature 0;
+ *   z_a = l_a * inv_t,  m = max z,  d_a = z_a - m,  e_a = expf(d_a),  S = (e0 + e1) + e2,
+ *   logp = d_action - logf(S)          (expf, logf: the device library's)
+ * `action` is the action written, whether the argmax, the draw or the explore branch chose it.  Epsilon is NOT folded into the
+ * probability: logp is the log of softmax(l * inv_t)[action], not of the epsilon-mixed distribution the actions follow. */
+int crl_policy_act_rollout(crl_policy *p, const uint8_t *frame_dev, int64_t frame_stride, const uint8_t *reset_dev, int32_t *actions_dev,
+                           int64_t action_stride, float *logits_dev, float *values_dev, float *logp_dev, void *stream);
+/* Replaces the weights in place, ordered on `stream`: act calls enqueued on it before this call use the old weights, calls after it
+ * the new ones; nothing synchronises the device.  Tensors as for crl_policy_create / _create_full (host pointers, torch layouts):
+ * conv3_w_host / conv3_b_host are the full-size network's and must be NULL for a LightActorCritic policy.  The critic pair is
+ * optional: NULL keeps the current critic.  The tensors are packed into one pinned host buffer that the policy keeps and reuses, and
+ * the host pointers are free again when the call returns; a second reload first waits (on the host, on an event) until the first
+ * one's copy has left that buffer.  The ring, its head, the play style and its counter are untouched.  Act calls on ANOTHER
+ * stream are the caller's to order. */
+int crl_policy_load_weights(crl_policy *p, const float *conv1_w_host, const float *conv1_b_host, const float *conv2_w_host,
+                            const float *conv2_b_host, const float *conv3_w_host /* full-size only, else NULL */,
+                            const float *conv3_b_host /* full-size only, else NULL */, const float *actor_w_host,
+                            const float *actor_b_host, const float *critic_w_host /* optional */, const float *critic_b_host /* optional */,
+                            void *stream);
+
 /* ---- league: per-env opponents of cPongTournament-v0 on the device --------------------------
  * Stands in for what a POPULATION of the reference's workers does together: each worker's TournamentEnvWrapper draws an opponent
  * of its own (pong/competitive_pong_env.py:27-33 reset_opponent -> random.choice(agent_names)) out of RANDOM (np.random.randint(3),
@@ -538,6 +584,19 @@ int crl_pool_add_full(crl_league *l, const float *conv1_w_host /*[16,4,4,4]*/, c
                       const float *conv2_w_host /*[32,16,4,4]*/, const float *conv2_b_host /*[32]*/,
                       const float *conv3_w_host /*[256,32,11,11]*/, const float *conv3_b_host /*[256]*/,
                       const float *actor_w_host /*[3,256]*/, const float *actor_b_host /*[3]*/, int64_t scratch_rows);
+/* crl_policy_load_weights for slot `agent` of a pool: a learner's newer snapshot replaces the weights of a CNN agent in place (the
+ * slot's device blob), ordered on `stream` like that call and through a pinned staging buffer of the league's own; a pool of
+ * CRL_LEAGUE_MAX_AGENTS append-only slots can so follow a learner for ever.  Tensors as for crl_league_add_light / crl_pool_add_full.
+ * Assignment, lists, play styles, the shared ring and the scratch are untouched.  Refuses (CRL_EINVAL, before any GPU call) a null
+ * argument, a slot outside the pool, a built-in slot and a slot of the other kind.  (Named crl_pool_* like crl_pool_add_full: the
+ * crl_league_* surface stays the thirteen entry points it was.) */
+int crl_pool_load_light(crl_league *l, int32_t agent, const float *conv1_w_host /*[16,4,4,4]*/, const float *conv1_b_host /*[16]*/,
+                        const float *conv2_w_host /*[16,16,2,2]*/, const float *conv2_b_host /*[16]*/,
+                        const float *actor_w_host /*[3,1600]*/, const float *actor_b_host /*[3]*/, void *stream);
+int crl_pool_load_full(crl_league *l, int32_t agent, const float *conv1_w_host /*[16,4,4,4]*/, const float *conv1_b_host /*[16]*/,
+                       const float *conv2_w_host /*[32,16,4,4]*/, const float *conv2_b_host /*[32]*/,
+                       const float *conv3_w_host /*[256,32,11,11]*/, const float *conv3_b_host /*[256]*/,
+                       const float *actor_w_host /*[3,256]*/, const float *actor_b_host /*[3]*/, void *stream);
 /* The play style of agent `agent` of the pool ("sampled actions" above), from the next crl_league_act on; host values, no GPU call.
  * Refuses (CRL_EINVAL) an agent outside the pool, a negative or non-finite temperature (or one so small that 1 / temperature is no
  * float32) and an epsilon outside [0, 1].  An agent at (0, 0) is served by the launch it always had.  (Named crl_sampling_*: the
