@@ -173,6 +173,14 @@ SIGNATURES = {
     "crl_arena_set_env_state": (i32, [vp, vp, vp, vp, vp]),
     "crl_arena_draw": (i32, [vp, vp, vp, vp]),
     "crl_arena_step": (i32, [vp, vp, vp, i64, vp, i32, vp, vp]),
+    "crl_rollout_create": (i32, [i32, i64, i64, P(vp)]),
+    "crl_rollout_destroy": (None, [vp]),
+    "crl_rollout_begin": (i32, [vp, vp, vp]),
+    "crl_rollout_record": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]),
+    "crl_rollout_outcome": (i32, [vp, i64, vp, i64, vp, vp]),
+    "crl_rollout_finish": (i32, [vp, vp, f64, f64, i32, vp]),
+    "crl_rollout_gather": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "crl_rollout_stats": (i32, [vp, P(f64)]),
 }
 SYMBOLS = list(SIGNATURES)
 

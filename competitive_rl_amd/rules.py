@@ -1,6 +1,7 @@
 """The host-side rules of the league, the ledger and the arena that need no GPU and no other module of the package: what a play style
-may be (``check_sampling``) and the numpy restatements of the device draws (include/crl.h "league draws", "sampled actions").  A leaf:
-``league``, ``ledger``, ``arena`` and ``policy_serving`` import it, it imports none of them.
+may be (``check_sampling``) and the numpy restatements of the device draws (include/crl.h "league draws", "sampled actions") and of
+the rollout storage's stack and GAE rules ("rollout storage").  A leaf: ``league``, ``ledger``, ``arena``, ``policy_serving`` and
+``rollout`` import it, it imports none of them.
 """
 import numpy as np
 
@@ -100,3 +101,53 @@ def league_draw_reference(seed, gid, counter, domain, m):
     tests and for callers that want to predict an assignment; the kernels do not use it."""
     c = _philox4x32_10(gid, counter, domain, seed)
     return ((c[0] * np.uint64(m)) >> np.uint64(32)).astype(np.int64)
+
+
+def rollout_stack_reference(rows, reset, depth_before=3):
+    """The stack rule of include/crl.h "rollout storage" in numpy.  ``rows``: uint8 [T + 3, N, 42, 42] -- rows 0..2 the three frames before
+    step 0 (oldest first), row t + 3 the frame pushed at step t; ``reset``: [T, N], non-zero where the stack was masked before the push;
+    ``depth_before``: depth[-1], a scalar or [N] -- 3 after ``begin`` with a stack or on a fresh storage, ``min(3, depth[T - 1])`` of the
+    rollout before after a carrying ``begin``.  depth[t] = 1 where reset[t], else min(4, depth[t - 1] + 1); plane j of sample (t, e) is
+    row t + j of env e if 3 - j < depth[t][e], else zeros.  Returns (stacks uint8 [T, N, 4, 42, 42], depth uint8 [T, N]).  Host code for
+    tests and for callers that want to check a gathered stack; the kernels do not use it."""
+    rows = np.asarray(rows, np.uint8)
+    flags = np.asarray(reset) != 0
+    steps, n = flags.shape
+    if rows.shape[:2] != (steps + 3, n):
+        raise ValueError(f"rows must be [T + 3, N, ...] = [{steps + 3}, {n}, ...], not {rows.shape}")
+    d = np.broadcast_to(np.asarray(depth_before, np.int64), (n,)).copy()
+    if d.min(initial=1) < 1 or d.max(initial=1) > 3:
+        raise ValueError("depth_before lies in [1, 3]")
+    depth = np.zeros((steps, n), np.uint8)
+    stacks = np.zeros((steps, n, 4) + rows.shape[2:], np.uint8)
+    for t in range(steps):
+        d = np.where(flags[t], 1, np.minimum(4, d + 1))
+        depth[t] = d
+        for j in range(4):
+            live = (3 - j) < d
+            stacks[t, live, j] = rows[t + j, live]
+    return stacks, depth
+
+
+def gae_reference(rewards, values, dones, last_values, gamma, lam):
+    """The GAE rule of include/crl.h "rollout storage" in numpy, float32 with one rounding per operation as the kernel forms it:
+    g = float32(gamma), gl = float32(g * float32(lam)); acc = 0; for t = T-1 .. 0: nd = done[t] ? 0 : 1, vnext = last_values at T-1 else
+    values[t+1], delta = (rewards[t] + (g * vnext) * nd) - values[t], acc = delta + (gl * nd) * acc, adv[t] = acc, ret[t] = acc +
+    values[t].  ``rewards``, ``values``, ``dones``: [T, N]; ``last_values``: [N].  Returns (adv, ret) float32 [T, N].  Host code for
+    tests; the kernels do not use it."""
+    r, v = np.asarray(rewards, np.float32), np.asarray(values, np.float32)
+    nd_all = np.where(np.asarray(dones) != 0, np.float32(0), np.float32(1)).astype(np.float32)
+    if not (r.shape == v.shape == nd_all.shape) or r.ndim != 2:
+        raise ValueError("rewards, values and dones are [T, N]")
+    vnext = np.broadcast_to(np.asarray(last_values, np.float32), r.shape[1:]).astype(np.float32)
+    g = np.float32(gamma)
+    gl = np.float32(g * np.float32(lam))
+    acc = np.zeros(r.shape[1:], np.float32)
+    adv, ret = np.zeros_like(r), np.zeros_like(r)
+    for t in range(r.shape[0] - 1, -1, -1):
+        nd = nd_all[t]
+        delta = ((r[t] + (g * vnext).astype(np.float32) * nd).astype(np.float32) - v[t]).astype(np.float32)
+        acc = (delta + (gl * nd).astype(np.float32) * acc).astype(np.float32)
+        adv[t], ret[t] = acc, (acc + v[t]).astype(np.float32)
+        vnext = v[t]
+    return adv, ret

@@ -772,6 +772,78 @@ int crl_arena_draw(crl_arena *a, const int32_t *pairs_dev, int32_t *pairs_out_de
 int crl_arena_step(crl_arena *a, const int32_t *pairs_dev, const float *reward_dev, int64_t reward_stride, const uint8_t *done_dev,
                    int32_t redraw, int32_t *pairs_out_dev, void *stream);
 
+/* ---- rollout storage: T steps of a learner's rollout on the device, GAE, minibatch gather -------------------
+ * Stands in for the storage a PPO / A2C trainer around the reference keeps between trainer.compute_action and its update: per step the
+ * stacked observation as FrameStackTensor holds it (float32 [N, 4, 42, 42], utils/utils.py:145-173: 28 224 bytes per env and step), the
+ * action, its log-probability, the value, the reward and the done flag; then returns and advantages, then shuffled minibatches.  A step
+ * adds ONE new 42 x 42 plane per env -- the other three planes of its stack are the planes of the three steps before it, as in the frame
+ * ring of a crl_policy -- so a crl_rollout keeps T + 3 planes per env and rebuilds the stack of a sample when it is gathered.  An
+ * object of its own beside crl_policy: the caller hands the act call's inputs and outputs over.  All work is ordered on the caller's
+ * stream; no call synchronises with the host except crl_rollout_stats.  crl_rollout_create, _destroy and _stats make the storage's
+ * device current themselves; every other call launches on the device that is current, so the caller has the storage's device current
+ * (as it has for the stream it passes).
+ *
+ * State (num_steps = T, num_envs = N, T * N < 2^31).  planes u8 [T + 3][N][1776]: a plane padded to 111 16-byte chunks as in the ring,
+ * step-major; row t + 3 is the frame pushed at step t, rows 0..2 the three frames before step 0, oldest first.  Per step and env:
+ * reset u8, depth u8, action int32, log-prob, value, reward, advantage and return float32, done u8.  Per env: depth_carry u8.
+ * Two float64 statistics.
+ *
+ * Stack rule (tests restate it in numpy: rules.rollout_stack_reference).  depth[t][e] is the number of planes of the stack of step t
+ * that are not masked, 1..4:
+ *   depth[t][e] = reset[t][e] ? 1 : min(4, depth[t-1][e] + 1);
+ *   depth[-1][e] = 3 after crl_rollout_begin with a stack and on a fresh object (whose history rows are zero): those rows are
+ *   physically what the ring held; after a carrying crl_rollout_begin it is min(3, depth[T-1][e]) of the rollout before.
+ *   Plane j (0 = the oldest) of sample (t, e) is row t + j of env e if 3 - j < depth[t][e], else all zeros.
+ * So the gathered stack of (t, e) is, byte for byte, what crl_policy_get_stack gave for env e right after the crl_policy_act_rollout call
+ * of step t with the same frames and reset flags: FrameStackTensor.update(obs, 1 - reset), utils/utils.py:158-170.
+ *
+ * GAE rule (tests restate it: rules.gae_reference).  One lane per env, float32 with one rounding per operation, no contraction;
+ * g = float32(gamma), gl = g * float32(lam) in float32, both formed once on the host:
+ *   acc = 0;  for t = T-1 .. 0:
+ *     nd = done[t] ? 0.0f : 1.0f;   vnext = (t == T-1) ? last_values : values[t+1];
+ *     delta = (rewards[t] + (g * vnext) * nd) - values[t];   acc = delta + (gl * nd) * acc;
+ *     adv[t] = acc;   ret[t] = acc + values[t].
+ *
+ * Statistics (when crl_rollout_finish is asked to normalise).  Mean and unbiased standard deviation of all T * N advantages in float64,
+ * two passes: mean = sum(x) / (T * N), then std = sqrt(sum((x - mean)^2) / (T * N - 1)), and std = 0 where T * N = 1 (the one
+ * advantage then normalises to (adv - mean32) / 1e-5f = 0).  Each sum has a fixed shape: workgroup w of
+ * G = min(256, ceil(T * N / 256)) adds elements w * 256 + lane, + G * 256, ... in order, its 256 lanes' sums go through a binary tree,
+ * and one final workgroup adds the G partial sums through the same tree.  No floating-point atomics: two runs give the same bits.
+ * A gathered advantage is then (adv - mean32) / (std32 + 1e-5f) in float32 with a true division, mean32 and std32 the float32
+ * roundings of the two statistics; without normalisation it is adv. */
+typedef struct crl_rollout crl_rollout;
+int crl_rollout_create(int32_t device, int64_t num_envs, int64_t num_steps, crl_rollout **out);
+void crl_rollout_destroy(crl_rollout *r);
+/* Starts a rollout: step 0 is recorded next.  stack_dev: u8 [N][4][42][42] as crl_policy_get_stack writes it, taken BEFORE the act call
+ * of step 0: its planes 1..3 become the history rows (plane 0 is the one that call rolls out).  NULL carries over: the last three rows
+ * and the depths of the finished rollout become the history (on a fresh object: zero rows at depth 3), so a rollout that continues the
+ * one before gathers what an uninterrupted one would.  Refuses (CRL_EINVAL) to carry over from a rollout that is not finished. */
+int crl_rollout_begin(crl_rollout *r, const uint8_t *stack_dev, void *stream);
+/* Step t, one launch: the inputs and outputs of its crl_policy_act_rollout call.  frame_dev / frame_stride: as that call took them
+ * (stride a multiple of 4 and >= 1764, pointer 4-byte aligned); reset_dev u8 [N] or NULL (no env flagged); actions_dev int32, env i
+ * at actions_dev[i * action_stride]; values_dev, logp_dev float32 [N].  actions, values and log-probs are each optional: NULL stores
+ * zeros.  t must be the next step: 0 after begin (or on a fresh object), then 1, 2, ... T - 1. */
+int crl_rollout_record(crl_rollout *r, int64_t t, const uint8_t *frame_dev, int64_t frame_stride, const uint8_t *reset_dev,
+                       const int32_t *actions_dev, int64_t action_stride, const float *values_dev, const float *logp_dev, void *stream);
+/* What the env answered to step t's actions: rewards_dev float32, env i at rewards_dev[i * reward_stride] (the learner's column of
+ * the env's (N, 2) reward buffer: stride 2); done_dev u8 [N] (any non-zero byte is a done).  In step order, each after its record. */
+int crl_rollout_outcome(crl_rollout *r, int64_t t, const float *rewards_dev, int64_t reward_stride, const uint8_t *done_dev, void *stream);
+/* After T outcomes: advantages and returns by the GAE rule; last_values_dev float32 [N] = the values of the observation after the last
+ * step (NULL: zeros); with normalize != 0 the statistics too.  May be called again (other gamma / lam) before the next begin. */
+int crl_rollout_finish(crl_rollout *r, const float *last_values_dev, double gamma, double lam, int32_t normalize, void *stream);
+/* A minibatch, one wavefront per sample: idx_dev int64 [B] on the device, flat indices t * N + e in any order, duplicates allowed.
+ * obs_out_dev: [B][4][42][42] as CRL_OBS_F32 (values 0..255, 16-byte aligned) or CRL_OBS_U8 (4-byte aligned), the stack by the stack
+ * rule; actions_out_dev int32 [B]; logp / values / returns / adv float32 [B], adv normalised if the finish was.  Every output is
+ * optional (NULL).  The validity of the indices is the caller's, as with every device-side index array of this header. */
+int crl_rollout_gather(crl_rollout *r, const int64_t *idx_dev, int64_t count, void *obs_out_dev, int32_t obs_dtype, int32_t *actions_out_dev,
+                       float *logp_out_dev, float *values_out_dev, float *returns_out_dev, float *adv_out_dev, void *stream);
+/* out2_host[0] = mean, [1] = std of the advantages, after a finish that normalises.  Synchronises the device (tests, logging). */
+int crl_rollout_stats(crl_rollout *r, double *out2_host);
+/* The host-side state machine refuses, with CRL_EINVAL and before any GPU call: a record whose t is not the next step or that follows a
+ * finish without a begin; an outcome without its record or out of step order; a finish before T outcomes; a gather before the finish;
+ * statistics that were not computed; a carrying begin on an unfinished rollout; null or misaligned pointers.  A refused call changes
+ * nothing. */
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
