@@ -128,6 +128,7 @@ SIGNATURES = {
     "crl_set_flags_event": (i32, [vp, vp]),
     "crl_kernel_time_stats": (i32, [vp, i32, P(f64), P(i64), P(f64)]),
     "crl_draw_raw_delta": (i32, [vp, vp, vp, i32, vp]),
+    "crl_step_raw_delta": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "crl_league_create": (i32, [i32, i64, i64, u64, P(vp)]),
     "crl_league_destroy": (None, [vp]),
     "crl_league_add_builtin": (i32, [vp, i32]),

@@ -565,6 +565,48 @@ int crl_draw_raw_delta(crl_ctx *c, uint8_t *obs_dev, uint64_t *drawn_dev, int32_
     return CRL_OK;
 }
 
+int crl_step_raw_delta(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, uint64_t *drawn_dev, float *rew_dev, uint8_t *done_dev, void *stream) {
+    CRL_ENTER(c);
+    if (!c || !actions_void || !obs_dev || !drawn_dev) return crl_fail(CRL_EINVAL, "null argument");
+    if (c->car || c->o.obs_mode != CRL_OBS_RAW_RGB) return crl_fail(CRL_ESTATE, "crl_step_raw_delta needs a Pong RAW_RGB context");
+    if ((uintptr_t)obs_dev % 16) return crl_fail(CRL_EINVAL, "crl_step_raw_delta: obs_dev must be 16-byte aligned");
+    if ((uintptr_t)drawn_dev % 8) return crl_fail(CRL_EINVAL, "crl_step_raw_delta: drawn_dev must be 8-byte aligned");
+    if (int rc = pending_action_error(c, true)) return rc;  // (reported once; this call did no work)
+    hipStream_t st = (hipStream_t)stream;
+    if (c->flags_ev) {
+        // the caller reads the flags ahead of the draw (crl_set_flags_event): the two launches of crl_step + crl_draw_raw_delta, the event between them
+        begin_timed(c, 0, st);
+        launch_pong_dynamics(c->s, c->src, (const int32_t *)actions_void, c->n, pong_mode(c), rew_dev, done_dev, st);
+        end_timed(c, 0, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->flags_ev, st));
+        begin_timed(c, 1, st);
+        launch_pong_raster_raw_delta(c->s.obs_frames, drawn_dev, c->n, c->atlas_rgb, c->band_span, c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st);
+        end_timed(c, 1, st);
+        HIP_TRY(hipGetLastError());
+        return CRL_OK;
+    }
+#ifdef CRL_ABLATION
+    if (getenv("CRL_RAW_STEP_SPLIT") && atoi(getenv("CRL_RAW_STEP_SPLIT"))) {  // the one-launch kernel's second phase alone, behind the dynamics launch
+        begin_timed(c, 0, st);
+        launch_pong_dynamics(c->s, c->src, (const int32_t *)actions_void, c->n, pong_mode(c), rew_dev, done_dev, st);
+        end_timed(c, 0, st);
+        begin_timed(c, 1, st);
+        launch_pong_step_raw_delta(c->s, c->src, (const int32_t *)actions_void, c->n, rew_dev, done_dev, drawn_dev, c->atlas_rgb, c->band_span,
+                                   c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st, 1);
+        end_timed(c, 1, st);
+        HIP_TRY(hipGetLastError());
+        return CRL_OK;
+    }
+#endif
+    begin_timed(c, 1, st);  // (slot 0 gets nothing on this path: there is no dynamics launch to bracket)
+    launch_pong_step_raw_delta(c->s, c->src, (const int32_t *)actions_void, c->n, rew_dev, done_dev, drawn_dev, c->atlas_rgb, c->band_span, c->ink_row0,
+                               c->ink_row1, obs_dev, pong_views(c), st);
+    end_timed(c, 1, st);
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
+}
+
 int crl_set_flags_event(crl_ctx *c, void *event) {
     CRL_ENTER(c);
     if (!c) return crl_fail(CRL_EINVAL, "null ctx");

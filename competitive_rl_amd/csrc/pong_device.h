@@ -208,6 +208,35 @@ __device__ inline void store_env(const PongSoA &s, int64_t i, const PongEnv &e) 
     s.serve_ctr[i] = e.serve_ctr;
 }
 
+// One raw step (1 step = 1 frame) of env i: DummyVecEnv.step_wait over PongDoublePlayerEnv._step with its auto-reset.  THE raw
+// step of this library: pong_dynamics_kernel<false> and pong_step_raw_delta_kernel both call it (-ffp-contract=off: the same bits
+// in both).  Returns the descriptor of the frame the step's observation shows, which it also stores in obs_frames[i].
+__device__ inline uint64_t raw_step_env(const PongSoA &s, const ServeSrc &src, const int32_t *__restrict__ actions, int64_t i, int64_t n,
+                                        float *__restrict__ rew, uint8_t *__restrict__ done_out, int single) {
+    PongEnv e = load_env(s, i);
+    // cPong-v0: one action per env, the right bat is the AutoBat = CHEAT_CODES on that side
+    const int2 a = single ? make_int2(actions[i], CRL_PONG_CHEAT) : reinterpret_cast<const int2 *>(actions)[i];
+    if (!action_ok(a.x) || !action_ok(a.y)) *s.bad_action = (action_ok(a.x) ? a.y : a.x) + 1;  // rare; any writer wins
+    int r_l, r_r;
+    const bool done = frame_step(e, a.x, a.y, src, i, r_l, r_r);
+    const float fl = (float)r_l, fr = (float)r_r;
+    if (rew) {
+        if (single) rew[i] = fl;
+        else reinterpret_cast<float2 *>(rew)[i] = make_float2(fl, fr);
+    }
+    reinterpret_cast<float2 *>(s.real_reward)[i] = make_float2(fl, fr);
+    if (done) {
+        const uint64_t t = frame_of(e);
+        s.term_frames[i] = t, s.term_frames[n + i] = t;
+        game_reset(e, src, i);
+    }
+    if (done_out) done_out[i] = done ? 1 : 0;
+    const uint64_t f = frame_of(e);
+    s.obs_frames[i] = f;
+    store_env(s, i, e);
+    return f;
+}
+
 // launchers (defined in the .hip files, called from crl_api.hip)
 struct PongMode {
     bool wrapped, single, replicate;  // MaxAndSkip path; cPong-v0 (AutoBat on the right); FrameStack fill
@@ -225,6 +254,12 @@ void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *at
 // device copy of pong_band_span_table()'s table for this atlas (22 x 22 pairs x 2 kinds x {first, last} bytes)
 void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, const uint8_t *band_span,
                                   int ink_row0, int ink_row1, uint8_t *obs, int views, hipStream_t st);
+// a raw step and its delta draw in one launch: raw_step_env() for every env, then what launch_pong_raster_raw_delta does with the
+// new descriptors (views = 1: cPong-v0, one action per env).  stepped (profiling build's CRL_RAW_STEP_SPLIT): the envs were stepped by
+// launch_pong_dynamics already, the launch only draws obs_frames[] -- what its second phase costs alone
+void launch_pong_step_raw_delta(const PongSoA &s, const ServeSrc &src, const int32_t *actions, int64_t n, float *rew, uint8_t *done,
+                                uint64_t *drawn, const uint8_t *atlas_rgb, const uint8_t *band_span, int ink_row0, int ink_row1, uint8_t *obs,
+                                int views, hipStream_t st, int stepped = 0);
 
 // Byte offsets of the dense INTER_AREA tables inside the blob the gray kernel stages into
 // LDS: xa/ya = float[5][R] weights (tap k of output index d at [k*R + d]); xs0/xn, ys0/yn =

@@ -38,30 +38,16 @@ __global__ __launch_bounds__(256) void pong_dynamics_kernel(PongSoA s, ServeSrc 
                                                             uint8_t *__restrict__ done_out, int single, int replicate) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (!WRAPPED) {
+        raw_step_env(s, src, actions, i, n, rew, done_out, single);
+        return;
+    }
     PongEnv e = load_env(s, i);
     // cPong-v0: one action per env, the right bat is the AutoBat = CHEAT_CODES on that side
     const int2 a = single ? make_int2(actions[i], CRL_PONG_CHEAT) : reinterpret_cast<const int2 *>(actions)[i];
     if (!action_ok(a.x) || !action_ok(a.y)) *s.bad_action = (action_ok(a.x) ? a.y : a.x) + 1;  // rare; any writer wins
     int r_l, r_r;
     bool done;
-    if (!WRAPPED) {
-        done = frame_step(e, a.x, a.y, src, i, r_l, r_r);
-        const float fl = (float)r_l, fr = (float)r_r;
-        if (rew) {
-            if (single) rew[i] = fl;
-            else reinterpret_cast<float2 *>(rew)[i] = make_float2(fl, fr);
-        }
-        reinterpret_cast<float2 *>(s.real_reward)[i] = make_float2(fl, fr);
-        if (done) {
-            const uint64_t t = frame_of(e);
-            s.term_frames[i] = t, s.term_frames[n + i] = t;
-            game_reset(e, src, i);
-        }
-        if (done_out) done_out[i] = done ? 1 : 0;
-        s.obs_frames[i] = frame_of(e);
-        store_env(s, i, e);
-        return;
-    }
     // ---- MaxAndSkipEnv.step, skip = 4: keep frames 2 and 3, break on done
     uint64_t k0 = s.keep[i], k1 = s.keep[n + i];
     double tot_l = 0.0, tot_r = 0.0;

@@ -240,17 +240,30 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 //   the launch inside the bench's event brackets ....... 91.4 -> 66.6 us; the step 0.1052 -> 0.0803 ms; the longest launch 436 -> 171 us
 static constexpr int kDeltaL = 32, kDeltaG = 4;  // lanes per (env, view); chunks per block (4: whole 64-byte memory requests)
 static_assert(kFrameChunks % kDeltaG == 0, "a view starts on a block boundary");
+// The one-launch step: the envs of a workgroup (kStepB) and of one of its wavefronts (kStepW; one view: two, a trip's worth).  Whether the
+// stores carry the non-temporal hint: the draw-only kernel's do not (kDeltaNT), the one-launch step's do (kStepNT) -- its workgroups
+// read and write the env state while others store pixels.  All chosen by measurement (profiles/r11_raw_summary.txt).
+static constexpr int kStepW = 1, kStepB = 16;
+static constexpr bool kDeltaNT = false, kStepNT = true;
+
+// a 16-byte store of the delta writer; NT: with the non-temporal hint (the same bytes either way)
+typedef uint32_t crl_u32x4 __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ void chunk_store(uint4 *p, const uint4 &v) {
+    if (NT) __builtin_nontemporal_store(crl_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<crl_u32x4 *>(p));
+    else *p = v;
+}
 
 // one court chunk of the view: q counts the view's chunks, q_row is the first chunk of `row`.  WRAP: q may lie up to two chunks
 // into the row above or below (a ball's block); a bat's block never leaves its row.
-template <bool WRAP>
+template <bool WRAP, bool NT>
 __device__ __forceinline__ void court_store(uint4 *__restrict__ out, int q_view, const Frame &f, bool mirror, int row, int q_row, int q) {
     int o = q - q_row;
     if (WRAP) {
         const int w = (o >= kRowChunks) - (o < 0);
         row += w, o -= w * kRowChunks;
     }
-    *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (uint32_t)((q_view + q) * 16)) = court_chunk(f, row, mirror ? kRowChunks - 1 - o : o, mirror);
+    chunk_store<NT>(reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (uint32_t)((q_view + q) * 16)), court_chunk(f, row, mirror ? kRowChunks - 1 - o : o, mirror));
 }
 
 // the source chunks [c0, c1] a ball at x covers; ok: some byte of it lies inside the row
@@ -265,27 +278,20 @@ __device__ __forceinline__ BallCols ball_cols(int x) {
     return c;
 }
 
-template <int VIEWS, int G>
-__global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
-                                                                    const uint4 *__restrict__ atlas_rgb, const uint8_t *__restrict__ band_span,
-                                                                    int ink_row0, int ink_row1, uint4 *__restrict__ obs, int64_t n) {
-    static_assert((G == 1 || G == 4) && (VIEWS == 1 || VIEWS == 2), "");
-    constexpr int L = kDeltaL, per_env = VIEWS * kFrameChunks, SH = G == 4 ? 2 : 0;
-    constexpr int E = 64 / L / VIEWS;  // whole envs per wavefront: one with two views -> uniform descriptor loads
-    const int64_t gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);  // this wavefront, of the grid
-    const int lane = (int)threadIdx.x & (L - 1), sub = ((int)threadIdx.x & 63) / L;
-    const int64_t env = gw * E + (E > 1 ? sub / VIEWS : 0);
-    const int view = sub % VIEWS;
-    const bool valid = env < n;
-    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
-    if (valid && view == 0 && lane == 0) drawn[env] = pn;
+// The delta draw of one (env, view) by its group of kDeltaL lanes: everything above from the blank tests on.  pn / po: the new
+// descriptor and the one the buffer holds; out: the env's first chunk.  Shared by the draw-only kernel and the one-launch step
+// below.  NT: the stores carry the non-temporal hint (profiles/r11_raw_summary.txt).
+template <int G, bool NT>
+__device__ __forceinline__ void raw_delta_draw(uint64_t pn, uint64_t po, int view, int lane, uint4 *__restrict__ out, const uint4 *__restrict__ atlas_rgb,
+                                               const uint8_t *__restrict__ band_span, int ink_row0, int ink_row1) {
+    static_assert(G == 1 || G == 4, "");
+    constexpr int L = kDeltaL, SH = G == 4 ? 2 : 0;
     const Frame f = unpack_frame(pn), g = unpack_frame(po);
     const bool blank_n = f.sl == 255, blank_o = g.sl == 255;
-    if (!valid || (blank_n && blank_o)) return;  // (two blank frames are equal)
-    uint4 *__restrict__ out = obs + env * per_env;
+    if (blank_n && blank_o) return;  // (two blank frames are equal)
     const int q_view = view * kFrameChunks;
     if (blank_n != blank_o) {  // the whole frame
-        for (int c = lane; c < kFrameChunks; c += L) out[q_view + c] = raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0);
+        for (int c = lane; c < kFrameChunks; c += L) chunk_store<NT>(out + (q_view + c), raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0));
         return;
     }
     const int j = lane & (G - 1), u = lane >> SH;  // this lane's chunk of a block; its (row, block) place within an object
@@ -300,7 +306,7 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
         }
         if (s1 >= kRowChunks) {  // every other pair (a game's end, set_state, a successor outside the atlas): every chunk of the ink rows
             const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
-            for (int c = lane; c < cn; c += L) out[c0 + c] = raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
+            for (int c = lane; c < cn; c += L) chunk_store<NT>(out + (c0 + c), raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0));
         } else if (s0 <= s1) {
             // place = (ink row, block of the row): a row's span touches at most nb blocks (it starts anywhere within its first
             // block), 1 << bs >= nb of them are a row's share of a trip's L / G places, and a trip takes (L / G) >> bs rows
@@ -314,7 +320,7 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
                 const int first = (q_row + (mir ? kRowChunks - 1 - s1 : s0)) >> SH, last = (q_row + (mir ? kRowChunks - 1 - s0 : s1)) >> SH;
                 for (int b0 = 0; b0 < nb; b0 += 1 << bs) {
                     const int blk = first + b0 + bu, q = (blk << SH) + j;  // (a block may reach into the neighbouring row: raw_chunk() draws that row's chunk)
-                    if (row < ink_row1 && blk <= last) out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
+                    if (row < ink_row1 && blk <= last) chunk_store<NT>(out + q, raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0));
                 }
             }
         }
@@ -330,13 +336,13 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
         const int dr = u >> 1, b = u & 1;
         if (cn.ok) {
             const int row = f.y + dr, q_row = row * kRowChunks, blk = ((q_row + n0) >> SH) + b;
-            if (dr < CRL_PONG_BALL && in_court(row) && blk <= ((q_row + n1) >> SH)) court_store<true>(out, q_view, f, mirror, row, q_row, (blk << SH) + j);
+            if (dr < CRL_PONG_BALL && in_court(row) && blk <= ((q_row + n1) >> SH)) court_store<true, NT>(out, q_view, f, mirror, row, q_row, (blk << SH) + j);
         }
         if (co.ok) {
             const int row = g.y + dr, q_row = row * kRowChunks, blk = ((q_row + o0) >> SH) + b;
             const bool again = cn.ok && (unsigned)(row - f.y) < (unsigned)CRL_PONG_BALL && blk >= ((q_row + n0) >> SH) && blk <= ((q_row + n1) >> SH);
             if (dr < CRL_PONG_BALL && in_court(row) && blk <= ((q_row + o1) >> SH) && !again)  // (again: the new ball's rectangle stores this block)
-                court_store<true>(out, q_view, f, mirror, row, q_row, (blk << SH) + j);
+                court_store<true, NT>(out, q_view, f, mirror, row, q_row, (blk << SH) + j);
         }
     }
     // a bat: the rows of the symmetric difference of [a, a + h) and [b, b + h) are [lo, lo + k) and [hi + h - k, hi + h),
@@ -348,11 +354,90 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
         asm("" : "+v"(u_q));  // ... which the compiler folds back into a quarter-rate 32-bit multiply per trip unless one term is opaque
         for (int t0 = 0; t0 < 2 * k; t0 += L >> SH) {
             const int t = t0 + u, row = (t < k ? lo : up) + t, q_row = (t < k ? lo_q : up_q) + t0 * kRowChunks + u_q;
-            if (t < 2 * k && in_court(row)) court_store<false>(out, q_view, f, mirror, row, q_row, ((q_row + o) & ~(G - 1)) + j);
+            if (t < 2 * k && in_court(row)) court_store<false, NT>(out, q_view, f, mirror, row, q_row, ((q_row + o) & ~(G - 1)) + j);
         }
     };
     bat(g.bl, f.bl, kBatLChunk);
     bat(g.br, f.br, kBatRChunk);
+}
+
+template <int VIEWS, int G, bool NT>
+__global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
+                                                                    const uint4 *__restrict__ atlas_rgb, const uint8_t *__restrict__ band_span,
+                                                                    int ink_row0, int ink_row1, uint4 *__restrict__ obs, int64_t n) {
+    static_assert(VIEWS == 1 || VIEWS == 2, "");
+    constexpr int L = kDeltaL, per_env = VIEWS * kFrameChunks;
+    constexpr int E = 64 / L / VIEWS;  // whole envs per wavefront: one with two views -> uniform descriptor loads
+    const int64_t gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);  // this wavefront, of the grid
+    const int lane = (int)threadIdx.x & (L - 1), sub = ((int)threadIdx.x & 63) / L;
+    const int64_t env = gw * E + (E > 1 ? sub / VIEWS : 0);
+    const int view = sub % VIEWS;
+    const bool valid = env < n;
+    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
+    if (valid && view == 0 && lane == 0) drawn[env] = pn;
+    if (!valid) return;
+    raw_delta_draw<G, NT>(pn, po, view, lane, obs + env * per_env, atlas_rgb, band_span, ink_row0, ink_row1);
+}
+
+// A raw step in one launch: raw_step_env() and the delta draw above in the same workgroup, so the step has no second launch, no
+// kernel boundary in front of the draw and no descriptor round trip through obs_frames[].  A workgroup owns B consecutive envs
+// and is B / W wavefronts.  Phase A: lanes 0 .. B-1 of its first wavefront step one env each (SoA state: coalesced loads and
+// stores), swap the new descriptors into the record and hand old and new to the others through LDS behind one barrier; the
+// others wait there and issue nothing.  Phase B: wavefront w holds the descriptors of envs w * W .. w * W + W - 1 in its lanes
+// 0 .. W-1 (every other lane: two blank ones, which the draw skips) and walks them, 64 / kDeltaL / VIEWS per trip as the draw-only
+// kernel's wavefronts do, taking each env's pair out of its lane -- with two views by readlane at the uniform trip index, so the
+// rectangles, trip counts and branches of raw_delta_draw() stay scalar code; with one view each 32-lane group fetches its env's
+// pair by a shuffle.  stepped (profiling build): phase A only reads the descriptors a dynamics launch left.
+// Measured on MI355X at 65 536 envs, two views, variants alternated inside one process over bench.py's window (r11_raw_summary.txt):
+//   draw-only kernel behind the dynamics kernel ....... 68.6 + 5.4 us in their brackets, the step 0.0825 ms
+//   first design: no LDS, every wavefront steps its own W = 16 envs in 16 lanes and draws them in sequence ... 78.0 us, 0.0826 ms
+//   B = 64, W = 8 / 16 / 32 / 64, plain stores ........ 81.5 / 77.2 / 82.1 / 91.8 us; phase B of W = 16 alone 73.9 us: envs in sequence
+//                                                       in one wavefront cost 7 us against one short wavefront per env, phase A 2 us
+//   B = 16, W = 1 (the draw-only kernel's mapping) .... 96.2 us with plain stores, 75.2 us with non-temporal ones, the step 0.0794 ms
+//   W = 1 B = 4 / 8, W = 2 B = 16 / 32, W = 4 B = 32 / 64, W = 8 / 16 B = 64, non-temporal ... 75.6-77.1 us
+// Workgroups outnumber the chip's slots at B = 16, so later ones step while earlier ones store; their state loads then compete
+// with pixel lines in the L2s unless the pixels bypass them.  The draw-only kernel is 1.7 us slower with the hint and keeps plain stores.
+template <int VIEWS, int G, int W, int B, bool NT>
+__global__ __launch_bounds__(64 * (B / W)) void pong_step_raw_delta_kernel(
+    PongSoA s, ServeSrc src, const int32_t *__restrict__ actions, int64_t n, float *__restrict__ rew, uint8_t *__restrict__ done_out,
+    uint64_t *__restrict__ drawn, const uint4 *__restrict__ atlas_rgb, const uint8_t *__restrict__ band_span, int ink_row0, int ink_row1,
+    uint4 *__restrict__ obs, int stepped) {
+    constexpr int L = kDeltaL, per_env = VIEWS * kFrameChunks;
+    constexpr int E = 64 / L / VIEWS;  // envs per trip of phase B
+    static_assert((VIEWS == 1 || VIEWS == 2) && B <= 64 && B % W == 0 && B / W <= 16 && W % E == 0 && (W & (W - 1)) == 0, "");
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), wl = (int)threadIdx.x & 63;
+    const int64_t b0 = (int64_t)blockIdx.x * B, e0 = b0 + wave * W;  // the workgroup's first env, this wavefront's
+    __shared__ uint64_t hand[2][B];
+    if (wave == 0 && wl < B) {
+        uint64_t pn = kBlankFrame, po = kBlankFrame;
+        const int64_t i = b0 + wl;
+        if (i < n) {
+            po = drawn[i];
+            pn = stepped ? s.obs_frames[i] : raw_step_env(s, src, actions, i, n, rew, done_out, VIEWS == 1);
+            drawn[i] = pn;
+        }
+        hand[0][wl] = pn, hand[1][wl] = po;
+    }
+    __syncthreads();
+    const int k = wave * W + (wl & (W - 1));
+    const uint64_t pn = wl < W ? hand[0][k] : kBlankFrame, po = wl < W ? hand[1][k] : kBlankFrame;
+    const int lane = wl & (L - 1), sub = wl / L;
+#pragma unroll 1
+    for (int t = 0; t < W; t += E) {
+        if (e0 + t >= n) break;  // (uniform)
+        uint32_t nl, nh, ol, oh;
+        if (VIEWS == 2) {
+            nl = __builtin_amdgcn_readlane((uint32_t)pn, t), nh = __builtin_amdgcn_readlane((uint32_t)(pn >> 32), t);
+            ol = __builtin_amdgcn_readlane((uint32_t)po, t), oh = __builtin_amdgcn_readlane((uint32_t)(po >> 32), t);
+        } else {
+            nl = __shfl((uint32_t)pn, t + sub), nh = __shfl((uint32_t)(pn >> 32), t + sub);
+            ol = __shfl((uint32_t)po, t + sub), oh = __shfl((uint32_t)(po >> 32), t + sub);
+        }
+        // (an env past n holds two blank descriptors: nothing is stored through its pointer)
+        const int64_t env = e0 + t + (VIEWS == 1 ? sub : 0);
+        raw_delta_draw<G, NT>(((uint64_t)nh << 32) | nl, ((uint64_t)oh << 32) | ol, VIEWS == 2 ? sub : 0, lane, obs + env * per_env, atlas_rgb, band_span,
+                              ink_row0, ink_row1);
+    }
 }
 
 #ifdef CRL_ABLATION  // superseded mapping (running sums over six rectangles, a slot decode per trip; every L and G): profiling build only, CRL_RAW_DELTA_SLOTS=1
@@ -567,18 +652,66 @@ void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64
     // (profiling build only: CRL_RAW_BAND_WHOLE=1 stores every chunk of the ink rows at any score change, as before the span table)
     static const bool band_whole = CRL_ABL(getenv("CRL_RAW_BAND_WHOLE") && atoi(getenv("CRL_RAW_BAND_WHOLE")));
     const uint8_t *span = band_whole ? nullptr : band_span;
-#define CRL_LAUNCH_DELTA_SPAN(V, G)                                                                                                      \
-    hipLaunchKernelGGL((pong_raster_raw_delta_kernel<V, G>), dim3((unsigned)((n * V * kDeltaL + 255) / 256)), dim3(256), 0, st, frames, drawn, at, \
+#define CRL_LAUNCH_DELTA_SPAN(V, G, NT)                                                                                                    \
+    hipLaunchKernelGGL((pong_raster_raw_delta_kernel<V, G, NT>), dim3((unsigned)((n * V * kDeltaL + 255) / 256)), dim3(256), 0, st, frames, drawn, at, \
                        span, ink_row0, ink_row1, ob, n)
+#ifdef CRL_ABLATION
+    // (profiling build only, two views in an aligned buffer: CRL_RAW_NT=1 stores with the non-temporal hint)
+    const bool abl_nt = getenv("CRL_RAW_NT") && atoi(getenv("CRL_RAW_NT"));
+    if (abl_nt != kDeltaNT && views == 2 && blocks_ok) {
+        CRL_LAUNCH_DELTA_SPAN(2, kDeltaG, !kDeltaNT);
+        return;
+    }
+#endif
     if (views == 2) {
-        if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(2, kDeltaG);
-        else CRL_LAUNCH_DELTA_SPAN(2, 1);
+        if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(2, kDeltaG, kDeltaNT);
+        else CRL_LAUNCH_DELTA_SPAN(2, 1, kDeltaNT);
     } else {
-        if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(1, kDeltaG);
-        else CRL_LAUNCH_DELTA_SPAN(1, 1);
+        if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(1, kDeltaG, kDeltaNT);
+        else CRL_LAUNCH_DELTA_SPAN(1, 1, kDeltaNT);
     }
 #undef CRL_LAUNCH_DELTA_SPAN
 #undef CRL_LAUNCH_DELTA
+}
+
+void launch_pong_step_raw_delta(const PongSoA &s, const ServeSrc &src, const int32_t *actions, int64_t n, float *rew, uint8_t *done,
+                                uint64_t *drawn, const uint8_t *atlas_rgb, const uint8_t *band_span, int ink_row0, int ink_row1, uint8_t *obs,
+                                int views, hipStream_t st, int stepped) {
+    if (n <= 0 || (views != 1 && views != 2)) return;
+    const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
+    uint4 *ob = reinterpret_cast<uint4 *>(obs);
+    const bool blocks_ok = (uintptr_t)obs % (16 * kDeltaG) == 0;  // (as in launch_pong_raster_raw_delta)
+#define CRL_LAUNCH_STEP(V, G, W, B, NT)                                                                                                          \
+    hipLaunchKernelGGL((pong_step_raw_delta_kernel<V, G, W, B, NT>), dim3((unsigned)((n + B - 1) / B)), dim3(64 * (B / W)), 0, st, s, src, actions, n, rew, \
+                       done, drawn, at, band_span, ink_row0, ink_row1, ob, stepped)
+#ifdef CRL_ABLATION
+    // (profiling build only, two views in an aligned buffer: CRL_RAW_STEP_W and CRL_RAW_STEP_B select the other candidates, CRL_RAW_NT=1
+    // the non-temporal stores; read at every launch, so that one process can alternate them)
+    const int abl_w = getenv("CRL_RAW_STEP_W") ? atoi(getenv("CRL_RAW_STEP_W")) : kStepW;
+    const int abl_b = getenv("CRL_RAW_STEP_B") ? atoi(getenv("CRL_RAW_STEP_B")) : kStepB;
+    const int abl_nt = getenv("CRL_RAW_NT") ? atoi(getenv("CRL_RAW_NT")) : (int)kStepNT;
+    if (views == 2 && blocks_ok && (abl_w != kStepW || abl_b != kStepB || (abl_nt != 0) != kStepNT)) {
+#define CRL_STEP_CASE(W, B)                                            \
+    if (abl_w == W && abl_b == B) {                                    \
+        if (abl_nt) CRL_LAUNCH_STEP(2, kDeltaG, W, B, true);           \
+        else CRL_LAUNCH_STEP(2, kDeltaG, W, B, false);                 \
+        return;                                                        \
+    }
+        CRL_STEP_CASE(1, 16) CRL_STEP_CASE(2, 16) CRL_STEP_CASE(2, 32) CRL_STEP_CASE(4, 32) CRL_STEP_CASE(4, 64) CRL_STEP_CASE(8, 64) CRL_STEP_CASE(16, 64)
+        CRL_STEP_CASE(32, 64) CRL_STEP_CASE(64, 64) CRL_STEP_CASE(1, 8) CRL_STEP_CASE(1, 4)
+#undef CRL_STEP_CASE
+        return;  // (no such variant: nothing is stepped, which the tests see)
+    }
+#endif
+    constexpr int W1 = kStepW < 2 ? 2 : kStepW;  // (one view: a trip takes two envs)
+    if (views == 2) {
+        if (blocks_ok) CRL_LAUNCH_STEP(2, kDeltaG, kStepW, kStepB, kStepNT);
+        else CRL_LAUNCH_STEP(2, 1, kStepW, kStepB, kStepNT);
+    } else {
+        if (blocks_ok) CRL_LAUNCH_STEP(1, kDeltaG, W1, kStepB, kStepNT);
+        else CRL_LAUNCH_STEP(1, 1, W1, kStepB, kStepNT);
+    }
+#undef CRL_LAUNCH_STEP
 }
 
 void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,

@@ -359,6 +359,7 @@ class HipPongVecEnv(VecEnv):
         # raw mode: the descriptors each buffer holds (int64 (n,), written by crl_draw_raw_delta) and the stamp that vouches for them
         self._drawn = [torch.empty((n,), dtype=torch.int64, device=dev) for _ in range(2)] if mode == "raw" else None
         self._drawn_stamp = [None, None]
+        self._fused_raw_step = True  # False: a raw step is always crl_step_stack + crl_draw_raw_delta (what the tests compare with)
         self._serial = 0  # steps + resets so far: lazy infos check it before drawing terminal observations
         self._rew = torch.zeros((n,) if self.single else (n, 2), dtype=torch.float32, device=dev)
         self._done = torch.zeros((n,), dtype=torch.uint8, device=dev)
@@ -538,7 +539,7 @@ class HipPongVecEnv(VecEnv):
         N.check(self._L.crl_check(self._h, self._stream()))
 
     def _step(self, actions, alias_ok, render=True, obs_out=None):
-        """One crl_step_stack call and the books that follow it.  The observation goes into the env's own buffer (which then flips), into
+        """One crl_step_stack call (a raw step into a buffer with a valid record: one crl_step_raw_delta call) and the books that follow it.  The observation goes into the env's own buffer (which then flips), into
         the caller's ``obs_out`` (no flip), or -- ``render=False`` -- nowhere: the own buffer still flips, undrawn, with its raw record
         as it was.  A bound FrameStackTensor is drawn with every rendered step.  Returns (buffer, agent 0's observation)."""
         own = obs_out is None
@@ -547,11 +548,20 @@ class HipPongVecEnv(VecEnv):
         delta = render and own and self.mode == "raw"  # (raw contexts take no stack: desc is None)
         # (the library first: a refused call -- e.g. the report of an earlier out-of-range action -- has not stepped the envs,
         # so the buffer flip, the serial that lazy infos check and _prev_buf stay where they are)
-        N.check(self._L.crl_step_stack(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(buf.data_ptr()) if render and not delta else None,
-                                       C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
-                                       None if desc is None else C.byref(desc), self._stream()))
-        if delta:
-            self._draw_raw(self._flip)
+        stamp = self._drawn_stamp[self._flip] if delta and self._fused_raw_step else None
+        if stamp is not None and stamp == (buf.data_ptr(), buf._version):
+            # the buffer's record is valid: the step and its delta draw in one launch (the stamp's books as in _draw_raw)
+            self._drawn_stamp[self._flip] = None
+            N.check(self._L.crl_step_raw_delta(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(buf.data_ptr()),
+                                               C.c_void_p(self._drawn[self._flip].data_ptr()), C.c_void_p(self._rew.data_ptr()),
+                                               C.c_void_p(self._done.data_ptr()), self._stream()))
+            self._drawn_stamp[self._flip] = (buf.data_ptr(), buf._version)
+        else:
+            N.check(self._L.crl_step_stack(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(buf.data_ptr()) if render and not delta else None,
+                                           C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
+                                           None if desc is None else C.byref(desc), self._stream()))
+            if delta:
+                self._draw_raw(self._flip)
         if own:
             self._prev_buf = self._obs[self._flip ^ 1]  # the observation before this step (still intact)
             self._flip ^= 1

@@ -248,6 +248,16 @@ int crl_draw_stack(crl_ctx *ctx, uint8_t *obs_dev, const crl_stack_desc *stack, 
  * to step without drawing. */
 int crl_draw_raw_delta(crl_ctx *ctx, uint8_t *obs_dev, uint64_t *drawn_dev, int32_t drawn_valid, void *stream);
 
+/* crl_step with obs_dev NULL followed by crl_draw_raw_delta(obs_dev, drawn_dev, 1), as ONE launch: every env is stepped and the chunks
+ * of its observation that differ from the record are stored by the wavefront that stepped it.  Same state, rewards, done flags,
+ * record and pixels as the two calls.  RAW_RGB Pong contexts (CRL_ESTATE otherwise); actions_dev, rew_dev and done_dev as crl_step's
+ * (the last two optional), obs_dev and drawn_dev as crl_draw_raw_delta's with drawn_valid = 1: the caller vouches that drawn_dev
+ * describes obs_dev.  A refused call (an argument, or the report of an earlier out-of-range action) steps nothing and leaves the
+ * buffer and the record as they were.  Timed in slot 1 as one launch: slot 0 gets no entry.  With an event set by
+ * crl_set_flags_event the call makes the two launches itself, the event between them (slots 0 and 1 as before). */
+int crl_step_raw_delta(crl_ctx *ctx, const void *actions_dev, uint8_t *obs_dev, uint64_t *drawn_dev, float *rew_dev, uint8_t *done_dev,
+                       void *stream);
+
 /* A hipEvent_t of the caller's (NULL: none) that every crl_step / crl_step_stack records on the step's stream right BEHIND the kernel
  * that writes rew_dev / done_dev and IN FRONT of the observation's draw.  The reference's step_envs walks the done flags on the host
  * after every step (utils/utils.py:33-42); a stream that waits for this event can copy them out while the step's 1-2 ms of raster
