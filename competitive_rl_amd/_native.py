@@ -66,6 +66,11 @@ class CrlOpts(C.Structure):
                 ("done_policy", C.c_int32), ("obs_dtype", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CrlPpoHyper(C.Structure):
+    """crl_ppo_hyper (include/crl.h "ppo update")."""
+    _fields_ = [(k, C.c_float) for k in ("clip", "vf_coef", "ent_coef", "lr", "beta1", "beta2", "eps", "max_grad_norm")]
+
+
 class CrlStackDesc(C.Structure):
     """crl_stack_desc (include/crl.h): a FrameStackTensor drawn by the step."""
     _fields_ = [("stack_dev", C.c_void_p), ("planes", C.c_int32), ("dtype", C.c_int32), ("agent", C.c_int32),
@@ -182,6 +187,17 @@ SIGNATURES = {
     "crl_rollout_finish": (i32, [vp, vp, f64, f64, i32, vp]),
     "crl_rollout_gather": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
     "crl_rollout_stats": (i32, [vp, P(f64)]),
+    "crl_ppo_create": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, P(vp)]),
+    "crl_ppo_destroy": (None, [vp]),
+    "crl_ppo_set_weights": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_ppo_get_weights": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_ppo_weights_dev": (i32, [vp, P(vp)]),
+    "crl_ppo_grad": (i32, [vp, vp, vp, i64, vp, vp]),
+    "crl_ppo_get_grad": (i32, [vp, P(vp), vp]),
+    "crl_ppo_step": (i32, [vp, vp, vp]),
+    "crl_ppo_stats": (i32, [vp, P(f64)]),
+    "crl_policy_load_weights_dev": (i32, [vp, vp, vp]),
+    "crl_pool_load_light_dev": (i32, [vp, i32, vp, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -283,6 +283,14 @@ int crl_pool_load_light(crl_league *l, int32_t agent, const float *conv1_w, cons
     return CRL_OK;
 }
 
+int crl_pool_load_light_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !blob_dev) return crl_fail(CRL_EINVAL, "crl_pool_load_light_dev: null argument");
+    if (int rc = pool_load_slot("crl_pool_load_light_dev", l, agent, CRL_LEAGUE_LIGHT)) return rc;
+    HIP_TRY(hipMemcpyAsync(l->raw[agent], blob_dev, (size_t)kLightRawFloats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CRL_OK;
+}
+
 int crl_pool_load_full(crl_league *l, int32_t agent, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b,
                        const float *conv3_w, const float *conv3_b, const float *actor_w, const float *actor_b, void *stream) {
     crl_fail_no_ctx();

@@ -762,6 +762,15 @@ int crl_policy_load_weights(crl_policy *p, const float *conv1_w, const float *co
     return CRL_OK;
 }
 
+int crl_policy_load_weights_dev(crl_policy *p, const float *blob_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!p || !blob_dev) return crl_fail(CRL_EINVAL, "crl_policy_load_weights_dev: null argument");
+    if (p->full) return crl_fail(CRL_EINVAL, "crl_policy_load_weights_dev: a full-size policy; the blob is a LightActorCritic's");
+    HIP_TRY(hipMemcpyAsync(p->raw, blob_dev, (size_t)(kLightRawFloats + kLightCriticFloats) * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    p->critic = true;
+    return CRL_OK;
+}
+
 int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base) {
     crl_fail_no_ctx();
     SampleArgs S{};

@@ -7,6 +7,7 @@
 // per step, utils/utils.py:145-173): 28 224 bytes per env and step there, 1 776 + 27 here.  An object of its own: nothing here reaches
 // into a crl_policy, the caller passes the act call's inputs and outputs in.
 #include "pong_ring.h"
+#include "pong_rollout.h"
 
 namespace crl {
 
@@ -228,6 +229,13 @@ struct crl_rollout {
     float *logp = nullptr, *values = nullptr, *rewards = nullptr, *adv = nullptr, *ret = nullptr;
     double *stats = nullptr;  // mean, std, then kRedGroups partial sums
 };
+
+namespace crl {
+RolloutView rollout_view(const crl_rollout *r) {
+    return RolloutView{r->planes, r->depth, r->actions, r->logp, r->ret, r->adv, r->normalize ? r->stats : nullptr, (uint32_t)r->n,
+                       (uint32_t)(r->n * r->steps - 1), r->state == kFinished};
+}
+}  // namespace crl
 
 extern "C" {
 

@@ -1,0 +1,165 @@
+"""A learner's PPO update for the LightActorCritic on the device (include/crl.h "ppo update", csrc/pong_ppo.hip).
+
+Closes the loop that ``Policy.act_rollout`` and ``RolloutStorage`` open: the gradient of the clipped-surrogate loss is computed straight
+from the storage's uint8 planes -- no float32 stack is ever materialised --, Adam steps the learner's master weights in place, and the
+new weights go into a served ``Policy`` or a league / arena slot by a device-to-device copy:
+
+    learner = LightPPO("checkpoint.npz", lr=2.5e-4)          # the weights need a critic
+    ...                                                       # a rollout as in rollout.py, storage.finish(...)
+    learner.update(storage, num_epochs=4, num_mini_batch=32)  # randperm, then grad + step per minibatch; nothing synchronises
+    learner.push(policy)                                      # the act calls enqueued after this use the new weights
+    learner.push(league, "learner")                           # ... and so does the pool's slot
+    print(learner.stats())                                    # (synchronises)
+
+The reference ships no trainer: the loss, its summation shape and the optimiser step are the header's written rule;
+``rules.ppo_loss_reference`` (autograd, float64) and ``rules.adam_reference`` (numpy float32) restate them.  There is no CPU path.
+"""
+import collections
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .policy_serving import _CRITIC_KEYS, _KEYS, _SHAPES, Policy, critic_of, load_light_weights
+from .rules import PPO_DEFAULTS, PPO_KEYS, adam_reference, ppo_loss_reference  # noqa: F401  (re-exported)
+
+# the policy blob of csrc/pong_league.h with its critic tail: offset and shape of each tensor, 8 488 floats with the pads
+BLOB_FLOATS = 8488
+BLOB_LAYOUT = collections.OrderedDict((("conv1_w", (0, (16, 4, 4, 4))), ("conv1_b", (1024, (16,))), ("conv2_w", (1040, (16, 16, 2, 2))),
+                                       ("conv2_b", (2064, (16,))), ("actor_w", (2080, (3, 1600))), ("actor_b", (6880, (3,))),
+                                       ("critic_w", (6884, (1, 1600))), ("critic_b", (8484, (1,)))))
+PPOStats = collections.namedtuple("PPOStats", ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "grad_norm", "steps"))
+
+
+def blob_views(blob):
+    """The eight tensors of a flat blob (a torch tensor or a numpy array of ``BLOB_FLOATS`` floats) as views, by key."""
+    return {k: blob[o:o + int(np.prod(s))].reshape(s) for k, (o, s) in BLOB_LAYOUT.items()}
+
+
+def _learner_weights(source):
+    """The eight float32 arrays of a dict, a checkpoint path or a light ``Policy``; the critic is required."""
+    if isinstance(source, Policy):
+        if not source.use_light_model:
+            raise ValueError("LightPPO trains the LightActorCritic; the policy serves the full-size network")
+        w, critic = source.weights, source.critic
+    elif isinstance(source, str):
+        w, critic = load_light_weights(source), critic_of(source, True, source)
+    else:
+        w, critic = {k: np.ascontiguousarray(source[k], np.float32) for k in _KEYS}, critic_of(source, True)
+        for k in _KEYS:
+            if w[k].shape != _SHAPES[k]:
+                raise ValueError(f"weights: {k} has shape {w[k].shape}, LightActorCritic on (4, 42, 42) needs {_SHAPES[k]}")
+    if critic is None:
+        raise ValueError("a learner needs a critic: critic_w / critic_b beside the weights")
+    return {**{k: w[k] for k in _KEYS}, **{k: critic[k] for k in _CRITIC_KEYS}}
+
+
+class LightPPO:
+    def __init__(self, weights_or_checkpoint, device=None, **hyper):
+        """``weights_or_checkpoint``: a dict of the eight arrays in torch layout (``rules.PPO_KEYS``), an ``.npz`` or reference checkpoint
+        that carries a critic, or a light ``Policy`` with one.  ``hyper``: ``clip``, ``vf_coef``, ``ent_coef``, ``lr``, ``betas``, ``eps``,
+        ``max_grad_norm`` (``rules.PPO_DEFAULTS``); attributes of the same names may be changed between calls."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("competitive_rl_amd.LightPPO needs a ROCm GPU; there is no CPU fallback")
+        unknown = set(hyper) - set(PPO_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown hyper-parameters {sorted(unknown)}; LightPPO takes {sorted(PPO_DEFAULTS)}")
+        self.hyper = dict(PPO_DEFAULTS, **hyper)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        w = _learner_weights(weights_or_checkpoint)
+        self._L = N.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_create(self.device.index or 0, *[w[k].ctypes.data_as(C.c_void_p) for k in PPO_KEYS], C.byref(h)))
+        self._h = h
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _hyper(self):
+        h = self.hyper
+        return N.CrlPpoHyper(h["clip"], h["vf_coef"], h["ent_coef"], h["lr"], h["betas"][0], h["betas"][1], h["eps"], h["max_grad_norm"])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.crl_ppo_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _dev_blob(self, ptr):
+        """A float32 (BLOB_FLOATS,) tensor over the learner's own device memory at ``ptr`` (valid while the learner lives)."""
+        iface = {"shape": (BLOB_FLOATS,), "typestr": "<f4", "data": (ptr, False), "version": 2}
+        holder = type("_Blob", (), {"__cuda_array_interface__": iface, "_keep": self})()
+        return torch.as_tensor(holder, device=self.device)
+
+    def grad(self, storage, idx):
+        """The gradient of the loss over the samples ``idx`` (int64 on the device, flat ``t * num_envs + e``, as ``storage.gather`` takes
+        them) of a finished ``RolloutStorage``, at the learner's weights: a dict of device VIEWS of the eight gradient tensors, for
+        callers with their own optimiser; the next ``grad`` overwrites them.  No synchronisation."""
+        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1, "idx: int64 (B,) on the learner's device"
+        assert storage.device == self.device, "the storage lives on another device"
+        idx = idx.contiguous()
+        hyper = self._hyper()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_grad(self._h, storage._h, C.c_void_p(idx.data_ptr()) if idx.numel() else None, idx.numel(), C.byref(hyper),
+                                         self._stream()))
+            p = C.c_void_p()
+            N.check(self._L.crl_ppo_get_grad(self._h, C.byref(p), None))
+        return blob_views(self._dev_blob(p.value))
+
+    def step(self):
+        """Clips the last gradient to ``max_grad_norm`` and takes one Adam step on the master weights, in place.  No synchronisation."""
+        hyper = self._hyper()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_step(self._h, C.byref(hyper), self._stream()))
+
+    def update(self, storage, num_epochs, num_mini_batch, generator=None):
+        """``num_epochs`` passes over the finished ``storage``: per pass one ``torch.randperm`` on the device (``generator``: a device
+        generator, for a reproducible order) cut into ``num_mini_batch`` batches of T * N // num_mini_batch samples, ``grad`` and ``step``
+        per batch.  Nothing synchronises."""
+        total = storage.num_steps * storage.num_envs
+        size = total // int(num_mini_batch)
+        assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
+        for _ in range(int(num_epochs)):
+            perm = torch.randperm(total, device=self.device, generator=generator)
+            for k in range(int(num_mini_batch)):
+                self.grad(storage, perm[k * size:(k + 1) * size])
+                self.step()
+
+    def push(self, target, name=None):
+        """The master weights into a served light ``Policy`` (its critic too), or into slot ``name`` (a name or an index) of a
+        ``LeagueEnvWrapper`` / ``LeagueArena``: one device-to-device copy ordered on the current stream, the host is not touched.  The
+        target's host-side copy of its weights (``Policy.weights``) is NOT refreshed: ``weights()`` has the learner's."""
+        p = C.c_void_p()
+        N.check(self._L.crl_ppo_weights_dev(self._h, C.byref(p)))
+        assert target.device == self.device, "the target lives on another device"
+        with torch.cuda.device(self.device):
+            if isinstance(target, Policy):
+                N.check(self._L.crl_policy_load_weights_dev(target._h, p, self._stream()))
+            else:
+                N.check(self._L.crl_pool_load_light_dev(target._h, target._agent_index(name), p, self._stream()))
+
+    def weights(self):
+        """The master weights as a dict of eight float32 numpy arrays in torch layout (synchronises)."""
+        w = {k: np.zeros(s, np.float32) for k, (_, s) in BLOB_LAYOUT.items()}
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_get_weights(self._h, *[w[k].ctypes.data_as(C.c_void_p) for k in PPO_KEYS]))
+        return w
+
+    def set_weights(self, weights_or_checkpoint):
+        """Replaces the master weights and zeroes Adam's moments and step count (synchronises)."""
+        w = _learner_weights(weights_or_checkpoint)
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_set_weights(self._h, *[w[k].ctypes.data_as(C.c_void_p) for k in PPO_KEYS]))
+
+    def stats(self):
+        """``PPOStats`` of the last ``grad``: the means of policy loss, value loss, entropy, ``old_logp - logp`` and the clipped share, the
+        gradient's norm before clipping, the optimiser steps taken.  Synchronises the device: logging and tests."""
+        out = (C.c_double * 7)()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_stats(self._h, out))
+        return PPOStats(*out[:6], int(out[6]))

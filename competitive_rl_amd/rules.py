@@ -151,3 +151,68 @@ def gae_reference(rewards, values, dones, last_values, gamma, lam):
         adv[t], ret[t] = acc, (acc + v[t]).astype(np.float32)
         vnext = v[t]
     return adv, ret
+
+
+PPO_KEYS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "actor_w", "actor_b", "critic_w", "critic_b")
+PPO_DEFAULTS = dict(clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5)
+
+
+def ppo_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None):
+    """The loss of include/crl.h "ppo update" with torch autograd on the CPU; ``dtype=torch.float64`` (the default) is the yardstick of
+    the device's gradient.  ``weights``: the eight tensors of ``PPO_KEYS`` in torch layout; ``stacks``: uint8 [B, 4, 42, 42]; ``actions``
+    int [B]; ``old_logp``, ``returns``, ``adv`` float [B] (``adv`` as the gather hands it out); ``hyper``: ``clip``, ``vf_coef``,
+    ``ent_coef`` (missing ones from ``PPO_DEFAULTS``).  Returns a dict: ``loss``, the five statistics ``policy``, ``value``,
+    ``entropy``, ``kl``, ``clipped`` (means over B), ``grads`` (the eight gradient arrays by key) and, per sample, ``z1`` [B, 16, 20, 20],
+    ``z2`` [B, 16, 10, 10], ``logits``, ``v``, ``logp``, ``ratio``, ``active`` (the branch with d policy / d logp = -A r).  Host code for
+    tests; the kernels do not use it."""
+    import torch
+    import torch.nn.functional as F
+
+    dtype = torch.float64 if dtype is None else dtype
+    h = dict(PPO_DEFAULTS, **(hyper or {}))
+    c, vf, ent = (float(np.float32(h[k])) for k in ("clip", "vf_coef", "ent_coef"))
+    w = {k: torch.tensor(np.asarray(weights[k], np.float32), dtype=dtype, requires_grad=True) for k in PPO_KEYS}
+    x = torch.tensor(np.asarray(stacks, np.uint8).astype(np.float32), dtype=dtype) / 255
+    a = torch.tensor(np.asarray(actions, np.int64))
+    olp, ret, A = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (old_logp, returns, adv))
+    z1 = F.conv2d(x, w["conv1_w"], w["conv1_b"], stride=2)
+    a1 = torch.where(z1 > 0, z1, torch.zeros_like(z1))
+    z2 = F.conv2d(a1, w["conv2_w"], w["conv2_b"], stride=2)
+    a2 = torch.where(z2 > 0, z2, torch.zeros_like(z2)).reshape(x.shape[0], 1600)
+    logits = a2 @ w["actor_w"].t() + w["actor_b"]
+    v = (a2 @ w["critic_w"].t() + w["critic_b"]).reshape(-1)
+    lp_all = torch.log_softmax(logits, dim=1)
+    logp = lp_all.gather(1, a[:, None]).reshape(-1)
+    ratio = torch.exp(logp - olp)
+    policy = -torch.minimum(ratio * A, torch.clamp(ratio, 1 - c, 1 + c) * A)
+    value = 0.5 * (ret - v) ** 2
+    entropy = -(lp_all.exp() * lp_all).sum(1)
+    loss = (policy + vf * value - ent * entropy).mean()
+    loss.backward()
+    r = ratio.detach()
+    active = ((A >= 0) & (r < 1 + c)) | ((A < 0) & (r > 1 - c))
+    n = lambda t: t.detach().numpy()  # noqa: E731
+    s = lambda t: float(t.detach())  # noqa: E731
+    return dict(loss=s(loss), policy=s(policy.mean()), value=s(value.mean()), entropy=s(entropy.mean()),
+                kl=s((olp - logp).mean()), clipped=float(((r < 1 - c) | (r > 1 + c)).to(dtype).mean()),
+                grads={k: n(w[k].grad) for k in PPO_KEYS}, z1=n(z1), z2=n(z2), logits=n(logits), v=n(v), logp=n(logp), ratio=n(r),
+                active=n(active))
+
+
+def adam_reference(params, m, v, grad, grad_norm, step, hyper=None):
+    """The optimiser step of include/crl.h "ppo update" in numpy float32, one rounding per operation: ``params``, ``m``, ``v``, ``grad``
+    float32 arrays of one shape; ``grad_norm``: the float64 square root of the float64 sum of the gradient's squares; ``step``: t, 1 for the first step;
+    ``hyper``: ``lr``, ``betas``, ``eps``, ``max_grad_norm``.  Returns the new (params, m, v).  Host code for tests."""
+    h = dict(PPO_DEFAULTS, **(hyper or {}))
+    f = np.float32
+    b1, b2, lr, eps, max_norm = f(h["betas"][0]), f(h["betas"][1]), f(h["lr"]), f(h["eps"]), f(h["max_grad_norm"])
+    bc1, bc2 = 1.0 - float(b1) ** int(step), 1.0 - float(b2) ** int(step)
+    omb1, omb2, step_size, bc2s = f(1.0 - float(b1)), f(1.0 - float(b2)), f(float(lr) / bc1), f(np.sqrt(bc2))
+    norm = f(np.float64(grad_norm))
+    coef = min(f(1.0), f(max_norm / f(norm + f(1e-6))))
+    p, m, v, g = (np.asarray(t, f) for t in (params, m, v, grad))
+    g = (g * coef).astype(f)
+    m = ((b1 * m).astype(f) + (omb1 * g).astype(f)).astype(f)
+    v = ((b2 * v).astype(f) + (omb2 * (g * g).astype(f)).astype(f)).astype(f)
+    denom = ((np.sqrt(v).astype(f) / bc2s).astype(f) + eps).astype(f)
+    return (p - (step_size * (m / denom).astype(f)).astype(f)).astype(f), m, v

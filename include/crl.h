@@ -854,6 +854,94 @@ int crl_rollout_stats(crl_rollout *r, double *out2_host);
  * statistics that were not computed; a carrying begin on an unfinished rollout; null or misaligned pointers.  A refused call changes
  * nothing. */
 
+/* ---- ppo update: the learner's gradient and optimiser step for the LightActorCritic on the device ----------------
+ * Closes the loop between crl_rollout_gather and crl_policy_load_weights: a crl_ppo holds a learner's master weights (float32, the
+ * policy blob: conv1 [16,4,4,4] | b1 [16] | conv2 [16,16,2,2] | b2 [16] | actor [3,1600] | ba [3] + 1 pad | critic [1,1600] | bc [1] + 3
+ * pads = 8 488 floats, 8 484 of them parameters) and Adam's two moments, computes the gradient of the loss below over a minibatch
+ * of a FINISHED crl_rollout straight from its stored uint8 planes, and steps.  The reference ships no trainer (utils/network.py has
+ * only the networks), so the loss is defined HERE; tests restate it with autograd in float64 (rules.ppo_loss_reference) and the
+ * optimiser in numpy float32 (rules.adam_reference).  All work is ordered on the caller's stream; only crl_ppo_create, _set_weights,
+ * _get_weights, _stats and a crl_ppo_get_grad that copies synchronise.  The caller has the learner's device current.
+ *
+ * Loss, per sample (stack = the sample's uint8 stack by the stack rule above, action, old_logp, ret as stored, A = the advantage as
+ * crl_rollout_gather hands it out: normalised if the finish normalised).  Every comparison is part of the rule:
+ *   x = stack / 255;  z1 = conv1(x) + b1 (4 x 4, stride 2: 16 x 20 x 20),  a1 = max(z1, 0);  z2 = conv2(a1) + b2 (2 x 2, stride 2:
+ *   16 x 10 x 10),  a2 = max(z2, 0), flattened channel-major to 1600 features;  logits = actor(a2),  v = critic(a2);
+ *   the ReLU's derivative is z > 0 ? 1 : 0;
+ *   logp_k = log_softmax(logits)_k,  p_k = exp(logp_k),  logp = logp_action.  The temperature is FIXED at 1: a learner whose actions
+ *   were drawn at another temperature is out of scope (its stored log-probs would be of another distribution);
+ *   r = exp(logp - old_logp);
+ *   policy  = -min(r A, clamp(r, 1 - c, 1 + c) A),  so  d policy / d logp = -A r  when (A >= 0 and r < 1 + c) or (A < 0 and r > 1 - c),
+ *             and 0 otherwise;
+ *   value   = 0.5 (ret - v)^2   (unclipped);
+ *   entropy = H = -sum_k p_k logp_k;
+ *   loss    = mean over the B samples of (policy + vf * value - ent * entropy).
+ * Closed forms the kernel uses:  d loss_b / d logit_k = (d policy / d logp) (1[k = action] - p_k) + ent p_k (logp_k + H),
+ * d loss_b / d v = vf (v - ret).  The convolutions are float32; from the features a2 on, the device works in float64 up to dlogits and
+ * dv, which are rounded once to float32: logits and v are float64 sums over the float32 features and weights (the head sums are long
+ * and cancel, and a sample's whole gradient hangs on v - ret and logp - old_logp), m = max logit, d_k = logit_k - m, e_k = exp(d_k),
+ * S = (e0 + e1) + e2, logp_k = d_k - log(S), p_k = e_k / S; c, vf, ent are the float32 values passed, widened.
+ * Statistics of a call: the means over the B samples of policy, value, entropy, old_logp - logp (the approximate KL) and of
+ * 1[r < 1 - c or r > 1 + c] (the clipped share); each sample's term is formed and summed in float64.
+ *
+ * Gradient: the exact derivative of `loss` with respect to the eight tensors, float32, in the blob's layout (pads zero).
+ * Summation shape -- a function of B alone, not of the device, the grid or any arrival order; no floating-point atomics; the same idx
+ * gives the same bits on every run:
+ *   groups of 8 consecutive idx entries; W = min(256, ceil(B / 8)) workgroups; workgroup w takes groups w, w + W, w + 2 W, ... in order.
+ *   Within a workgroup: a group is 50 tiles of 16 conv2 positions q = 16 t + j (sample q / 100, position q % 100), tile t belongs to
+ *   wavefront t % 8.  Conv gradients: a wavefront adds its tiles in order into float32 matrix accumulators (v_mfma_f32_16x16x4_f32,
+ *   four positions per step), over all its groups; at the end the eight wavefronts' accumulators are added in wavefront order 0..7.
+ *   Conv biases: per-lane float32 sums in the same order, then a butterfly over the lanes.  Head weights: thread f of 512 adds
+ *   d_k[e] * a2[e][f] for the group's samples e = 0..7 in order, fused multiply-add, over all its groups; head biases: one thread, same
+ *   order.  A logit or value of the forward pass: lane l of 64 adds features l, l + 64, ... (float64 fused multiply-add), then a butterfly.
+ *   Then element i of the gradient = (partial_0[i] + partial_1[i] + ... + partial_{W-1}[i], float32, in this order) / float32(B).
+ *   Sum of squares of the 8 488 elements in float64: 34 blocks of 256 consecutive elements, each through a binary tree
+ *   (s[i] += s[i + 128], then 64, ... 1), then the 34 block sums in order.  Statistics: per workgroup in sample order, then over w.
+ *
+ * Optimiser step.  float32, one rounding per operation, no contraction, sqrt and / correctly rounded:
+ *   norm = float32(sqrt(sum of squares, float64));   coef = min(1, max_grad_norm / (norm + 1e-6f))   (torch's clip_grad_norm_);
+ *   t = steps taken + 1;  on the host in double: bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, then float32: omb1 = 1 - beta1, omb2 = 1 - beta2,
+ *   step_size = lr / bc1, bc2s = sqrt(bc2)   (beta1, beta2, lr read as the float32 values passed);
+ *   g = grad * coef;   m = beta1 * m + omb1 * g;   v = beta2 * v + omb2 * (g * g);
+ *   p = p - step_size * (m / (sqrtf(v) / bc2s + eps))                                      (torch.optim.Adam without amsgrad / decay).
+ * Defaults of the Python layer, common PPO practice for this network (Atari-style PPO): clip 0.2, vf_coef 0.5, ent_coef 0.01,
+ * lr 2.5e-4, betas (0.9, 0.999), eps 1e-5, max_grad_norm 0.5. */
+typedef struct crl_ppo_hyper {
+    float clip, vf_coef, ent_coef, lr, beta1, beta2, eps, max_grad_norm;
+} crl_ppo_hyper;
+typedef struct crl_ppo crl_ppo;
+/* Tensors as for crl_policy_create plus the critic of crl_policy_set_critic (host pointers, torch layouts; the critic is required).
+ * crl_ppo_set_weights also zeroes both moments and the step count.  Both synchronise the device. */
+int crl_ppo_create(int32_t device, const float *conv1_w_host, const float *conv1_b_host, const float *conv2_w_host, const float *conv2_b_host,
+                   const float *actor_w_host, const float *actor_b_host, const float *critic_w_host, const float *critic_b_host, crl_ppo **out);
+void crl_ppo_destroy(crl_ppo *p);
+int crl_ppo_set_weights(crl_ppo *p, const float *conv1_w_host, const float *conv1_b_host, const float *conv2_w_host, const float *conv2_b_host,
+                        const float *actor_w_host, const float *actor_b_host, const float *critic_w_host, const float *critic_b_host);
+/* The master weights as they stand, into eight host arrays of the torch shapes.  Synchronises the device. */
+int crl_ppo_get_weights(crl_ppo *p, float *conv1_w_host, float *conv1_b_host, float *conv2_w_host, float *conv2_b_host, float *actor_w_host,
+                        float *actor_b_host, float *critic_w_host, float *critic_b_host);
+/* *blob_dev = the master blob on the device (8 488 floats, the layout above), valid until crl_ppo_destroy: what
+ * crl_policy_load_weights_dev and crl_pool_load_light_dev take. */
+int crl_ppo_weights_dev(crl_ppo *p, const float **blob_dev);
+/* The gradient and the statistics of the samples idx_dev[0 .. count) (int64 on the device, flat t * N + e, any order, duplicates
+ * allowed, validity the caller's as for crl_rollout_gather), at the learner's current weights; uses hyper's clip, vf_coef, ent_coef.
+ * Three launches on `stream`.  Refuses (CRL_EINVAL, before any GPU call) a null argument, count < 1, a rollout that is not finished. */
+int crl_ppo_grad(crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper, void *stream);
+/* The last gradient: *grad_dev = its device blob (optional; for a caller with an optimiser of its own, overwritten by the next
+ * crl_ppo_grad), grad_out_host = a copy of the 8 488 floats (optional; synchronises the device). */
+int crl_ppo_get_grad(crl_ppo *p, const float **grad_dev, float *grad_out_host);
+/* Clip + Adam on the last gradient, the master blob updated in place: one launch.  Uses hyper's lr, betas, eps, max_grad_norm. */
+int crl_ppo_step(crl_ppo *p, const crl_ppo_hyper *hyper, void *stream);
+/* out7_host: the five statistics of the last crl_ppo_grad, [5] its gradient's norm (before clipping, float64), [6] the optimiser steps
+ * taken.  Synchronises the device (logging, tests). */
+int crl_ppo_stats(crl_ppo *p, double *out7_host);
+/* crl_policy_load_weights from DEVICE memory: blob_dev (8 488 floats, the layout above, critic included) replaces the weights and the
+ * critic of a LightActorCritic policy by one device-to-device copy ordered on `stream`; no host buffer, no synchronisation.  Refuses
+ * (CRL_EINVAL, before any GPU call) a null argument and a full-size policy.  crl_pool_load_light_dev: the same into slot `agent` of a
+ * league's or an arena's pool (the first 6 884 floats: a slot has no critic); refuses what crl_pool_load_light refuses. */
+int crl_policy_load_weights_dev(crl_policy *p, const float *blob_dev, void *stream);
+int crl_pool_load_light_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
