@@ -10,9 +10,9 @@ from .frame_stack import FrameStackTensor
 from .tournament import (TournamentEnvWrapper, get_builtin_agent_names, get_compute_action_function, get_random_policy,
                          get_rule_based_policy)
 from .policy_serving import Policy
-from .rules import adam_reference, gae_reference, ppo_loss_reference, rollout_logp_reference, rollout_stack_reference
+from .rules import adam_reference, gae_reference, ppo_full_loss_reference, ppo_loss_reference, rollout_logp_reference, rollout_stack_reference
 from .rollout import RolloutBatch, RolloutStorage
-from .ppo import LightPPO, PPOStats
+from .ppo import FullPPO, LightPPO, PPOStats
 from .league import LeagueEnvWrapper
 from .ledger import LeagueLedger, ledger_draw_reference, pfsp_weights_reference
 from .arena import ArenaBooks, LeagueArena, arena_draw_reference, balance_weights_reference
@@ -38,6 +38,6 @@ def register_competitive_envs():
     register_car_racing()
 
 
-__all__ = ["make_envs", "DummyVecEnv", "SubprocVecEnv", "make_env_a2c_atari", "make_car_racing", "make_car_racing_double", "EnvThunk", "HipPongVecEnv", "HipCarVecEnv", "VecEnv", "VecEnvWrapper", "tile_images", "LazyInfos", "FrameStackTensor", "TournamentEnvWrapper", "LeagueEnvWrapper", "LeagueLedger", "ledger_draw_reference", "pfsp_weights_reference", "LeagueArena", "ArenaBooks", "arena_draw_reference", "balance_weights_reference", "Policy", "rollout_logp_reference", "RolloutStorage", "RolloutBatch", "LightPPO", "PPOStats", "ppo_loss_reference", "adam_reference", "gae_reference", "rollout_stack_reference", "make_competitive_car_racing", "step_envs", "evaluate", "evaluate_two_policies", "evaluate_two_policies_in_batch", "CHEAT_CODES", "get_builtin_agent_names", "get_compute_action_function", "get_random_policy", "get_rule_based_policy",
+__all__ = ["make_envs", "DummyVecEnv", "SubprocVecEnv", "make_env_a2c_atari", "make_car_racing", "make_car_racing_double", "EnvThunk", "HipPongVecEnv", "HipCarVecEnv", "VecEnv", "VecEnvWrapper", "tile_images", "LazyInfos", "FrameStackTensor", "TournamentEnvWrapper", "LeagueEnvWrapper", "LeagueLedger", "ledger_draw_reference", "pfsp_weights_reference", "LeagueArena", "ArenaBooks", "arena_draw_reference", "balance_weights_reference", "Policy", "rollout_logp_reference", "RolloutStorage", "RolloutBatch", "LightPPO", "FullPPO", "PPOStats", "ppo_loss_reference", "ppo_full_loss_reference", "adam_reference", "gae_reference", "rollout_stack_reference", "make_competitive_car_racing", "step_envs", "evaluate", "evaluate_two_policies", "evaluate_two_policies_in_batch", "CHEAT_CODES", "get_builtin_agent_names", "get_compute_action_function", "get_random_policy", "get_rule_based_policy",
            "register_pong", "register_car_racing", "register_competitive_envs",
            "ShardSpec", "shard_of", "all_gather_step", "StepGather"]

@@ -198,6 +198,11 @@ SIGNATURES = {
     "crl_ppo_stats": (i32, [vp, P(f64)]),
     "crl_policy_load_weights_dev": (i32, [vp, vp, vp]),
     "crl_pool_load_light_dev": (i32, [vp, i32, vp, vp]),
+    "crl_ppo_create_full": (i32, [i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(vp)]),
+    "crl_ppo_set_weights_full": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_ppo_get_weights_full": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_policy_load_full_dev": (i32, [vp, vp, vp]),
+    "crl_pool_load_full_dev": (i32, [vp, i32, vp, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

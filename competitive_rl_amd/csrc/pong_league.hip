@@ -306,6 +306,14 @@ int crl_pool_load_full(crl_league *l, int32_t agent, const float *conv1_w, const
     return CRL_OK;
 }
 
+int crl_pool_load_full_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !blob_dev) return crl_fail(CRL_EINVAL, "crl_pool_load_full_dev: null argument");
+    if (int rc = pool_load_slot("crl_pool_load_full_dev", l, agent, CRL_POOL_KIND_FULL)) return rc;
+    HIP_TRY(hipMemcpyAsync(l->raw[agent], blob_dev, (size_t)policy_full_blob_floats() * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CRL_OK;
+}
+
 int crl_sampling_set_agent(crl_league *l, int32_t agent, float temperature, float epsilon) {
     crl_fail_no_ctx();
     SampleArgs S{};

@@ -771,6 +771,16 @@ int crl_policy_load_weights_dev(crl_policy *p, const float *blob_dev, void *stre
     return CRL_OK;
 }
 
+int crl_policy_load_full_dev(crl_policy *p, const float *blob_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!p || !blob_dev) return crl_fail(CRL_EINVAL, "crl_policy_load_full_dev: null argument");
+    if (!p->full) return crl_fail(CRL_EINVAL, "crl_policy_load_full_dev: a LightActorCritic policy; the blob is a full-size network's");
+    HIP_TRY(hipMemcpyAsync(policy_full_blob(p->full), blob_dev, (size_t)(policy_full_blob_floats() + policy_full_critic_floats()) * sizeof(float),
+                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    p->critic = true;
+    return CRL_OK;
+}
+
 int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base) {
     crl_fail_no_ctx();
     SampleArgs S{};

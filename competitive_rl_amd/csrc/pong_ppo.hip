@@ -23,6 +23,7 @@
 #include "crl_internal.h"
 #include "pong_league.h"
 #include "pong_net.h"
+#include "pong_ppo.h"
 #include "pong_ring.h"
 #include "pong_rollout.h"
 
@@ -37,7 +38,6 @@ static constexpr int kGMaxGroups = 256;              // W <= 256
 static constexpr int kFeat = 1600;
 static constexpr int kBlob = kLightRawFloats + kLightCriticFloats;  // 8488: the policy blob with its critic tail (pads included, zero)
 static constexpr int kHeadIter = (kFeat + kGThreads - 1) / kGThreads;  // 4
-static constexpr int kStatN = 5;                     // policy loss, value loss, entropy, old_logp - logp, clipped
 static constexpr int kTileStride = 17;               // a 16 x 16 LDS tile, rows padded
 static constexpr int kScrWave = 5 * 16 * kTileStride;  // per wavefront: a1 of the four classes, dz2
 
@@ -51,10 +51,6 @@ static_assert(kGWaves == kGE, "the heads phase gives a wavefront to a sample");
 static_assert(kLdsGrad <= 160 * 1024, "the gradient kernel's LDS must fit a CU");
 static_assert(kGWaves * kRedWave * 4 <= kLdsBuf + kLdsA2, "the final reduction reuses the staging buffers");
 
-struct PpoHyperDev {
-    float clip, vf, ent;
-};
-
 struct GradArgs {
     RolloutView r;
     const int64_t *idx;
@@ -64,13 +60,6 @@ struct GradArgs {
     double *stat_part;   // [W][kStatN]
     PpoHyperDev h;
 };
-
-__device__ inline float div255(float b) {  // b / 255, correctly rounded (Markstein), as the forward kernel forms it
-    const float rcp = 1.0f / 255.0f;
-    const float qv = b * rcp;
-    const float rem = __builtin_fmaf(qv, -255.0f, b);
-    return __builtin_fmaf(rem, rcp, qv);
-}
 
 // the wavefront's own LDS traffic in program order (a tile is written by some lanes and read by others)
 __device__ inline void wave_lds_sync() {
@@ -215,26 +204,7 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a)
                     const double v = (double)a.raw[kLightBc] + s3;
                     const int act = (int)sh_sc[e * 4 + 0];
                     const double olp = (double)sh_sc[e * 4 + 1], ret = (double)sh_sc[e * 4 + 2], A = (double)sh_sc[e * 4 + 3];
-                    const double m = fmax(fmax(l[0], l[1]), l[2]);
-                    const double d[3] = {l[0] - m, l[1] - m, l[2] - m};
-                    const double ex[3] = {exp(d[0]), exp(d[1]), exp(d[2])};
-                    const double S = (ex[0] + ex[1]) + ex[2];
-                    const double logS = log(S);
-                    const double lp[3] = {d[0] - logS, d[1] - logS, d[2] - logS};
-                    const double p[3] = {ex[0] / S, ex[1] / S, ex[2] / S};
-                    const double logp = lp[act];
-                    const double ratio = exp(logp - olp);
-                    const double lo = 1.0 - (double)a.h.clip, hi = 1.0 + (double)a.h.clip;
-                    const double surr1 = ratio * A, surr2 = fmin(fmax(ratio, lo), hi) * A;
-                    const bool active = (A >= 0.0 && ratio < hi) || (A < 0.0 && ratio > lo);
-                    const double glp = active ? -(A * ratio) : 0.0;
-                    const double H = -((p[0] * lp[0] + p[1] * lp[1]) + p[2] * lp[2]);
-#pragma unroll
-                    for (int k = 0; k < 3; k++) dl[k] = (float)(glp * ((k == act ? 1.0 : 0.0) - p[k]) + (double)a.h.ent * (p[k] * (lp[k] + H)));
-                    const double dif = v - ret;
-                    dv = (float)((double)a.h.vf * dif);
-                    st[0] = -fmin(surr1, surr2), st[1] = 0.5 * (dif * dif), st[2] = H;
-                    st[3] = olp - logp, st[4] = (ratio < lo || ratio > hi) ? 1.0 : 0.0;
+                    ppo_sample_terms(l, v, act, olp, ret, A, a.h, dl, dv, st);
                 }
                 sh_dh[e * 4 + 0] = dl[0], sh_dh[e * 4 + 1] = dl[1], sh_dh[e * 4 + 2] = dl[2], sh_dh[e * 4 + 3] = dv;
 #pragma unroll
@@ -409,12 +379,13 @@ struct StepArgs {
     const float *grad;
     const double *red;  // [0]: the gradient's sum of squares
     float max_norm, b1, b2, omb1, omb2, step_size, bc2_sqrt, eps;
+    int n;  // the blob's floats
 };
 
-// include/crl.h "ppo update", optimiser step: float32, one rounding per operation (-ffp-contract=off; sqrtf and / correctly rounded)
+// include/crl.h "ppo update", optimiser step, over a blob of a.n floats (either learner's): float32, one rounding per operation (-ffp-contract=off; sqrtf and / correctly rounded)
 __global__ __launch_bounds__(256) void pong_ppo_step_kernel(StepArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= kBlob) return;
+    if (i >= a.n) return;
     const float norm = (float)sqrt(a.red[0]);
     const float coef = fminf(1.0f, a.max_norm / (norm + 1e-6f));
     const float g = a.grad[i] * coef;
@@ -428,14 +399,6 @@ __global__ __launch_bounds__(256) void pong_ppo_step_kernel(StepArgs a) {
 }  // namespace crl
 
 using namespace crl;
-
-struct crl_ppo {
-    int device = 0;
-    float *raw = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *partials = nullptr;
-    double *stat_part = nullptr, *sq_part = nullptr, *red = nullptr;
-    int64_t steps = 0;  // optimiser steps taken (the t of the bias corrections)
-    bool have_grad = false;
-};
 
 static void ppo_pack(float *blob, const float *const t[8]) {
     for (int i = 0; i < kBlob; i++) blob[i] = 0.f;
@@ -456,6 +419,7 @@ extern "C" {
 void crl_ppo_destroy(crl_ppo *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    ppo_full_destroy(p->full);
     for (void *q : {(void *)p->raw, (void *)p->m, (void *)p->v, (void *)p->grad, (void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red})
         if (q) (void)hipFree(q);
     delete p;
@@ -466,6 +430,7 @@ int crl_ppo_set_weights(crl_ppo *p, const float *conv1_w, const float *conv1_b, 
     crl_fail_no_ctx();
     if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b || !critic_w || !critic_b)
         return crl_fail(CRL_EINVAL, "crl_ppo_set_weights: null argument (a learner needs its critic)");
+    if (p->full) return crl_fail(CRL_EINVAL, "crl_ppo_set_weights: a full-size learner (crl_ppo_set_weights_full)");
     HIP_TRY(hipSetDevice(p->device));
     std::vector<float> blob(kBlob);
     const float *const t[8] = {conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b, critic_w, critic_b};
@@ -487,7 +452,7 @@ int crl_ppo_create(int32_t device, const float *conv1_w, const float *conv1_b, c
     *out = nullptr;
     HIP_TRY(hipSetDevice(device));
     crl_ppo *p = new crl_ppo();
-    p->device = device;
+    p->device = device, p->blob_floats = kBlob;
     const char *who = "crl_ppo_create";
     int rc = crl_dev_zalloc(&p->raw, kBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->m, kBlob * sizeof(float), who);
@@ -515,6 +480,7 @@ int crl_ppo_get_weights(crl_ppo *p, float *conv1_w, float *conv1_b, float *conv2
     crl_fail_no_ctx();
     if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b || !critic_w || !critic_b)
         return crl_fail(CRL_EINVAL, "crl_ppo_get_weights: null argument");
+    if (p->full) return crl_fail(CRL_EINVAL, "crl_ppo_get_weights: a full-size learner (crl_ppo_get_weights_full)");
     HIP_TRY(hipSetDevice(p->device));
     std::vector<float> blob(kBlob);
     HIP_TRY(hipDeviceSynchronize());
@@ -541,6 +507,11 @@ int crl_ppo_grad(crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev,
     const RolloutView view = rollout_view(rollout);
     if (!view.finished) return crl_fail(CRL_EINVAL, "crl_ppo_grad: the rollout is not finished (crl_rollout_finish computes returns and advantages)");
     hipStream_t st = (hipStream_t)stream;
+    if (p->full) {
+        if (int rc = ppo_full_grad(p, view, idx_dev, count, PpoHyperDev{hyper->clip, hyper->vf_coef, hyper->ent_coef}, st)) return rc;
+        p->have_grad = true;
+        return CRL_OK;
+    }
     const int64_t ngroups = (count + kGE - 1) / kGE;
     const int groups = (int)(ngroups < kGMaxGroups ? ngroups : kGMaxGroups);
     GradArgs a{view, idx_dev, count, p->raw, p->partials, p->stat_part, PpoHyperDev{hyper->clip, hyper->vf_coef, hyper->ent_coef}};
@@ -560,7 +531,7 @@ int crl_ppo_get_grad(crl_ppo *p, const float **grad_dev, float *grad_out_host) {
     if (grad_out_host) {
         HIP_TRY(hipSetDevice(p->device));
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(grad_out_host, p->grad, kBlob * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(grad_out_host, p->grad, (size_t)p->blob_floats * sizeof(float), hipMemcpyDeviceToHost));
     }
     return CRL_OK;
 }
@@ -574,8 +545,8 @@ int crl_ppo_step(crl_ppo *p, const crl_ppo_hyper *hyper, void *stream) {
     const double b1 = (double)hyper->beta1, b2 = (double)hyper->beta2;
     const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
     StepArgs a{p->raw, p->m, p->v, p->grad, p->red, hyper->max_grad_norm, hyper->beta1, hyper->beta2, (float)(1.0 - b1), (float)(1.0 - b2),
-               (float)((double)hyper->lr / bc1), (float)sqrt(bc2), hyper->eps};
-    hipLaunchKernelGGL(pong_ppo_step_kernel, dim3(kRedBlocks), dim3(256), 0, (hipStream_t)stream, a);
+               (float)((double)hyper->lr / bc1), (float)sqrt(bc2), hyper->eps, p->blob_floats};
+    hipLaunchKernelGGL(pong_ppo_step_kernel, dim3((p->blob_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     p->steps = t;
     return CRL_OK;

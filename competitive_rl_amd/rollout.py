@@ -17,10 +17,11 @@ it -- and rebuilds the float32 (or uint8) stack of every sample in the gather ke
     for batch in storage.minibatches(num_mini_batch):
         batch.obs, batch.actions, batch.old_log_probs, batch.values, batch.returns, batch.advantages
 
-For the LightActorCritic the update itself stays on the device too (ppo.py, include/crl.h "ppo update"): the gradient is computed from the
-stored uint8 planes, no float32 stack is gathered, and the new weights reach the served policy by a device-to-device copy:
+The update itself stays on the device too, for both networks (ppo.py: ``LightPPO``, include/crl.h "ppo update", and ``FullPPO``, "ppo update,
+full size"): the gradient is computed from the stored uint8 planes, no float32 stack is gathered, and the new weights reach the served
+policy by a device-to-device copy:
 
-    learner = LightPPO(weights_with_critic)
+    learner = LightPPO(weights_with_critic)                   # FullPPO(...) for Policy(use_light_model=False)
     ...                                                       # the rollout above, storage.finish(...)
     learner.update(storage, num_epochs=4, num_mini_batch=32)  # randperm, grad + step per minibatch, no synchronisation
     learner.push(policy)                                      # and / or learner.push(league, "learner")

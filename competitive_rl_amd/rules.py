@@ -157,30 +157,39 @@ PPO_KEYS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "actor_w", "actor_b", "c
 PPO_DEFAULTS = dict(clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5)
 
 
-def ppo_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None):
-    """The loss of include/crl.h "ppo update" with torch autograd on the CPU; ``dtype=torch.float64`` (the default) is the yardstick of
-    the device's gradient.  ``weights``: the eight tensors of ``PPO_KEYS`` in torch layout; ``stacks``: uint8 [B, 4, 42, 42]; ``actions``
-    int [B]; ``old_logp``, ``returns``, ``adv`` float [B] (``adv`` as the gather hands it out); ``hyper``: ``clip``, ``vf_coef``,
-    ``ent_coef`` (missing ones from ``PPO_DEFAULTS``).  Returns a dict: ``loss``, the five statistics ``policy``, ``value``,
-    ``entropy``, ``kl``, ``clipped`` (means over B), ``grads`` (the eight gradient arrays by key) and, per sample, ``z1`` [B, 16, 20, 20],
-    ``z2`` [B, 16, 10, 10], ``logits``, ``v``, ``logp``, ``ratio``, ``active`` (the branch with d policy / d logp = -A r).  Host code for
-    tests; the kernels do not use it."""
+def _light_forward(F, torch, w, x):
+    z1 = F.conv2d(x, w["conv1_w"], w["conv1_b"], stride=2)
+    a1 = torch.where(z1 > 0, z1, torch.zeros_like(z1))
+    z2 = F.conv2d(a1, w["conv2_w"], w["conv2_b"], stride=2)
+    a2 = torch.where(z2 > 0, z2, torch.zeros_like(z2)).reshape(x.shape[0], 1600)
+    return a2, dict(z1=z1, z2=z2)
+
+
+def _full_forward(F, torch, w, x):
+    z1 = F.conv2d(x, w["conv1_w"], w["conv1_b"], stride=2)
+    a1 = torch.where(z1 > 0, z1, torch.zeros_like(z1))
+    z2 = F.conv2d(a1, w["conv2_w"], w["conv2_b"], stride=2, padding=2)
+    a2 = torch.where(z2 > 0, z2, torch.zeros_like(z2)).reshape(x.shape[0], 3872)
+    z3 = a2 @ w["conv3_w"].reshape(256, 3872).t() + w["conv3_b"]  # (the 11 x 11 convolution over the whole of a2)
+    a3 = torch.where(z3 > 0, z3, torch.zeros_like(z3))
+    return a3, dict(z1=z1, z2=z2, z3=z3)
+
+
+def _ppo_loss(keys, forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype):
+    """The loss of include/crl.h "ppo update" behind the features of ``forward``: shared by the two references below."""
     import torch
     import torch.nn.functional as F
 
     dtype = torch.float64 if dtype is None else dtype
     h = dict(PPO_DEFAULTS, **(hyper or {}))
     c, vf, ent = (float(np.float32(h[k])) for k in ("clip", "vf_coef", "ent_coef"))
-    w = {k: torch.tensor(np.asarray(weights[k], np.float32), dtype=dtype, requires_grad=True) for k in PPO_KEYS}
+    w = {k: torch.tensor(np.asarray(weights[k], np.float32), dtype=dtype, requires_grad=True) for k in keys}
     x = torch.tensor(np.asarray(stacks, np.uint8).astype(np.float32), dtype=dtype) / 255
     a = torch.tensor(np.asarray(actions, np.int64))
     olp, ret, A = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (old_logp, returns, adv))
-    z1 = F.conv2d(x, w["conv1_w"], w["conv1_b"], stride=2)
-    a1 = torch.where(z1 > 0, z1, torch.zeros_like(z1))
-    z2 = F.conv2d(a1, w["conv2_w"], w["conv2_b"], stride=2)
-    a2 = torch.where(z2 > 0, z2, torch.zeros_like(z2)).reshape(x.shape[0], 1600)
-    logits = a2 @ w["actor_w"].t() + w["actor_b"]
-    v = (a2 @ w["critic_w"].t() + w["critic_b"]).reshape(-1)
+    feat, pre = forward(F, torch, w, x)
+    logits = feat @ w["actor_w"].t() + w["actor_b"]
+    v = (feat @ w["critic_w"].t() + w["critic_b"]).reshape(-1)
     lp_all = torch.log_softmax(logits, dim=1)
     logp = lp_all.gather(1, a[:, None]).reshape(-1)
     ratio = torch.exp(logp - olp)
@@ -195,8 +204,30 @@ def ppo_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=N
     s = lambda t: float(t.detach())  # noqa: E731
     return dict(loss=s(loss), policy=s(policy.mean()), value=s(value.mean()), entropy=s(entropy.mean()),
                 kl=s((olp - logp).mean()), clipped=float(((r < 1 - c) | (r > 1 + c)).to(dtype).mean()),
-                grads={k: n(w[k].grad) for k in PPO_KEYS}, z1=n(z1), z2=n(z2), logits=n(logits), v=n(v), logp=n(logp), ratio=n(r),
-                active=n(active))
+                grads={k: n(w[k].grad) for k in keys}, logits=n(logits), v=n(v), logp=n(logp), ratio=n(r),
+                active=n(active), **{k: n(z) for k, z in pre.items()})
+
+
+def ppo_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None):
+    """The loss of include/crl.h "ppo update" with torch autograd on the CPU; ``dtype=torch.float64`` (the default) is the yardstick of
+    the device's gradient.  ``weights``: the eight tensors of ``PPO_KEYS`` in torch layout; ``stacks``: uint8 [B, 4, 42, 42]; ``actions``
+    int [B]; ``old_logp``, ``returns``, ``adv`` float [B] (``adv`` as the gather hands it out); ``hyper``: ``clip``, ``vf_coef``,
+    ``ent_coef`` (missing ones from ``PPO_DEFAULTS``).  Returns a dict: ``loss``, the five statistics ``policy``, ``value``,
+    ``entropy``, ``kl``, ``clipped`` (means over B), ``grads`` (the eight gradient arrays by key) and, per sample, ``z1`` [B, 16, 20, 20],
+    ``z2`` [B, 16, 10, 10], ``logits``, ``v``, ``logp``, ``ratio``, ``active`` (the branch with d policy / d logp = -A r).  Host code for
+    tests; the kernels do not use it."""
+    return _ppo_loss(PPO_KEYS, _light_forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype)
+
+
+PPO_FULL_KEYS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "actor_w", "actor_b", "critic_w", "critic_b")
+
+
+def ppo_full_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None):
+    """``ppo_loss_reference`` for the full-size ActorCritic (include/crl.h "ppo update, full size"): the same loss behind conv1 (4 x 4,
+    stride 2), conv2 (4 x 4, stride 2, padding 2) and conv3 (11 x 11 over the whole of a2, written as the 3872 -> 256 product).
+    ``weights``: the ten tensors of ``PPO_FULL_KEYS`` in torch layout.  The same return dict, with ``z2`` [B, 32, 11, 11] and, beside it,
+    ``z3`` [B, 256].  Host code for tests; the kernels do not use it."""
+    return _ppo_loss(PPO_FULL_KEYS, _full_forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype)
 
 
 def adam_reference(params, m, v, grad, grad_norm, step, hyper=None):

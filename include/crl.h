@@ -942,6 +942,69 @@ int crl_ppo_stats(crl_ppo *p, double *out7_host);
 int crl_policy_load_weights_dev(crl_policy *p, const float *blob_dev, void *stream);
 int crl_pool_load_light_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream);
 
+/* ---- ppo update, full size: the same update for the full-size ActorCritic (utils/network.py:14-50) ----------------
+ * The loss, the per-sample closed forms, the statistics and the optimiser step are those of "ppo update", unchanged: temperature 1, an
+ * unclipped value loss, every comparison part of the rule, a ReLU's derivative z > 0 ? 1 : 0.  Only the network differs:
+ *   x = stack / 255;  z1 = conv1(x) + b1 (4 x 4, stride 2: 16 x 20 x 20),  a1 = max(z1, 0);
+ *   z2 = conv2(a1) + b2 (4 x 4, stride 2, padding 2: 32 x 11 x 11),  a2 = max(z2, 0), flattened channel-major to 3872;
+ *   z3 = conv3(a2) + b3 (11 x 11 over the whole of a2: the 3872 -> 256 product),  a3 = max(z3, 0);  logits = actor(a3),  v = critic(a3).
+ * The three convolutions are float32.  conv1 and conv2 are the served forward pass's arithmetic (conv1 with exact products of the bytes and
+ * weight / 255); conv3 is NOT: it adds its products in eleven segments (below), so the logits the learner recomputes agree with those
+ * crl_policy_act_rollout served to within float32 rounding, not bit for bit;
+ * from the features a3 on the device works in float64 up to dlogits and dv, which are rounded once to float32.
+ *
+ * Master blob = the blob of a full-size crl_policy, so a push is one device-to-device copy:
+ *   w1 [16,4,4,4] | b1 [16] | w2 [32,16,4,4] | b2 [32] | w3 [256,3872] | b3 [256] | wa [3,256] | ba [3] + 1 pad | wc [1,256] | bc [1] + 3 pads
+ * = 1 001 784 floats, 1 001 780 of them parameters, torch layouts; pads are zero in the weights, the gradient and both moments and stay so.
+ *
+ * Summation shape -- a function of B and the learner's scratch_rows S alone, not of the device, the grid or any arrival order; no
+ * floating-point atomics; the same idx on the same (B, S) gives the same bits on every run and every learner object.  "Matrix step":
+ * one v_mfma_f32_16x16x4_f32, four terms added to a float32 accumulator.
+ *   Chunks: samples [0, S), [S, 2 S), ... of idx, in order; row = a sample's place in its chunk.  Every sum below runs over a chunk's
+ *   rows as described and carries on from the value the previous chunks left (the accumulator STARTS from it; the first chunk from 0).
+ *   z3[c] = (segment_0 + segment_1 + ... + segment_10, float32, in this order) + b3[c]; segment i covers k = 352 i .. 352 i + 351 of a2 and
+ *   is one accumulator from 0: 22 slabs of 16 in order, a slab in matrix steps j = 0 .. 3, step j adding the terms k = 16 slab + 4 q + j,
+ *   q = 0 .. 3 (the served forward pass runs all 3872 through ONE accumulator; eleven keep the float32 error of a log-probability, and so
+ *   of the statistics, near that of its logits).
+ *   A logit or v: lane l of 64 adds features l, l + 64, l + 128, l + 192 (float64 fused multiply-add), then a butterfly (32, 16, .. 1).
+ *   dz3[c] = (((wa[0][c] dl0) + wa[1][c] dl1) + wa[2][c] dl2) + wc[c] dv, float32 fused multiply-adds after the first product, times (a3[c] > 0).
+ *   wa, wc, b3 (column sums of dz3), ba, bc and the statistics, two levels: slice s = the chunk's rows 256 s .. 256 s + 255; a slice's sum
+ *   starts from 0 and takes its rows in order (wa, wc: fused multiply-add d[row] * a3[row][c]; the others: additions; the statistics in
+ *   float64); then the slices' sums are added in slice order onto the previous chunks' value.  A statistic's mean = its sum / B.
+ *   w3[oc][k] (= sum over samples of dz3[oc] a2[k]): one accumulator per element, a matrix step per four consecutive rows in order
+ *   (rows past the chunk's end enter as zeros).
+ *   dz2[k] = (sum_c dz3[c] w3[c][k]) * (a2[k] > 0): one accumulator from 0, matrix steps g = 0 .. 15, j = 0 .. 3 in this order, step
+ *   (g, j) adding the four terms c = 16 g + 4 q + j, q = 0 .. 3.
+ *   conv2, conv1: W = min(256, B, S) workgroups; workgroup w takes rows w, w + W, ... of every chunk, in order, into ONE set of
+ *   accumulators per launch: w2[oc][ic][tap]: per row 31 matrix steps over the positions 4 s .. 4 s + 3 of 121 (+ 3 zeros), in order;
+ *   da1[ic] at a padded position (2 yh + py, 2 xh + px): from 0, 32 matrix steps oc = 0 .. 31, each adding the four taps (py + 2 a, px +
+ *   2 b), (a, b) = (0,0), (0,1), (1,0), (1,1), times dz2[oc][yh - a][xh - b];  dz1 = da1 * (a1 > 0);  w1[oc][ic][tap]: per row 100 matrix
+ *   steps over the positions 4 s .. 4 s + 3 of 400, B operand = byte / 255 correctly rounded;  b2[oc]: 8 float32 sums, sum i over the
+ *   positions i, i + 8, ... of the rows in order, then a butterfly (1, 2, 4) at the launch's end;  b1[oc]: 16 sums over positions i, i + 16,
+ *   ..., butterfly (1, 2, 4, 8).  A workgroup's sums of a chunk are ADDED to its partial blob of the chunks before (the first writes it).
+ *   Element i of the gradient = (partial_0[i] + ... + partial_{W-1}[i] in this order | the one sum) / float32(B).
+ *   Sum of squares in float64: 3 914 blocks of 256 consecutive elements, each through a binary tree (s[i] += s[i + 128], then 64, .. 1);
+ *   then 256 sums t = block sums t, t + 256, ... in order, through the same tree.
+ *
+ * crl_ppo_create_full returns the same crl_ppo type: crl_ppo_grad, _step, _stats, _get_grad (1 001 784 floats), _weights_dev and _destroy
+ * work on either kind.  scratch_rows: rows of activation scratch (17.6 KB each), 0 = 16 384, otherwise in [64, 2^20] (a
+ * smaller chunk only multiplies launches).  crl_ppo_grad launches eight kernels per chunk and two at the end.  crl_ppo_set_weights / _get_weights refuse a full-size learner and the _full variants a light one
+ * (CRL_EINVAL, before any GPU call).  Tensors: host pointers, torch layouts (conv3 [256,32,11,11]); the critic is required. */
+int crl_ppo_create_full(int32_t device, int64_t scratch_rows, const float *conv1_w_host, const float *conv1_b_host, const float *conv2_w_host,
+                        const float *conv2_b_host, const float *conv3_w_host, const float *conv3_b_host, const float *actor_w_host,
+                        const float *actor_b_host, const float *critic_w_host, const float *critic_b_host, crl_ppo **out);
+int crl_ppo_set_weights_full(crl_ppo *p, const float *conv1_w_host, const float *conv1_b_host, const float *conv2_w_host, const float *conv2_b_host,
+                             const float *conv3_w_host, const float *conv3_b_host, const float *actor_w_host, const float *actor_b_host,
+                             const float *critic_w_host, const float *critic_b_host);
+int crl_ppo_get_weights_full(crl_ppo *p, float *conv1_w_host, float *conv1_b_host, float *conv2_w_host, float *conv2_b_host, float *conv3_w_host,
+                             float *conv3_b_host, float *actor_w_host, float *actor_b_host, float *critic_w_host, float *critic_b_host);
+/* The full-size learner's blob (crl_ppo_weights_dev: 1 001 784 floats, critic included) into a full-size policy, or its first 1 001 524
+ * floats into full-size slot `agent` of a pool (a slot has no critic): one device-to-device copy ordered on `stream`.  Refuse
+ * (CRL_EINVAL, before any GPU call) a null argument and a LightActorCritic policy / what crl_pool_load_full refuses.
+ * crl_policy_load_weights_dev keeps refusing a full-size policy: its blob is the light learner's. */
+int crl_policy_load_full_dev(crl_policy *p, const float *blob_dev, void *stream);
+int crl_pool_load_full_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);

@@ -1,0 +1,75 @@
+"""The written rule of include/crl.h "ppo update, full size" on the CPU: rules.ppo_full_loss_reference against itself in float32, its exactly
+zero gradient on a zero-advantage batch, the blob layout of ppo.FULL_BLOB_LAYOUT, and the invariants of tests/ppo_full_cases.py (shares,
+screening cap, fault models) that tests/test_hip_ppo_full.py relies on -- all from references alone."""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from competitive_rl_amd.rules import PPO_FULL_KEYS, ppo_full_loss_reference  # noqa: E402
+from tests import ppo_full_cases as P  # noqa: E402
+
+
+def test_float64_reference_agrees_with_its_float32_within_e_ref():
+    """on every chosen batch a THIRD float32 evaluation -- the samples rotated by half the batch, an order neither of the two runs behind
+    e_ref has -- lies within the budget FACTOR x e_ref that a float32 evaluation of the rule is held to, and e_ref itself is float32-sized
+    (below 1e-4 of the tensor's largest element: 1 000 ulps)"""
+    _, w, batches = P.chosen()
+    for (n, b), bt in batches.items():
+        g32 = bt.ro.reference(w, np.roll(bt.idx, bt.b // 2), torch.float32)["grads"]
+        err = P.rel_err(g32, bt.r64["grads"])
+        for k in PPO_FULL_KEYS:
+            assert g32[k].shape == w[k].shape and err[k] <= bt.budget[k] and bt.e_ref[k] <= 1e-4, (n, b, k, err[k], bt.e_ref[k])
+
+
+def test_zero_advantage_batch_without_value_and_entropy_terms_has_exactly_zero_gradients():
+    ro = P.rollout(11)
+    idx = np.arange(9)
+    zero = np.zeros(9, np.float32)
+    ref = ppo_full_loss_reference(P.chosen()[1], ro.stacks[idx], ro.actions.reshape(-1)[idx], ro.logp.reshape(-1)[idx], ro.ret[idx], zero,
+                                  dict(clip=0.2, vf_coef=0.0, ent_coef=0.0))
+    assert ref["z3"].shape == (9, 256) and ref["z2"].shape == (9, 32, 11, 11)
+    assert all(not ref["grads"][k].any() for k in PPO_FULL_KEYS)
+
+
+def test_full_blob_layout_tiles_the_blob_with_only_the_stated_pads():
+    from competitive_rl_amd.ppo import FULL_BLOB_FLOATS, FULL_BLOB_LAYOUT, blob_views
+
+    assert FULL_BLOB_FLOATS == 1001784 and tuple(FULL_BLOB_LAYOUT) == PPO_FULL_KEYS
+    covered = np.zeros(FULL_BLOB_FLOATS, np.int32)
+    for k, (o, s) in FULL_BLOB_LAYOUT.items():
+        assert s == P.base_weights()[k].shape
+        covered[o:o + int(np.prod(s))] += 1
+    assert covered.max() == 1 and np.flatnonzero(covered == 0).tolist() == [1001523, 1001781, 1001782, 1001783]  # ba + 1 pad, bc + 3 pads
+    assert int(covered.sum()) == 1001780
+    v = blob_views(np.arange(FULL_BLOB_FLOATS, dtype=np.float32))
+    assert tuple(v) == PPO_FULL_KEYS and v["conv3_w"].shape == (256, 32, 11, 11) and v["conv3_w"][0, 0, 0, 0] == 9264 and v["critic_b"][0] == 1001780
+
+
+def test_the_chosen_batches_hold_the_conditions_the_gpu_test_relies_on():
+    amount, w, batches = P.chosen()
+    zero, other, acts = P.shares(list(batches.values()))
+    assert zero >= 0.10 and other >= 0.30 and acts == {0, 1, 2}, (amount, zero, other, acts)
+    cand, dropped = sum(b.candidates for b in batches.values()), sum(b.dropped for b in batches.values())
+    print("amount %g: zero-gradient share %.3f, other %.3f; screening dropped %d of %d candidates" % (amount, zero, other, dropped, cand))
+    assert dropped <= P.DROP_CAP * cand, (dropped, cand)
+    for (n, b), bt in batches.items():
+        assert len(bt.idx) == b and (b < 67 or len(set(bt.idx.tolist())) < b), "idx carries duplicates"
+        assert all(np.abs(bt.r64[k]).min() >= bt.delta_z for k in P.PRE)
+        print("N %d B %d: dz %.3g dr %.3g dropped %d / %d, e_ref %s" % (n, b, bt.delta_z, bt.delta_r, bt.dropped, bt.candidates,
+                                                                        " ".join("%s %.2g" % kv for kv in bt.e_ref.items())))
+    assert any((P.rollout(n).depth < 4).any() for n in P.PATTERN)
+
+
+@pytest.mark.parametrize("fault", P.FAULTS)
+def test_every_fault_model_lies_two_budgets_away(fault):
+    """each fault is at least 2 x budget away in some tensor on every batch that can show it, and is shown by at least four of the six"""
+    _, w, batches = P.chosen()
+    shown = 0
+    for key, bt in batches.items():
+        m = bt.fault_margin(fault, w)
+        print(fault, key, m)
+        if m is not None:
+            assert m >= 2, (fault, key, m)
+            shown += 1
+    assert shown >= 4, (fault, shown)
