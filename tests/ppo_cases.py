@@ -34,6 +34,27 @@ STATISTICS: absolute errors, the same FACTOR x e_ref; the floor is, for the poli
 ulps of the batch's largest |logit| -- the floor tests/policy_f64_cases.py gives the logits themselves: these three are functions of
 log-probabilities, and a log-probability formed from float32 features cannot be known better than its logits --, and 2 ulps of
 max(|statistic|, 1) for the value loss and the clipped share.
+
+BIG_CASES, (N 67, B 2500).  pong_ppo.hip launches W = min(256, ceil(B / 8)) workgroups and workgroup w takes the groups w, w + W, ...: at
+B <= 130 every workgroup runs one pass, so nothing in CASES makes a workgroup re-use its LDS buffers or carry its accumulators, bias and
+head sums and statistics into a second pass -- which every batch above 2048 samples does (B = 262 144: 128 passes).  2500 is 313 groups:
+workgroups 0 .. 56 run two passes, the rest one, and the last group is partial (4 samples) and is a SECOND pass (workgroup 56).  The
+batch is built by ``big()`` on rollout(67) at the weights chosen() has chosen, by the same candidate draw and screening (3128
+candidates); it takes no part in chosen()'s shares, AMOUNT or the 10 % drop cap over CASES, which come out bit-identical.  Its own cap:
+at most BIG_DROP_CAP = 20 % of its candidates dropped (the value ppo_full_cases.DROP_CAP uses; 426 / 3128 = 13.6 %), and it must fill.
+
+SEQ32, the third float32 reference behind the big batches' e_ref: the float32 autograd gradient of each sample's own loss term, added
+one sample at a time in idx order into a float32 accumulator, divided by float32(B) at the end; the statistics the same way.  It is the
+strictly sequential order (the idea of policy_oracle.forward_seq32), and the shape the headers prescribe for the full-size w3 and head
+slices.  Two references are not enough at these sizes: torch's blocked sums over B are nearly exact on the short tensors, so e_ref
+over forward and reverse alone describes torch's summation and not float32 summation.  Measured on one x86 host, seq32's error over that
+two-reference e_ref: light B 2500 critic_w 7.9, critic_b 3.3, actor_b 2.8, actor_w 2.0; full B 601 critic_b 11.0, conv3_b 6.2, actor_b 3.5,
+conv3_w 2.2 -- a CORRECT strictly sequential float32 kernel would fail a two-reference budget on critic_b.  FACTOR stays 10.
+
+FAULT MODELS between passes (BIG_FAULTS, float64): pass_repeats -- a later pass sees its workgroup's previous inputs, so the samples at
+positions >= 8 x 256 are those 2048 places earlier; earlier_pass_lost -- a later pass overwrites instead of adding, so only each
+workgroup's last pass is left (groups 57 .. 312) and the sum is still divided by B.  test_ppo_rules.py asserts every fault model, old
+and new, at least 2 x the three-reference budget away on the big batch.
 """
 import math
 
@@ -48,6 +69,9 @@ T = 6
 FACTOR = 10  # (see above)
 HYPER = dict(clip=0.2, vf_coef=0.5, ent_coef=0.1)  # (ent_coef: keeps the omitted-entropy fault 2 x budget away on every batch)
 CASES = ((1, 1), (1, 7), (11, 8), (11, 9), (67, 67), (67, 130))
+BIG_CASES = ((67, 2500),)  # (313 groups on 256 workgroups: see the module docstring)
+GROUP, WORKGROUPS = 8, 256  # pong_ppo.hip: samples per group, the most workgroups a launch has
+BIG_DROP_CAP = 0.20
 PATTERN = {1: "two_consecutive", 11: "random", 67: "random"}
 AMOUNTS = (0.002, 0.005, 0.01, 0.02, 0.05, 0.1)
 STAT_KEYS = ("policy", "value", "entropy", "kl", "clipped")
@@ -114,10 +138,10 @@ def rollout(n):
     return _rollouts[n]
 
 
-def rel_err(got, want):
+def rel_err(got, want, keys=PPO_KEYS):
     """per tensor: max|got - want| / max|want| (0 where the tensor's float64 gradient is exactly zero and so is the other)"""
     out = {}
-    for k in PPO_KEYS:
+    for k in keys:
         top = float(np.abs(want[k]).max())
         out[k] = float(np.abs(np.asarray(got[k], np.float64) - want[k]).max()) / top if top > 0 else float(np.abs(got[k]).max())
     return out
@@ -132,10 +156,47 @@ def references32(ro, weights, idx, **kw):
     return fwd, rev
 
 
-class Batch:
-    """The kept batch of (n, b) at the learner weights `weights`: idx, the float64 reference, e_ref and the budget per tensor"""
+def seq32(reference, idx, keys=PPO_KEYS, cache=True):
+    """The third float32 reference of BIG_CASES, strictly sequential over the samples: the float32 autograd gradient of each sample's own
+    loss term (``reference(idx[i:i + 1])``, a batch of one) added one sample at a time, in idx order, into a float32 accumulator and
+    divided by float32(B) at the end; the five statistics the same way from the per-sample float32 terms.  ``cache``: a sample that idx
+    repeats is evaluated once (the same bits either way; the full-size module turns it off, 4 MB of gradient per sample)."""
+    per, acc, stats = {}, None, {k: np.float32(0) for k in STAT_KEYS}
+    for p, i in enumerate(idx.tolist()):
+        one = per.get(i)
+        if one is None:
+            r = reference(idx[p:p + 1])
+            one = ({k: r["grads"][k] for k in keys}, {k: np.float32(r[k]) for k in STAT_KEYS})
+            assert all(g.dtype == np.float32 for g in one[0].values())
+            if cache:
+                per[i] = one
+        acc = {k: one[0][k].copy() for k in keys} if acc is None else {k: acc[k] + one[0][k] for k in keys}
+        stats = {k: np.float32(stats[k] + one[1][k]) for k in STAT_KEYS}
+    count = np.float32(len(idx))
+    assert all(acc[k].dtype == np.float32 for k in keys)
+    return dict(grads={k: acc[k] / count for k in keys}, **{k: float(np.float32(stats[k] / count)) for k in STAT_KEYS})
 
-    def __init__(self, n, b, weights):
+
+def set_budgets(bt, refs, keys):
+    """The budget rule of the module docstring on ``bt.r64`` and the float32 references ``refs`` (two, or three with seq32 last): sets
+    errs, e_ref and budget per tensor, stat_errs, stat_e_ref and stat_budget per statistic"""
+    bt.ref_names = ("forward", "reverse", "seq32")[:len(refs)]
+    bt.errs = [rel_err(r["grads"], bt.r64["grads"], keys) for r in refs]
+    bt.e_ref = {k: max(e[k] for e in bt.errs) for k in keys}
+    bt.budget = {k: max(FACTOR * bt.e_ref[k], 2 * ULP1) for k in keys}
+    # the statistics: absolute errors, FACTOR x e_ref, the floors of the module docstring
+    bt.stat_errs = [{k: abs(r[k] - bt.r64[k]) for k in STAT_KEYS} for r in refs]
+    bt.stat_e_ref = {k: max(e[k] for e in bt.stat_errs) for k in STAT_KEYS}
+    logit_floor = 2 * C.ulp32(np.abs(bt.r64["logits"]).max())
+    floor = {k: logit_floor if k in ("policy", "entropy", "kl") else 2 * ULP1 * max(abs(bt.r64[k]), 1.0) for k in STAT_KEYS}
+    bt.stat_budget = {k: max(FACTOR * bt.stat_e_ref[k], floor[k]) for k in STAT_KEYS}
+
+
+class Batch:
+    """The kept batch of (n, b) at the learner weights `weights`: idx, the float64 reference, e_ref and the budget per tensor.
+    ``sequential``: seq32 joins the two float32 references behind e_ref (BIG_CASES); the screening is the same either way."""
+
+    def __init__(self, n, b, weights, sequential=False):
         self.n, self.b, self.ro = n, b, rollout(n)
         ro, c = self.ro, np.float32(HYPER["clip"])
         rs = np.random.RandomState(1000 * n + b)
@@ -149,18 +210,14 @@ class Batch:
         zmin = np.minimum(np.abs(r64["z1"]).reshape(len(cand), -1).min(1), np.abs(r64["z2"]).reshape(len(cand), -1).min(1))
         redge = np.minimum(np.abs(r64["ratio"] - (1 - float(c))), np.abs(r64["ratio"] - (1 + float(c))))
         keep = (zmin >= self.delta_z) & (redge >= self.delta_r)
-        self.candidates, self.dropped = len(cand), int((~keep).sum())
-        assert keep.sum() >= b, (n, b, int(keep.sum()))
+        self.candidates, self.dropped, self.kept = len(cand), int((~keep).sum()), int(keep.sum())
+        assert self.kept >= b, (n, b, self.kept)  # every batch fills
         self.idx = cand[keep][:b].copy()
         self.r64 = ro.reference(weights, self.idx)
-        self.errs = [rel_err(r["grads"], self.r64["grads"]) for r in references32(ro, weights, self.idx)]
-        self.e_ref = {k: max(e[k] for e in self.errs) for k in PPO_KEYS}
-        self.budget = {k: max(FACTOR * self.e_ref[k], 2 * ULP1) for k in PPO_KEYS}
-        # the statistics: absolute errors, FACTOR x e_ref, the floors of the module docstring
-        self.stat_e_ref = {k: max(abs(r[k] - self.r64[k]) for r in references32(ro, weights, self.idx)) for k in STAT_KEYS}
-        logit_floor = 2 * C.ulp32(np.abs(self.r64["logits"]).max())
-        floor = {k: logit_floor if k in ("policy", "entropy", "kl") else 2 * ULP1 * max(abs(self.r64[k]), 1.0) for k in STAT_KEYS}
-        self.stat_budget = {k: max(FACTOR * self.stat_e_ref[k], floor[k]) for k in STAT_KEYS}
+        refs = references32(ro, weights, self.idx)
+        if sequential:
+            refs += (seq32(lambda one: ro.reference(weights, one, torch.float32), self.idx),)
+        set_budgets(self, refs, PPO_KEYS)
 
     # ---- fault models: the gradient a subtly wrong kernel would return, in float64
     def fault(self, name, weights):
@@ -182,6 +239,20 @@ class Batch:
             return self.ro.reference(weights, self.idx, stacks=self.ro.unmasked)["grads"]
         if name == "no_entropy":
             return self.ro.reference(weights, self.idx, hyper=dict(HYPER, ent_coef=0.0))["grads"]
+        # ---- between the passes of one workgroup (BIG_CASES): workgroup w of WORKGROUPS takes the groups w, w + WORKGROUPS, ...
+        span = GROUP * WORKGROUPS
+        if name == "pass_repeats":  # a later pass sees its workgroup's previous inputs: the samples `span` places earlier
+            if self.b <= span:
+                return None
+            idx = self.idx.copy()
+            idx[span:] = self.idx[:self.b - span]
+            return self.ro.reference(weights, idx)["grads"]
+        if name == "earlier_pass_lost":  # a later pass overwrites: only each workgroup's last pass is left (the sum is still divided by B)
+            lost = GROUP * max(0, -(-self.b // GROUP) - WORKGROUPS)
+            if lost == 0:
+                return None
+            part = self.ro.reference(weights, self.idx[lost:])["grads"]
+            return {k: part[k] * ((self.b - lost) / self.b) for k in PPO_KEYS}
         raise KeyError(name)
 
     def fault_margin(self, name, weights):
@@ -194,6 +265,7 @@ class Batch:
 
 
 FAULTS = ("dropped_last", "missing_tap", "unmasked", "no_entropy")
+BIG_FAULTS = FAULTS + ("pass_repeats", "earlier_pass_lost")
 _state = {}
 
 
@@ -217,3 +289,11 @@ def chosen():
         else:
             raise AssertionError("no AMOUNT gives the required shares")
     return _state["amount"], _state["weights"], _state["batches"]
+
+
+def big():
+    """{(n, b): Batch} of BIG_CASES at the weights chosen() chose (they take no part in that choice) -- once per process, read-only"""
+    if "big" not in _state:
+        w = chosen()[1]
+        _state["big"] = {(n, b): Batch(n, b, w, sequential=True) for n, b in BIG_CASES}
+    return _state["big"]

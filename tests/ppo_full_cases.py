@@ -17,6 +17,25 @@ BUDGET per tensor max(FACTOR x e_ref, 2 ulp), statistics as in ppo_cases.
 
 FAULT MODELS: dropped_last (the batch's last sample never added), missing_tap (conv2's tap (3, 3) never accumulated), unmasked,
 no_entropy, w3_last_row (the conv3_w gradient alone lacks the batch's last sample: the K tail of the gW3 product).
+
+BIG_CASES, (N 67, B 601), run at the default scratch_rows and at BIG_ROWS = 320.  With B <= 130 (and 130 rows in chunks of 64) every
+workgroup of ppo_full_back_kernel sees at most one row per launch, the two-level head sum has one slice per chunk and the front kernel's
+row loop runs once: nothing in CASES holds gW1 / gW2 / gb1 / gb2 across rows while the LDS tiles are re-filled, adds a second slice, or
+adds several slices onto a previous chunk's sum -- which production (B 65 536 in chunks of 16 384: 64 rows per workgroup, 64 slices) does
+all the time.  601 rows in one chunk: the back kernel's 256 workgroups take three rows (0 .. 88) or two; three head slices 256 + 256 +
+89; the front loop runs twice on 89 of 512 workgroups; the last heads workgroup holds one row; 601 % 4 = 1, so dropped_last and
+w3_last_row show.  In chunks of 320: 320 and 281 rows, each two slices with a partial second one, W = 256 with one or two rows per
+workgroup, the second chunk adding onto the first one's sums.  ``big()`` builds the batch on rollout(67) at the weights chosen() has
+chosen, by the same candidate draw and screening (905 candidates, 102 dropped = 11.3 %, its own cap DROP_CAP); it takes no part in
+chosen()'s shares, AMOUNT or the cap over CASES, which come out bit-identical.
+
+Its e_ref is over THREE float32 references: forward, reverse and ppo_cases.seq32 (per-sample float32 gradients added one at a time in
+idx order, / float32(B)); ppo_cases' docstring has the reason and the measured ratios (critic_b: seq32 is 11 x the two-reference e_ref).
+
+FAULT MODELS between rows, slices and chunks (BIG_FAULTS, float64): pass_repeats -- a later row sees its workgroup's previous inputs:
+the samples at positions >= 256 are those 256 places earlier; earlier_pass_lost -- a later row overwrites: only each workgroup's last
+row (positions 345 .. 600) is left, the sum still divided by B; slice_lost -- wa, ba, wc, bc and b3 lack the rows of the last slice
+(512 .. 600); chunk_restart -- the run at BIG_ROWS: every tensor holds the second chunk's sum alone, divided by B.
 """
 import math
 
@@ -24,15 +43,18 @@ import numpy as np
 import torch
 
 from competitive_rl_amd.rules import PPO_FULL_KEYS, gae_reference, ppo_full_loss_reference, rollout_stack_reference
-from tests import policy_f64_cases as C
 from tests.policy_full_weights import make_weights
-from tests.ppo_cases import CASES, FACTOR, HYPER, PATTERN, STAT_KEYS, ULP1, T
+from tests.ppo_cases import CASES, FACTOR, HYPER, PATTERN, STAT_KEYS, ULP1, T, seq32, set_budgets
 from tests.test_rollout_storage_rules import reset_pattern
 
 KEYS = PPO_FULL_KEYS
+HEAD_KEYS = ("conv3_b", "actor_w", "actor_b", "critic_w", "critic_b")  # what the two-level head sum forms
 AMOUNTS = (0.1, 0.2, 0.3, 0.5)
 DROP_CAP = 0.20
 PRE = ("z1", "z2", "z3")
+BIG_CASES = ((67, 601),)  # (three rows per workgroup, three head slices; in chunks of BIG_ROWS two chunks of two slices: see above)
+BIG_ROWS = 320            # scratch_rows of the chunked run of BIG_CASES
+SLICE, BACK_MAX = 256, 256  # pong_ppo_full.hip: rows per head slice, the most workgroups the back kernel has
 
 
 def base_weights():
@@ -115,7 +137,7 @@ def references32(ro, weights, idx):
 class Batch:
     """The kept batch of (n, b) at the learner weights `weights`: idx, the float64 reference, e_ref and the budget per tensor"""
 
-    def __init__(self, n, b, weights):
+    def __init__(self, n, b, weights, sequential=False):
         self.n, self.b, self.ro = n, b, rollout(n)
         ro, c = self.ro, np.float32(HYPER["clip"])
         rs = np.random.RandomState(1000 * n + b)
@@ -134,21 +156,20 @@ class Batch:
         self.idx = cand[keep][:b].copy()
         self.r64 = ro.reference(weights, self.idx)
         refs = references32(ro, weights, self.idx)
-        self.errs = [rel_err(r["grads"], self.r64["grads"]) for r in refs]
-        self.e_ref = {k: max(e[k] for e in self.errs) for k in KEYS}
-        self.budget = {k: max(FACTOR * self.e_ref[k], 2 * ULP1) for k in KEYS}
-        # the statistics: absolute errors, FACTOR x e_ref, the floors of ppo_cases' docstring
-        self.stat_e_ref = {k: max(abs(r[k] - self.r64[k]) for r in refs) for k in STAT_KEYS}
-        logit_floor = 2 * C.ulp32(np.abs(self.r64["logits"]).max())
-        floor = {k: logit_floor if k in ("policy", "entropy", "kl") else 2 * ULP1 * max(abs(self.r64[k]), 1.0) for k in STAT_KEYS}
-        self.stat_budget = {k: max(FACTOR * self.stat_e_ref[k], floor[k]) for k in STAT_KEYS}
+        if sequential:
+            refs += (seq32(lambda one: ro.reference(weights, one, torch.float32), self.idx, KEYS, cache=False),)
+        set_budgets(self, refs, KEYS)  # (FACTOR x e_ref, the floors of ppo_cases' docstring)
 
     # ---- fault models: the gradient a subtly wrong kernel would return, in float64
-    def _without_last(self, weights):
-        if self.b == 1:
+    def _only(self, weights, lo, hi):
+        """the samples at positions [lo, hi) alone, the sum still divided by B"""
+        if hi <= lo:
             return {k: np.zeros_like(self.r64["grads"][k]) for k in KEYS}
-        part = self.ro.reference(weights, self.idx[:-1])["grads"]
-        return {k: part[k] * ((self.b - 1) / self.b) for k in KEYS}
+        part = self.ro.reference(weights, self.idx[lo:hi])["grads"]
+        return {k: part[k] * ((hi - lo) / self.b) for k in KEYS}
+
+    def _without_last(self, weights):
+        return self._only(weights, 0, self.b - 1)
 
     def fault(self, name, weights):
         g64 = self.r64["grads"]
@@ -166,6 +187,22 @@ class Batch:
             return self.ro.reference(weights, self.idx, hyper=dict(HYPER, ent_coef=0.0))["grads"]
         if name == "w3_last_row":  # the K tail of the gW3 product: conv3_w alone lacks the last sample
             return dict(g64, conv3_w=self._without_last(weights)["conv3_w"])
+        # ---- between the rows of one workgroup, the slices and the chunks (BIG_CASES)
+        if name == "pass_repeats":  # a later row sees its workgroup's previous inputs: the samples BACK_MAX places earlier
+            if self.b <= BACK_MAX:
+                return None
+            idx = self.idx.copy()
+            idx[BACK_MAX:] = self.idx[:self.b - BACK_MAX]
+            return self.ro.reference(weights, idx)["grads"]
+        if name == "earlier_pass_lost":  # a later row overwrites: only each workgroup's last row is left
+            return None if self.b <= BACK_MAX else self._only(weights, self.b - BACK_MAX, self.b)
+        if name == "slice_lost":  # the head tensors lack the rows of the last slice
+            if self.b <= SLICE:
+                return None
+            part = self._only(weights, 0, SLICE * ((self.b - 1) // SLICE))
+            return dict(g64, **{k: part[k] for k in HEAD_KEYS})
+        if name == "chunk_restart":  # the run at BIG_ROWS: every tensor holds the last chunk's sum alone
+            return None if self.b <= BIG_ROWS else self._only(weights, BIG_ROWS * ((self.b - 1) // BIG_ROWS), self.b)
         raise KeyError(name)
 
     def fault_margin(self, name, weights):
@@ -178,6 +215,7 @@ class Batch:
 
 
 FAULTS = ("dropped_last", "missing_tap", "unmasked", "no_entropy", "w3_last_row")
+BIG_FAULTS = FAULTS + ("pass_repeats", "earlier_pass_lost", "slice_lost", "chunk_restart")
 _state = {}
 
 
@@ -201,3 +239,11 @@ def chosen():
         else:
             raise AssertionError("no AMOUNT gives the required shares")
     return _state["amount"], _state["weights"], _state["batches"]
+
+
+def big():
+    """{(n, b): Batch} of BIG_CASES at the weights chosen() chose (they take no part in that choice) -- once per process, read-only"""
+    if "big" not in _state:
+        w = chosen()[1]
+        _state["big"] = {(n, b): Batch(n, b, w, sequential=True) for n, b in BIG_CASES}
+    return _state["big"]

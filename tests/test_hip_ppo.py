@@ -6,7 +6,16 @@ conv1_w 0.30, conv1_b 0.31, conv2_w 0.37, conv2_b 0.35, actor_w 0.37, actor_b 0.
 value 0.40, entropy 0.14, kl 0.08, clipped 0.  2. The same idx twice: identical bits.  3. A batch of 9 in the zero-gradient branch with
 vf = ent = 0: an exactly zero actor gradient.  4. step() against rules.adam_reference fed the device's own gradient and norm, bit for bit, three steps,
 a max_grad_norm that clips and one that does not.  5. push() into a Policy and a league slot against a fresh Policy of
-learner.weights(), bit for bit.  6. update() against the same explicit grad / step sequence, bit for bit.  8. The host-side refusals."""
+learner.weights(), bit for bit.  6. update() against the same explicit grad / step sequence, bit for bit.  8. The host-side refusals.
+
+9. .. 12. ppo_cases.BIG_CASES, (N 67, B 2500): 313 groups on 256 workgroups, so workgroups 0 .. 56 run a SECOND pass over the LDS buffers
+with the accumulators, the bias and head sums and the statistics carried over (the last of them on a partial group of 4) -- what every
+batch above 2048 samples does and no batch of CASES reaches.  9. The gradients and 10. the statistics and the gradient norm against float64
+within the three-reference budget (forward, reverse, seq32); 11. the same idx twice on one learner and on a second one: identical bits,
+statistics included (a race between passes shows here first); 12. a batch of 9 on the same learner afterwards: the bits of a fresh
+learner (no stale partials when the 256 workgroups become 2).  Measured on an MI355X: the largest error / budget is conv1_w 0.02,
+conv1_b 0.01, conv2_w 0.02, conv2_b 0.02, actor_w 0.02, actor_b 0.02, critic_w 0.02, critic_b 0.03; statistics: policy 0.00, value 0.00,
+entropy 0.00, kl 0.01, clipped 0."""
 import ctypes
 
 import numpy as np
@@ -263,3 +272,54 @@ def test_host_side_refusals():
     with pytest.raises(ValueError, match="critic"):
         LightPPO({k: v for k, v in P.base_weights().items() if not k.startswith("critic")})
     full.close(), fresh.close(), lr.close()
+
+
+# ---- 9. .. 12. BIG_CASES: 313 groups on 256 workgroups, so workgroups 0 .. 56 run a second pass (the last of them on a partial group)
+def big_run(n, b):
+    """(the device's gradients, its statistics) of big batch (n, b), once per process"""
+    if (n, b) not in _runs:
+        lr = learner()
+        g = _host(lr.grad(storage(n), torch.from_numpy(P.big()[(n, b)].idx.astype(np.int64)).cuda()))
+        _runs[(n, b)] = (g, lr.stats())
+        lr.close()
+    return _runs[(n, b)]
+
+
+@pytest.mark.parametrize("n,b", P.BIG_CASES)
+def test_big_batch_gradients_against_float64(n, b):
+    _need_gpu()
+    bt = P.big()[(n, b)]
+    g, _ = big_run(n, b)
+    err = P.rel_err(g, bt.r64["grads"])
+    print("ppo grad N %d B %d: " % (n, b) + "  ".join("%s err %.3g budget %.3g (%.2f)" % (k, err[k], bt.budget[k], err[k] / bt.budget[k]) for k in PPO_KEYS))
+    for k in PPO_KEYS:
+        assert g[k].shape == bt.r64["grads"][k].shape and err[k] <= bt.budget[k], (k, err[k], bt.budget[k])
+
+
+@pytest.mark.parametrize("n,b", P.BIG_CASES)
+def test_big_batch_statistics_against_float64(n, b):
+    _need_gpu()
+    bt = P.big()[(n, b)]
+    g, st = big_run(n, b)
+    got = dict(zip(P.STAT_KEYS, st[:5]))
+    print("ppo stats N %d B %d: " % (n, b) + "  ".join("%s %.6g err %.3g budget %.3g (%.2f)" % (k, got[k], abs(got[k] - bt.r64[k]), bt.stat_budget[k],
+                                                                                                 abs(got[k] - bt.r64[k]) / bt.stat_budget[k]) for k in P.STAT_KEYS))
+    for k in P.STAT_KEYS:
+        assert abs(got[k] - bt.r64[k]) <= bt.stat_budget[k], (k, got[k], bt.r64[k], bt.stat_budget[k])
+    sq = sum(float((g[k].astype(np.float64) ** 2).sum()) for k in PPO_KEYS)
+    assert abs(st.grad_norm - np.sqrt(sq)) <= 1e-12 * np.sqrt(sq) and st.steps == 0
+
+
+@pytest.mark.parametrize("n,b", P.BIG_CASES)
+def test_big_batch_gives_the_same_bits_and_leaves_nothing_behind(n, b):
+    """the big batch twice on one learner and against a second learner (the cached run): identical bits, statistics included; then a
+    batch of 9 on the same learner -- two workgroups where there were 256 -- gives the bits of a fresh learner"""
+    _need_gpu()
+    idx = torch.from_numpy(P.big()[(n, b)].idx.astype(np.int64)).cuda()
+    first, stats = big_run(n, b)
+    lr = learner()
+    for _ in range(2):
+        assert _same_bits(_host(lr.grad(storage(n), idx)), first) and lr.stats() == stats
+    small, small_stats = run(11, 9)
+    assert _same_bits(_host(lr.grad(storage(11), torch.from_numpy(P.chosen()[2][(11, 9)].idx.astype(np.int64)).cuda())), small) and lr.stats() == small_stats
+    lr.close()

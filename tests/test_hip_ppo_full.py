@@ -12,7 +12,17 @@ refusals.
 
 Measured on an MI355X (docs/LAB_NOTES_ppo_full_update.md has every batch): the largest error / budget over the seven runs is
 conv1_w 0.08, conv1_b 0.05, conv2_w 0.12, conv2_b 0.11, conv3_w 0.12, conv3_b 0.24, actor_w 0.11, actor_b 0.12, critic_w 0.11, critic_b 0.28;
-statistics: policy 0.06, value 0.04, entropy 0.17, kl 0.26, clipped 0.00."""
+statistics: policy 0.06, value 0.04, entropy 0.17, kl 0.26, clipped 0.00.
+
+10. .. 13. ppo_full_cases.BIG_CASES, (N 67, B 601), at the default scratch_rows (one chunk: the back kernel's workgroups 0 .. 88 take three
+rows and the rest two with gW1, gW2, gb1, gb2 held across them; three head slices 256 + 256 + 89; the front kernel's row loop; a last
+heads workgroup of one row) and at scratch_rows = BIG_ROWS = 320 (chunks of 320 and 281, each of two slices with a partial second one,
+the second chunk adding onto the first one's sums: ``first == 0`` with ``slices > 1``) -- what production's 64 rows per workgroup and
+64 slices per chunk do and no batch of CASES reaches.  10. The gradients and 11. the statistics and the gradient norm against float64
+within the three-reference budget (forward, reverse, seq32); 12. the same idx twice on one learner and on a second one: identical bits,
+statistics included; 13. a batch of 9 on the same learner afterwards: the bits of a fresh learner.  Measured on an MI355X: the largest
+error / budget over the two runs is conv1_w 0.03, conv1_b 0.02, conv2_w 0.06, conv2_b 0.03, conv3_w 0.11, conv3_b 0.09, actor_w 0.05,
+actor_b 0.04, critic_w 0.03, critic_b 0.03; statistics: policy 0.01, value 0.02, entropy 0.00, kl 0.00, clipped 0.00."""
 import ctypes
 
 import numpy as np
@@ -327,3 +337,62 @@ def test_host_side_refusals():
     with pytest.raises(TypeError, match="FullPPO takes"):
         FullPPO(P.base_weights(), momentum=0.9)
     small.close(), big.close(), fresh.close(), full.close(), light.close()
+
+
+# ---- 10. .. 13. BIG_CASES: B = 601 in one chunk (three rows per back workgroup, three head slices, the front kernel's row loop) and in
+# chunks of BIG_ROWS (two chunks of two slices each, the second chunk adding onto the first one's sums)
+BIG_RUNS = [(n, b, rows) for n, b in P.BIG_CASES for rows in (None, P.BIG_ROWS)]
+
+
+def _big_idx(n, b):
+    return torch.from_numpy(P.big()[(n, b)].idx.astype(np.int64)).cuda()
+
+
+def big_run(n, b, rows):
+    """(the device's gradients, its statistics) of big batch (n, b) at scratch_rows `rows`, once per process"""
+    if (n, b, rows) not in _runs:
+        lr = learner(rows)
+        g = _host(lr.grad(storage(n), _big_idx(n, b)))
+        _runs[(n, b, rows)] = (g, lr.stats())
+        lr.close()
+    return _runs[(n, b, rows)]
+
+
+@pytest.mark.parametrize("n,b,rows", BIG_RUNS)
+def test_big_batch_gradients_against_float64(n, b, rows):
+    _need_gpu()
+    bt = P.big()[(n, b)]
+    g, _ = big_run(n, b, rows)
+    err = P.rel_err(g, bt.r64["grads"])
+    print("ppo full grad N %d B %d rows %s: " % (n, b, rows) + "  ".join("%s err %.3g budget %.3g (%.2f)" % (k, err[k], bt.budget[k], err[k] / bt.budget[k]) for k in KEYS))
+    for k in KEYS:
+        assert g[k].shape == bt.r64["grads"][k].shape and err[k] <= bt.budget[k], (k, err[k], bt.budget[k])
+
+
+@pytest.mark.parametrize("n,b,rows", BIG_RUNS)
+def test_big_batch_statistics_against_float64(n, b, rows):
+    _need_gpu()
+    bt = P.big()[(n, b)]
+    g, st = big_run(n, b, rows)
+    got = dict(zip(P.STAT_KEYS, st[:5]))
+    print("ppo full stats N %d B %d rows %s: " % (n, b, rows) + "  ".join("%s %.6g err %.3g budget %.3g (%.2f)" % (
+        k, got[k], abs(got[k] - bt.r64[k]), bt.stat_budget[k], abs(got[k] - bt.r64[k]) / bt.stat_budget[k]) for k in P.STAT_KEYS))
+    for k in P.STAT_KEYS:
+        assert abs(got[k] - bt.r64[k]) <= bt.stat_budget[k], (k, got[k], bt.r64[k], bt.stat_budget[k])
+    sq = sum(float((g[k].astype(np.float64) ** 2).sum()) for k in KEYS)
+    assert abs(st.grad_norm - np.sqrt(sq)) <= 1e-12 * np.sqrt(sq) and st.steps == 0
+
+
+@pytest.mark.parametrize("n,b,rows", BIG_RUNS)
+def test_big_batch_gives_the_same_bits_and_leaves_nothing_behind(n, b, rows):
+    """the big batch twice on one learner and against a second learner (the cached run): identical bits, statistics included; then a
+    batch of 9 on the same learner -- nine back workgroups and one slice where there were 256 and three -- gives the bits of a fresh
+    learner of the same scratch_rows"""
+    _need_gpu()
+    first, stats = big_run(n, b, rows)
+    lr, fresh = learner(rows), learner(rows)
+    for _ in range(2):
+        assert _same_bits(_host(lr.grad(storage(n), _big_idx(n, b))), first) and lr.stats() == stats
+    want = _host(fresh.grad(storage(11), _idx(11, 9)))
+    assert _same_bits(_host(lr.grad(storage(11), _idx(11, 9))), want) and lr.stats() == fresh.stats() and any(want[k].any() for k in KEYS)
+    lr.close(), fresh.close()

@@ -149,3 +149,50 @@ def test_every_fault_model_lies_two_budgets_away(fault):
             assert m >= 2, (fault, key, m)
             shown += 1
     assert shown >= 4, (fault, shown)
+
+
+# ---- BIG_CASES: the batch at which a workgroup takes a second group
+def test_the_big_batch_leaves_the_chosen_batches_alone_and_holds_its_own_conditions():
+    """BIG_CASES are built at the chosen weights and take no part in choosing them: chosen() hands out the same objects before and after
+    big() ran, and a fresh Batch of an existing case has the same idx and budgets.  Then the big batch's own conditions: its drop cap,
+    that it fills, the screening margin, both branches of the clipped ratio, shallow stacks, the group arithmetic the GPU test
+    relies on, and seq32 among the references behind e_ref."""
+    amount, w, batches = P.chosen()
+    before = {key: (bt.idx.copy(), dict(bt.budget), dict(bt.stat_budget)) for key, bt in batches.items()}
+    big = P.big()
+    assert P.chosen()[0] == amount and P.chosen()[1] is w and P.chosen()[2] is batches and set(batches) == set(P.CASES)
+    again = P.Batch(11, 9, w)
+    for key, bt in list(batches.items()) + [((11, 9), again)]:
+        assert np.array_equal(bt.idx, before[key][0]) and bt.budget == before[key][1] and bt.stat_budget == before[key][2] and len(bt.errs) == 2
+    assert set(big) == set(P.BIG_CASES) == {(67, 2500)}
+    for (n, b), bt in big.items():
+        groups = -(-b // P.GROUP)
+        assert groups == 313 and groups - P.WORKGROUPS == 57 and b % P.GROUP == 4  # workgroups 0 .. 56 run two passes, the last one partial
+        assert bt.ro is P.rollout(n) and len(bt.idx) == b and bt.kept >= b and len(set(bt.idx.tolist())) < b
+        assert bt.dropped <= P.BIG_DROP_CAP * bt.candidates, (bt.dropped, bt.candidates)
+        assert np.abs(bt.r64["z1"]).min() >= bt.delta_z and np.abs(bt.r64["z2"]).min() >= bt.delta_z
+        zero, shallow = float((~bt.r64["active"]).mean()), float((bt.ro.depth[bt.idx] < 4).mean())
+        assert zero >= 0.10 and shallow > 0 and set(bt.ro.actions.reshape(-1)[bt.idx].tolist()) == {0, 1, 2}, (zero, shallow)
+        assert bt.ref_names == ("forward", "reverse", "seq32") and len(bt.errs) == 3
+        two = {k: max(e[k] for e in bt.errs[:2]) for k in PPO_KEYS}
+        assert all(bt.e_ref[k] == max(two[k], bt.errs[2][k]) and bt.budget[k] == max(P.FACTOR * bt.e_ref[k], 2 * P.ULP1) for k in PPO_KEYS)
+        assert all(bt.stat_e_ref[k] == max(e[k] for e in bt.stat_errs) and len(bt.stat_errs) == 3 for k in P.STAT_KEYS)
+        print("big N %d B %d: dz %.3g dr %.3g dropped %d / %d (%.1f %%), zero-gradient share %.3f, depth < 4 share %.3f" % (
+            n, b, bt.delta_z, bt.delta_r, bt.dropped, bt.candidates, 100.0 * bt.dropped / bt.candidates, zero, shallow))
+        print("big N %d B %d: e_ref %s" % (n, b, " ".join("%s %.2g" % kv for kv in bt.e_ref.items())))
+        print("big N %d B %d: seq32 error / two-reference e_ref %s" % (n, b, " ".join("%s %.2g" % (k, bt.errs[2][k] / two[k]) for k in PPO_KEYS)))
+        print("big N %d B %d: statistics e_ref %s (seq32 %s)" % (n, b, " ".join("%s %.2g" % kv for kv in bt.stat_e_ref.items()),
+                                                                " ".join("%s %.2g" % kv for kv in bt.stat_errs[2].items())))
+
+
+@pytest.mark.parametrize("fault", P.BIG_FAULTS)
+def test_every_fault_model_lies_two_budgets_away_on_the_big_batch(fault):
+    """the single-pass faults above, and the two between passes: a later pass that sees its workgroup's previous samples, a later pass
+    that overwrites the earlier one's sums -- each at least 2 x the three-reference budget away, and the big batch shows every one"""
+    w = P.chosen()[1]
+    for key, bt in P.big().items():
+        m = bt.fault_margin(fault, w)
+        print("big", fault, key, m)
+        assert m is not None and m >= 2, (fault, key, m)
+    if fault not in P.FAULTS:
+        assert all(bt.fault(fault, w) is None for bt in P.chosen()[2].values())  # (no batch of CASES reaches a second pass)
