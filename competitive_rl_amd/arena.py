@@ -16,7 +16,7 @@ each env holds a pair, the whole round-robin runs side by side, and the env's ne
   an object beside the league as ``crl_ledger`` is: ``ArenaBooks`` below is its thin binding (device tensors in, device tensors out;
   ``DeviceBooks`` of books.py with the pair as key), ``LeagueArena`` ties it to an env and the agent pool of league.py;
 * nothing synchronises with the host unless the caller asks for host values (``counters()``, ``payoff()``, ``weights()``,
-  ``state_dict()``, ``play()`` every ``check_every`` steps).
+  ``state_dict()``, ``play()`` every ``check_every`` steps) or hands over ids of its own (``set_pairs`` checks their range on the host).
 
 The rules are written down in include/crl.h ("arena books", "arena draws", "balance weights") and restated in numpy at the end of this
 module (``arena_draw_reference``, ``balance_weights_reference``).  There is no torch model and no CPU path here.
@@ -139,7 +139,8 @@ class LeagueArena(AgentPool):
         return t
 
     def set_pairs(self, left, right):
-        """``left`` / ``right``: an agent name or index for every env, or one index per env ((N,) array / tensor)."""
+        """``left`` / ``right``: an agent name or index for every env, or one index per env ((N,) array / tensor).  The ids are
+        range-checked on the host, which synchronises with the current stream: not for the hot loop (``draw_pairs`` is)."""
         both = torch.stack([self._ids(left, "left"), self._ids(right, "right")], 1).contiguous()
         if int(both.min()) < 0 or int(both.max()) >= len(self.agent_names):
             raise ValueError(f"agent ids must index agent_names (0..{len(self.agent_names) - 1})")

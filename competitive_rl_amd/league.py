@@ -17,7 +17,9 @@ int32 ``assignment`` per env on the device (index into ``agent_names``) and serv
   (include/crl.h "sampled actions", restated by ``league_sample_reference`` below); the same trained snapshot can sit in a pool
   twice, as the stochastic policy its trainer improves and as its greedy version;
 * ``set_opponents`` / ``reset_opponent(name)`` assign, ``reset_opponent()`` draws one opponent per env, ``resample_on_done=True``
-  re-draws the opponent of every env whose episode ended, inside the step -- all without a host synchronisation;
+  re-draws the opponent of every env whose episode ended, inside the step -- all without a host synchronisation, except
+  ``set_opponents`` with one id PER ENV: the wrapper checks the range of those ids on the host before it hands them to the kernels
+  (``crl_league_set_assignment`` itself does not wait);
 * every draw is Philox4x32-10 keyed by (seed, GLOBAL env id) with a per-env counter (include/crl.h "league draws"), so the result does
   not depend on how a batch is cut into shards.  RANDOM here is therefore ANOTHER stream than the reference's ``np.random.randint(3)``
   (``get_random_policy`` is untouched and still numpy's);
@@ -301,7 +303,9 @@ class LeagueEnvWrapper(AgentPool):
 
     # ---- assignment
     def set_opponents(self, ids):
-        """``ids``: an agent name or index for every env, or one index per env ((N,) array / tensor; a device tensor stays there)."""
+        """``ids``: an agent name or index for every env, or one index per env ((N,) array / tensor; a device tensor stays there).  A name
+        or a single index is one launch on the current stream, no synchronisation; per-env ids are range-checked on the host first,
+        which SYNCHRONISES with the current stream: not for the hot loop (``ledger.update(..., out=)`` / ``resample_on_done`` redraw there)."""
         if isinstance(ids, str):
             assert ids in self.agent_names, self.agent_names
             ids = self.agent_names.index(ids)
