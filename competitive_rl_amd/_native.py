@@ -203,6 +203,17 @@ SIGNATURES = {
     "crl_ppo_get_weights_full": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "crl_policy_load_full_dev": (i32, [vp, vp, vp]),
     "crl_pool_load_full_dev": (i32, [vp, i32, vp, vp]),
+    "crl_policy_get_blob": (i32, [vp, vp, i64, P(i32), vp]),
+    "crl_policy_get_sampling": (i32, [vp, P(f32), P(f32), P(u64), P(i64), P(u32)]),
+    "crl_policy_resume_sampling": (i32, [vp, f32, f32, u64, i64, u32]),
+    "crl_pool_get_blob": (i32, [vp, i32, vp, i64, vp]),
+    "crl_pool_get_counters": (i32, [vp, P(u64), P(i64), P(u32), vp, vp]),
+    "crl_pool_set_counters": (i32, [vp, u32, vp, vp]),
+    "crl_rollout_get_info": (i32, [vp, P(i32)]),
+    "crl_rollout_get_state": (i32, [vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_rollout_set_state": (i32, [vp, P(i32), i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_ppo_get_state": (i32, [vp, vp, vp, vp, i64, P(i64), P(i64), vp]),
+    "crl_ppo_set_state": (i32, [vp, vp, vp, vp, i64, i64, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

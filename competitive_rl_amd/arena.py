@@ -254,13 +254,17 @@ class LeagueArena(AgentPool):
 
     def state_dict(self):
         """The arena's own state as host arrays (synchronises): the books, the pairs, both seats' frame rings and the observation
-        buffer the next step acts on, and the pool's play styles (``sampling``: [temperature, epsilon] rows in pool order).  The env's
-        state is the env's (``env.state_dict()``).  RANDOM's action counter is the league's -- it is the counter of the sampled and
-        explored actions too -- and starts over with ``load_state_dict``: a pool with RANDOM, or with an agent that samples or explores,
-        continues with other such actions than the original run."""
+        buffer the next step acts on, the pool's play styles (``sampling``: [temperature, epsilon] rows in pool order) and ``pool``, the
+        pool's part (``pool_state_dict(stack=False)``: the seed, the act-call counter -- RANDOM's, and the counter of the sampled and
+        explored actions too --, the draw counters and the CNN slots' weights as the device holds them).  The env's state is the
+        env's (``env.state_dict()``).  With ``pool``, ``load_state_dict`` continues RANDOM's, the sampled and the explored actions
+        where the original run's would; a dict WITHOUT it (one saved before the key existed) loads as it always did: that counter
+        starts over, and a pool with RANDOM, or with an agent that samples or explores, continues with other such actions than
+        the original run."""
         return {"agent_names": list(self.agent_names), "books": self.books.state_dict(), "pairs": self._pairs.cpu().numpy(),
                 "stack": self.get_stack().cpu().numpy(), "obs": None if self._buf is None else self._buf.cpu().numpy(), "redraw_on_done": self.redraw_on_done,
-                "sampling": np.array([self.sampling()[n] for n in self.agent_names], np.float32).reshape(-1, 2)}
+                "sampling": np.array([self.sampling()[n] for n in self.agent_names], np.float32).reshape(-1, 2),
+                "pool": self.pool_state_dict(stack=False)}
 
     def load_state_dict(self, sd):
         if list(sd["agent_names"]) != self.agent_names:
@@ -281,8 +285,14 @@ class LeagueArena(AgentPool):
                 raise ValueError(f"load_state_dict: sampling must hold a (temperature, epsilon) row per agent, got shape {styles.shape}")
             for t, e in styles:
                 check_sampling(t, e)
+        pool = sd.get("pool")  # (a state dict from before the pool's part: the act-call counter starts over, the slots keep their weights)
+        if pool is not None:
+            self.check_pool_state_dict(pool)
         self._seed = int(books["seed"])
-        self._seed_pool(self._seed)
+        if pool is not None:
+            self.load_pool_state_dict(pool, styles=False)  # (the styles are the `sampling` key's, below, as before)
+        else:
+            self._seed_pool(self._seed)
         if styles is not None:
             for a, (t, e) in enumerate(styles):
                 self.set_sampling(a, float(t), float(e))

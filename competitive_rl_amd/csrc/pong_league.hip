@@ -314,6 +314,41 @@ int crl_pool_load_full_dev(crl_league *l, int32_t agent, const float *blob_dev, 
     return CRL_OK;
 }
 
+int crl_pool_get_blob(crl_league *l, int32_t agent, float *blob_out_host, int64_t blob_floats, void *stream) {
+    crl_fail_no_ctx();
+    if (!l || !blob_out_host) return crl_fail(CRL_EINVAL, "crl_pool_get_blob: null argument");
+    if (agent < 0 || agent >= l->agents) return crl_fail(CRL_EINVAL, "crl_pool_get_blob: agent %d is not in the pool of %d", agent, l->agents);
+    if (l->kind[agent] != CRL_LEAGUE_LIGHT && l->kind[agent] != CRL_POOL_KIND_FULL)
+        return crl_fail(CRL_EINVAL, "crl_pool_get_blob: agent %d is a built-in agent without weights", agent);
+    const int64_t floats = l->kind[agent] == CRL_LEAGUE_LIGHT ? (int64_t)kLightRawFloats : policy_full_blob_floats();
+    if (blob_floats != floats)
+        return crl_fail(CRL_EINVAL, "crl_pool_get_blob: blob_floats %lld, but the slot's blob holds %lld", (long long)blob_floats, (long long)floats);
+    HIP_TRY(hipSetDevice(l->device));
+    HIP_TRY(hipMemcpyAsync(blob_out_host, l->raw[agent], (size_t)floats * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return CRL_OK;
+}
+
+int crl_pool_get_counters(crl_league *l, uint64_t *seed, int64_t *env_id_base, uint32_t *act_calls, uint32_t *draw_ctr_out_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l) return crl_fail(CRL_EINVAL, "crl_pool_get_counters: null pool");
+    if (draw_ctr_out_dev)
+        HIP_TRY(hipMemcpyAsync(draw_ctr_out_dev, l->draw_ctr, (size_t)l->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (seed) *seed = l->seed;
+    if (env_id_base) *env_id_base = l->env_id_base;
+    if (act_calls) *act_calls = l->step;
+    return CRL_OK;
+}
+
+int crl_pool_set_counters(crl_league *l, uint32_t act_calls, const uint32_t *draw_ctr_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!l) return crl_fail(CRL_EINVAL, "crl_pool_set_counters: null pool");
+    if (draw_ctr_dev)
+        HIP_TRY(hipMemcpyAsync(l->draw_ctr, draw_ctr_dev, (size_t)l->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    l->step = act_calls;
+    return CRL_OK;
+}
+
 int crl_sampling_set_agent(crl_league *l, int32_t agent, float temperature, float epsilon) {
     crl_fail_no_ctx();
     SampleArgs S{};

@@ -585,6 +585,7 @@ struct crl_policy {
     PolicyFull *full = nullptr;  // crl_policy_create_full: ActorCritic instead of LightActorCritic (pong_policy_full.hip)
     bool sampling = false;       // crl_policy_set_sampling with a temperature or an epsilon that is not 0: the SAMPLE kernels
     SampleArgs S{};              // S.n: crl_policy_act / _act_rollout calls since create / crl_policy_set_sampling
+    float temperature = 0.f, epsilon = 0.f;  // ... as crl_policy_set_sampling took them (crl_policy_get_sampling)
     bool critic = false;         // crl_policy_set_critic / _load_weights gave a critic head (the blob's tail, zero until then)
     WeightStage stage{};         // crl_policy_load_weights: the pinned host copy of the blob
 #ifdef CRL_ABLATION
@@ -781,14 +782,49 @@ int crl_policy_load_full_dev(crl_policy *p, const float *blob_dev, void *stream)
     return CRL_OK;
 }
 
-int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base) {
+// crl_policy_set_sampling (`who`, calls 0) and crl_policy_resume_sampling
+static int policy_set_sampling(const char *who, crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base, uint32_t calls) {
     crl_fail_no_ctx();
     SampleArgs S{};
-    if (int rc = sample_args_from(temperature, epsilon, "crl_policy_set_sampling", &S)) return rc;
-    if (!p || env_id_base < 0) return crl_fail(CRL_EINVAL, "crl_policy_set_sampling: null policy or a negative env_id_base");
-    S.seed = seed, S.id_base = env_id_base, S.n = 0;
+    if (int rc = sample_args_from(temperature, epsilon, who, &S)) return rc;
+    if (!p || env_id_base < 0) return crl_fail(CRL_EINVAL, "%s: null policy or a negative env_id_base", who);
+    S.seed = seed, S.id_base = env_id_base, S.n = calls;
     p->S = S;
+    p->temperature = temperature, p->epsilon = epsilon;
     p->sampling = sample_active(S);
+    return CRL_OK;
+}
+
+int crl_policy_set_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base) {
+    return policy_set_sampling("crl_policy_set_sampling", p, temperature, epsilon, seed, env_id_base, 0u);
+}
+
+int crl_policy_resume_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base, uint32_t calls) {
+    return policy_set_sampling("crl_policy_resume_sampling", p, temperature, epsilon, seed, env_id_base, calls);
+}
+
+int crl_policy_get_sampling(crl_policy *p, float *temperature, float *epsilon, uint64_t *seed, int64_t *env_id_base, uint32_t *calls) {
+    crl_fail_no_ctx();
+    if (!p) return crl_fail(CRL_EINVAL, "crl_policy_get_sampling: null policy");
+    if (temperature) *temperature = p->temperature;
+    if (epsilon) *epsilon = p->epsilon;
+    if (seed) *seed = p->S.seed;
+    if (env_id_base) *env_id_base = p->S.id_base;
+    if (calls) *calls = p->S.n;
+    return CRL_OK;
+}
+
+int crl_policy_get_blob(crl_policy *p, float *blob_out_host, int64_t blob_floats, int32_t *has_critic_out, void *stream) {
+    crl_fail_no_ctx();
+    if (!p || !blob_out_host) return crl_fail(CRL_EINVAL, "crl_policy_get_blob: null argument");
+    const int64_t floats = p->full ? policy_full_blob_floats() + policy_full_critic_floats() : (int64_t)(kLightRawFloats + kLightCriticFloats);
+    if (blob_floats != floats)
+        return crl_fail(CRL_EINVAL, "crl_policy_get_blob: blob_floats %lld, but this policy's blob holds %lld", (long long)blob_floats, (long long)floats);
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemcpyAsync(blob_out_host, p->full ? policy_full_blob(p->full) : p->raw, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost,
+                           (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (has_critic_out) *has_critic_out = p->critic ? 1 : 0;
     return CRL_OK;
 }
 

@@ -52,6 +52,7 @@ __device__ inline void ppo_sample_terms(const double (&l)[3], const double v, co
 
 // the full-size learner behind the common entry points of pong_ppo.hip (p->full is set)
 void ppo_full_destroy(PpoFull *f);
+int64_t ppo_full_scratch_rows(const PpoFull *f);  // samples per chunk of a minibatch: part of the summation shape (crl_ppo_get_state)
 int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, hipStream_t st);
 
 }  // namespace crl

@@ -566,4 +566,39 @@ int crl_ppo_stats(crl_ppo *p, double *out7_host) {
     return CRL_OK;
 }
 
+int crl_ppo_get_state(crl_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t blob_floats, int64_t *steps_out,
+                      int64_t *scratch_rows_out, void *stream) {
+    crl_fail_no_ctx();
+    if (!p) return crl_fail(CRL_EINVAL, "crl_ppo_get_state: null learner");
+    if ((blob_out_host || m_out_host || v_out_host) && blob_floats != p->blob_floats)
+        return crl_fail(CRL_EINVAL, "crl_ppo_get_state: blob_floats %lld, but this learner's blob holds %d", (long long)blob_floats, p->blob_floats);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
+    HIP_TRY(hipSetDevice(p->device));
+    if (blob_out_host) HIP_TRY(hipMemcpyAsync(blob_out_host, p->raw, bytes, hipMemcpyDeviceToHost, st));
+    if (m_out_host) HIP_TRY(hipMemcpyAsync(m_out_host, p->m, bytes, hipMemcpyDeviceToHost, st));
+    if (v_out_host) HIP_TRY(hipMemcpyAsync(v_out_host, p->v, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (steps_out) *steps_out = p->steps;
+    if (scratch_rows_out) *scratch_rows_out = p->full ? ppo_full_scratch_rows(p->full) : 0;
+    return CRL_OK;
+}
+
+int crl_ppo_set_state(crl_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t blob_floats, int64_t steps, void *stream) {
+    crl_fail_no_ctx();
+    if (!p || !blob_host || !m_host || !v_host) return crl_fail(CRL_EINVAL, "crl_ppo_set_state: null argument (weights and both moments are set together)");
+    if (blob_floats != p->blob_floats)
+        return crl_fail(CRL_EINVAL, "crl_ppo_set_state: blob_floats %lld, but this learner's blob holds %d", (long long)blob_floats, p->blob_floats);
+    if (steps < 0) return crl_fail(CRL_EINVAL, "crl_ppo_set_state: steps must be >= 0, not %lld", (long long)steps);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemcpyAsync(p->raw, blob_host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->m, m_host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->v, v_host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    p->steps = steps, p->have_grad = false;
+    return CRL_OK;
+}
+
 }  // extern "C"

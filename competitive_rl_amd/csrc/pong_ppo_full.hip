@@ -635,6 +635,8 @@ void ppo_full_destroy(PpoFull *f) {
     delete f;
 }
 
+int64_t ppo_full_scratch_rows(const PpoFull *f) { return f->scratch_rows; }
+
 int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, hipStream_t st) {
     PpoFull *f = p->full;
     const int64_t S = f->scratch_rows;

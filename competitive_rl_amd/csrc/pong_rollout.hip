@@ -404,4 +404,86 @@ int crl_rollout_stats(crl_rollout *r, double *out2_host) {
     return CRL_OK;
 }
 
+int crl_rollout_get_info(crl_rollout *r, int32_t *out4_host) {
+    crl_fail_no_ctx();
+    if (!r || !out4_host) return crl_fail(CRL_EINVAL, "crl_rollout_get_info: null argument");
+    out4_host[0] = r->state, out4_host[1] = r->recorded, out4_host[2] = r->outcomes, out4_host[3] = r->normalize ? 1 : 0;
+    if (r->state == kFinished) out4_host[1] = out4_host[2] = r->steps;
+    if (r->state == kFresh) out4_host[1] = out4_host[2] = 0;
+    return CRL_OK;
+}
+
+// crl_rollout_get_state (to_storage = false) and crl_rollout_set_state: the same arrays, the copies turned round.  The planes lose /
+// regain their 12 bytes of padding in a pitched copy (the padding stays zero: no set ever writes it).
+struct RolloutArrays {
+    uint8_t *planes, *front_depth, *reset, *depth;
+    int32_t *actions;
+    float *logp, *values, *rewards;
+    uint8_t *done;
+    float *returns, *adv;
+    double *stats;
+};
+
+static int rollout_copy_state(const char *who, crl_rollout *r, bool to_storage, int64_t row0, int64_t rows, int64_t steps, const RolloutArrays &x,
+                              hipStream_t st) {
+    const int64_t n = r->n, T = r->steps;
+    if (row0 < 0 || rows < 0 || row0 + rows > T + kHist) return crl_fail(CRL_EINVAL, "%s: plane rows [%lld, %lld) outside [0, %lld]", who, (long long)row0, (long long)(row0 + rows), (long long)(T + kHist));
+    if (steps < 0 || steps > T) return crl_fail(CRL_EINVAL, "%s: steps %lld outside [0, %lld]", who, (long long)steps, (long long)T);
+    auto copy = [&](void *ext, void *own, size_t bytes) -> hipError_t {
+        if (!ext || !bytes) return hipSuccess;
+        return hipMemcpyAsync(to_storage ? own : ext, to_storage ? ext : own, bytes, hipMemcpyDeviceToDevice, st);
+    };
+    if (x.planes && rows) {
+        uint8_t *own = r->planes + row0 * n * kPlanePad;
+        const size_t plane = (size_t)kDim * kDim;
+        if (to_storage) HIP_TRY(hipMemcpy2DAsync(own, kPlanePad, x.planes, plane, plane, (size_t)(rows * n), hipMemcpyDeviceToDevice, st));
+        else HIP_TRY(hipMemcpy2DAsync(x.planes, plane, own, kPlanePad, plane, (size_t)(rows * n), hipMemcpyDeviceToDevice, st));
+    }
+    const size_t sn = (size_t)(steps * n), tn = (size_t)(T * n);
+    HIP_TRY(copy(x.front_depth, r->depth_carry, (size_t)n));
+    HIP_TRY(copy(x.reset, r->reset, sn));
+    HIP_TRY(copy(x.depth, r->depth, sn));
+    HIP_TRY(copy(x.actions, r->actions, sn * 4));
+    HIP_TRY(copy(x.logp, r->logp, sn * 4));
+    HIP_TRY(copy(x.values, r->values, sn * 4));
+    HIP_TRY(copy(x.rewards, r->rewards, sn * 4));
+    HIP_TRY(copy(x.done, r->done, sn));
+    HIP_TRY(copy(x.returns, r->ret, tn * 4));
+    HIP_TRY(copy(x.adv, r->adv, tn * 4));
+    HIP_TRY(copy(x.stats, r->stats, 2 * sizeof(double)));
+    return CRL_OK;
+}
+
+int crl_rollout_get_state(crl_rollout *r, int64_t row0, int64_t rows, uint8_t *planes_out_dev, uint8_t *front_depth_out_dev, int64_t steps,
+                          uint8_t *reset_out_dev, uint8_t *depth_out_dev, int32_t *actions_out_dev, float *logp_out_dev, float *values_out_dev,
+                          float *rewards_out_dev, uint8_t *done_out_dev, float *returns_out_dev, float *adv_out_dev, double *stats_out_dev,
+                          void *stream) {
+    crl_fail_no_ctx();
+    if (!r) return crl_fail(CRL_EINVAL, "crl_rollout_get_state: null storage");
+    const RolloutArrays x{planes_out_dev, front_depth_out_dev, reset_out_dev, depth_out_dev, actions_out_dev, logp_out_dev, values_out_dev,
+                          rewards_out_dev, done_out_dev, returns_out_dev, adv_out_dev, stats_out_dev};
+    return rollout_copy_state("crl_rollout_get_state", r, false, row0, rows, steps, x, (hipStream_t)stream);
+}
+
+int crl_rollout_set_state(crl_rollout *r, const int32_t *info4_host, int64_t row0, int64_t rows, const uint8_t *planes_dev,
+                          const uint8_t *front_depth_dev, int64_t steps, const uint8_t *reset_dev, const uint8_t *depth_dev,
+                          const int32_t *actions_dev, const float *logp_dev, const float *values_dev, const float *rewards_dev,
+                          const uint8_t *done_dev, const float *returns_dev, const float *adv_dev, const double *stats_dev, void *stream) {
+    crl_fail_no_ctx();
+    if (!r || !info4_host) return crl_fail(CRL_EINVAL, "crl_rollout_set_state: null argument");
+    const int state = info4_host[0], recorded = info4_host[1], outcomes = info4_host[2];
+    const bool ok = state >= kFresh && state <= kFinished && outcomes >= 0 && outcomes <= recorded && recorded <= r->steps &&
+                    (state != kFresh || recorded == 0) && (state != kFinished || outcomes == r->steps);
+    if (!ok)
+        return crl_fail(CRL_EINVAL, "crl_rollout_set_state: state %d with %d steps recorded and %d outcomes does not fit a storage of %d steps", state, recorded,
+                        outcomes, r->steps);
+    const RolloutArrays x{const_cast<uint8_t *>(planes_dev), const_cast<uint8_t *>(front_depth_dev), const_cast<uint8_t *>(reset_dev),
+                          const_cast<uint8_t *>(depth_dev), const_cast<int32_t *>(actions_dev), const_cast<float *>(logp_dev),
+                          const_cast<float *>(values_dev), const_cast<float *>(rewards_dev), const_cast<uint8_t *>(done_dev),
+                          const_cast<float *>(returns_dev), const_cast<float *>(adv_dev), const_cast<double *>(stats_dev)};
+    if (int rc = rollout_copy_state("crl_rollout_set_state", r, true, row0, rows, steps, x, (hipStream_t)stream)) return rc;
+    r->state = state, r->recorded = recorded, r->outcomes = outcomes, r->normalize = info4_host[3] != 0;
+    return CRL_OK;
+}
+
 }  // extern "C"

@@ -28,7 +28,11 @@ int32 ``assignment`` per env on the device (index into ``agent_names``) and serv
   frames it really showed.  With an assignment that never changes this is ``TournamentEnvWrapper`` with that opponent, bit for bit;
 * ``ledger=True`` (or a ``LeagueLedger``) books every finished episode to the opponent that played it, on the device, behind the step;
   with ``resample_on_done`` the next opponent is then the LEDGER's weighted draw (``LeagueLedger.set_weights`` / ``pfsp_weights``)
-  instead of the uniform one.  Without a ledger the wrapper runs the launches it always ran.
+  instead of the uniform one.  Without a ledger the wrapper runs the launches it always ran;
+* ``state_dict()`` / ``load_state_dict()`` (and ``pool_state_dict()`` / ``load_pool_state_dict()`` of the pool alone) hold what a
+  continuation needs and the device alone knows -- the act-call and opponent draw counters, the CNN slots' weights as served, the rings,
+  the assignment, the books -- so that a league rebuilt in a new process goes on with the draws and actions of the original
+  (include/crl.h "checkpoint / resume").
 
 The forward pass, the draws and the partition of the envs by agent are HIP behind ``crl_league_*`` / ``crl_pool_add_full``
 (csrc/pong_league.hip, csrc/pong_policy.hip, csrc/pong_policy_full.hip); there is no torch model and no CPU path in this module.
@@ -39,6 +43,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import checkpoint as K
 from .ledger import LeagueLedger
 from .policy_serving import (_FULL_KEYS, _FULL_SHAPES, _KEYS, _SHAPES, BUILTIN_CHECKPOINTS, Policy, check_full_weights, load_full_weights,
                              load_light_weights)
@@ -231,6 +236,84 @@ class AgentPool:
         assert tuple(s.shape) == (self._rows, 4, 42, 42)
         N.check(self._L.crl_league_set_stack(self._h, C.c_void_p(s.data_ptr()), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()
+
+    # ---- checkpoint / resume: the pool's part (include/crl.h "checkpoint / resume")
+    def pool_counters(self, draw_counters=True):
+        """(seed, env_id_base, act calls, draw counters): the key of the pool's draws, the global id of row 0, the act-call counter --
+        the ``n`` of RANDOM's and of every sampled or explored action -- as host ints, and the per-row opponent draw counters as an
+        int32 device tensor holding the uint32 bits (a copy enqueued on the current stream, no synchronisation; None without
+        ``draw_counters``: then there is no GPU work at all)."""
+        seed, base, calls = C.c_uint64(), C.c_int64(), C.c_uint32()
+        ctr = torch.empty((self._rows,), dtype=torch.int32, device=self.device) if draw_counters else None
+        N.check(self._L.crl_pool_get_counters(self._h, C.byref(seed), C.byref(base), C.byref(calls), C.c_void_p(ctr.data_ptr()) if draw_counters else None,
+                                              self._stream()))
+        return seed.value, base.value, calls.value, ctr
+
+    def slot_weights(self, agent):
+        """The weights the device serves for CNN agent ``agent`` (a name or an index) right now, read back behind everything enqueued on
+        the current stream (a learner's ``push``, ``update_agent``): float32 arrays in torch layout under the keys ``update_agent``
+        takes.  SYNCHRONISES with the current stream.  A built-in agent has none."""
+        a = self._agent_index(agent)
+        if self._kinds[a] not in (N.CRL_LEAGUE_LIGHT, N.CRL_POOL_KIND_FULL):
+            raise ValueError(f"{self.agent_names[a]} is a built-in agent without weights")
+        layout, floats = K.layout_of(self._kinds[a] == N.CRL_LEAGUE_LIGHT, critic=False)
+        blob = np.empty(floats, np.float32)
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_pool_get_blob(self._h, a, blob.ctypes.data_as(C.c_void_p), floats, self._stream()))
+        return K.split_blob(blob, layout)
+
+    def pool_state_dict(self, stack=True):
+        """The pool's state as host arrays (SYNCHRONISES with the current stream): ``agent_names`` and ``kinds``, ``rows``, the ``seed``,
+        ``env_id_base``, the act-call counter ``act_calls``, the per-row opponent draw counters ``draw_ctr``, the play styles
+        (``sampling``: [temperature, epsilon] rows in pool order), per LIGHT / FULL slot the ``weights`` as the device holds them
+        (``slot_weights``) and, with ``stack``, the shared rings as ``get_stack()`` shows them."""
+        seed, base, calls, ctr = self.pool_counters()
+        styles = self.sampling()
+        sd = {"kind": "AgentPool", "rows": self._rows, "agent_names": list(self.agent_names), "kinds": [int(k) for k in self._kinds], "seed": seed,
+              "env_id_base": base, "act_calls": calls, "draw_ctr": ctr.cpu().numpy().view(np.uint32),
+              "sampling": np.array([styles[n] for n in self.agent_names], np.float32).reshape(-1, 2),
+              "weights": {n: self.slot_weights(a) for a, n in enumerate(self.agent_names) if self._kinds[a] in (N.CRL_LEAGUE_LIGHT, N.CRL_POOL_KIND_FULL)}}
+        if stack:
+            sd["stack"] = self.get_stack().cpu().numpy()
+        return sd
+
+    def check_pool_state_dict(self, sd):
+        """What ``load_pool_state_dict`` refuses, raised before anything is written: another list of names or kinds, other ``rows`` or
+        another ``env_id_base``, counters out of range, a style ``check_sampling`` refuses, a slot's tensor or the rings in a wrong
+        shape.  Returns what the load writes."""
+        K.check_header(sd, "AgentPool", "the pool", rows=self._rows, agent_names=list(self.agent_names), kinds=[int(k) for k in self._kinds],
+                       env_id_base=self.pool_counters(draw_counters=False)[1])
+        seed, calls = K.check_counter(sd.get("seed"), 64, "seed", "the pool"), K.check_counter(sd.get("act_calls"), 32, "act_calls", "the pool")
+        ctr = K.check_array(sd, "draw_ctr", (self._rows,), 4, "the pool")
+        styles = K.check_array(sd, "sampling", (len(self.agent_names), 2), 4, "the pool").view(np.float32)
+        styles = [K.check_style(t, e, f"the pool, {n}") for n, (t, e) in zip(self.agent_names, styles)]
+        weights = {}
+        for a, n in enumerate(self.agent_names):
+            if self._kinds[a] in (N.CRL_LEAGUE_LIGHT, N.CRL_POOL_KIND_FULL):
+                layout, floats = K.layout_of(self._kinds[a] == N.CRL_LEAGUE_LIGHT, critic=False)
+                w = sd.get("weights", {}).get(n) if isinstance(sd.get("weights"), dict) else None
+                K.join_blob(w, layout, floats, f"the pool, slot {n}")
+                weights[n] = {k: w[k] for k in layout}
+        stack = K.check_array(sd, "stack", (self._rows, 4, 42, 42), 1, "the pool") if sd.get("stack") is not None else None
+        return seed, calls, ctr, styles, weights, stack
+
+    def load_pool_state_dict(self, sd, styles=True):
+        """Puts a ``pool_state_dict()`` back: seed and counters, play styles (unless ``styles`` is false: the arena's own ``sampling``
+        key says them), every CNN slot's weights and (if the dict has them) the rings, so that RANDOM, the sampled and explored actions
+        and the opponent draws continue where the original's would.  Everything is looked at before anything is written
+        (``check_pool_state_dict``): a refused load raises a ``ValueError`` and leaves the pool as it was.  Ordered on the current
+        stream and SYNCHRONISES with it."""
+        seed, calls, ctr, loaded_styles, weights, stack = self.check_pool_state_dict(sd)
+        self._seed_pool(seed)  # (zeroes both counters; they are written below)
+        ctr_dev = torch.from_numpy(ctr.view(np.int32).copy()).to(self.device)
+        N.check(self._L.crl_pool_set_counters(self._h, calls, C.c_void_p(ctr_dev.data_ptr()), self._stream()))
+        for a, (t, e) in enumerate(loaded_styles if styles else ()):
+            self.set_sampling(a, t, e)
+        for n, w in weights.items():
+            self.update_agent(n, w)
+        if stack is not None:
+            self.set_stack(stack.view(np.uint8))
+        torch.cuda.current_stream(self.device).synchronize()  # the staging tensors above are this call's own
 
     # ---- lifetime: the handle's part
     def _seed_pool(self, seed):
@@ -440,6 +523,52 @@ class LeagueEnvWrapper(AgentPool):
         self._seed_pool(s)
         if self.ledger is not None:
             self.ledger.seed(s)
+
+    # ---- checkpoint / resume
+    def state_dict(self):
+        """The league's own state as host arrays (SYNCHRONISES with the current stream): the pool (``pool_state_dict()``: names, kinds,
+        seed, the act-call and opponent draw counters, play styles, the CNN slots' weights as the device holds them, the rings), the
+        ``assignment``, ``resample_on_done``, ``prev_opponent_obs`` -- a host copy of what the opponents act on next: the env's buffers
+        are redrawn only by its next step -- and the ledger's ``state_dict()`` when the league has one.  The wrapped env's state is the
+        env's own (``env.state_dict()``)."""
+        prev = self.prev_opponent_obs
+        if prev is not None:
+            prev = prev.cpu().numpy() if isinstance(prev, torch.Tensor) else np.array(prev)
+        return {"kind": "LeagueEnvWrapper", "num_envs": self.num_envs, "pool": self.pool_state_dict(), "assignment": self.assignment.cpu().numpy(),
+                "resample_on_done": self.resample_on_done, "prev_opponent_obs": prev,
+                "ledger": None if self.ledger is None else self.ledger.state_dict()}
+
+    def load_state_dict(self, sd):
+        """Puts a ``state_dict()`` back into a league built over the same pool (names and kinds in the same order; seeds and weights
+        may differ: they are loaded).  Everything is looked at before anything is written: another pool, another ``num_envs``, ids
+        outside the pool, an observation or a ring of another shape, books that do not fit raise a ``ValueError`` and leave the league
+        and its ledger as they were.  Ordered on the current stream and SYNCHRONISES with it.  ``prev_opponent_obs`` becomes a device
+        tensor of the league's own.  The wrapped env is loaded by the caller (``env.load_state_dict``)."""
+        K.check_header(sd, "LeagueEnvWrapper", "the league", num_envs=self.num_envs)
+        if not isinstance(sd.get("pool"), dict):
+            raise K.refuse("the league: the pool's part is missing")
+        self.check_pool_state_dict(sd["pool"])
+        ids = K.check_array(sd, "assignment", (self.num_envs,), 4, "the league").view(np.int32)
+        if ids.min() < 0 or ids.max() >= len(self.agent_names):
+            raise K.refuse(f"the league: the assignment must index agent_names (0..{len(self.agent_names) - 1})")
+        prev = sd.get("prev_opponent_obs")
+        if prev is not None:
+            prev = np.ascontiguousarray(prev)
+            if prev.ndim not in (3, 4) or prev.shape[0] != self.num_envs or prev.shape[-2:] != (42, 42):
+                raise K.refuse(f"the league: prev_opponent_obs of shape {prev.shape}; the opponents act on ({self.num_envs}, K, 42, 42) frames")
+        if (sd.get("ledger") is None) != (self.ledger is None):
+            raise K.refuse("the league: %s" % ("the state dict has books, this league has no ledger" if self.ledger is None
+                                               else "this league has a ledger, the state dict has no books"))
+        if self.ledger is not None:
+            self.ledger.check_state_dict(sd["ledger"])
+        self.load_pool_state_dict(sd["pool"])
+        t = torch.from_numpy(ids.copy()).to(self.device)
+        N.check(self._L.crl_league_set_assignment(self._h, C.c_void_p(t.data_ptr()), 0, self._stream()))
+        self.resample_on_done = bool(sd["resample_on_done"])
+        self.prev_opponent_obs = None if prev is None else torch.from_numpy(prev).to(self.device)
+        if self.ledger is not None:
+            self.ledger.load_state_dict(sd["ledger"])
+        torch.cuda.current_stream(self.device).synchronize()  # the staging tensors above are this call's own
 
     def close(self):
         if self._close_pool():

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import checkpoint as K
 from .rules import check_sampling, rollout_logp_reference  # noqa: F401  (re-exported)
 
 ASSETS = os.path.join(N.PKG, "assets")
@@ -262,6 +263,59 @@ class Policy:
         ``set_sampling(0, 0)`` is greedy again; ``compute_action`` keeps its own (host-side) sampling."""
         t, e = check_sampling(temperature, epsilon)
         N.check(self._L.crl_policy_set_sampling(self._h, t, e, int(seed) & (2 ** 64 - 1), int(env_id_base)))
+
+    # ---- checkpoint / resume (include/crl.h "checkpoint / resume")
+    def sampling(self):
+        """Host dict of the play style as ``set_sampling`` took it -- ``temperature``, ``epsilon``, ``seed``, ``env_id_base`` -- and
+        ``calls``, the act calls since construction or the last ``set_sampling`` (the counter of the draws).  No GPU work."""
+        t, e, seed, base, calls = C.c_float(), C.c_float(), C.c_uint64(), C.c_int64(), C.c_uint32()
+        N.check(self._L.crl_policy_get_sampling(self._h, C.byref(t), C.byref(e), C.byref(seed), C.byref(base), C.byref(calls)))
+        return {"temperature": t.value, "epsilon": e.value, "seed": seed.value, "env_id_base": base.value, "calls": calls.value}
+
+    def device_weights(self):
+        """The weights THE DEVICE serves right now, read back behind everything enqueued on the current stream (a learner's ``push``,
+        a ``load_weights``): a dict of float32 arrays in torch layout under the keys ``load_weights`` takes, ``critic_w`` / ``critic_b``
+        among them if the policy has a critic.  ``Policy.weights`` is the host's copy and goes stale with a ``push``; this does not.
+        SYNCHRONISES with the current stream."""
+        layout, floats = K.layout_of(self.use_light_model)
+        blob, has = np.empty(floats, np.float32), C.c_int32()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_policy_get_blob(self._h, blob.ctypes.data_as(C.c_void_p), floats, C.byref(has), self._stream()))
+        w = K.split_blob(blob, layout)
+        if not has.value:
+            for k in _CRITIC_KEYS:
+                del w[k]
+        return w
+
+    def state_dict(self):
+        """Everything a continuation needs, as host arrays (SYNCHRONISES with the current stream): ``kind``, ``network`` (light /
+        full), ``num_envs``, ``weights`` as the device holds them now (``device_weights()``, not ``self.weights``), the frame ring as
+        ``get_stack()`` shows it and ``sampling()``: the play style WITH its call counter."""
+        return {"kind": "Policy", "network": K.NETWORKS[self.use_light_model], "num_envs": self.num_envs, "weights": self.device_weights(),
+                "stack": self.get_stack().cpu().numpy(), "sampling": self.sampling()}
+
+    def load_state_dict(self, sd):
+        """Puts a ``state_dict()`` back: the weights (with the critic if the dict has one; without, the current critic stays), the
+        ring, the play style and its call counter -- the next act call draws what the original's next call drew.  ``self.weights`` /
+        ``self.critic`` become what was loaded.  Everything is looked at before anything is written: the other network, another
+        ``num_envs``, a misshapen tensor or ring and a style that ``check_sampling`` refuses raise a ``ValueError`` and leave the
+        policy as it was.  Ordered on the current stream and SYNCHRONISES with it."""
+        K.check_header(sd, "Policy", "Policy", network=K.NETWORKS[self.use_light_model], num_envs=self.num_envs)
+        w = sd.get("weights")
+        has_critic = isinstance(w, dict) and all(k in w for k in _CRITIC_KEYS)
+        layout, floats = K.layout_of(self.use_light_model, has_critic)
+        K.join_blob(w, layout, floats, "Policy weights")  # (the shapes; load_weights packs them again)
+        stack = K.check_array(sd, "stack", (self.num_envs, 4, 42, 42), 1, "Policy")
+        s = sd.get("sampling")
+        if not isinstance(s, dict) or set(s) != {"temperature", "epsilon", "seed", "env_id_base", "calls"}:
+            raise K.refuse("Policy: sampling must hold temperature, epsilon, seed, env_id_base and calls")
+        t, e = K.check_style(s["temperature"], s["epsilon"], "Policy")
+        seed, base = K.check_counter(s["seed"], 64, "seed", "Policy"), K.check_counter(s["env_id_base"], 63, "env_id_base", "Policy")
+        calls = K.check_counter(s["calls"], 32, "calls", "Policy")
+        self.load_weights({k: w[k] for k in layout})
+        self.set_stack(stack.view(np.uint8))  # (synchronises: the staging tensor is this call's own)
+        N.check(self._L.crl_policy_resume_sampling(self._h, t, e, seed, base, calls))
+        torch.cuda.current_stream(self.device).synchronize()
 
     def get_stack(self):
         out = torch.empty((self.num_envs, 4, 42, 42), dtype=torch.uint8, device=self.device)

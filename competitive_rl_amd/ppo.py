@@ -25,20 +25,11 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import checkpoint as K
+from .checkpoint import BLOB_FLOATS, BLOB_LAYOUT, FULL_BLOB_FLOATS, FULL_BLOB_LAYOUT  # noqa: F401  (the blobs' layouts; re-exported)
 from .policy_serving import _CRITIC_KEYS, _FULL_KEYS, _KEYS, _SHAPES, Policy, check_full_weights, critic_of, load_full_weights, load_light_weights
 from .rules import PPO_DEFAULTS, PPO_FULL_KEYS, PPO_KEYS, adam_reference, ppo_full_loss_reference, ppo_loss_reference  # noqa: F401  (re-exported)
 
-# the policy blob of csrc/pong_league.h with its critic tail: offset and shape of each tensor, 8 488 floats with the pads
-BLOB_FLOATS = 8488
-BLOB_LAYOUT = collections.OrderedDict((("conv1_w", (0, (16, 4, 4, 4))), ("conv1_b", (1024, (16,))), ("conv2_w", (1040, (16, 16, 2, 2))),
-                                       ("conv2_b", (2064, (16,))), ("actor_w", (2080, (3, 1600))), ("actor_b", (6880, (3,))),
-                                       ("critic_w", (6884, (1, 1600))), ("critic_b", (8484, (1,)))))
-# the blob of a full-size crl_policy (csrc/pong_policy_full.hip) with its critic tail: 1 001 784 floats with the pads
-FULL_BLOB_FLOATS = 1001784
-FULL_BLOB_LAYOUT = collections.OrderedDict((("conv1_w", (0, (16, 4, 4, 4))), ("conv1_b", (1024, (16,))), ("conv2_w", (1040, (32, 16, 4, 4))),
-                                            ("conv2_b", (9232, (32,))), ("conv3_w", (9264, (256, 32, 11, 11))), ("conv3_b", (1000496, (256,))),
-                                            ("actor_w", (1000752, (3, 256))), ("actor_b", (1001520, (3,))), ("critic_w", (1001524, (1, 256))),
-                                            ("critic_b", (1001780, (1,)))))
 PPOStats = collections.namedtuple("PPOStats", ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "grad_norm", "steps"))
 
 
@@ -184,6 +175,47 @@ class _PPOLearner:
         with torch.cuda.device(self.device):
             N.check(self._L.crl_ppo_stats(self._h, out))
         return PPOStats(*out[:6], int(out[6]))
+
+    # ---- checkpoint / resume (include/crl.h "checkpoint / resume")
+    def _get_state(self, want_blobs=True):
+        """(weights blob, m blob, v blob, steps, scratch_rows) as the device holds them, behind the work enqueued on the current stream"""
+        blobs = [np.empty(self._FLOATS, np.float32) if want_blobs else None for _ in range(3)]
+        steps, rows = C.c_int64(), C.c_int64()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_get_state(self._h, *[b.ctypes.data_as(C.c_void_p) if want_blobs else None for b in blobs], self._FLOATS,
+                                              C.byref(steps), C.byref(rows), self._stream()))
+        return blobs[0], blobs[1], blobs[2], steps.value, rows.value
+
+    def state_dict(self):
+        """Everything a continuation needs, as host arrays (SYNCHRONISES with the current stream): ``kind``, the master ``weights`` by
+        key, Adam's moments ``m`` and ``v`` by key in the same layout, the optimiser ``steps`` taken, ``hyper`` and, for ``FullPPO``,
+        ``scratch_rows`` (part of the summation shape).  The last gradient and its statistics are not state."""
+        w, m, v, steps, rows = self._get_state()
+        sd = {"kind": type(self).__name__, "weights": K.split_blob(w, self._LAYOUT), "m": K.split_blob(m, self._LAYOUT),
+              "v": K.split_blob(v, self._LAYOUT), "steps": steps, "hyper": {k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in self.hyper.items()}}
+        if rows:
+            sd["scratch_rows"] = rows
+        return sd
+
+    def load_state_dict(self, sd):
+        """Puts a ``state_dict()`` back: weights, both moments and the step count together, and ``hyper``.  Everything is looked at
+        before anything is written: the other learner's dict, a missing or misshapen tensor, a negative step count, unknown
+        hyper-parameters or -- ``FullPPO`` -- another ``scratch_rows`` raise a ``ValueError`` and leave the learner as it was.  Ordered
+        on the current stream and SYNCHRONISES with it.  Afterwards the learner has no gradient: ``step()`` / ``stats()`` refuse until
+        the next ``grad``, as on a fresh learner."""
+        name = type(self).__name__
+        K.check_header(sd, name, name)
+        rows = self._get_state(want_blobs=False)[4]
+        if rows and int(sd.get("scratch_rows", -1)) != rows:
+            raise K.refuse(f"{name}: scratch_rows is {sd.get('scratch_rows')} in the state dict and {rows} here (it is part of the summation shape)")
+        blobs = [K.join_blob(sd.get(k), self._LAYOUT, self._FLOATS, f"{name} {k}") for k in ("weights", "m", "v")]
+        steps = K.check_counter(sd.get("steps"), 63, "steps", name)
+        hyper = sd.get("hyper", self.hyper)
+        if not isinstance(hyper, dict) or set(hyper) - set(PPO_DEFAULTS):
+            raise K.refuse(f"{name}: hyper must be a dict with keys of {sorted(PPO_DEFAULTS)}")
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_set_state(self._h, *[b.ctypes.data_as(C.c_void_p) for b in blobs], self._FLOATS, steps, self._stream()))
+        self.hyper = dict(PPO_DEFAULTS, **{k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in hyper.items()})
 
 
 class LightPPO(_PPOLearner):

@@ -31,9 +31,11 @@ Torch allocates, draws the permutation and names the stream; everything else is 
 import collections
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _native as N
+from . import checkpoint as K
 from .policy_serving import Policy
 from .rules import gae_reference, rollout_stack_reference  # noqa: F401  (re-exported)
 
@@ -80,7 +82,9 @@ class RolloutStorage:
     __del__ = close
 
     def nbytes(self):
-        """Device bytes the storage holds: (T + 3) padded planes per env, 27 bytes per env and step, a depth byte per env, the statistics."""
+        """Device bytes the storage holds: (T + 3) padded planes per env, 27 bytes per env and step, a depth byte per env, the statistics.
+        A checkpoint between iterations, ``state_dict(contents=False)``, is 3 * 1764 + 1 = 5 293 host bytes per env whatever T is
+        (``state_nbytes``)."""
         t, n = self.num_steps, self.num_envs
         return (t + 3) * n * 1776 + t * n * 27 + n + (2 + 256) * 8
 
@@ -144,6 +148,138 @@ class RolloutStorage:
         with self._on_device():
             N.check(self._L.crl_rollout_stats(self._h, out))
         return out[0], out[1]
+
+    # ---- checkpoint / resume (include/crl.h "checkpoint / resume")
+    _STEP_FIELDS = (("reset", torch.uint8), ("depth", torch.uint8), ("actions", torch.int32), ("log_probs", torch.float32), ("values", torch.float32))
+    _OUTCOME_FIELDS = (("rewards", torch.float32), ("dones", torch.uint8))
+
+    def _info(self):
+        out = (C.c_int32 * 4)()
+        N.check(self._L.crl_rollout_get_info(self._h, out))
+        return ("fresh", "active", "finished")[out[0]], out[1], out[2], bool(out[3])
+
+    def _copy_state(self, call, info, row0, planes, front_depth, steps, per_step, returns=None, adv=None, stats=None):
+        """``crl_rollout_get_state`` / ``_set_state`` over device tensors; ``per_step``: dict name -> tensor or None"""
+        f = per_step
+        args = [row0, 0 if planes is None else planes.shape[0], _ptr(planes), _ptr(front_depth), steps, _ptr(f.get("reset")), _ptr(f.get("depth")),
+                _ptr(f.get("actions")), _ptr(f.get("log_probs")), _ptr(f.get("values")), _ptr(f.get("rewards")), _ptr(f.get("dones")), _ptr(returns), _ptr(adv),
+                _ptr(stats), self._stream()]
+        with self._on_device():
+            N.check(call(self._h, *args) if info is None else call(self._h, info, *args))
+
+    def state_nbytes(self, contents=True):
+        """Host bytes of ``state_dict(contents)``'s arrays for a finished rollout: ``contents=False`` is 3 planes and a depth byte per
+        env, 3 * 1764 + 1 = 5 293 bytes per env whatever T is; ``contents=True`` adds the T + 3 planes, the front depth and 27 bytes
+        per env and step: (T + 6) * 1764 + 2 + 27 T bytes per env."""
+        t, n = self.num_steps, self.num_envs
+        return n * (3 * 1764 + 1) + (n * ((t + 3) * 1764 + 1 + 27 * t) if contents else 0)
+
+    def state_dict(self, contents=True):
+        """Everything a continuation needs, as host arrays (SYNCHRONISES with the current stream).  Always: ``kind``, ``num_steps``,
+        ``num_envs``, ``gamma``, ``gae_lambda``, ``normalize_advantage``, ``step``, ``outcomes``, ``state`` (fresh / active / finished),
+        ``finished``, and the carry -- what ``begin(None)`` would continue from: ``carry_planes`` uint8 (3, N, 42, 42), oldest first,
+        and ``carry_depth`` uint8 (N,), how many of them each env's stack may show; None in the middle of a rollout, where
+        ``begin(None)`` is refused.
+        ``contents=True`` adds, under ``contents``, everything recorded so far: ``planes`` (step + 3, N, 42, 42) -- the three planes in
+        front of step 0, then one per recorded step -- with ``front_depth``, per recorded step ``reset``, ``depth``, ``actions``,
+        ``log_probs``, ``values``, per outcome ``rewards`` and ``dones``, and after ``finish`` the ``returns``, the ``advantages``,
+        ``adv_mean`` / ``adv_std`` (float64) and whether the finish ``normalized``.  A checkpoint taken in the middle of a rollout, or
+        between ``finish`` and ``update``, continues exactly: ``record`` / ``outcome`` of the remaining steps, ``finish``, ``stats()``,
+        ``gather``, the learners' ``grad`` and a following ``begin(None)`` give the original's bits.
+        ``contents=False`` is the small form for a checkpoint BETWEEN iterations (after the update, before the next ``begin(None)``):
+        5 293 bytes per env (``state_nbytes``) instead of ``nbytes()``'s (T + 3) * 1776 + 27 T.  Loaded, the storage stands in front of
+        ``begin(None)`` with that carry; what was recorded is gone.  In the middle of a rollout it is refused."""
+        state, recorded, outcomes, normalized = self._info()
+        T, n, dev = self.num_steps, self.num_envs, self.device
+        if not contents and state == "active" and recorded:
+            raise ValueError("state_dict(contents=False) in the middle of a rollout would drop the steps recorded so far: pass contents=True")
+        sd = {"kind": "RolloutStorage", "num_steps": T, "num_envs": n, "gamma": self.gamma, "gae_lambda": self.gae_lambda,
+              "normalize_advantage": self.normalize_advantage, "step": self.step, "outcomes": outcomes, "state": state, "finished": state == "finished",
+              "carry_planes": None, "carry_depth": None, "contents": None}
+        if state != "active" or not recorded:  # the carry of the NEXT rollout: rows T .. T + 2 at min(3, depth[T - 1]) once finished, else the front rows
+            planes = torch.empty((3, n, 42, 42), dtype=torch.uint8, device=dev)
+            if state == "finished":
+                depth = torch.empty((T, n), dtype=torch.uint8, device=dev)
+                self._copy_state(self._L.crl_rollout_get_state, None, T, planes, None, T, {"depth": depth})
+                depth = depth[T - 1].clamp(max=3)
+            else:
+                depth = torch.empty((n,), dtype=torch.uint8, device=dev)
+                self._copy_state(self._L.crl_rollout_get_state, None, 0, planes, depth, 0, {})
+            sd["carry_planes"], sd["carry_depth"] = planes.cpu().numpy(), depth.cpu().numpy()
+        if contents:
+            planes = torch.empty((recorded + 3, n, 42, 42), dtype=torch.uint8, device=dev)
+            front = torch.empty((n,), dtype=torch.uint8, device=dev)
+            f = {k: torch.empty((recorded, n), dtype=d, device=dev) for k, d in self._STEP_FIELDS}
+            self._copy_state(self._L.crl_rollout_get_state, None, 0, planes, front, recorded, f)
+            g = {k: torch.empty((outcomes, n), dtype=d, device=dev) for k, d in self._OUTCOME_FIELDS}
+            self._copy_state(self._L.crl_rollout_get_state, None, 0, None, None, outcomes, g)
+            c = {"planes": planes.cpu().numpy(), "front_depth": front.cpu().numpy(), **{k: v.cpu().numpy() for k, v in {**f, **g}.items()}}
+            if state == "finished":
+                ret, adv = (torch.empty((T, n), dtype=torch.float32, device=dev) for _ in range(2))
+                stats = torch.zeros((2,), dtype=torch.float64, device=dev)
+                self._copy_state(self._L.crl_rollout_get_state, None, 0, None, None, 0, {}, ret, adv, stats if normalized else None)
+                stats = stats.cpu().numpy()
+                c.update(returns=ret.cpu().numpy(), advantages=adv.cpu().numpy(), adv_mean=float(stats[0]), adv_std=float(stats[1]), normalized=normalized)
+            sd["contents"] = c
+        return sd
+
+    def load_state_dict(self, sd):
+        """Puts a ``state_dict()`` of either form back.  Everything is looked at before anything is written: other T or N, a ``step``
+        outside [0, T], arrays of the wrong shape or a carry that is missing raise a ``ValueError`` and leave the storage as it was.
+        ``gamma``, ``gae_lambda`` and ``normalize_advantage`` become the dict's.  Ordered on the current stream and SYNCHRONISES with it
+        (the staging tensors are the call's own)."""
+        T, n, dev, what = self.num_steps, self.num_envs, self.device, "RolloutStorage"
+        K.check_header(sd, what, what, num_steps=T, num_envs=n)
+        state = sd.get("state")
+        if state not in ("fresh", "active", "finished"):
+            raise K.refuse(f"{what}: state must be fresh, active or finished, not {state!r}")
+        step, outcomes = K.check_counter(sd.get("step"), 31, "step", what), K.check_counter(sd.get("outcomes"), 31, "outcomes", what)
+        if step > T or outcomes > step or (state == "finished" and outcomes != T) or (state == "fresh" and step):
+            raise K.refuse(f"{what}: step {step} and {outcomes} outcomes do not fit a {state} rollout of {T} steps")
+        try:
+            gamma, lam, norm = float(sd["gamma"]), float(sd["gae_lambda"]), bool(sd["normalize_advantage"])
+        except (KeyError, TypeError, ValueError):
+            raise K.refuse(f"{what}: gamma, gae_lambda and normalize_advantage are needed") from None
+        c = sd.get("contents")
+        np_of = {torch.uint8: 1, torch.int32: 4, torch.float32: 4}
+        if c is None:
+            if state == "active" and step:
+                raise K.refuse(f"{what}: a state dict without contents cannot continue in the middle of a rollout (step {step})")
+            planes = K.check_array(sd, "carry_planes", (3, n, 42, 42), 1, what).view(np.uint8)
+            front = K.check_array(sd, "carry_depth", (n,), 1, what).view(np.uint8)
+            info, recorded, f, g, fin = (C.c_int32 * 4)(0, 0, 0, 0), 0, {}, {}, None
+        else:
+            if not isinstance(c, dict):
+                raise K.refuse(f"{what}: contents must be a dict")
+            recorded = T if state == "finished" else step
+            planes = K.check_array(c, "planes", (recorded + 3, n, 42, 42), 1, what).view(np.uint8)
+            front = K.check_array(c, "front_depth", (n,), 1, what).view(np.uint8)
+            f = {k: K.check_array(c, k, (recorded, n), np_of[d], what) for k, d in self._STEP_FIELDS}
+            g = {k: K.check_array(c, k, (outcomes, n), np_of[d], what) for k, d in self._OUTCOME_FIELDS}
+            fin, normalized = None, False
+            if state == "finished":
+                fin = [K.check_array(c, k, (T, n), 4, what).view(np.float32) for k in ("returns", "advantages")]
+                normalized = bool(c.get("normalized"))
+                try:
+                    fin.append(np.array([float(c["adv_mean"]), float(c["adv_std"])], np.float64))
+                except (KeyError, TypeError, ValueError):
+                    raise K.refuse(f"{what}: adv_mean and adv_std are needed after a finish") from None
+            info = (C.c_int32 * 4)(("fresh", "active", "finished").index(state), recorded, outcomes, int(normalized))
+
+        def up(a, dtype):  # (the bits as they are, under the storage's dtype)
+            as_np = {torch.uint8: np.uint8, torch.int32: np.int32, torch.float32: np.float32, torch.float64: np.float64}[dtype]
+            return torch.from_numpy(np.ascontiguousarray(a).view(as_np).copy()).to(dev)
+
+        fd = {k: up(f[k], d) for k, d in self._STEP_FIELDS if k in f}
+        self._copy_state(self._L.crl_rollout_set_state, info, 0, up(planes, torch.uint8), up(front, torch.uint8), recorded, fd)
+        if g and outcomes:
+            self._copy_state(self._L.crl_rollout_set_state, info, 0, None, None, outcomes, {k: up(g[k], d) for k, d in self._OUTCOME_FIELDS})
+        if fin is not None:
+            self._copy_state(self._L.crl_rollout_set_state, info, 0, None, None, 0, {}, up(fin[0], torch.float32), up(fin[1], torch.float32),
+                             up(fin[2], torch.float64))
+        self.step = 0 if c is None else step
+        self.gamma, self.gae_lambda, self.normalize_advantage = gamma, lam, norm
+        torch.cuda.current_stream(dev).synchronize()  # the staging tensors above are this call's own
 
     def empty_batch(self, batch_size, obs_dtype=torch.float32, fields=None):
         """Buffers for ``gather(idx, out=...)`` of ``batch_size`` samples; a field not named in ``fields`` is None and is not gathered."""

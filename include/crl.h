@@ -1005,6 +1005,77 @@ int crl_ppo_get_weights_full(crl_ppo *p, float *conv1_w_host, float *conv1_b_hos
 int crl_policy_load_full_dev(crl_policy *p, const float *blob_dev, void *stream);
 int crl_pool_load_full_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream);
 
+/* ---- checkpoint / resume: what a training loop needs to stop and go on, bit for bit ----------------
+ * The reference's trainers checkpoint the model's state_dict and the optimiser's (torch.save); a loop that never leaves the device
+ * also has to carry what lives on the device only.  Per object, the state is:
+ *
+ *   crl_ctx (Pong, CarRacing)  crl_get_state / crl_set_state, crl_car_get_state / _set_state (above).
+ *   crl_ledger, crl_arena      counters, running episodes, draw counters, weights, seed (their get / set calls above).
+ *   crl_policy                 the weight blob AS THE DEVICE HOLDS IT (after crl_policy_load_weights_dev / _load_full_dev the host has
+ *                              no copy), whether it carries a critic, the frame ring (crl_policy_get_stack), the play style
+ *                              (temperature, epsilon, seed, env_id_base) and its call counter, the n of "sampled actions".
+ *   crl_league (the pool)      per CNN slot the weight blob as the device holds it, the seed, the act-call counter (the n of RANDOM's
+ *                              and of every sampled or explored action), the per-env opponent draw counters, the play styles
+ *                              (crl_sampling_get_agent), the assignment (crl_league_get_assignment), the rings (crl_league_get_stack).
+ *   crl_rollout                where the rollout stands (fresh / in progress / finished, steps recorded, steps with an outcome, whether
+ *                              the finish normalised), the three planes in front of step 0 with their depth, every recorded step's
+ *                              plane, reset flag, depth, action, log-prob and value, every outcome's reward and done, and after the
+ *                              finish returns, advantages and the two float64 statistics.
+ *   crl_ppo                    the master blob, Adam's two moments in the blob's layout (pads zero), the optimiser steps taken and,
+ *                              full size, scratch_rows (part of the summation shape).  The last gradient and its statistics are NOT
+ *                              state: after crl_ppo_set_state the learner has no gradient until the next crl_ppo_grad.
+ *
+ * The getters that fill HOST memory copy on `stream` and wait for that copy: they are ordered behind the work enqueued on `stream`
+ * (a crl_policy_load_weights_dev, a crl_ppo_step) and synchronise with it.  The setters are ordered on `stream` likewise and return
+ * when their copies are done, so the caller's buffers are free again.  Nothing here is for the hot loop, and no act / record / grad /
+ * step launch changes.  All refuse (CRL_EINVAL, before any GPU call) a null object and what is said below. */
+/* The policy's blob, critic tail included: `blob_floats` must be 8 488 (LightActorCritic: conv1 | b1 | conv2 | b2 | actor | ba + 1 pad |
+ * critic | bc + 3 pads, torch layouts) or 1 001 784 (full size: conv1 | b1 | conv2 | b2 | conv3 | b3 | actor | ba + 1 pad | critic |
+ * bc + 3 pads), the policy's own.  has_critic_out (optional): 1 if a critic was ever set (the tail is zero otherwise). */
+int crl_policy_get_blob(crl_policy *p, float *blob_out_host, int64_t blob_floats, int32_t *has_critic_out, void *stream);
+/* The play style as crl_policy_set_sampling took it, and the call counter: crl_policy_act / _act_rollout calls since create or the last
+ * crl_policy_set_sampling.  Every out pointer is optional.  Host values, no GPU work. */
+int crl_policy_get_sampling(crl_policy *p, float *temperature, float *epsilon, uint64_t *seed, int64_t *env_id_base, uint32_t *calls);
+/* crl_policy_set_sampling that continues at call `calls` instead of 0: the next act call draws with n = calls. */
+int crl_policy_resume_sampling(crl_policy *p, float temperature, float epsilon, uint64_t seed, int64_t env_id_base, uint32_t calls);
+/* Slot `agent`'s blob (a slot has no critic): `blob_floats` must be 6 884 (CRL_LEAGUE_LIGHT) or 1 001 524 (CRL_POOL_KIND_FULL), the
+ * slot's own; a built-in agent has none and is refused. */
+int crl_pool_get_blob(crl_league *l, int32_t agent, float *blob_out_host, int64_t blob_floats, void *stream);
+/* The pool's counters.  seed, env_id_base, act_calls (the crl_league_act calls since create / crl_league_seed): optional host values;
+ * draw_ctr_out_dev: optional uint32 [num_envs] on the device, a copy enqueued on `stream` (no synchronisation). */
+int crl_pool_get_counters(crl_league *l, uint64_t *seed, int64_t *env_id_base, uint32_t *act_calls, uint32_t *draw_ctr_out_dev, void *stream);
+/* ... and their setter (the seed is crl_league_seed's, which zeroes both counters: call it first).  draw_ctr_dev: uint32 [num_envs] on
+ * the device or NULL (the draw counters stay); the copy is enqueued on `stream`, the buffer is the caller's until it has run. */
+int crl_pool_set_counters(crl_league *l, uint32_t act_calls, const uint32_t *draw_ctr_dev, void *stream);
+/* Where the rollout stands: out4_host = {0 fresh / 1 in progress / 2 finished, steps recorded, steps with an outcome, 1 if the finish
+ * normalised}.  Host values, no GPU work. */
+int crl_rollout_get_info(crl_rollout *r, int32_t *out4_host);
+/* Copies of the storage's arrays into DEVICE buffers of the caller, enqueued on `stream` (no synchronisation); every pointer is
+ * optional.  planes_out_dev: u8 [rows][N][42][42], plane rows row0 .. row0 + rows - 1 of the T + 3 the storage holds (rows 0 .. 2 are
+ * the planes in front of step 0, row t + 3 is step t's), without the padding; front_depth_out_dev: u8 [N], the depth those three
+ * planes are carried at.  The per-step arrays hold steps [0, steps): reset, depth, done u8 [steps][N], actions int32, logp, values,
+ * rewards float32.  returns / adv: float32 [T][N], stats: float64 [2] (mean, std); what they hold before a finish is unspecified.
+ * Refuses rows outside [0, T + 3] and steps outside [0, T]. */
+int crl_rollout_get_state(crl_rollout *r, int64_t row0, int64_t rows, uint8_t *planes_out_dev, uint8_t *front_depth_out_dev, int64_t steps,
+                          uint8_t *reset_out_dev, uint8_t *depth_out_dev, int32_t *actions_out_dev, float *logp_out_dev, float *values_out_dev,
+                          float *rewards_out_dev, uint8_t *done_out_dev, float *returns_out_dev, float *adv_out_dev, double *stats_out_dev,
+                          void *stream);
+/* The reverse: info4_host as crl_rollout_get_info gives it, looked at before anything is written (state in [0, 2]; outcomes <= recorded
+ * <= T; fresh: both 0; finished: both T), the arrays as above (NULL: that array stays).  The copies are enqueued on `stream`; the
+ * buffers are the caller's until they have run. */
+int crl_rollout_set_state(crl_rollout *r, const int32_t *info4_host, int64_t row0, int64_t rows, const uint8_t *planes_dev,
+                          const uint8_t *front_depth_dev, int64_t steps, const uint8_t *reset_dev, const uint8_t *depth_dev,
+                          const int32_t *actions_dev, const float *logp_dev, const float *values_dev, const float *rewards_dev,
+                          const uint8_t *done_dev, const float *returns_dev, const float *adv_dev, const double *stats_dev, void *stream);
+/* The learner's master blob and Adam's two moments, each `blob_floats` floats in the blob's layout (8 488 or 1 001 784, the learner's
+ * own; each pointer optional), the optimiser steps taken and scratch_rows (0 for the light learner). */
+int crl_ppo_get_state(crl_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t blob_floats, int64_t *steps_out,
+                      int64_t *scratch_rows_out, void *stream);
+/* Weights, moments and step count together (crl_ppo_set_weights* keep zeroing the moments): all three blobs are required, steps >= 0.
+ * The learner then has no gradient: crl_ppo_step / _stats / _get_grad refuse until the next crl_ppo_grad. */
+int crl_ppo_set_state(crl_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t blob_floats, int64_t steps,
+                      void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
