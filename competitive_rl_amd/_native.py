@@ -27,6 +27,9 @@ CRL_LEDGER_COUNTERS = 6  # rows of the counters tensor, in this order (enum crl_
 CRL_LEDGER_COUNTER_NAMES = ("episodes", "wins", "losses", "draws", "return_sum", "length_sum")
 CRL_LEDGER_PFSP_HARD, CRL_LEDGER_PFSP_VARIANCE = 0, 1
 CRL_ARENA_DOMAIN_PAIR = 0x4C475550
+CRL_CAR_DRIVER_DOMAIN = 0x43524430  # "CRD0": car c draws under CRL_CAR_DRIVER_DOMAIN + c (include/crl.h "car drivers")
+CRL_CAR_DRIVER_RANDOM, CRL_CAR_DRIVER_RULE_BASED = 0, 1
+CRL_CAR_DRIVER_SLOTS = 16
 CRL_ARENA_COUNTERS = 6  # planes of the counters tensor, in this order (enum crl_arena_counter); each plane is [left][right]
 CRL_ARENA_COUNTER_NAMES = ("episodes", "left_wins", "right_wins", "draws", "return_sum", "length_sum")
 
@@ -214,6 +217,15 @@ SIGNATURES = {
     "crl_rollout_set_state": (i32, [vp, P(i32), i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "crl_ppo_get_state": (i32, [vp, vp, vp, vp, i64, P(i64), P(i64), vp]),
     "crl_ppo_set_state": (i32, [vp, vp, vp, vp, i64, i64, vp]),
+    "crl_car_driver_create": (i32, [vp, u64, P(vp)]),
+    "crl_car_driver_destroy": (None, [vp]),
+    "crl_car_driver_set_style": (i32, [vp, i32, i32, f32, i32, f32, f32]),
+    "crl_car_driver_get_style": (i32, [vp, i32, P(i32), P(f32), P(i32), P(f32), P(f32)]),
+    "crl_car_driver_set_assignment": (i32, [vp, vp, vp]),
+    "crl_car_driver_get_assignment": (i32, [vp, vp, vp]),
+    "crl_car_driver_act": (i32, [vp, vp, vp]),
+    "crl_car_driver_get_counters": (i32, [vp, P(u64), P(i64)]),
+    "crl_car_driver_set_counters": (i32, [vp, u64, i64]),
 }
 SYMBOLS = list(SIGNATURES)
 

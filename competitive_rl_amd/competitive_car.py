@@ -12,11 +12,16 @@ Here the N envs are one HipCarVecEnv batch.  The opponent's actions stay on the 
 reference's per-env call protocol (numpy (K, 96, 96) in, one action out), which costs a host round trip
 per step.  As in the reference (make_competitive_car_racing.py:53), ``action_repeat`` is accepted but not
 forwarded to the envs.
+
+``opponent_policy`` may also be the NAME of a built-in driver (``get_builtin_car_driver_names()``: "RANDOM", "RULE_BASED") or of a style
+given in ``styles``: car 1 is then driven by ``CarDrivers.act`` on the device from the env's own state, with the same timing -- its action
+for step t + 1 is formed right after step t (or after the reset) -- and nothing touches the host.
 """
 import numpy as np
 import torch
 
 from . import spaces
+from .car_drivers import CarDrivers
 from .vec_env import VecEnv, _EnvList
 from .vec_env_car import HipCarVecEnv
 
@@ -48,8 +53,8 @@ class _Agent0Infos:
 
 class HipCompetitiveCarVecEnv(VecEnv):
     def __init__(self, opponent_policy, num_envs, seed=0, frame_stack=4, dones="dummy", batched=False, device=None, output="torch",
-                 env_id_base=0):
-        assert callable(opponent_policy)
+                 env_id_base=0, styles=None):
+        assert callable(opponent_policy) or isinstance(opponent_policy, str)
         self.opponent_policy, self.batched = opponent_policy, bool(batched)
         self.env = HipCarVecEnv(num_envs, seed=seed, device=device, env_id_base=env_id_base, output="torch", dones=dones,
                                 action_repeat=None, frame_stack=frame_stack, players=2, done_policy="car0")
@@ -60,8 +65,17 @@ class HipCompetitiveCarVecEnv(VecEnv):
         self._act = torch.zeros((num_envs, 2, 2), dtype=torch.float32, device=self.device)
         self.opponent_action = None
         self.envs = _EnvList(self)
+        self.drivers = None
+        if isinstance(opponent_policy, str):  # a built-in driver: served on the device, keyed by the env's seed
+            self.drivers = CarDrivers(self.env, seed=seed)
+            for name, params in (styles or {}).items():
+                self.drivers.set_style(name, **params)
+            self.drivers.assign(1, opponent_policy)  # (an unknown name: ValueError)
 
     def _opponent(self, obs):
+        if self.drivers is not None:  # car 1's rows of the action tensor, filled in place from the state the call before committed
+            self.drivers.act(self._act)
+            return
         theirs = obs[:, self.K:]
         if self.batched:
             a = self.opponent_policy(theirs)
@@ -82,7 +96,8 @@ class HipCompetitiveCarVecEnv(VecEnv):
     def step_async(self, actions):
         a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float32))
         self._act[:, 0] = a.to(self.device, torch.float32).reshape(self.num_envs, -1)[:, :2]
-        self._act[:, 1] = self.opponent_action
+        if self.drivers is None:
+            self._act[:, 1] = self.opponent_action
 
     def step_wait(self):
         self.env.step_async(self._act)
@@ -94,6 +109,8 @@ class HipCompetitiveCarVecEnv(VecEnv):
         return self.env.seed(seed)
 
     def close(self):
+        if self.drivers is not None:
+            self.drivers.close()
         self.env.close()
 
     def get_attr(self, attr_name, indices=None):
@@ -110,9 +127,9 @@ class HipCompetitiveCarVecEnv(VecEnv):
 
 
 def make_competitive_car_racing(opponent_policy, seed=0, num_envs=3, asynchronous=False, frame_stack=4, action_repeat=None, *,
-                                batched=False, device=None, output="torch", env_id_base=0):
-    assert callable(opponent_policy)
+                                batched=False, device=None, output="torch", env_id_base=0, styles=None):
+    assert callable(opponent_policy) or isinstance(opponent_policy, str)
     asynchronous = asynchronous and num_envs > 1
     return HipCompetitiveCarVecEnv(opponent_policy, num_envs, seed=seed, frame_stack=frame_stack,
                                    dones="subproc" if asynchronous else "dummy", batched=batched, device=device, output=output,
-                                   env_id_base=env_id_base)
+                                   env_id_base=env_id_base, styles=styles)

@@ -775,6 +775,8 @@ int crl_render_raw(crl_ctx *c, const crl_pong_frame *frames_host, int64_t count,
 
 }  // extern "C"
 
+crl_car_ctx *crl_ctx_car(crl_ctx *c) { return c ? c->car : nullptr; }
+
 // ---- state exchange: device SoA <-> host AoS
 template <class T>
 static int d2h(std::vector<T> &v, const T *dev, int64_t first, int64_t count, hipStream_t st) {

@@ -507,6 +507,8 @@ const uint8_t *crl_car_done_flags(const crl_car_ctx *c) { return c->done_car; }
 const int32_t *crl_car_info_steps(const crl_car_ctx *c) { return c->info_steps; }
 const int32_t *crl_car_info_elapsed(const crl_car_ctx *c) { return c->info_elapsed; }
 int crl_car_players(const crl_car_ctx *c) { return c->s.players; }
+const crl::CarSoA *crl_car_soa(const crl_car_ctx *c) { return &c->s; }
+int64_t crl_car_env_id_base(const crl_car_ctx *c) { return c->src.env_id_base; }
 
 int crl_car_render(crl_car_ctx *c, uint8_t *obs_dev, hipStream_t st) {
     if (c->K > 1) return crl_fail(CRL_ESTATE, "crl_render on a stacked CarRacing context would advance the stack");

@@ -66,6 +66,14 @@ const uint8_t *crl_car_done_flags(const crl_car_ctx *c);
 const int32_t *crl_car_info_steps(const crl_car_ctx *c);
 const int32_t *crl_car_info_elapsed(const crl_car_ctx *c);
 int crl_car_players(const crl_car_ctx *c);
+// what an object beside a CarRacing context (crl_car_driver) reads of it: the context's CarRacing half (nullptr for a Pong context),
+// the device state's arrays (car_device.h) and the global id of env 0
+namespace crl {
+struct CarSoA;
+}
+crl_car_ctx *crl_ctx_car(crl_ctx *c);
+const crl::CarSoA *crl_car_soa(const crl_car_ctx *c);
+int64_t crl_car_env_id_base(const crl_car_ctx *c);
 int crl_car_step(crl_car_ctx *c, const float *actions_dev, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, hipStream_t st,
                  crl_timer *tm);
 int crl_car_get_state_impl(crl_car_ctx *c, crl_car_env_state *out, int64_t first, int64_t count, hipStream_t st);

@@ -247,3 +247,121 @@ def adam_reference(params, m, v, grad, grad_norm, step, hyper=None):
     v = ((b2 * v).astype(f) + (omb2 * (g * g).astype(f)).astype(f)).astype(f)
     denom = ((np.sqrt(v).astype(f) / bc2s).astype(f) + eps).astype(f)
     return (p - (step_size * (m / denom).astype(f)).astype(f)).astype(f), m, v
+
+
+# ---- include/crl.h "car drivers": the built-in CarRacing agents
+CAR_DRIVER_KINDS = ("RANDOM", "RULE_BASED")
+CAR_DRIVER_MAX_LOOKAHEAD = 64
+CAR_DRIVER_GAS_GAIN = 0.1    # CRL_CAR_DRIVER_GAS_GAIN
+CAR_DRIVER_CURVE_SLOW = 0.5  # CRL_CAR_DRIVER_CURVE_SLOW
+# the preset of style slot 1 (CRL_CAR_DRIVER_DEFAULT_*), tuned closed loop on the CPU (docs/LAB_NOTES_car_drivers.md)
+CAR_DRIVER_DEFAULT_STYLE = dict(kind="RULE_BASED", target_speed=45.0, lookahead=4, steer_gain=1.5, epsilon=0.0)
+
+
+def check_car_style(kind="RULE_BASED", target_speed=None, lookahead=None, steer_gain=None, epsilon=None):
+    """What ``crl_car_driver_set_style`` accepts, as the values it receives: a kind of ``CAR_DRIVER_KINDS`` (name or index), finite
+    float32 ``target_speed`` and ``steer_gain`` >= 0, an integer ``lookahead`` in [0, 64] and an ``epsilon`` in [0, 1].  Missing
+    parameters are the default style's.  Returns the complete style as a dict (``kind`` as its name)."""
+    d = CAR_DRIVER_DEFAULT_STYLE
+    if isinstance(kind, str):
+        if kind not in CAR_DRIVER_KINDS:
+            raise ValueError(f"kind must be one of {CAR_DRIVER_KINDS}, not {kind!r}")
+    elif isinstance(kind, (int, np.integer)) and 0 <= int(kind) < len(CAR_DRIVER_KINDS):
+        kind = CAR_DRIVER_KINDS[int(kind)]
+    else:
+        raise ValueError(f"kind must be one of {CAR_DRIVER_KINDS}, not {kind!r}")
+    ts = np.float32(d["target_speed"] if target_speed is None else target_speed)
+    sg = np.float32(d["steer_gain"] if steer_gain is None else steer_gain)
+    la = d["lookahead"] if lookahead is None else lookahead
+    e = np.float32(d["epsilon"] if epsilon is None else epsilon)
+    for name, v in (("target_speed", ts), ("steer_gain", sg)):
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{name} must be finite and >= 0, not {v}")
+    if isinstance(la, bool) or not isinstance(la, (int, np.integer)) or not 0 <= int(la) <= CAR_DRIVER_MAX_LOOKAHEAD:
+        raise ValueError(f"lookahead must be an integer in [0, {CAR_DRIVER_MAX_LOOKAHEAD}], not {la!r}")
+    if not 0 <= e <= 1:
+        raise ValueError(f"epsilon must lie in [0, 1], not {epsilon}")
+    return dict(kind=kind, target_speed=float(ts), lookahead=int(la), steer_gain=float(sg), epsilon=float(e))
+
+
+def car_tile_boxes(tile_poly):
+    """The float32 box (x0, y0, x1, y1) of every tile of float32 polygons [..., 5, 2], as the env keeps it (``tile_aabb``): the
+    minimum and maximum of the five float32 vertices."""
+    p = np.asarray(tile_poly, np.float32)
+    return np.concatenate([p.min(axis=-2), p.max(axis=-2)], axis=-1)
+
+
+def car_driver_draws(seed, gid, car, call):
+    """The Philox call of "car drivers": the words (x0, x1, x2, x3) of counter (gid lo, gid hi, call, CRL_CAR_DRIVER_DOMAIN + car)
+    under key (seed lo, seed hi), as uint64 arrays holding 32 bits.  ``gid`` and ``call`` broadcast; ``car`` is 0 or 1."""
+    return _philox4x32_10(gid, call, N.CRL_CAR_DRIVER_DOMAIN + int(car), seed)
+
+
+def car_driver_unit(x):
+    """A Philox word as a float32 in [-1, 1): float32(int32(x >> 8) - 2^23) * 2^-23 (every step exact)."""
+    return ((np.asarray(x, np.uint64) >> np.uint64(8)).astype(np.int64) - (1 << 23)).astype(np.float32) * np.float32(2.0 ** -23)
+
+
+def _clamp1(x):
+    one = np.float32(1)
+    return np.where(x < -one, -one, np.where(x > one, one, x)).astype(np.float32)
+
+
+def car_driver_reference(hull, wheels, done, boxes, n, style, seed, gid, car, call):
+    """The rule of include/crl.h "car drivers" in numpy float32, one rounding per operation, bit for bit what ``car_driver_kernel``
+    writes for car ``car`` (0 or 1) of E envs at act call ``call``:
+      hull    float32 [E, 4]     the car's hull body: cx, cy, vx, vy
+      wheels  float32 [E, 4, 2]  the centres of its wheel bodies 0..3 (0, 1 front; 2, 3 rear)
+      done    [E]                its done flag
+      boxes   float32 [E, T, 4]  the env's tile boxes (x0, y0, x1, y1), ``car_tile_boxes`` of its track; rows >= n are not read
+      n       int [E]            the env's tile count
+      style   a dict as ``check_car_style`` returns it (missing parameters are the default style's)
+      seed, gid [E], call        the key, the GLOBAL env ids and the act-call counter of the draws
+    Returns float32 [E, 2]: (steer, gas > 0 / brake < 0).  Host code for tests and for driving the CPU checker; the kernels do not
+    use it."""
+    f = np.float32
+    s = check_car_style(**style)
+    hull, wheels, boxes = np.asarray(hull, f), np.asarray(wheels, f), np.asarray(boxes, f)
+    E = hull.shape[0]
+    if hull.shape != (E, 4) or wheels.shape != (E, 4, 2) or boxes.ndim != 3 or boxes.shape[0] != E or boxes.shape[2] != 4:
+        raise ValueError("hull [E, 4], wheels [E, 4, 2], boxes [E, T, 4]")
+    n = np.broadcast_to(np.asarray(n, np.int64), (E,))
+    done = np.broadcast_to(np.asarray(done), (E,)) != 0
+    if n.max(initial=0) > boxes.shape[1]:
+        raise ValueError("n exceeds the rows of boxes")
+    gid = np.broadcast_to(np.asarray(gid, np.uint64), (E,))
+    x = car_driver_draws(seed, gid, car, np.broadcast_to(np.asarray(call, np.uint64), (E,)))
+    rnd = np.stack([car_driver_unit(x[0]), car_driver_unit(x[1])], axis=1)
+    explore = np.ones(E, bool) if s["kind"] == "RANDOM" else x[2] < np.uint64(sample_eps_q(s["epsilon"]))
+    out = np.zeros((E, 2), f)
+    half, one, zero = f(0.5), f(1), f(0)
+    with np.errstate(all="ignore"):
+        live = ~done & (n > 0)
+        nn = np.maximum(n, 1)
+        tx = (boxes[..., 0] + boxes[..., 2]) * half
+        ty = (boxes[..., 1] + boxes[..., 3]) * half
+        cx, cy, vx, vy = hull[:, 0], hull[:, 1], hull[:, 2], hull[:, 3]
+        dx, dy = tx - cx[:, None], ty - cy[:, None]
+        d2 = dx * dx + dy * dy
+        d2 = np.where(d2 == d2, d2, f(np.inf))
+        d2 = np.where(np.arange(boxes.shape[1])[None, :] < nn[:, None], d2, f(np.inf))
+        near = np.argmin(d2, axis=1)  # (the first index among equals)
+        goal = (near + s["lookahead"]) % nn
+        rows = np.arange(E)
+        ax, ay = tx[rows, goal] - cx, ty[rows, goal] - cy
+        hx = (wheels[:, 0, 0] + wheels[:, 1, 0]) * half - (wheels[:, 2, 0] + wheels[:, 3, 0]) * half
+        hy = (wheels[:, 0, 1] + wheels[:, 1, 1]) * half - (wheels[:, 2, 1] + wheels[:, 3, 1]) * half
+        cr = hx * ay - hy * ax
+        dt = hx * ax + hy * ay
+        den = np.sqrt(hx * hx + hy * hy) * np.sqrt(ax * ax + ay * ay)
+        ok = den > zero
+        safe = np.where(ok, den, one)
+        sn, cs = np.where(ok, cr / safe, zero), np.where(ok, dt / safe, one)
+        e = np.where(cs >= zero, sn, np.where(sn > zero, one, np.where(sn < zero, -one, zero))).astype(f)
+        steer = _clamp1(-(f(s["steer_gain"]) * e))
+        speed = np.sqrt(vx * vx + vy * vy)
+        want = f(s["target_speed"]) * (one - f(CAR_DRIVER_CURVE_SLOW) * np.abs(e))
+        gas = _clamp1((want - speed) * f(CAR_DRIVER_GAS_GAIN))
+    ruled = np.stack([steer, gas], axis=1).astype(f)
+    out[live] = np.where(explore[:, None], rnd, ruled)[live]
+    return out

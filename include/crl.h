@@ -1076,6 +1076,78 @@ int crl_ppo_get_state(crl_ppo *p, float *blob_out_host, float *m_out_host, float
 int crl_ppo_set_state(crl_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t blob_floats, int64_t steps,
                       void *stream);
 
+/* ---- car drivers: built-in CarRacing agents served from the env's own device state --------------
+ * Stands in for the opponent_policy of make_competitive_car_racing (car_racing/make_competitive_car_racing.py:10-58), for which the
+ * reference ships nothing, and is CarRacing's counterpart of Pong's RANDOM and RULE_BASED (pong/builtin_policies.py:44-58): RULE_BASED
+ * reads the env's state, as the cheat code does.  An object beside a CarRacing context (as the ledger is beside the league): it READS
+ * the context's committed state and writes the caller's action tensor, nothing else.  One launch per crl_car_driver_act on the
+ * caller's stream serves every car of every env; nothing synchronises with the host.
+ *
+ * Styles and assignment.  Up to CRL_CAR_DRIVER_SLOTS styles: kind (enum crl_car_driver_kind), target_speed (float32, world units per
+ * second), lookahead (tiles, 0..CRL_CAR_DRIVER_MAX_LOOKAHEAD), steer_gain (float32), epsilon (float32 in [0, 1]).  Slot 0 is preset
+ * to RANDOM, slot 1 to RULE_BASED with CRL_CAR_DRIVER_DEFAULT_* (epsilon 0); the other slots are empty until set.  The assignment is
+ * an int32 per (env, car), [N][players]: the car's style slot; a value outside [0, CRL_CAR_DRIVER_SLOTS) -- -1 by convention, the
+ * state after create -- or an empty slot leaves the car's two floats of the action tensor as they are.
+ *
+ * The rule (rules.car_driver_reference restates it in numpy, bit for bit).  Everything is float32 with ONE rounding per operation: no
+ * contraction, no fast-math intrinsics, sqrt and / correctly rounded; a + b + c is never written, every sum below has two terms.
+ * Inputs of car c of env i: its hull body's cx, cy, vx, vy; the centres (wx_k, wy_k) of its wheel bodies k = 0..3 (WHEELPOS order,
+ * car_racing/car_dynamics.py:23-26: 0, 1 front, 2, 3 rear); its done flag; the env's tile count n and tile boxes (x0, y0, x1, y1)_t,
+ * t < n (the minimum and maximum of the tile polygon's five float32 vertices).  Output (steer, gas): the env's two-component action
+ * (process_action, car_racing_multi_players.py:528-540): steer > 0 turns right (the env applies steer(-a[0]), :554), gas > 0
+ * accelerates, gas < 0 brakes.
+ *   0. done != 0 or n <= 0: (0, 0).  Nothing below is evaluated.
+ *   1. draw: ONE call x = Philox4x32-10(counter = (gid & 0xFFFFFFFF, gid >> 32, call, CRL_CAR_DRIVER_DOMAIN + c), key = (seed &
+ *      0xFFFFFFFF, seed >> 32)) -- the generator of "league draws"; gid = env_id_base + i, the env's GLOBAL id (the context's
+ *      env_id_base), call = the number of crl_car_driver_act calls since create / crl_car_driver_set_counters (0 for the first; it
+ *      moves for every car, assigned or not) -- gives x0..x3.  unit(x) = float32(int32(x >> 8) - 8388608) * 2^-23, in [-1, 1), exact.
+ *      RANDOM: (unit(x0), unit(x1)).  RULE_BASED: with eps_q = min(floor(epsilon * 2^32), 0xFFFFFFFF) (in double from the float32
+ *      epsilon, as "sampled actions"), if x2 < eps_q the action is RANDOM's; epsilon has no effect on RANDOM.
+ *   2. nearest tile: tx_t = (x0_t + x1_t) * 0.5, ty_t = (y0_t + y1_t) * 0.5; dx = tx_t - cx, dy = ty_t - cy;
+ *      d_t = (dx * dx) + (dy * dy), a NaN d_t counts as +inf; nearest = the t < n with the smallest d_t, the LOWEST t among equals.
+ *   3. target: g = (nearest + lookahead) mod n;  ax = tx_g - cx, ay = ty_g - cy.
+ *   4. heading, without trigonometry: hx = (wx_0 + wx_1) * 0.5 - (wx_2 + wx_3) * 0.5, hy likewise: rear axle's midpoint to front's.
+ *      cr = (hx * ay) - (hy * ax);  dt = (hx * ax) + (hy * ay);  den = sqrt((hx * hx) + (hy * hy)) * sqrt((ax * ax) + (ay * ay)).
+ *      If den > 0: sn = cr / den, cs = dt / den; otherwise (zero, or NaN) sn = 0, cs = 1.
+ *      e = sn if cs >= 0; otherwise (the target lies behind) 1 if sn > 0, -1 if sn < 0, else 0.
+ *   5. steer = clamp(-(steer_gain * e)).
+ *   6. v = sqrt((vx * vx) + (vy * vy));  want = target_speed * (1 - CRL_CAR_DRIVER_CURVE_SLOW * |e|);
+ *      gas = clamp((want - v) * CRL_CAR_DRIVER_GAS_GAIN).
+ *   clamp(x) = -1 if x < -1, 1 if x > 1, else x (a NaN passes).
+ * A draw depends on (seed, global env id, car, call) alone and the rest on the env's state: shards of a batch act as the whole batch.
+ * The default style's constants were tuned closed loop on the CPU checker (docs/LAB_NOTES_car_drivers.md). */
+#define CRL_CAR_DRIVER_SLOTS 16
+#define CRL_CAR_DRIVER_MAX_LOOKAHEAD 64
+#define CRL_CAR_DRIVER_DOMAIN 0x43524430u /* "CRD0"; car 1 draws under "CRD1" */
+#define CRL_CAR_DRIVER_GAS_GAIN 0.1f
+#define CRL_CAR_DRIVER_CURVE_SLOW 0.5f
+#define CRL_CAR_DRIVER_DEFAULT_TARGET_SPEED 45.0f
+#define CRL_CAR_DRIVER_DEFAULT_LOOKAHEAD 4
+#define CRL_CAR_DRIVER_DEFAULT_STEER_GAIN 1.5f
+enum crl_car_driver_kind { CRL_CAR_DRIVER_RANDOM = 0, CRL_CAR_DRIVER_RULE_BASED = 1 };
+typedef struct crl_car_driver crl_car_driver;
+/* Drivers for the envs of CarRacing context `ctx`, which must outlive them; seed = the key of the draws.  Refuses (CRL_EINVAL, before
+ * any GPU call) a null argument and a Pong context. */
+int crl_car_driver_create(crl_ctx *ctx, uint64_t seed, crl_car_driver **out);
+void crl_car_driver_destroy(crl_car_driver *d);
+/* Style slot `slot`, from the next crl_car_driver_act on; host values, no GPU call.  Refuses (CRL_EINVAL; the values are looked at
+ * first, then the handle) a slot outside [0, CRL_CAR_DRIVER_SLOTS), a kind outside the enum, a non-finite or negative target_speed or
+ * steer_gain, a lookahead outside [0, CRL_CAR_DRIVER_MAX_LOOKAHEAD] and an epsilon outside [0, 1].  _get_style: kind -1 = empty. */
+int crl_car_driver_set_style(crl_car_driver *d, int32_t slot, int32_t kind, float target_speed, int32_t lookahead, float steer_gain,
+                             float epsilon);
+int crl_car_driver_get_style(crl_car_driver *d, int32_t slot, int32_t *kind, float *target_speed, int32_t *lookahead, float *steer_gain,
+                             float *epsilon);
+/* ids_dev int32 [N][players] on the device, copied (device to device, on `stream`) into the driver's own array. */
+int crl_car_driver_set_assignment(crl_car_driver *d, const int32_t *ids_dev, void *stream);
+int crl_car_driver_get_assignment(crl_car_driver *d, int32_t *ids_out_dev, void *stream);
+/* opponent_policy(obs) for every assigned car: actions_dev float32 [N][players][2], the layout crl_step takes.  Enqueued on `stream`
+ * behind a crl_step / crl_reset of the context on the same stream it sees the state that call committed, the auto-reset of finished
+ * envs included -- the observation the reference's wrapper hands its opponent (make_competitive_car_racing.py:24-33). */
+int crl_car_driver_act(crl_car_driver *d, float *actions_dev, void *stream);
+/* Resume: the key and the act-call counter (host values; calls in [0, 2^32)). */
+int crl_car_driver_get_counters(crl_car_driver *d, uint64_t *seed, int64_t *calls);
+int crl_car_driver_set_counters(crl_car_driver *d, uint64_t seed, int64_t calls);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
