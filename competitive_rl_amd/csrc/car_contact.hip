@@ -11,9 +11,6 @@
 // not collide with wheels).  friction = sqrt(0.2*0.2), restitution = 0, polygonRadius = 0.01.
 #include <stdlib.h>
 
-#ifdef CRL_ABLATION
-#include "car_obs_tile.h"
-#endif
 #include "car_solver.h"
 
 namespace crl {
@@ -302,10 +299,6 @@ __global__ __launch_bounds__(64) void car_narrow_kernel(CarSoA s, CarConsts Kv, 
     // scratch, and reading them from device memory makes every vertex a dependent ~200-cycle load: stage them in LDS)
     __shared__ CarConsts Ks;
     const int lane = threadIdx.x;
-#ifdef CRL_ABLATION
-    const unsigned long long sn0 = __builtin_readcyclecounter();
-    unsigned long long acc1 = 0, acc2 = 0, acc3 = 0, nslot = 0;
-#endif
     if (urgent) __builtin_amdgcn_s_setprio(3);  // in front of the touching solve it heads the step's critical path; run ahead, at the end of the
                                                 // previous step, it must not take issue slots from that step's last frames and the next car_step_kernel
     const int n_front = s.coupled_count[0], n_back = s.coupled_count[7];
@@ -343,14 +336,7 @@ __global__ __launch_bounds__(64) void car_narrow_kernel(CarSoA s, CarConsts Kv, 
     // (One copy per PAIR -- 17 KB per workgroup -- allowed eight workgroups per CU: 2 300 coupled envs took two rounds of the kernel.)
     __shared__ WPoly wp[16];
     const int64_t M = 2 * s.n;
-#ifdef CRL_ABLATION
-    const unsigned long long sn1 = __builtin_readcyclecounter();
-#endif
     for (int slot = slot0 + (int)blockIdx.x; slot < slot1; slot += gridDim.x) {
-#ifdef CRL_ABLATION
-        const unsigned long long sa = __builtin_readcyclecounter();
-        unsigned long long sb = sa;
-#endif
         const int64_t env = slot < n_front ? s.coupled_list[slot] : s.coupled_list[s.n - 1 - (slot - n_front)];
         // (collide-ahead) an env that finished while coupled: its new episode's bodies, still staged; no manifolds to warm-start from
         const bool fresh = cls && cls[env] == 3;
@@ -380,9 +366,6 @@ __global__ __launch_bounds__(64) void car_narrow_kernel(CarSoA s, CarConsts Kv, 
                 ccx[k] = wc.x, ccy[k] = wc.y, crad[k] = cq[2];
             }
             const float dx = ccx[0] - ccx[1], dy = ccy[0] - ccy[1], rr = crad[0] + crad[1];
-#ifdef CRL_ABLATION
-            sb = __builtin_readcyclecounter();
-#endif
             const bool cand = !(dx * dx + dy * dy > rr * rr);
             // (wave-uniform: does any candidate pair of this env involve the hull's octagon?)
             const bool big = __any(cand && (shape_of(K, fa).n > 4 || shape_of(K, fb).n > 4));
@@ -404,9 +387,6 @@ __global__ __launch_bounds__(64) void car_narrow_kernel(CarSoA s, CarConsts Kv, 
                 else collide_polygons_w<4>(c, shape_of(K, fa), xf[0], wp[fa], nl[fa < 4 ? fa : 4], shape_of(K, fb), xf[1], wp[8 + fb], nl[fb < 4 ? fb : 4]);
             }
         }
-#ifdef CRL_ABLATION
-        const unsigned long long sc = __builtin_readcyclecounter();
-#endif
         const bool hit = active && c.count > 0;
         const unsigned long long m = __ballot(hit);
         const int rank = (int)__popcll(m & ((1ull << lane) - 1ull));
@@ -439,17 +419,7 @@ __global__ __launch_bounds__(64) void car_narrow_kernel(CarSoA s, CarConsts Kv, 
             if (nc) s.touch_all[atomicAdd(s.coupled_count + 5, 1)] = (int32_t)env;
             if (nc >= 2) s.touch_multi[atomicAdd(s.coupled_count + 6, 1)] = (int32_t)env;
         }
-#ifdef CRL_ABLATION
-        const unsigned long long sd = __builtin_readcyclecounter();
-        acc1 += sb - sa, acc2 += sc - sb, acc3 += sd - sc, nslot++;
-#endif
     }
-#ifdef CRL_ABLATION
-    if (lane == 0 && s.stamps && nslot) {
-        unsigned long long *q = s.stamps + 32;
-        atomicAdd(q + 0, sn1 - sn0), atomicAdd(q + 1, acc1), atomicAdd(q + 2, acc2), atomicAdd(q + 3, acc3), atomicAdd(q + 7, nslot);
-    }
-#endif
 }
 
 // ---- (2) envs whose boxes overlap but where nothing touches: two islands of their own, exactly the per-car kernel,
@@ -705,9 +675,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
     const int pair = (threadIdx.x >> 1) % EPW;  // (lane pairs past EPW repeat the first ones' envs and store nothing)
     const int slot = slot_base + pair;
     const bool live = slot < list_count && (threadIdx.x >> 1) < EPW;
-#ifdef CRL_ABLATION
-    const unsigned long long st0 = __builtin_readcyclecounter();
-#endif
     // (lanes past the end of the list ride along on the last env's data and store nothing: the DPP swaps and the uniform
     // loop bounds below want every lane of the wavefront in step)
     const int64_t env = list[slot < list_count ? slot : list_count - 1];
@@ -839,9 +806,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
     }
     bool tail1 = false, tail2 = false;  // contacts past NK (TAIL only)
     for (int k = NK; k < nc_wave; k++) tail1 = tail1 || __any(k < nc && tc[k < nc ? k : 0].count == 1), tail2 = tail2 || __any(k < nc && tc[k < nc ? k : 0].count == 2);
-#ifdef CRL_ABLATION
-    const unsigned long long st1 = __builtin_readcyclecounter();
-#endif
     const int jmode = isl_joint_mode(r);
 #pragma unroll 1
     for (int it = 0; it < 180; it++) {
@@ -866,10 +830,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
         for (int k = NK; k < nc; k++) ct[k].nimp[0] = tc[k].nimp0, ct[k].nimp[1] = tc[k].nimp1, ct[k].timp[0] = tc[k].timp0, ct[k].timp[1] = tc[k].timp1;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#ifdef CRL_ABLATION
-    const unsigned long long st2 = __builtin_readcyclecounter();
-    int pos_iters = 0;
-#endif
     // (the poses did not change since the car was loaded: from the LDS copy again, so that they need no registers across the
     // velocity iterations)
     r.H.cx = mH.cx, r.H.cy = mH.cy, r.H.a = mH.a;
@@ -889,9 +849,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
 #pragma unroll 1
     for (int it = 0; it < 60; it++) {
         float minSep = 0.0f;
-#ifdef CRL_ABLATION
-        pos_iters = it + 1;
-#endif
 #pragma unroll
         for (int k = 0; k < NK; k++) contact_pos<FM>(r, kc[k], ct[k < nc ? k : 0], me, hlc, minSep);
         if (TAIL) {
@@ -912,11 +869,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
             break;
         }
     }
-#ifdef CRL_ABLATION
-    const unsigned long long st3 = __builtin_readcyclecounter();
-    int pi_wave = pos_iters;
-    for (int d = 1; d < 64; d <<= 1) pi_wave = max(pi_wave, __shfl_xor(pi_wave, d));
-#endif
     // one island: it sleeps only when all ten bodies have been still long enough
     const float mo = __shfl_xor(mm, 1);
     if (fminf(mm, mo) >= TIME_TO_SLEEP && solved) {
@@ -929,17 +881,11 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
         for (int i = threadIdx.x; i < nc * kCW; i += 64) out[(i / kCW) * kContactWords + i % kCW] = src[i];
     }
     if (!live) return;
-#ifdef CRL_ABLATION
-    const unsigned long long st3b = __builtin_readcyclecounter();
-#endif
     for (int b = 0; b < 5; b++) s.sleep[b * M + me * s.n + env] = slp[b];
 
     // ---- store bodies, joints and the manifolds with their impulses
     store_car_pos(s, M, me * s.n + env, r);
     s.first_step[me * s.n + env] = 0;
-#ifdef CRL_ABLATION
-    const unsigned long long st3c = __builtin_readcyclecounter();
-#endif
     if (me != 0) return;
     s.n_contact[env] = nc;
     float *out = s.contact + env * (int64_t)(kMaxContacts * kContactWords);
@@ -952,16 +898,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
         o[11] = __uint_as_float(c.id[0]), o[12] = __uint_as_float(c.id[1]);
         o[13] = c.nimp[0], o[14] = c.nimp[1], o[15] = c.timp[0], o[16] = c.timp[1];
     }
-#ifdef CRL_ABLATION
-    if (threadIdx.x == 0 && s.stamps) {
-        const unsigned long long st4 = __builtin_readcyclecounter();
-        unsigned long long *q = s.stamps + 8 * (NK - 1);
-        atomicAdd(q + 0, st1 - st0), atomicAdd(q + 1, st2 - st1), atomicAdd(q + 2, st3 - st2), atomicAdd(q + 3, st4 - st3);
-        atomicAdd(q + 4, (unsigned long long)pi_wave), atomicMax(q + 5, st4 - st0), atomicAdd(q + 6, st3c - st3b), atomicAdd(q + 7, 1ull);
-        unsigned long long *m = s.stamps + 40 + 4 * (NK - 1);  // per class: longest velocity phase, longest position phase, wavefronts that ran all 60 position iterations
-        atomicMax(m + 0, st2 - st1), atomicMax(m + 1, st3 - st2), atomicAdd(m + 2, pi_wave >= 60 ? 1ull : 0ull), atomicMax(m + 3, st1 - st0);
-    }
-#endif
 }
 #undef CRL_SEL
 #undef CRL_PUT
@@ -973,37 +909,6 @@ __device__ __forceinline__ void touch_solve(const CarSoA &s, const CarConsts &K,
 // published by the wheel sensors' stream: one tile takes a lone wavefront ~75 us, so two or eight tiles in a row behind a solve are
 // slower than the list launch that draws them side by side -- and a kernel that spins on another kernel's output deadlocks as soon
 // as both are only partly dispatched.  docs/LAB_NOTES_r04.md.)
-#ifdef CRL_ABLATION
-// Epilogue of the touching solve (round 5, profiling build only: measured, not kept): the solving wavefront also prepares the VIEWS of its
-// envs' frames -- camera (double-double atan2 / sincos, ~15 us of latency) and the car polygons' scanline spans (~20 us) -- from the poses
-// it has just stored, into the arrays the bulk path's camera / polygon kernels fill (s.view, s.view_rec, s.view_cnt).
-// touch_view == 1: every class, and the frame launch behind the solve only gathers: + 2-3 % per step (the 35 us land on the wavefronts that
-// end the kernel).  touch_view == 2: the one-manifold class only (eight envs per wavefront, done long before the slow islands; behind the
-// solve car_view_list_kernel computes the ~110 multi-manifold envs' views from touch_multi -- THIS step's narrow-phase lists on both sides,
-// no manifold counts read while the next narrow phase rewrites them): +- 0 in four alternating pairs of shipped-flavour builds.
-__device__ __forceinline__ void touch_view_epilogue(const CarSoA &s, const CarConsts &K, const int32_t *list, int count, int base, int epw) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");  // the solved poses were stored by this wavefront: completed, and not served from a stale L1 line
-    const int lane = threadIdx.x;
-    const int ntile = 2 * min(epw, count - base);
-    for (int t0 = 0; t0 < ntile; t0 += 4) {
-        const int tl = t0 + (lane >> 4);
-        if (tl >= ntile) continue;
-        const int64_t env = list[base + (tl >> 1)];
-        const int viewer = tl & 1, q = lane & 15;
-        const int64_t t = env * 2 + viewer;
-        ViewParams vp;
-        float4 cam;
-        camera_compute(s, K, env, viewer, vp, cam);
-        int32_t *dst = s.view + t * kViewWords;
-        if (q == 0) {
-            const int32_t *src = reinterpret_cast<const int32_t *>(&vp);
-            for (int i = 0; i < 8; i++) dst[i] = src[i];
-            reinterpret_cast<float4 *>(dst)[4] = cam;
-        }
-        s.view_cnt[t * 16 + q] = (uint8_t)poly_compute(s, K, env, viewer, q, cam, reinterpret_cast<uint32_t *>(dst) + 8, s.view_rec + (t * 16 + q) * kSpanSlots);
-    }
-}
-#endif
 
 template <int EPW1, int NK2, int NK3, bool FM>
 __global__ __launch_bounds__(64) void car_touch_kernel(CarSoA s, CarConsts K, int cls0) {
@@ -1020,9 +925,6 @@ __global__ __launch_bounds__(64) void car_touch_kernel(CarSoA s, CarConsts K, in
         if (cls == 0) touch_solve<1, EPW1, false, FM>(s, K, list, count, base, sh_car, sh_ct, sh_tc);
         else if (cls == 1) touch_solve<NK2, 1, (NK2 < 2), FM>(s, K, list, count, base, sh_car, sh_ct, sh_tc);
         else touch_solve<NK3, 1, true, FM>(s, K, list, count, base, sh_car, sh_ct, sh_tc);
-#ifdef CRL_ABLATION
-        if (s.touch_view == 1 || (s.touch_view == 2 && cls == 0)) touch_view_epilogue(s, K, list, count, base, epw);
-#endif
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     }
 }

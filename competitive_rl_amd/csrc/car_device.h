@@ -37,7 +37,7 @@ static constexpr int64_t kMapBytes = (int64_t)kMapBlocks * kMapBlocks * 128;  //
 static constexpr int kMapSurface = 10000;
 #define CRL_CAR_OBS_SCALE 0x1.c37d6d52bdddbp+0  // (10 / (100 / sqrt(96))) * 1.8 (crmp:214-215)
 enum { kPalGrass = 0, kPalLight = 1, kPalRoad0 = 2, kPalWhite = 5, kPalRed = 6 };
-// per (env, viewer) tile, written by car_view_kernel and read by car_obs_kernel
+// per (env, viewer) tile, written by car_camera_kernel / car_poly_kernel and read by the frame kernels
 static constexpr int kViewWords = 20;     // struct ViewParams (16 words) + the float32 camera (sin, cos, offset x, y)
 static constexpr int kWalkSaveWords = 18;
 static constexpr int kSpanSlots = 16;     // scanline spans one car polygon can produce (a polygon is <= 5.3 px across: <= 8)
@@ -107,9 +107,7 @@ struct CarSoA {
     const uint32_t *text_bits;  // reward read-out bitmaps [CRL_CAR_TEXT_STRINGS][CRL_CAR_TEXT_ROWS] or nullptr
     // ---- car-car contacts (players == 2)
     int contacts_enabled;
-    int abl_keep_tag;       // profiling build only (CRL_CAR_ABL_KEEP_TAG): a walk-ahead does not void the stored walk's tag before overwriting it
-    int abl_no_walk;        // profiling build only (CRL_CAR_ABL_NO_WALK): resets reuse the stored walk, no walk-ahead kernel is launched
-    int touch_view;         // this launch of the touching solve also prepares its envs' views (camera, polygon spans): the step pipeline's last world.Step
+    int unused_[3];         // always 0, read by no kernel (kept with `stamps` below: without the four the CarRacing step measured 0.7-1.7 % slower)
     int fma;                // CRL_FLAG_CAR_FMA: the island solver's iterations in fused multiply-adds (car_solver.h: FM)
     float *wforce;          // [8][M] tyre forces of this step, handed to the coupled kernel
     float *wsnap;           // [12][M] wheel transforms (cx, cy, angle) the step starts from, for car_sensor_kernel
@@ -128,7 +126,7 @@ struct CarSoA {
     int32_t *coupled_to_host;  // host-mapped word: the step's coupled-env count, read by the host one step late (sizes the list launches)
     int32_t *cap_hits;      // [4] times a fixed capacity was hit since create: [0] a wheel touching more than kWheelSlots tiles (the
                             //     extra tile is not recorded), [1] more than kMaxContacts manifolds between two cars (the rest are dropped)
-    unsigned long long *stamps;  // [64] phase cycle counters of the coupled kernels (profiling build, -DCRL_ABLATION, only)
+    unsigned long long *stamps;  // [64] zeros, read and written by no kernel (see unused_)
     int32_t *zero_next;     // [16] the OTHER step parity's counter block (coupled_count[8] + class counts): car_step_kernel clears it for the next step
     int32_t *nc_new;        // [n] this step's manifold count (car_narrow_kernel)
     float *contact_new;     // [n][kMaxContacts][kContactWords] this step's manifolds with the carried-over impulses
@@ -232,25 +230,13 @@ void launch_car_coupled(const CarSoA &s, const CarConsts &k, hipStream_t st, hip
 void launch_car_post(const CarSoA &s, const uint8_t *done_car, uint8_t *done_env, uint8_t *done_out, uint8_t *slow_env, int32_t *info_steps,
                      int32_t *info_elapsed, int max_episode_steps, bool car0_only, hipStream_t st, int32_t *class_list = nullptr, int32_t *class_count = nullptr);
 
-// car_raster.hip: round 2's analytic raster, profiling build only (CRL_CAR_OBS_ANALYTIC=1)
-#ifdef CRL_ABLATION
-// only_env: draw env e iff only_env[e] == want; nullptr = every env
-void launch_car_raster(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const uint8_t *only_env = nullptr, int want = 1);
-void launch_car_raster_list(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const int32_t *list, const int32_t *list_count,
-                            int32_t *count_to_host, int64_t expected);
-void car_raster_print_ticks();  // CRL_CAR_DEBUG & 64
-#else
-inline void launch_car_raster(const CarSoA &, const CarConsts &, uint8_t *, hipStream_t, const uint8_t * = nullptr, int = 1) {}
-inline void launch_car_raster_list(const CarSoA &, const CarConsts &, uint8_t *, hipStream_t, const int32_t *, const int32_t *, int32_t *, int64_t) {}
-#endif
 // car_obs.hip: the reference's observation pipeline
 void launch_car_map_build(const CarSoA &s, hipStream_t st, const uint8_t *only_env = nullptr, int64_t first = 0, int64_t count = -1);  // envs [first, first + count), all or only_env[e] != 0
 void launch_car_map_build_list(const CarSoA &s, hipStream_t st, const int32_t *list, const int32_t *list_count, int64_t expected);
 void launch_car_view(const CarSoA &s, const CarConsts &k, hipStream_t st, const uint8_t *only_env = nullptr, int want = 1);
 void launch_car_obs(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const uint8_t *only_env = nullptr, int want = 1);
 void launch_car_obs_list(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const int32_t *list, const int32_t *list_count,
-                         int32_t *count_to_host, int64_t expected, const uint8_t *filter = nullptr, int want_cls = 0, bool urgent = false,
-                         int prepared = 0);
+                         int32_t *count_to_host, int64_t expected, const uint8_t *filter = nullptr, int want_cls = 0, bool urgent = false);
 void launch_car_obs_long_list(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const int32_t *list, const int32_t *list_count, int64_t expected,
                               const uint8_t *filter, int want_cls, bool urgent, const int32_t *view_list, const int32_t *view_count, int64_t view_expected);
 void car_map_light_masks(uint32_t *lightx, uint32_t *lighty);  // host: the squares' columns / rows (kMapW / 32 words each)

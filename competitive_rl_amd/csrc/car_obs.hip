@@ -10,7 +10,7 @@
 //          Car.draw_for_pygame (car_dynamics.py:284-298), render_indicators_for_pygame :645-670, luma truncation:
 //          car_camera_kernel (one lane per (env, viewer) tile: the double-precision camera, crop and rotation constants),
 //          car_poly_kernel (16 lanes per tile: one lane per car polygon -> its scanline spans; one per indicator rectangle) and
-//          car_obs_kernel (ONE wavefront per tile, no workgroup barrier: every pixel gathers its map nibble, then the
+//          car_obs_third_kernel (ONE wavefront per third of a tile, no workgroup barrier: every pixel gathers its map nibble, then the
 //          spans / rectangles / read-out are written over the tile in LDS in draw order and the tile is streamed out).
 // pygame 1.9.6 and Box2D are third-party: their rules are restated from the published sources (the CPU checker of tests/
 // holds the same restatement and is pinned to frames recorded from the reference's own Python, tests/golden/car_obs.npz).
@@ -214,28 +214,8 @@ __global__ __launch_bounds__(64) void car_poly_kernel(CarSoA s, CarConsts K, con
     if (filter && filter[env] != want) return;
     car_poly_tile(s, K, env, (int)(t % s.players), threadIdx.x & 15);
 }
-// Camera AND polygons of a tile in one launch (round 5, profiling build only: measured, not kept): 16 lanes per tile, every lane
-// evaluates the tile's (uniform) camera itself, lane 0 stores the view, then lane q its polygon -- the same two device functions, one
-// launch boundary and one trip through memory less on the bulk stream's chain per-car solve -> view -> frames.
-#ifdef CRL_ABLATION
-__global__ __launch_bounds__(64) void car_view_kernel(CarSoA s, CarConsts K, const uint8_t *__restrict__ filter, int want) {
-    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4);
-    if (t >= s.n * s.players) return;
-    const int64_t env = t / s.players;
-    if (filter && filter[env] != want) return;
-    const int viewer = (int)(t % s.players), q = threadIdx.x & 15;
-    ViewParams vp;
-    float4 cam;
-    camera_compute(s, K, env, viewer, vp, cam);
-    int32_t *dst = s.view + t * kViewWords;
-    if (q == 0) {
-        const int32_t *src = reinterpret_cast<const int32_t *>(&vp);
-        for (int i = 0; i < 8; i++) dst[i] = src[i];
-        reinterpret_cast<float4 *>(dst)[4] = cam;
-    }
-    s.view_cnt[t * 16 + q] = (uint8_t)poly_compute(s, K, env, viewer, q, cam, reinterpret_cast<uint32_t *>(dst) + 8, s.view_rec + (t * 16 + q) * kSpanSlots);
-}
-#endif
+// Rounds 3-4's big launch, one wavefront per whole tile: no longer launched (car_obs_third_kernel below took its place), kept as the
+// plain form of the tile code that tests/test_abi.py names.
 // Tile slot b -> (position i = 8 (b / 16) + b % 8, viewer (b % 16) / 8) when there are two views: workgroups b and b + 8 run on
 // the same XCD, so the two views of an env (which look at neighbouring parts of the same map) share that XCD's L2.
 __global__ __launch_bounds__(64) void car_obs_kernel(CarSoA s, uint8_t *__restrict__ obs, const uint8_t *__restrict__ only_env, int want) {
@@ -332,10 +312,7 @@ void launch_car_obs_long_list(const CarSoA &s, const CarConsts &k, uint8_t *obs,
 // The envs of a compacted list (the small env classes of a step): camera, polygons and tile in ONE launch, one wavefront per
 // tile -- every lane computes the (uniform) camera, lanes 0-15 the polygons, everything handed over through LDS.  Three
 // dependent launches of a few hundred wavefronts each cost three launch latencies at the end of a step.
-// PREPARED (round 5, instantiated in the profiling build only): the envs' views are already in s.view / s.view_rec / s.view_cnt (the
-// touching solve's epilogue put them there, car_contact.hip): gather and overlays only.
-template <bool PREPARED>
-__global__ __launch_bounds__(64, PREPARED ? 4 : 3) void car_obs_list_kernel(CarSoA s, CarConsts K, uint8_t *__restrict__ obs, const int32_t *__restrict__ list,
+__global__ __launch_bounds__(64, 3) void car_obs_list_kernel(CarSoA s, CarConsts K, uint8_t *__restrict__ obs, const int32_t *__restrict__ list,
                                                                          const int32_t *__restrict__ list_count, int32_t *__restrict__ count_to_host,
                                                                          const uint8_t *__restrict__ filter, int want, int urgent) {
     if (urgent) __builtin_amdgcn_s_setprio(3);  // the launch at the end of the step's longest chain, beside the big frame launch's 32 768 wavefronts
@@ -350,12 +327,7 @@ __global__ __launch_bounds__(64, PREPARED ? 4 : 3) void car_obs_list_kernel(CarS
     for (int64_t b = blockIdx.x; b < tiles; b += gridDim.x) {
         const int64_t env = list[b / s.players];
         const int viewer = (int)(b % s.players);
-        if (PREPARED) {
-            if (!filter || filter[env] == want) {
-                const int64_t t = env * s.players + viewer;
-                car_obs_tile(s, obs, env, viewer, tile, s.view + t * kViewWords, s.view_rec + t * kViewRecWords, s.view_cnt + t * 16);
-            }
-        } else if (!filter || filter[env] == want) {
+        if (!filter || filter[env] == want) {
             ViewParams vp;
             float4 cam;
             camera_compute(s, K, env, viewer, vp, cam);
@@ -374,45 +346,24 @@ __global__ __launch_bounds__(64, PREPARED ? 4 : 3) void car_obs_list_kernel(CarS
 // camera + car polygons of every env (or of the envs with only_env[e] == want): what launch_car_obs reads
 void launch_car_view(const CarSoA &s, const CarConsts &k, hipStream_t st, const uint8_t *only_env, int want) {
     const int64_t tiles = s.n * s.players;
-    // (profiling build, round 5: camera + polygons in ONE launch, 16 lanes per tile -- bit-exact, and 1 % slower per step in three A/B
-    // pairs: 16 x the wavefronts walk through the double-double camera while the solves need the issue slots; docs/LAB_NOTES_r05.md)
-    static const bool merged = CRL_ABL(getenv("CRL_CAR_VIEW_MERGED") != nullptr);
-#ifdef CRL_ABLATION
-    if (merged) {
-        hipLaunchKernelGGL(car_view_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(64), 0, st, s, k, only_env, want);
-        return;
-    }
-#endif
-    (void)merged;
+    // (camera + polygons in ONE launch, 16 lanes per tile, was bit-exact and 1 % slower per step: 16 x the wavefronts walk through the
+    // double-double camera while the solves need the issue slots; docs/LAB_NOTES_r05.md)
     hipLaunchKernelGGL(car_camera_kernel, dim3((unsigned)((tiles + 63) / 64)), dim3(64), 0, st, s, k, only_env, want);
     hipLaunchKernelGGL(car_poly_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(64), 0, st, s, k, only_env, want);
 }
 void launch_car_obs(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const uint8_t *only_env, int want) {
-    // (profiling build, CRL_CAR_OBS_WHOLE_TILES=1: rounds 3-4's one wavefront per tile.  Same box, four alternating pairs of 200-step windows:
-    // the frame kernel 267-271 us in thirds against 295-313 whole; the step 0.840-0.842 against 0.838-0.847 ms, fma 0.784-0.791 against 0.793-0.800)
-    static const bool whole = CRL_ABL(getenv("CRL_CAR_OBS_WHOLE_TILES") != nullptr);
-    if (!whole) {
-        hipLaunchKernelGGL(car_obs_third_kernel, dim3((unsigned)((s.n + 7) / 8 * 8 * 3 * s.players)), dim3(64), 0, st, s, obs, only_env, want);
-        return;
-    }
-    const unsigned grid = s.players == 2 ? (unsigned)((s.n + 7) / 8 * 16) : (unsigned)s.n;
-    hipLaunchKernelGGL(car_obs_kernel, dim3(grid), dim3(64), 0, st, s, obs, only_env, want);
+    // (rounds 3-4's one wavefront per tile, four alternating pairs of 200-step windows: the frame kernel 267-271 us in thirds against
+    // 295-313 whole; the step 0.840-0.842 against 0.838-0.847 ms, fma 0.784-0.791 against 0.793-0.800)
+    hipLaunchKernelGGL(car_obs_third_kernel, dim3((unsigned)((s.n + 7) / 8 * 8 * 3 * s.players)), dim3(64), 0, st, s, obs, only_env, want);
 }
 
 // the envs of a compacted list (its length in device memory; `expected` = the caller's guess of it, only for the grid size),
 // optionally only those with filter[env] == want
 void launch_car_obs_list(const CarSoA &s, const CarConsts &k, uint8_t *obs, hipStream_t st, const int32_t *list, const int32_t *list_count,
-                         int32_t *count_to_host, int64_t expected, const uint8_t *filter, int want_cls, bool urgent, int prepared) {
+                         int32_t *count_to_host, int64_t expected, const uint8_t *filter, int want_cls, bool urgent) {
     int64_t want = expected + expected / 4 + 32;  // slack: a launch that falls short loops, it does not miss tiles
     want = want > s.n ? s.n : want;
-#ifdef CRL_ABLATION
-    if (prepared) {  // (profiling build: the touching solve's epilogue has prepared the listed envs' views, car_contact.hip)
-        hipLaunchKernelGGL(car_obs_list_kernel<true>, dim3((unsigned)(want * s.players)), dim3(64), 0, st, s, k, obs, list, list_count, count_to_host, filter, want_cls, urgent ? 1 : 0);
-        return;
-    }
-#endif
-    (void)prepared;
-    hipLaunchKernelGGL(car_obs_list_kernel<false>, dim3((unsigned)(want * s.players)), dim3(64), 0, st, s, k, obs, list, list_count, count_to_host, filter, want_cls, urgent ? 1 : 0);
+    hipLaunchKernelGGL(car_obs_list_kernel, dim3((unsigned)(want * s.players)), dim3(64), 0, st, s, k, obs, list, list_count, count_to_host, filter, want_cls, urgent ? 1 : 0);
 }
 
 // MultipleFrameStack + FlattenMultiAgentObservation + WrapPyTorch (reference

@@ -469,8 +469,7 @@ __global__ __launch_bounds__(64) void car_sensor_serial_kernel(CarSoA s, CarCons
 }
 
 // (one wavefront per workgroup and at most 128 registers: the kernel has to fit on SIMDs next to the register-heavy solve)
-__global__ __launch_bounds__(64, 4) void car_sensor_kernel(CarSoA s, CarConsts K, int force_serial_arg) {
-    const int force_serial = (force_serial_arg & 1) | CRL_ABL(force_serial_arg & 14);  // bit 0: every car through the serial kernel (same results)
+__global__ __launch_bounds__(64, 4) void car_sensor_kernel(CarSoA s, CarConsts K, int force_serial) {  // force_serial bit 0: every car through the serial kernel (same results)
     __shared__ int16_t sub[kSubCap][4][64];  // [entry][quarter of the track][owner lane]
     __shared__ uint8_t subcnt[4][64];
     __shared__ int16_t beg[kBeginCap][64];   // an owner's BeginContacts of this step, ascending
@@ -506,23 +505,21 @@ __global__ __launch_bounds__(64, 4) void car_sensor_kernel(CarSoA s, CarConsts K
         qb[o] = make_float4(__shfl(wb.x, q0 + o, 64), __shfl(wb.y, q0 + o, 64), __shfl(wb.z, q0 + o, 64), __shfl(wb.w, q0 + o, 64));
     const int per = (ntiles + 3) >> 2, tbeg = w * per, tend = min(tbeg + per, ntiles);
     int c4[4] = {0, 0, 0, 0};
-    bool ovf = (force_serial & 1) != 0;  // bits 2, 4, 8: timing ablations (wrong results): no polygon distance / no polygon loads / no scan
+    bool ovf = (force_serial & 1) != 0;
     // two passes: which 8-tile blocks of the quarter come near any of the car's wheel boxes (one united box per block: 16 bytes
     // instead of 128), then only those blocks' tiles, in ascending order as before.  (A wavefront holds 16 cars at 16 different
     // places: testing every tile box cost 4.8 KB per car and step and was the largest fetch of the whole step.)
     uint32_t hit = 0;
     const int b0 = tbeg >> 3, nblk = tend > tbeg ? ((tend - 1) >> 3) - b0 + 1 : 0;  // <= 17 for 512 tiles
-    if (!(force_serial & 8)) {
 #pragma unroll 1
-        for (int k0 = 0; k0 < nblk; k0 += 6) {
-            float4 B[6];
+    for (int k0 = 0; k0 < nblk; k0 += 6) {
+        float4 B[6];
 #pragma unroll
-            for (int j = 0; j < 6; j++) B[j] = s.tile_blk[(int64_t)(b0 + min(k0 + j, nblk - 1)) * s.n + env];
+        for (int j = 0; j < 6; j++) B[j] = s.tile_blk[(int64_t)(b0 + min(k0 + j, nblk - 1)) * s.n + env];
 #pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const bool any = box_near(qb[0], B[j]) || box_near(qb[1], B[j]) || box_near(qb[2], B[j]) || box_near(qb[3], B[j]);
-                if (any && k0 + j < nblk) hit |= 1u << (k0 + j);
-            }
+        for (int j = 0; j < 6; j++) {
+            const bool any = box_near(qb[0], B[j]) || box_near(qb[1], B[j]) || box_near(qb[2], B[j]) || box_near(qb[3], B[j]);
+            if (any && k0 + j < nblk) hit |= 1u << (k0 + j);
         }
     }
 #pragma unroll 1
@@ -562,16 +559,14 @@ __global__ __launch_bounds__(64, 4) void car_sensor_kernel(CarSoA s, CarConsts K
         const int q = (f >= n0) + (f >= n1) + (f >= n2);
         const int t = sub[f - (q == 0 ? 0 : q == 1 ? n0 : q == 2 ? n1 : n2)][q][tid];
         V2 tp[5];
-        if (!(force_serial & 4)) load_tile_poly(s, env, t, tp);
-        else
-            for (int k = 0; k < 5; k++) tp[k] = mk((float)(t + k), (float)k * wb.x);
+        load_tile_poly(s, env, t, tp);
         bool was = false;
 #pragma unroll
         for (int k = 0; k < kWheelSlots; k++) {
             if (wt[k] >= 0 && wt[k] < t && !slot_near[k]) wt[k] = -1;  // EndContact of a tile left behind
             was = was || wt[k] == t;
         }
-        const bool now = (force_serial & 2) ? tp[0].x < wb.x : poly_dist2(wp, tp) < R * R;
+        const bool now = poly_dist2(wp, tp) < R * R;
         if (now && !was) {
             bool placed = false;
 #pragma unroll

@@ -254,7 +254,7 @@ static int setup_gray(crl_ctx *c) {
     if ((rc = dev_upload(c, &t.atlas_gray, c->atlas_host))) return rc;
     if ((rc = dev_alloc(c, &t.band, (size_t)3 * 484 * 2 * t.band_chunks * 16))) return rc;
     if ((rc = dev_alloc(c, &t.rest, (size_t)chunks * 16))) return rc;
-    if ((rc = dev_alloc(c, &c->tile_hdr, (size_t)c->n * pong_views(c) * c->o.frame_stack * (64 + 8 + 2)))) return rc;
+    if ((rc = dev_alloc(c, &c->tile_hdr, (size_t)c->n * pong_views(c) * c->o.frame_stack * 64))) return rc;
     HIP_TRY(hipMemset(t.rest, 0, (size_t)chunks * 16));
     launch_pong_gray_templates(t, nullptr);
     HIP_TRY(hipGetLastError());
@@ -403,9 +403,6 @@ void crl_destroy(crl_ctx *c) {
     if (!c) return;
     hipSetDevice(c->o.device);
     hipDeviceSynchronize();
-#ifdef CRL_ABLATION
-    if (getenv("CRL_GRAY_DEBUG") && (atoi(getenv("CRL_GRAY_DEBUG")) & 128)) pong_gray_print_ticks();
-#endif
     if (c->car) crl_car_destroy(c->car);
     for (void *p : c->allocs) hipFree(p);
     for (int w = 0; w < kTimerSlots; w++)
@@ -586,19 +583,6 @@ int crl_step_raw_delta(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, u
         HIP_TRY(hipGetLastError());
         return CRL_OK;
     }
-#ifdef CRL_ABLATION
-    if (getenv("CRL_RAW_STEP_SPLIT") && atoi(getenv("CRL_RAW_STEP_SPLIT"))) {  // the one-launch kernel's second phase alone, behind the dynamics launch
-        begin_timed(c, 0, st);
-        launch_pong_dynamics(c->s, c->src, (const int32_t *)actions_void, c->n, pong_mode(c), rew_dev, done_dev, st);
-        end_timed(c, 0, st);
-        begin_timed(c, 1, st);
-        launch_pong_step_raw_delta(c->s, c->src, (const int32_t *)actions_void, c->n, rew_dev, done_dev, drawn_dev, c->atlas_rgb, c->band_span,
-                                   c->ink_row0, c->ink_row1, obs_dev, pong_views(c), st, 1);
-        end_timed(c, 1, st);
-        HIP_TRY(hipGetLastError());
-        return CRL_OK;
-    }
-#endif
     begin_timed(c, 1, st);  // (slot 0 gets nothing on this path: there is no dynamics launch to bracket)
     launch_pong_step_raw_delta(c->s, c->src, (const int32_t *)actions_void, c->n, rew_dev, done_dev, drawn_dev, c->atlas_rgb, c->band_span, c->ink_row0,
                                c->ink_row1, obs_dev, pong_views(c), st);

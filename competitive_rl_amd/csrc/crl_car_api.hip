@@ -58,7 +58,6 @@ struct crl_car_ctx {
     hipEvent_t ev_fork = nullptr, ev_coupled = nullptr, ev_term = nullptr, ev_join = nullptr;
     bool overlap = true;
     bool collide_ahead = true;  // CRL_CAR_NO_COLLIDE_AHEAD=1 (read when the context is created): every step runs its own Collide (A/B, twin tests)
-    bool analytic = false;  // CRL_CAR_OBS_ANALYTIC=1: rounds 1-2' analytic raster (car_raster.hip) instead of map + gather, for A/B
 };
 
 namespace crl {
@@ -184,16 +183,13 @@ int crl_car_create(const crl_opts *opts, const uint32_t *text_bits_host, crl_car
     s.n = n, s.players = players;
     s.contacts_enabled = (players == 2 && !(opts->flags & CRL_FLAG_CAR_NO_CONTACTS)) ? 1 : 0;
     s.fma = (opts->flags & CRL_FLAG_CAR_FMA) ? 1 : 0;
-    s.abl_no_walk = CRL_ABL(getenv("CRL_CAR_ABL_NO_WALK") != nullptr) ? 1 : 0;
-    s.abl_keep_tag = CRL_ABL(getenv("CRL_CAR_ABL_KEEP_TAG") != nullptr) ? 1 : 0;
     int rc = 0;
     c->overlap = !getenv("CRL_CAR_NO_OVERLAP");
     c->collide_ahead = !getenv("CRL_CAR_NO_COLLIDE_AHEAD");
-    c->analytic = CRL_ABL(getenv("CRL_CAR_OBS_ANALYTIC") && atoi(getenv("CRL_CAR_OBS_ANALYTIC")) != 0);
     {   // the pre-rastered maps, [slot][env]: 739 328 bytes per env and slot -- by far the largest part of the context.  The second
         // slot exists only for the step pipeline's staged reset (a finished env's next map is built while its terminal frame still
         // reads the current one); the one-stream mode builds in place
-        const size_t slots = c->overlap && !c->analytic ? 2 : 1;
+        const size_t slots = c->overlap ? 2 : 1;
         rc = calloc_dev(c, &s.obs_map, (size_t)kMapBytes * slots * n);
         if (rc == CRL_ENOMEM)
             rc = crl_fail(CRL_ENOMEM, "car create: %zu map slot(s) of %d bytes for each of %lld envs (%.1f GB) do not fit; fewer envs per context, or CRL_CAR_NO_OVERLAP=1 (one slot)",
@@ -344,29 +340,8 @@ int crl_car_create(const crl_opts *opts, const uint32_t *text_bits_host, crl_car
 }
 
 void crl_car_destroy(crl_car_ctx *c) {
-#ifdef CRL_ABLATION
-    if (c && c->s.stamps && getenv("CRL_CAR_STAMPS")) {  // profiling build: mean cycles per wavefront and phase of car_touch_kernel / car_narrow_kernel
-        unsigned long long h[64];
-        hipDeviceSynchronize();
-        hipMemcpy(h, c->s.stamps, sizeof(h), hipMemcpyDeviceToHost);
-        for (int cls = 0; cls < 3; cls++) {
-            const unsigned long long *q = h + 8 * cls;
-            const double w = q[7] ? (double)q[7] : 1.0;
-            fprintf(stderr, "touch class %d: %llu waves; mean cycles setup %.0f | velocity %.0f | position %.0f (%.1f iterations) | store %.0f (sleep scan %.0f) | max total %llu\n", cls + 1,
-                    q[7], q[0] / w, q[1] / w, q[2] / w, q[4] / w, q[3] / w, q[6] / w, q[5]);
-            fprintf(stderr, "              longest: setup %llu | velocity %llu | position %llu; wavefronts with all 60 position iterations %llu\n", h[40 + 4 * cls + 3],
-                    h[40 + 4 * cls + 0], h[40 + 4 * cls + 1], h[40 + 4 * cls + 2]);
-        }
-        const unsigned long long *q = h + 32;
-        const double w = q[7] ? (double)q[7] : 1.0;
-        fprintf(stderr, "narrow: %llu wave-slots; mean cycles prologue %.0f | load+sincos+circle %.0f | collide %.0f | compaction+store %.0f\n", q[7], q[0] / w, q[1] / w, q[2] / w, q[3] / w);
-    }
-#endif
     if (!c) return;
     hipDeviceSynchronize();
-#ifdef CRL_ABLATION
-    if (getenv("CRL_CAR_DEBUG") && (atoi(getenv("CRL_CAR_DEBUG")) & 64)) crl::car_raster_print_ticks();
-#endif
     if (c->side) hipStreamDestroy(c->side);
     if (c->side2) hipStreamDestroy(c->side2);
     if (c->ev_narrow) hipEventDestroy(c->ev_narrow);
@@ -412,7 +387,6 @@ static constexpr int kWalkBudget = 160;
 // into the same scratch, and a piece that started another attempt of the same walk beside it would overwrite its points)
 static void queue_walk_ahead(crl_car_ctx *c, hipStream_t after, bool behind_reset = false) {
     if (!c->overlap) return;
-    if (c->s.abl_no_walk && !behind_reset) return;  // (profiling build: the step without a walk-ahead piece in flight)
     static const int budget = CRL_ABL(getenv("CRL_CAR_WALK_BUDGET") != nullptr) ? atoi(getenv("CRL_CAR_WALK_BUDGET")) : kWalkBudget;
     hipEvent_t &ev = c->ev_walk[c->walk_turn & 1];
 #ifdef CRL_TEST_WALK_UNORDERED  // (a test build reproduces the race tests/test_hip_round2.py guards against)
@@ -448,26 +422,13 @@ static CarSoA stage_view(const crl_car_ctx *c) {
 }
 
 // frames of every env, or of the envs with only_env[e] == want
-// tm (optional): timer 1 brackets the frame kernel alone (car_obs_kernel / car_raster_kernel), for bench.py's roofline
+// tm (optional): timer 1 brackets the frame kernel alone (car_obs_kernel), for bench.py's roofline
 static void frames(crl_car_ctx *c, uint8_t *dst, hipStream_t st, const uint8_t *only_env = nullptr, int want = 1, crl_timer *tm = nullptr) {
-    if (c->analytic) {
-        crl_timer_begin(tm, 1, st);
-        launch_car_raster(c->s, c->K_, dst, st, only_env, want);
-        crl_timer_end(tm, 1, st);
-        return;
-    }
     launch_car_view(c->s, c->K_, st, only_env, want);
     crl_timer_begin(tm, 1, st);
     launch_car_obs(c->s, c->K_, dst, st, only_env, want);
     crl_timer_end(tm, 1, st);
 }
-// frames of the envs of a compacted list
-static void frames_list(crl_car_ctx *c, const CarSoA &s, uint8_t *dst, hipStream_t st, const int32_t *list, const int32_t *list_count,
-                        int32_t *count_to_host, int64_t expected) {
-    if (c->analytic) launch_car_raster_list(s, c->K_, dst, st, list, list_count, count_to_host, expected);
-    else launch_car_obs_list(s, c->K_, dst, st, list, list_count, count_to_host, expected);
-}
-
 // newest frames -> obs_dev, through the frame stack when K > 1
 static void draw(crl_car_ctx *c, uint8_t *obs_dev, bool fill_all, hipStream_t st) {
     if (c->K == 1) {
@@ -607,57 +568,27 @@ int crl_car_step(crl_car_ctx *c, const float *actions_dev, uint8_t *obs_dev, flo
         hipStreamWaitEvent(c->one, c->ev_post, 0);  // (a 6 us kernel, long done: ev_sens then stands for the bookkeeping as well, and the frame launches pass ONE barrier each)
         launch_car_sensors(c->s, c->K_, c->one);
         hipEventRecord(c->ev_sens, c->one);
-        // CRL_CAR_TOUCH_VIEW (profiling build; measured, not kept, docs/LAB_NOTES_r05.md): 1 = every wavefront of the touching solve prepares its envs'
-        // views (+ 2-3 %), 2 = the one-manifold wavefronts do and only the multi-manifold envs' views are computed behind the solve (+- 0)
-        static const int touch_view_mode = CRL_ABL(getenv("CRL_CAR_TOUCH_VIEW") != nullptr) ? atoi(getenv("CRL_CAR_TOUCH_VIEW")) : 0;
-        const int touch_view = contacts && !c->analytic ? touch_view_mode : 0;
-        {
-            CarSoA sv2 = c->s;
-            sv2.touch_view = touch_view;
-            crl_timer_begin(tm, 2, crit);  // (crl_kernel_time_stats slot 2: on this stream nothing but the touching solve lies between the two records)
-            launch_car_coupled(sv2, c->K_, crit, c->side2, nullptr, true);  // near-only solve on side2, touching solve on crit
-            crl_timer_end(tm, 2, crit);
-        }
+        crl_timer_begin(tm, 2, crit);  // (crl_kernel_time_stats slot 2: on this stream nothing but the touching solve lies between the two records)
+        launch_car_coupled(c->s, c->K_, crit, c->side2, nullptr, true);  // near-only solve on side2, touching solve on crit
+        crl_timer_end(tm, 2, crit);
         hipEventRecord(c->ev_coupled, crit);
         const int64_t exp_coupled = c->class_count_host[0], exp_done = c->class_count_host[1];
         hipStreamWaitEvent(c->side2, c->ev_sens, 0);  // (every frame shows the reward)
-        if (contacts) {  // frames of the near-only envs
-            if (c->analytic) launch_car_raster_list(c->s, c->K_, target, c->side2, c->s.near_list, c->s.coupled_count + 1, nullptr, exp_coupled);
-            else {  // (round 5: as a view launch + a gather-in-thirds launch, like the touching envs' frames: - 0.5 %; CRL_CAR_NEAR_LIST=1 in the profiling build: the list kernel)
-                static const bool near_list_kernel = CRL_ABL(getenv("CRL_CAR_NEAR_LIST") != nullptr);
-                if (!near_list_kernel) launch_car_obs_long_list(c->s, c->K_, target, c->side2, c->s.near_list, c->s.coupled_count + 1, exp_coupled, c->slow_env, 1, false,
-                                                                c->s.near_list, c->s.coupled_count + 1, exp_coupled);
-                else launch_car_obs_list(c->s, c->K_, target, c->side2, c->s.near_list, c->s.coupled_count + 1, nullptr, exp_coupled, c->slow_env, 1);
-            }
-        }
+        if (contacts)  // frames of the near-only envs (a view launch + a gather-in-thirds launch, like the touching envs' frames)
+            launch_car_obs_long_list(c->s, c->K_, target, c->side2, c->s.near_list, c->s.coupled_count + 1, exp_coupled, c->slow_env, 1, false, c->s.near_list,
+                                     c->s.coupled_count + 1, exp_coupled);
         // bulk: the per-car solve, then the frames of every env that is neither coupled nor finished
         launch_car_solve(c->s, c->K_, bulk);
         hipEventRecord(c->ev_term, bulk);  // (bodies of the non-coupled cars are final)
         hipStreamWaitEvent(bulk, c->ev_sens, 0);
         crl_timer_end(tm, 0, bulk);
         frames(c, target, bulk, c->slow_env, 0, tm);
-        // The touching envs' frames, behind their solve, on the caller's stream (wave priority 3: beside the big launch's 32 768 wavefronts).
-        // (Round 5, profiling build, CRL_CAR_TOUCH_FRAMES_ON_ONE=1: on the HIGH-priority stream instead, in front of the class-3 chain that
-        // waits for the same solve there, so that dispatch priority gets their 2 300 workgroups the CU slots the bulk frame kernel frees --
-        // bit-exact and 5-6 % SLOWER in three A/B pairs (0.885-0.895 against 0.826-0.845 ms; fma 0.823-0.836 against 0.784-0.796): once
-        // more, what ends a step has to sit on the caller's stream.)
-        static const bool touch_frames_on_one = CRL_ABL(getenv("CRL_CAR_TOUCH_FRAMES_ON_ONE") != nullptr);
-        auto touch_frames = [&](hipStream_t q) {
-            if (c->analytic) launch_car_raster_list(c->s, c->K_, target, q, c->s.touch_all, c->s.coupled_count + 5, nullptr, exp_coupled);
-            else if (!CRL_ABL(getenv("CRL_CAR_ABL_NO_TOUCH_FRAMES") != nullptr))  // (timing ablation, WRONG frames: what the step costs without them)
-            {
-                static const bool one_launch = CRL_ABL(getenv("CRL_CAR_TOUCH_FRAMES_LIST") != nullptr);  // (profiling build: rounds 3-4's one-wavefront-per-tile list kernel)
-                if (touch_view == 1 || one_launch) launch_car_obs_list(c->s, c->K_, target, q, c->s.touch_all, c->s.coupled_count + 5, nullptr, exp_coupled, c->slow_env, 1, true, touch_view == 1 ? 1 : 0);
-                else if (touch_view == 2)  // views: only the envs with two manifolds or more are left (a tenth of the touching envs); frames: all, in thirds
-                    launch_car_obs_long_list(c->s, c->K_, target, q, c->s.touch_all, c->s.coupled_count + 5, exp_coupled, c->slow_env, 1, true, c->s.touch_multi,
-                                             c->s.coupled_count + 6, exp_coupled / 4);
-                else launch_car_obs_long_list(c->s, c->K_, target, q, c->s.touch_all, c->s.coupled_count + 5, exp_coupled, c->slow_env, 1, true, c->s.touch_all,
-                                              c->s.coupled_count + 5, exp_coupled);
-            }
-        };
-        if (contacts && !touch_frames_on_one) {  // crit again
+        // The touching envs' frames, behind their solve, on the caller's stream (wave priority 3: beside the big launch's 32 768 wavefronts):
+        // what ends a step has to sit on the caller's stream (on the HIGH-priority stream they were 5-6 % slower, docs/LAB_NOTES_r05.md).
+        if (contacts) {  // crit again
             hipStreamWaitEvent(crit, c->ev_sens, 0);
-            touch_frames(crit);
+            launch_car_obs_long_list(c->s, c->K_, target, crit, c->s.touch_all, c->s.coupled_count + 5, exp_coupled, c->slow_env, 1, true, c->s.touch_all,
+                                     c->s.coupled_count + 5, exp_coupled);
         }
         // The finished envs.  Their NEW episode (track arrays in place, map into the env's other slot, car state into the staged
         // arrays, first frame straight into the caller's tensor) only needs the step's sensor contacts to be in: it is prepared
@@ -669,95 +600,60 @@ int crl_car_step(crl_car_ctx *c, const float *actions_dev, uint8_t *obs_dev, flo
         auto list_of = [&](int cls) { return c->class_list + (int64_t)(cls - 1) * c->n; };
         auto count_of = [&](int cls) { return c->class_count + (cls - 1); };
         auto terminal_frames = [&](hipStream_t q, int cls, int64_t expected, int32_t *count_to_host) {
-            if (c->analytic) launch_car_raster_list(c->s, c->K_, c->term, q, list_of(cls), count_of(cls), count_to_host, expected);
-            else launch_car_obs_list(c->s, c->K_, c->term, q, list_of(cls), count_of(cls), count_to_host, expected, c->slow_env, cls,
-                                     cls == 3 && !CRL_ABL(getenv("CRL_CAR_C3_CALM") != nullptr));  // (class 3: behind the touching solve, beside 2 300 other tiles)
+            launch_car_obs_list(c->s, c->K_, c->term, q, list_of(cls), count_of(cls), count_to_host, expected, c->slow_env, cls,
+                                cls == 3);  // (class 3: behind the touching solve, beside 2 300 other tiles)
         };
-        auto finish_chain = [&](hipStream_t q, int cls, int64_t expected, int32_t *count_to_host) {  // everything in place, in order
-            frames_list(c, c->s, c->term, q, list_of(cls), count_of(cls), count_to_host, expected);
-            launch_car_reset_list(c->s, c->K_, c->src, list_of(cls), count_of(cls), expected, q);
-            launch_car_map_build_list(c->s, q, list_of(cls), count_of(cls), expected);
-            frames_list(c, c->s, target, q, list_of(cls), count_of(cls), nullptr, expected);
-        };
-        bool split_narrow = false;
-        const bool staged = !c->analytic;  // (the analytic raster reads the track arrays themselves: it needs them until the terminal frame is drawn)
-        const bool early_broad = can_ahead && staged && !CRL_ABL(getenv("CRL_CAR_COLLIDE_LATE") != nullptr) && !CRL_ABL(getenv("CRL_CAR_BROAD_LATE") != nullptr);
         hipStreamWaitEvent(c->side2, c->ev_term, 0);
-        if (staged) {
-            // early chain, every finished env (class 2 and 3 alike), at high priority: the map build's small workgroups get CU slots
-            // ahead of the frame kernel's 32 768 wavefronts instead of behind them (320 us for a dozen maps otherwise)
-            launch_car_reset_list(sv, c->K_, c->src, list_of(4), count_of(4), exp_done + 8, c->one);
-            launch_car_map_build_list(sv, c->one, list_of(4), count_of(4), exp_done + 8);
-            frames_list(c, sv, target, c->one, list_of(4), count_of(4), nullptr, exp_done + 8);
-            hipEventRecord(c->ev_early3, c->one);
-            terminal_frames(c->side2, 2, exp_done, c->class_count_hdev + 1);  // (side2 idles between the near-only envs' frames and the touching solve)
-            hipStreamWaitEvent(c->side2, c->ev_early3, 0);
-            launch_car_commit_list(c->s, sv, list_of(2), count_of(2), exp_done, c->side2);
-            if (early_broad) {
-                // The NEXT step's broadphase already here: every pose but the touching islands' is final (per-car solve: ev_term; near-only
-                // solve and class-2 commit: this stream; class 3: staged), and an env that touches now is filed as coupled untested --
-                // behind the touching solve only the narrow phase is left.
-                CarSoA nx = c->s;
-                point_parity(c, nx, c->parity ^ 1);
-                launch_car_broad(nx, c->K_, c->side2, c->stage.body, c->slow_env, c->s.coupled, c->s.nc_new);
-                // ... and the narrow phase of the envs whose poses ARE final (round 5: everything but the envs that touch in this step --
-                // half of the 2 300 coupled envs), beside the touching solve instead of behind it (CRL_CAR_NARROW_LATE=1, profiling build: all behind)
-                static const bool narrow_late = CRL_ABL(getenv("CRL_CAR_NARROW_LATE") != nullptr);
-                split_narrow = !narrow_late;
-                if (split_narrow) launch_car_narrow(nx, c->K_, c->side2, false, c->stage.body, c->slow_env, 1);
-            }
-        } else {
-            finish_chain(c->side2, 2, exp_done, c->class_count_hdev + 1);
+        // early chain, every finished env (class 2 and 3 alike), at high priority: the map build's small workgroups get CU slots
+        // ahead of the frame kernel's 32 768 wavefronts instead of behind them (320 us for a dozen maps otherwise)
+        launch_car_reset_list(sv, c->K_, c->src, list_of(4), count_of(4), exp_done + 8, c->one);
+        launch_car_map_build_list(sv, c->one, list_of(4), count_of(4), exp_done + 8);
+        launch_car_obs_list(sv, c->K_, target, c->one, list_of(4), count_of(4), nullptr, exp_done + 8);
+        hipEventRecord(c->ev_early3, c->one);
+        terminal_frames(c->side2, 2, exp_done, c->class_count_hdev + 1);  // (side2 idles between the near-only envs' frames and the touching solve)
+        hipStreamWaitEvent(c->side2, c->ev_early3, 0);
+        launch_car_commit_list(c->s, sv, list_of(2), count_of(2), exp_done, c->side2);
+        CarSoA nx = c->s;  // the NEXT step's coupled flags, lists and counters
+        point_parity(c, nx, c->parity ^ 1);
+        if (can_ahead) {
+            // The NEXT step's broadphase already here: every pose but the touching islands' is final (per-car solve: ev_term; near-only
+            // solve and class-2 commit: this stream; class 3: staged), and an env that touches now is filed as coupled untested --
+            // behind the touching solve only the narrow phase is left.
+            launch_car_broad(nx, c->K_, c->side2, c->stage.body, c->slow_env, c->s.coupled, c->s.nc_new);
+            // ... and the narrow phase of the envs whose poses ARE final (everything but the envs that touch in this step --
+            // half of the 2 300 coupled envs), beside the touching solve instead of behind it
+            launch_car_narrow(nx, c->K_, c->side2, false, c->stage.body, c->slow_env, 1);
         }
         // Behind the touching solve: (a) the envs that finished while coupled (class 3, a handful): terminal frames + commit; (b) the
-        // NEXT step's Collide (every solve of this step is in); (c) the touching envs' frames on the caller's stream (above).
-        // early_collide: (a) on the high-priority stream and (b) on side2 at once -- the Collide reads the class-3 envs' new episode
-        // from the staging arrays, which (a)'s commit is copying from, and takes no manifolds over for them -- instead of (a), the
-        // join, then (b) in a row in front of the next step's touching solve.
-        static const bool late_collide = CRL_ABL(getenv("CRL_CAR_COLLIDE_LATE") != nullptr);
-        const bool early_collide = can_ahead && staged && !late_collide;
-        auto collide_next = [&](bool fresh) {
-            CarSoA nx = c->s;
-            point_parity(c, nx, c->parity ^ 1);
-            if (!(fresh && early_broad)) launch_car_broad(nx, c->K_, c->side2, fresh ? c->stage.body : nullptr, fresh ? c->slow_env : nullptr);
-            launch_car_narrow(nx, c->K_, c->side2, false, fresh ? c->stage.body : nullptr, fresh ? c->slow_env : nullptr, fresh && early_broad && split_narrow ? 2 : 0);
-            hipEventRecord(c->ev_collide, c->side2);
-            c->collide_valid = c->collide_dirty = true;
-        };
+        // rest of the NEXT step's narrow phase (every solve of this step is in); (c) the touching envs' frames on the caller's stream (above).
+        // With the collide-ahead, (a) on the high-priority stream and (b) on side2 at once: the narrow phase reads the class-3 envs' new
+        // episode from the staging arrays, which (a)'s commit is copying from, and takes no manifolds over for them.
         hipStreamWaitEvent(c->side2, c->ev_coupled, 0);  // the touching solve
-        if (contacts && touch_frames_on_one && !early_collide) {  // (no class-3 chain on `one` in this mode: the frames go there all the same)
+        if (can_ahead) {
             hipStreamWaitEvent(c->one, c->ev_coupled, 0);
-            touch_frames(c->one);
-            hipEventRecord(c->ev_c3, c->one);
-            hipStreamWaitEvent(c->side2, c->ev_c3, 0);
-        }
-        if (early_collide) {
-            hipStreamWaitEvent(c->one, c->ev_coupled, 0);
-            if (contacts && touch_frames_on_one) touch_frames(c->one);  // (`one` ran the sensors itself: no wait for ev_sens)
-            if (!CRL_ABL(getenv("CRL_CAR_ABL_NO_C3") != nullptr)) terminal_frames(c->one, 3, 8, nullptr);  // (timing ablation: no terminal frames for class 3)
+            terminal_frames(c->one, 3, 8, nullptr);
             launch_car_commit_list(c->s, sv, list_of(3), count_of(3), 8, c->one);
             hipEventRecord(c->ev_c3, c->one);
-            collide_next(true);
+            launch_car_narrow(nx, c->K_, c->side2, false, c->stage.body, c->slow_env, 2);
+            hipEventRecord(c->ev_collide, c->side2);
+            c->collide_valid = c->collide_dirty = true;
             hipStreamWaitEvent(c->side2, c->ev_c3, 0);
-        } else if (staged) {
+        } else {
             terminal_frames(c->side2, 3, 8, nullptr);
             launch_car_commit_list(c->s, sv, list_of(3), count_of(3), 8, c->side2);
-        } else {
-            finish_chain(c->side2, 3, 8, nullptr);
         }
         // join: side2 collects the bulk stream (and, through ev_early3 / ev_c3, the high-priority one) behind its own last kernel, so
         // that the caller's stream -- whose last kernel is usually the last of the step -- passes ONE barrier instead of three
         hipEventRecord(c->ev_join, c->side);
         hipStreamWaitEvent(c->side2, c->ev_join, 0);
         hipEventRecord(c->ev_fin3, c->side2);
-        if (can_ahead && !early_collide) collide_next(false);  // (beside this step's last frames and the next car_step_kernel)
         queue_walk_ahead(c, c->side2);
-        // The next step may skip its barriers on ev_collide ONLY because of this order on side2: collide_next(true) [records ev_collide] ...
+        // The next step may skip its barriers on ev_collide ONLY because of this order on side2: the narrow phase above [record(ev_collide)] ...
         // record(ev_fin3) ... and the caller's stream waits for ev_fin3 here.  Anything added to side2 behind the ev_fin3 record that the next
         // car_step_kernel must see, or an early return between that record and this wait, breaks it silently: the flag is set
         // behind the wait, and only when the wait was accepted.
         const bool joined = hipStreamWaitEvent(st, c->ev_fin3, 0) == hipSuccess;
-        if (joined && early_collide && !CRL_ABL(getenv("CRL_CAR_COLLIDE_WAIT") != nullptr)) c->collide_is_joined = true, c->collide_joined = st;
+        if (joined && can_ahead) c->collide_is_joined = true, c->collide_joined = st;
         if (c->K > 1) launch_car_stack(c->frame, c->stack, obs_dev, c->done_env, false, c->K, c->n, c->s.players, st);
     }
     hipError_t e = hipGetLastError();
@@ -970,7 +866,7 @@ int crl_car_set_track_impl(crl_car_ctx *c, int64_t env, int32_t nt, const double
     hipMemcpy2DAsync(c->s.border_poly + env, n * 4, bp.data(), 4, 4, (size_t)nt * 8, hipMemcpyHostToDevice, st);
     hipMemcpy2DAsync(c->s.border + env, n, bflag.data(), 1, 1, (size_t)nt, hipMemcpyHostToDevice, st);
     if (start_pose) hipMemcpy2DAsync(c->s.start_pose + env, n * 4, start_pose, 4, 4, 3, hipMemcpyHostToDevice, st);
-    // env-major copies (analytic raster, map build)
+    // env-major copies (map build)
     hipMemcpyAsync(c->s.tile_poly_em + env * kCarMaxTiles * 10, tp.data(), (size_t)nt * 40, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(c->s.tile_aabb_em + env * kCarMaxTiles, aabb.data(), (size_t)nt * 16, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(c->s.border_poly_em + env * kCarMaxTiles * 8, bp.data(), (size_t)nt * 32, hipMemcpyHostToDevice, st);

@@ -28,8 +28,8 @@ int crl_dev_zalloc(T **p, size_t bytes, const char *what) {
     return e == hipSuccess ? CRL_OK : crl_hip_fail(e, what);
 }
 
-// Timing ablations that give WRONG results (skip a phase to size it) exist only in a profiling build (-DCRL_ABLATION):
-// in the shipped library their switches read as zero and the compiler drops the branches.
+// The switches of the profiling build (-DCRL_ABLATION: CRL_POLICY_MFMA, CRL_GRAY_SWEEP, CRL_CAR_WALK_BUDGET -- bit-exact alternatives
+// that tests A/B against the shipped path): in the shipped library they read as zero and the compiler drops the branches.
 #ifdef CRL_ABLATION
 #define CRL_ABL(x) (x)
 #else

@@ -200,8 +200,7 @@ static int frame_stack_update_impl(float *stack_dev, const float *src_dev, const
     const int64_t threads = n * (vec ? hw / 4 : hw);
     const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
     using namespace crl;
-    static const bool flat_off = getenv("CRL_FRAME_STACK_COLUMNS") != nullptr;  // (A/B: the out-of-place update as the column walk)
-    if (vec && src_dev != stack_dev && !flat_off) {
+    if (vec && src_dev != stack_dev) {
         const int64_t totc = (int64_t)c * k * hw / 4, per_env = (totc + 256 * CRL_FS_U - 1) / (256 * CRL_FS_U);
         if (n * per_env < (int64_t)1 << 31) {
             const dim3 g2((unsigned)(n * per_env));

@@ -255,11 +255,10 @@ void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *at
 void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, const uint8_t *band_span,
                                   int ink_row0, int ink_row1, uint8_t *obs, int views, hipStream_t st);
 // a raw step and its delta draw in one launch: raw_step_env() for every env, then what launch_pong_raster_raw_delta does with the
-// new descriptors (views = 1: cPong-v0, one action per env).  stepped (profiling build's CRL_RAW_STEP_SPLIT): the envs were stepped by
-// launch_pong_dynamics already, the launch only draws obs_frames[] -- what its second phase costs alone
+// new descriptors (views = 1: cPong-v0, one action per env)
 void launch_pong_step_raw_delta(const PongSoA &s, const ServeSrc &src, const int32_t *actions, int64_t n, float *rew, uint8_t *done,
                                 uint64_t *drawn, const uint8_t *atlas_rgb, const uint8_t *band_span, int ink_row0, int ink_row1, uint8_t *obs,
-                                int views, hipStream_t st, int stepped = 0);
+                                int views, hipStream_t st);
 
 // Byte offsets of the dense INTER_AREA tables inside the blob the gray kernel stages into
 // LDS: xa/ya = float[5][R] weights (tap k of output index d at [k*R + d]); xs0/xn, ys0/yn =
@@ -315,6 +314,5 @@ struct GrayJob {
 void launch_pong_gray_templates(const GrayTables &t, hipStream_t st);      // fills t.band and t.rest
 void launch_pong_gray_f32ref_tables(const GrayTables &t, hipStream_t st);  // fills t.f32_top and t.f32_bot
 void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t st);
-void pong_gray_print_ticks();  // profiling build: CRL_GRAY_DEBUG & 128
 
 }  // namespace crl

@@ -40,7 +40,6 @@
                     for (int w = lane; w < (RR >> 2); w += 64) out32[w] = 0u;
                 continue;
             }
-            GRAY_TICK(0)
             // ---- 1. template loads into registers (L2); the box arithmetic and the row / column
             //         words below overlap their latency, the LDS tile is filled afterwards
             const uint4 *__restrict__ band4 =
@@ -50,7 +49,6 @@
             for (int it = 0; it < TI; it++) {
                 const int c = lane + 64 * it;
                 tv[it] = make_uint4(0, 0, 0, 0);
-                if (dbg & 32) continue;
                 if (c < bb) tv[it] = band4[c];
                 else if (c < chunks && (c < zc0 || c >= zc1)) tv[it] = rest4[c];
             }
@@ -91,19 +89,16 @@
                     xmin = min(xmin, bx[i].x0), xmax = max(xmax, bx[i].x0 + bx[i].w);
                 }
             }
-            const int total = (dbg & 1) ? 0 : pre[6];
-            GRAY_TICK(1)
+            const int total = pre[6];
             uint32_t *rowpack = rowpack_[wave], *colpack = colpack_[wave];
-            if (fast_ok && !(dbg & 2)) {
+            if (fast_ok) {
                 for (int dy = ymin + lane; dy < ymax; dy += 64) rowpack[dy] = row_pack<MAXT>(tabs, q.t, rc, dy);
                 for (int dx = xmin + lane; dx < xmax; dx += 64) colpack[dx] = col_pack<MAXT>(tabs, q.t, rc, dx);
             }
-            GRAY_TICK(2)
 #pragma unroll
             for (int it = 0; it < TI; it++)
                 if (lane + 64 * it < chunks) tl4[lane + 64 * it] = tv[it];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            GRAY_TICK(3)
             for (int p = lane; p < total; p += 64) {
                 int dy, dx;
                 const bool band_px = p < pre[0];
@@ -126,7 +121,6 @@
                 tl[dy * R + dx] = v;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            GRAY_TICK(4)
             // ---- 3. stream the tile out
             if (f32) {
                 const uint32_t *tl32 = reinterpret_cast<const uint32_t *>(tl);
@@ -143,10 +137,6 @@
                             outf[lane + 64 * (g0 + gi)] = make_float4((float)(px[gi] & 255u), (float)((px[gi] >> 8) & 255u), (float)((px[gi] >> 16) & 255u),
                                                                       (float)(px[gi] >> 24));
                 }
-            } else if (dbg & 64) {
-#pragma unroll
-                for (int it = 0; it < TI; it++)
-                    if (lane + 64 * it < chunks) out[lane + 64 * it] = tv[it];
             } else if (vec16) {
                 // all LDS reads first, then the stores (a rolled loop would wait for every read in turn)
                 uint4 ov[TI];
@@ -160,5 +150,4 @@
                 for (int w = lane; w < (RR >> 2); w += 64) out32[w] = tl32[w];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            GRAY_TICK(5)
         }

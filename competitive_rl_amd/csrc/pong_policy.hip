@@ -163,10 +163,9 @@ template <bool BF, bool LIST, bool SAMPLE, bool VALUE = false>
 __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWeightsM W, uint8_t *__restrict__ ring, int head,
                                                                   const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                   int32_t *__restrict__ actions, int64_t action_stride,
-                                                                  float *__restrict__ logits_out, int64_t n_arg, unsigned *__restrict__ ticket, int dbg_arg,
+                                                                  float *__restrict__ logits_out, int64_t n_arg, unsigned *__restrict__ ticket,
                                                                   const int32_t *__restrict__ env_list, const unsigned *__restrict__ count_dev, SampleArgs S, HeadArgs H) {
     const int64_t n = LIST ? (int64_t)*count_dev : n_arg;
-    const int dbg = CRL_ABL(dbg_arg);  // timing ablations / phase stamps: profiling build only
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *sh_buf = smem;                                             // [2][kME][4][kPlanePad]
     float *sh_wa = reinterpret_cast<float *>(smem + 2 * kMBuf);         // [3][1600]; VALUE: [4][1600], the critic last
@@ -282,34 +281,23 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
             }
         }
     };
-    long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-    const long long tstart = tprev;
-#define MTICK(K)                                                \
-    if (dbg & 4) {                                              \
-        const long long now_ = __builtin_readcyclecounter();    \
-        tk[K] += now_ - tprev;                                  \
-        tprev = now_;                                           \
-    }
     while (g < ngroups) {
         const int64_t env0 = g * kME;
         const int envs_here = (int)((n - env0) < kME ? (n - env0) : kME);
         uint8_t *buf = sh_buf + cur * kMBuf;
         float *part_out = sh_part + cur * (kME * kPos * 3);
         if (tid == 0) sh_ticket[cur ^ 1] = atomicAdd(ticket, 1u);
-        MTICK(3)
         // LIST: the next group's list entries are requested here and awaited behind the reduction and the write-back below -- the
         // one place of the iteration where nothing of this workgroup is in flight that the wait could drain
         i32x4 ia, ib;
         if constexpr (LIST)
             if (g1 < ngroups) group_idx_load(ia, ib, env_list, g1 * kME);
         if (gprev >= 0) finish_group(gprev, cur ^ 1, ix_prev);
-        MTICK(4)
         if constexpr (!LIST)
             if (g1 < ngroups) {  // the next group streams into the other buffer during the convolutions
                 const int64_t e1 = g1 * kME;
                 group_request_m<false>(sh_buf + (cur ^ 1) * kMBuf, ring, head, frame, frame_stride, e1, ix_next, (int)((n - e1) < kME ? (n - e1) : kME), wave, lane);
             }
-        MTICK(5)
         // the new frame also replaces plane `head` of the ring in HBM
         for (int i = tid; i < envs_here * kPlaneChunks; i += kMThreads) {
             const int fe = i / kPlaneChunks, c = i - fe * kPlaneChunks;
@@ -322,7 +310,6 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                 group_idx_pin(ix_next, ia, ib);
                 group_request_m<true>(sh_buf + (cur ^ 1) * kMBuf, ring, head, frame, frame_stride, e1, ix_next, (int)((n - e1) < kME ? (n - e1) : kME), wave, lane);
             }
-        MTICK(0)
         // The patch of tile t + kMWaves is gathered and converted WHILE tile t's MFMAs run: the two are independent, so the
         // scheduler threads the vector work between the matrix instructions (a wavefront that converts first and multiplies
         // afterwards leaves the matrix pipe idle 44 % of the time even with a partner on the SIMD).
@@ -373,35 +360,19 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
             }
         };
         float xnext[6][6];
-        if (!CRL_MFMA_PREFETCH || BF) {
-        } else if (dbg & 1) {  // ablation: no gather
-#pragma unroll
-            for (int r = 0; r < 6; r++)
-#pragma unroll
-                for (int k = 0; k < 6; k++) xnext[r][k] = 0.25f * (float)(r + k + lk);
-        } else if (wave < kMTiles) gather(wave, xnext);
+        if (CRL_MFMA_PREFETCH && !BF && wave < kMTiles) gather(wave, xnext);
         for (int t = wave; t < kMTiles; t += kMWaves) {
             const int q = 16 * t + lj, e = q / kPos, pos = q - e * kPos;
             float xin[6][6];
             bf8 bx[4][2];
             if constexpr (BF) {
-                if (dbg & 1) {  // ablation: no gather
-#pragma unroll
-                    for (int c = 0; c < 4; c++)
-#pragma unroll
-                        for (int i = 0; i < 2; i++) {
-                            const u32x4 v = {0x3f803f80u + (unsigned)lk, 0x40004000u, 0x3f803f80u, 0x40004000u + (unsigned)c};
-                            bx[c][i] = __builtin_bit_cast(bf8, v);
-                        }
-                } else {
-                    gather_bf(t, bx);
-                }
+                gather_bf(t, bx);
             } else if (CRL_MFMA_PREFETCH) {
 #pragma unroll
                 for (int r = 0; r < 6; r++)
 #pragma unroll
                     for (int k = 0; k < 6; k++) xin[r][k] = xnext[r][k];
-                if (t + kMWaves < kMTiles && !(dbg & 1)) gather(t + kMWaves, xnext);
+                if (t + kMWaves < kMTiles) gather(t + kMWaves, xnext);
             } else {
                 gather(t, xin);
             }
@@ -431,10 +402,6 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                     if ((c * 4 + r) & 1) d2b = __builtin_amdgcn_mfma_f32_16x16x4f32(w2[c][r], hval, d2b, 0, 0, 0);
                     else d2a = __builtin_amdgcn_mfma_f32_16x16x4f32(w2[c][r], hval, d2a, 0, 0, 0);
                 }
-            if (dbg & 2) {  // ablation: no actor / cross-lane sums
-                if (lk == 0) part_out[q * 3] = d2a[0] + d2b[1], part_out[q * 3 + 1] = 0.f, part_out[q * 3 + 2] = 0.f;
-                continue;
-            }
             // ---- actor: lane (position lj, channels 4 lk + r)
             float l0 = 0.f, l1 = 0.f, l2 = 0.f, lv = 0.f;
 #pragma unroll
@@ -456,10 +423,8 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
                 if (lk == 0 && (lj & 3) == 0) sh_vpart[cur * (kME * kVBlocks) + (q >> 2)] = lv;
             }
         }
-        MTICK(1)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's share of the next group has landed (and the ticket is back)
         __syncthreads();                                    // ... everybody's has, and every tile of this group is in part_out
-        MTICK(2)
         gprev = g;
         g = g1;
         g1 = (int64_t)gridDim.x + sh_ticket[cur ^ 1];
@@ -467,12 +432,6 @@ __global__ __launch_bounds__(kMThreads, 1) void pong_policy_mfma_kernel(PolicyWe
         if constexpr (LIST) ix_prev = ix_cur, ix_cur = ix_next;
     }
     if (gprev >= 0) finish_group(gprev, cur ^ 1, ix_prev);
-    if ((dbg & 4) && logits_out && lane == 0 && blockIdx.x < 64) {  // profiling: cycles per phase of every wavefront of the first workgroups
-        float *o = logits_out + (blockIdx.x * kMWaves + wave) * 8;
-        for (int k = 0; k < 7; k++) o[k] = (float)tk[k];
-        o[7] = (float)(__builtin_readcyclecounter() - tstart);
-    }
-#undef MTICK
 }
 
 // ring <-> logical order (tests, checkpoints): plane j of the model's stack is ring plane (head + j) & 3
@@ -549,20 +508,20 @@ hipError_t policy_light_prepare() {
 // which the kernel reads itself), else null; sample: null = argmax; bf = false: profiling build only, dense only; heads: the rollout
 // launch (dense, bf only), else null.
 static hipError_t policy_mfma_launch(bool bf, const float *raw, uint8_t *ring, int head, const uint8_t *frame, int64_t frame_stride, int32_t *actions,
-                                     int64_t action_stride, float *logits, int64_t n, int cus, unsigned *ticket, int dbg, const int32_t *env_list,
+                                     int64_t action_stride, float *logits, int64_t n, int cus, unsigned *ticket, const int32_t *env_list,
                                      const unsigned *count_dev, const SampleArgs *sample, const HeadArgs *heads, hipStream_t st) {
     const int64_t groups = (n + kME - 1) / kME;
     const unsigned grid = (unsigned)(groups < cus ? groups : cus);
     const MfmaEntry &k = kMfmaKernels[(heads ? 4 : CRL_ABL(!bf) ? 6 : env_list ? 2 : 0) + (sample ? 1 : 0)];
     hipLaunchKernelGGL(k.kernel, dim3(grid), dim3(kMThreads), k.lds, st, light_weights(raw), ring, head, frame, frame_stride, actions, action_stride, logits,
-                       env_list ? (int64_t)0 : n, ticket, dbg, env_list, count_dev, sample ? *sample : SampleArgs{}, heads ? *heads : HeadArgs{});
+                       env_list ? (int64_t)0 : n, ticket, env_list, count_dev, sample ? *sample : SampleArgs{}, heads ? *heads : HeadArgs{});
     return hipGetLastError();
 }
 
 hipError_t policy_light_act_list(const float *raw, uint8_t *ring, int head, const uint8_t *frame, int64_t frame_stride, int32_t *actions,
                                  int64_t action_stride, float *logits, const int32_t *env_list, const unsigned *count_dev, int64_t max_envs, int cus,
                                  unsigned *ticket, const SampleArgs *sample, hipStream_t st) {
-    return policy_mfma_launch(true, raw, ring, head, frame, frame_stride, actions, action_stride, logits, max_envs, cus, ticket, 0, env_list, count_dev,
+    return policy_mfma_launch(true, raw, ring, head, frame, frame_stride, actions, action_stride, logits, max_envs, cus, ticket, env_list, count_dev,
                               sample, nullptr, st);
 }
 
@@ -688,13 +647,11 @@ static int policy_act(const char *who, crl_policy *p, const uint8_t *frame_dev, 
         HIP_TRY(hipMemsetAsync(p->ticket, 0, sizeof(unsigned), st));
         // The matrix-pipe kernel, conv1 as three exact bf16 products per tap (430 us at 65 536 envs).  Profiling build only
         // (CRL_POLICY_MFMA): 1 = the same kernel with conv1 on the fp32 matrix instruction (757 us), 0 = the packed-FMA kernel of
-        // round 1 (725-805 us, pong_policy_packed.inc); CRL_POLICY_MFMA_DEBUG skips phases (wrong outputs).  The rollout launch has
-        // the one kernel.
+        // round 1 (725-805 us, pong_policy_packed.inc).  The rollout launch has the one kernel.
         static const int use_mfma = CRL_ABL(getenv("CRL_POLICY_MFMA") != nullptr) ? atoi(getenv("CRL_POLICY_MFMA")) : 3;
-        static const int mdbg = CRL_ABL(getenv("CRL_POLICY_MFMA_DEBUG") ? atoi(getenv("CRL_POLICY_MFMA_DEBUG")) : 0);
         const HeadArgs H{p->raw + kLightWc, p->raw + kLightBc, values_dev, logp_dev};
         if (heads)
-            e = policy_mfma_launch(true, p->raw, p->ring, p->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, p->cus, p->ticket, 0,
+            e = policy_mfma_launch(true, p->raw, p->ring, p->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, p->cus, p->ticket,
                                    nullptr, nullptr, sample, &H, st);
         else
 #ifdef CRL_ABLATION
@@ -702,7 +659,7 @@ static int policy_act(const char *who, crl_policy *p, const uint8_t *frame_dev, 
                                    p->ticket, p->sampling, S, st, &e))
 #endif
             e = policy_mfma_launch(use_mfma == 3, p->raw, p->ring, p->head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, p->n, p->cus,
-                                   p->ticket, mdbg, nullptr, nullptr, sample, nullptr, st);
+                                   p->ticket, nullptr, nullptr, sample, nullptr, st);
     }
     if (e != hipSuccess) return crl_fail(CRL_EHIP, "%s: %s", who, hipGetErrorString(e));
     p->head = (p->head + 1) & 3;

@@ -103,14 +103,12 @@ __device__ inline void group_write_back(const uint8_t *shbuf, uint8_t *__restric
 // one's idle phases run under the other's convolutions.  Tables that do not depend on the group (actor weights,
 // biases) are staged once.
 // SAMPLE: the action epilogue follows include/crl.h "sampled actions" (sample_action) instead of the plain argmax.
-template <int DBG, bool SAMPLE = false>  // DBG: 0 production, 1 ablation switches (CRL_POLICY_DEBUG bits 1, 2), 2 production code + phase cycle counters (4)
+template <bool SAMPLE = false>
 __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(PolicyWeights W, uint8_t *__restrict__ ring, int head,
                                                                            const uint8_t *__restrict__ frame, int64_t frame_stride,
                                                                            int32_t *__restrict__ actions, int64_t action_stride,
-                                                                           float *__restrict__ logits_out, int64_t n, int dbg_arg, int phase_sleeps,
-                                                                           unsigned *__restrict__ ticket, SampleArgs S) {
-    const int dbg = DBG == 1 ? dbg_arg : 0;  // CRL_POLICY_DEBUG (profiling only): 1 skip the convolutions, 2 skip the patch gather
-    const bool timed = DBG != 0 && (dbg_arg & 4) && n >= 8192;  // the counters go into logits_out (needs n * 12 >= 66 560 bytes)
+                                                                           float *__restrict__ logits_out, int64_t n, unsigned *__restrict__ ticket,
+                                                                           SampleArgs S) {
     __shared__ __attribute__((aligned(16))) uint8_t sh_in[kEnvsPerWg][CRL_POLICY_STACK][kPlanePad];
     __shared__ float sh_wa[3 * 1600];
     __shared__ __attribute__((aligned(8))) float sh_b2[16];  // conv2.bias; actor bias: no VMEM loads inside the loop,
@@ -132,25 +130,6 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
     const int b1lane = __float_as_int(b1i);
     const int wave = tid >> 6, lane = tid & 63;
     __syncthreads();
-    // The two workgroups of a CU start together and have the same period, so left alone they stay IN phase: both in
-    // the convolutions (sharing the FMA pipes), then both in staging / reduction (pipes idle).  The second half of the
-    // grid (the workgroups that land in the CUs' second slots) starts half a period late.
-    {
-        const int mode = phase_sleeps >> 8, reps = phase_sleeps & 255;
-        const bool late = mode == 0 ? blockIdx.x >= (gridDim.x + 1) / 2 : mode == 1 ? (blockIdx.x & 1) : mode == 2 ? ((blockIdx.x >> 3) & 1) : ((blockIdx.x >> 8) & 1);
-        if (late)
-            for (int i = 0; i < reps; i++) __builtin_amdgcn_s_sleep(127);
-    }
-
-    long long tacc[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-    int gcount = 0;
-#define CRL_TICK(K)                                        \
-    if (timed) {                                           \
-        const long long now_ = __builtin_readcyclecounter(); \
-        tacc[K] += now_ - tprev;                           \
-        tprev = now_;                                      \
-    }
-    if (timed) tprev = __builtin_readcyclecounter();
     // Groups are handed out by a ticket counter, not b, b + grid, ...: the SIMDs favour their OLDEST wavefront, so the
     // workgroup that reached a CU first runs about twice as fast as its co-resident (cycle-counter timelines: 48 k vs
     // 96 k cycles per group) and a static split leaves the slow half to finish alone.
@@ -163,9 +142,7 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's share has landed
         __syncthreads();                                    // ... everybody's has
         const int64_t g_next = (int64_t)gridDim.x + sh_ticket;  // rewritten only after this iteration's last barrier
-        CRL_TICK(0)
         group_write_back(&sh_in[0][0][0], ring, head, env0, envs_here, tid);
-        CRL_TICK(1)
       for (int pass = 0; pass < kPasses; pass++) {
         const int task = pass * kPolicyThreads + tid;
         const int e = task < kEnvsPerWg * kPos ? task / kPos : kEnvsPerWg - 1;
@@ -192,7 +169,7 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
                     // inside the padded plane
                     const uint8_t *row = &sh_in[e][(head + 1 + ic) & 3][(4 * y2 + r) * kDim + 4 * x2];
                     const uint32_t *p32 = reinterpret_cast<const uint32_t *>(row - 2 * (r & 1));
-                    uint32_t w0 = (dbg & 2) ? 0x01020304u : p32[0], w1 = (dbg & 2) ? 0x0506u : p32[1];
+                    uint32_t w0 = p32[0], w1 = p32[1];
                     if (r & 1) w0 = (w0 >> 16) | (w1 << 16), w1 >>= 16;
                     const f2 b[3] = {f2{(float)(w0 & 255u), (float)((w0 >> 8) & 255u)}, f2{(float)((w0 >> 16) & 255u), (float)(w0 >> 24)},
                                      f2{(float)(w1 & 255u), (float)((w1 >> 8) & 255u)}};
@@ -203,9 +180,6 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
                         in[ic][r][k] = __builtin_elementwise_fma(rem, rcp, q);
                     }
                 }
-            CRL_TICK(2)
-            if (timed && logits_out && tid == 0 && (blockIdx.x == 48 || blockIdx.x == 304) && gcount < 12)
-                reinterpret_cast<long long *>(logits_out)[8192 + (blockIdx.x == 304) * 64 + gcount * 4 + pass * 2] = __builtin_readcyclecounter();
             f2 acc[8];  // conv2 accumulators, output channels (2p, 2p + 1)
 #pragma unroll
             for (int p = 0; p < 8; p++) acc[p] = reinterpret_cast<const f2 *>(sh_b2)[p];
@@ -248,7 +222,7 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
     wbatch_wait(CUR);                   \
     wbatch_request(NXT, wp + (OFS));    \
     WORK
-            for (int cp = 0; cp < ((dbg & 1) ? 0 : 8); cp++) {  // conv1 output channels (2cp, 2cp + 1) == conv2 input channels
+            for (int cp = 0; cp < 8; cp++) {  // conv1 output channels (2cp, 2cp + 1) == conv2 input channels
                 const f2 bias = f2{__int_as_float(__builtin_amdgcn_readlane(b1lane, 2 * cp)),
                                    __int_as_float(__builtin_amdgcn_readlane(b1lane, 2 * cp + 1))};
                 f2 h00 = bias, h01 = bias, h10 = bias, h11 = bias;
@@ -264,9 +238,6 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
                 wp += 256;
             }
             wbatch_wait(wa_);  // drain the padding request
-            CRL_TICK(3)
-            if (timed && logits_out && tid == 0 && (blockIdx.x == 48 || blockIdx.x == 304) && gcount < 12)
-                reinterpret_cast<long long *>(logits_out)[8192 + (blockIdx.x == 304) * 64 + gcount * 4 + pass * 2 + 1] = __builtin_readcyclecounter();
 #undef CRL_STEP
 #undef CRL_CONV1_BATCH
 #undef CRL_CONV2_BATCH
@@ -279,7 +250,6 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
             }
         }
         if (live) sh_part[task][0] = l0, sh_part[task][1] = l1, sh_part[task][2] = l2;
-        CRL_TICK(4)
       }
         __syncthreads();
         // fixed-shape sum over the 100 positions of an env (4 groups of 25, then the 4 groups): the result
@@ -300,21 +270,8 @@ __global__ __launch_bounds__(kPolicyThreads) void pong_policy_light_kernel(Polic
         if (tid < kEnvsPerWg && env0 + tid < n)
             action_epilogue<SAMPLE>(S, env0 + tid, sh_logit[tid][0], sh_logit[tid][1], sh_logit[tid][2], actions, action_stride, logits_out);
         __syncthreads();  // sh_logit / sh_in are rewritten by the next group
-        CRL_TICK(5)
-        gcount++;
         g = g_next;
     }
-    if (timed && logits_out && lane == 0 && blockIdx.x < 512) {  // where the hardware put this wavefront (HW_ID: simd, cu, sh, se, ...)
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        reinterpret_cast<unsigned *>(logits_out)[4096 + (blockIdx.x * 4 + wave) * 2] = hwid;
-        reinterpret_cast<unsigned *>(logits_out)[4096 + (blockIdx.x * 4 + wave) * 2 + 1] = xcc;
-    }
-    if (timed && logits_out && tid == 0)  // profiling: cycles per phase of this workgroup's first wavefront
-        for (int k = 0; k < 6; k++) logits_out[blockIdx.x * 6 + k] = (float)tacc[k];
-#undef CRL_TICK
 }
 
 // ---- host: the weight stream of a crl_policy (owned through W.stream) and the launch
@@ -341,20 +298,17 @@ static hipError_t packed_policy_create(PolicyWeights &W, const float *conv1_w, c
     return e;
 }
 
-// The one entry of crl_policy_act.  False: this process did not select the packed-FMA kernel (CRL_POLICY_MFMA is 1, 3 or unset and
-// CRL_POLICY_DEBUG is not set) and nothing was launched; true: *err is the launch's outcome.  `ticket` is zeroed by the caller.
+// The one entry of crl_policy_act.  False: this process did not select the packed-FMA kernel (CRL_POLICY_MFMA is 1, 3 or unset)
+// and nothing was launched; true: *err is the launch's outcome.  `ticket` is zeroed by the caller.
 static bool packed_policy_act(const PolicyWeights &W, int use_mfma, uint8_t *ring, int head, int64_t n, int cus, const uint8_t *frame_dev,
                               int64_t frame_stride, int32_t *actions_dev, int64_t action_stride, float *logits_dev, unsigned *ticket, bool sampling,
                               const SampleArgs &S, hipStream_t st, hipError_t *err) {
-    static const int dbg = getenv("CRL_POLICY_DEBUG") ? atoi(getenv("CRL_POLICY_DEBUG")) : 0;  // skips phases (wrong outputs)
-    if ((use_mfma == 1 || use_mfma == 3) && !dbg) return false;
-    static const int phase = getenv("CRL_POLICY_PHASE") ? atoi(getenv("CRL_POLICY_PHASE")) : 0;  // x 8 128 cycles
+    if (use_mfma == 1 || use_mfma == 3) return false;
     const int64_t groups = (n + kEnvsPerWg - 1) / kEnvsPerWg;
-    static const int per_cu = getenv("CRL_POLICY_WGS") ? atoi(getenv("CRL_POLICY_WGS")) : 2;  // tuning experiments only
-    const unsigned grid = (unsigned)(groups < per_cu * cus ? groups : per_cu * cus);  // persistent: two workgroups per CU
-    const auto kernel = dbg == 4 ? pong_policy_light_kernel<2> : dbg ? pong_policy_light_kernel<1> : sampling ? pong_policy_light_kernel<0, true> : pong_policy_light_kernel<0>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolicyThreads), 0, st, W, ring, head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, n, dbg,
-                       phase, ticket, S);
+    const unsigned grid = (unsigned)(groups < 2 * cus ? groups : 2 * cus);  // persistent: two workgroups per CU
+    const auto kernel = sampling ? pong_policy_light_kernel<true> : pong_policy_light_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolicyThreads), 0, st, W, ring, head, frame_dev, frame_stride, actions_dev, action_stride, logits_dev, n, ticket,
+                       S);
     *err = hipGetLastError();
     return true;
 }

@@ -76,7 +76,6 @@ struct GrayGeom {
     const uint8_t *y_first, *y_last;   // [210]
     const uint8_t *tab_blob;           // dense tap tables + first/last maps, staged into LDS per workgroup
     GrayTabOfs t;
-    int debug;                         // ablation switches for profiling builds (0 in production)
 };
 
 // Builds the templates with the exact evaluator (ball and bats moved off-screen), so the
@@ -110,17 +109,6 @@ struct Box {
     int x0, y0, w, h;  // output-pixel box
 };
 
-__device__ inline Box rect_box(const GrayGeom &q, int c0, int c1, int r0, int r1) {
-    // source rect [c0,c1) x [r0,r1) (already in view coordinates) -> affected output box
-    c0 = max(c0, 0), c1 = min(c1, CRL_PONG_W), r0 = max(r0, 0), r1 = min(r1, CRL_PONG_H);
-    Box b = {0, 0, 0, 0};
-    if (c0 >= c1 || r0 >= r1) return b;
-    b.x0 = q.x_first[c0], b.y0 = q.y_first[r0];
-    b.w = q.x_last[c1 - 1] - b.x0 + 1, b.h = q.y_last[r1 - 1] - b.y0 + 1;
-    return b;
-}
-
-[[maybe_unused]] static constexpr int kTileLds = 7168;  // >= 84*84, multiple of 16
 static constexpr int kTabLds = 6144;   // dense tap tables + first/last maps (4.6 KB at R = 84)
 static constexpr int kMaxR = 96;       // largest resized_dim the LDS tile holds (84) rounded up
 
@@ -130,51 +118,6 @@ struct Rects {
     int ax, ay, bx, by;      // balls of frame a / b
     int la, lb, ra, rb;      // y of the view-left bat in a / b, view-right bat in a / b
 };
-
-// Exact INTER_AREA value of one output pixel whose footprint lies in source rows that hold
-// no score ink (rows >= ink_row1): those rows are white bands or court rectangles, so the
-// source pixel is a few interval tests instead of a table lookup.  Same f32 operation
-// order as eval_pixel.
-template <int MAXT>
-__device__ inline uint8_t eval_fast(const uint8_t *__restrict__ tabs, const GrayTabOfs &o, int R, const Rects &q, int dy,
-                                    int dx) {
-    const float *xa = reinterpret_cast<const float *>(tabs + o.xa), *ya = reinterpret_cast<const float *>(tabs + o.ya);
-    const int sx0 = tabs[o.xs0 + dx], nx = tabs[o.xn + dx], sy0 = tabs[o.ys0 + dy], ny = tabs[o.yn + dy];
-    float p[MAXT];
-    unsigned xb[MAXT];
-#pragma unroll
-    for (int k = 0; k < MAXT; k++) {
-        const int c = sx0 + k;
-        p[k] = xa[k * R + dx];  // table holds 255 * alpha
-        const unsigned m = ((unsigned)(c - q.ax) < (unsigned)CRL_PONG_BALL ? 1u : 0u) |
-                           ((unsigned)(c - q.bx) < (unsigned)CRL_PONG_BALL ? 2u : 0u) |
-                           ((unsigned)(c - CRL_PONG_BATL_X) < (unsigned)CRL_PONG_BAT_W ? 4u : 0u) |
-                           ((unsigned)(c - CRL_PONG_BATR_X) < (unsigned)CRL_PONG_BAT_W ? 8u : 0u);
-        xb[k] = k < nx ? m : 0u;
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXT; j++) {
-        if (j < ny) {
-            const int r = sy0 + j;
-            const bool white = r < CRL_PONG_TOP || r >= CRL_PONG_BOTTOM;
-            unsigned yb = ((unsigned)(r - q.ay) < (unsigned)CRL_PONG_BALL ? 1u : 0u) |
-                          ((unsigned)(r - q.by) < (unsigned)CRL_PONG_BALL ? 2u : 0u) |
-                          (((unsigned)(r - q.la) < (unsigned)CRL_PONG_BAT_H || (unsigned)(r - q.lb) < (unsigned)CRL_PONG_BAT_H) ? 4u : 0u) |
-                          (((unsigned)(r - q.ra) < (unsigned)CRL_PONG_BAT_H || (unsigned)(r - q.rb) < (unsigned)CRL_PONG_BAT_H) ? 8u : 0u);
-            float buf = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXT; k++) {
-                const bool on = k < nx && (white || (xb[k] & yb) != 0u);
-                buf = on ? buf + p[k] : buf;
-            }
-            const float t = ya[j * R + dy] * buf;
-            sum = (j == 0) ? t : sum + t;
-        }
-    }
-    const int v = (int)rintf(sum);
-    return (uint8_t)min(max(v, 0), 255);
-}
 
 __device__ inline Box rect_box_lds(const uint8_t *__restrict__ tabs, const GrayTabOfs &o, int c0, int c1, int r0, int r1) {
     c0 = max(c0, 0), c1 = min(c1, CRL_PONG_W), r0 = max(r0, 0), r1 = min(r1, CRL_PONG_H);
@@ -199,142 +142,9 @@ __device__ inline Box rect_box_lds_nb(const uint8_t *__restrict__ tabs, const Gr
     return b;
 }
 
-#ifdef CRL_ABLATION  // the first tile kernel (four tiles per workgroup, per-pixel evaluator): profiling build only, CRL_GRAY_DEBUG=8
-__global__ __launch_bounds__(256) void pong_raster_gray_kernel(const uint64_t *__restrict__ ring, int64_t n, GrayCtx g,
-                                                               GrayGeom q, uint8_t *__restrict__ obs) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[4][kTileLds];
-    __shared__ __attribute__((aligned(16))) uint8_t tabs[kTabLds];
-    // stage the constant tap tables once per workgroup (L2-resident source)
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(q.tab_blob);
-        uint4 *dst = reinterpret_cast<uint4 *>(tabs);
-        for (int i = threadIdx.x; i < (q.t.total >> 4); i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    const int tiles_per_env = q.views * q.K;
-    if (tile >= n * tiles_per_env) return;
-    const int64_t env = tile / tiles_per_env;
-    const int t = (int)(tile - env * tiles_per_env);
-    const int view = t / q.K, plane = t - view * q.K;
-    const int rp = 4 - q.K + plane;  // ring plane
-    const uint64_t pa = ring[(int64_t)(2 * rp + 0) * n + env], pb = ring[(int64_t)(2 * rp + 1) * n + env];
-    const Frame fa = unpack_frame(pa), fb = unpack_frame(pb);
-    const int R = q.R, RR = R * R, chunks = (RR + 15) >> 4;
-    // R*R % 16 == 0 (R = 84): 16-byte stores; otherwise (R = 42: 1764 B tiles) dword stores
-    const bool vec16 = (RR & 15) == 0;
-    uint4 *__restrict__ out = reinterpret_cast<uint4 *>(obs + tile * (int64_t)RR);
-    uint32_t *__restrict__ out32 = reinterpret_cast<uint32_t *>(obs + tile * (int64_t)RR);
-    uint8_t *tl = lds[wave];
-    uint4 *tl4 = reinterpret_cast<uint4 *>(tl);
-
-    const bool blank_a = fa.sl == 255, blank_b = fb.sl == 255;
-    if (blank_a && blank_b) {  // plane erased by a done (FrameStackTensor mask)
-        if (vec16)
-            for (int c = lane; c < chunks; c += 64) out[c] = make_uint4(0, 0, 0, 0);
-        else
-            for (int w = lane; w < (RR >> 2); w += 64) out32[w] = 0u;
-        return;
-    }
-    // fast path needs one score pair for the whole plane (a point scored between the two
-    // kept frames puts two different texts under the max)
-    // The score rows come pre-resized from the band table when the two kept frames show
-    // the same score pair, or pairs one point apart (a point scored between the two
-    // max-pooled frames puts two texts under the max).  Anything else (only reachable
-    // through set_state or the never-written initial buffers) is evaluated per pixel.
-    bool slow = blank_a || blank_b;
-    int variant = 0, sp = fa.sl * 22 + fa.sr;
-    if (!slow && (fa.sl != fb.sl || fa.sr != fb.sr)) {
-        const int spb = fb.sl * 22 + fb.sr;
-        if (fb.sl == fa.sl + 1 && fb.sr == fa.sr) variant = 1;
-        else if (fb.sl == fa.sl && fb.sr == fa.sr + 1) variant = 2;
-        else if (fa.sl == fb.sl + 1 && fa.sr == fb.sr) variant = 1, sp = spb;
-        else if (fa.sl == fb.sl && fa.sr == fb.sr + 1) variant = 2, sp = spb;
-        else slow = true;
-    }
-    if (q.debug & 4) slow = false;
-
-    // ---- 1. fill
-    const int bb = q.band_chunks;
-    const uint4 *__restrict__ band4 =
-        reinterpret_cast<const uint4 *>(q.band) + (int64_t)((slow ? 0 : (variant * 484 + sp)) * 2 + view) * bb;
-    const uint4 *__restrict__ rest4 = reinterpret_cast<const uint4 *>(q.rest);
-    const int zc0 = (q.zero_row0 * R + 15) >> 4, zc1 = (q.zero_row1 * R) >> 4;  // chunks fully inside zero rows
-    for (int c = lane; c < chunks; c += 64) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (!(q.debug & 2)) {
-            if (c < bb) v = band4[c];
-            else if (c < zc0 || c >= zc1) v = rest4[c];
-        }
-        tl4[c] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-
-    // ---- 2. patch: boxes of the six rectangles in view coordinates
-    const bool m = view == 1;
-    Rects rc;
-    rc.ax = blank_a ? -1000 : (m ? CRL_PONG_W - fa.x - CRL_PONG_BALL : fa.x), rc.ay = blank_a ? -1000 : fa.y;
-    rc.bx = blank_b ? -1000 : (m ? CRL_PONG_W - fb.x - CRL_PONG_BALL : fb.x), rc.by = blank_b ? -1000 : fb.y;
-    rc.la = blank_a ? -1000 : (m ? fa.br : fa.bl), rc.ra = blank_a ? -1000 : (m ? fa.bl : fa.br);
-    rc.lb = blank_b ? -1000 : (m ? fb.br : fb.bl), rc.rb = blank_b ? -1000 : (m ? fb.bl : fb.br);
-    Box bx[6];
-    {
-        const Box none = {0, 0, 0, 0};
-        bx[0] = blank_a ? none : rect_box_lds(tabs, q.t, rc.ax, rc.ax + CRL_PONG_BALL, max(rc.ay, CRL_PONG_TOP), min(rc.ay + CRL_PONG_BALL, CRL_PONG_BOTTOM));
-        bx[1] = blank_a ? none : rect_box_lds(tabs, q.t, CRL_PONG_BATL_X, CRL_PONG_BATL_X + CRL_PONG_BAT_W, rc.la, rc.la + CRL_PONG_BAT_H);
-        bx[2] = blank_a ? none : rect_box_lds(tabs, q.t, CRL_PONG_BATR_X, CRL_PONG_BATR_X + CRL_PONG_BAT_W, rc.ra, rc.ra + CRL_PONG_BAT_H);
-        const bool same_ball = rc.ax == rc.bx && rc.ay == rc.by;
-        bx[3] = (blank_b || same_ball) ? none : rect_box_lds(tabs, q.t, rc.bx, rc.bx + CRL_PONG_BALL, max(rc.by, CRL_PONG_TOP), min(rc.by + CRL_PONG_BALL, CRL_PONG_BOTTOM));
-        bx[4] = (blank_b || rc.la == rc.lb) ? none : rect_box_lds(tabs, q.t, CRL_PONG_BATL_X, CRL_PONG_BATL_X + CRL_PONG_BAT_W, rc.lb, rc.lb + CRL_PONG_BAT_H);
-        bx[5] = (blank_b || rc.ra == rc.rb) ? none : rect_box_lds(tabs, q.t, CRL_PONG_BATR_X, CRL_PONG_BATR_X + CRL_PONG_BAT_W, rc.rb, rc.rb + CRL_PONG_BAT_H);
-    }
-    int pre[7];
-    pre[0] = slow ? q.band_rows * R : 0;  // slow path: evaluate every pixel of the score rows
-#pragma unroll
-    for (int i = 0; i < 6; i++) pre[i + 1] = pre[i] + bx[i].w * bx[i].h;
-    const int total = (q.debug & 1) ? 0 : pre[6];
-    const bool fast_ok = q.t.fast_ok != 0;
-    for (int p = lane; p < total; p += 64) {
-        int dy, dx;
-        const bool band_px = p < pre[0];
-        if (band_px) {
-            dy = p / R, dx = p - dy * R;
-        } else {
-            int i = 0;
-#pragma unroll
-            for (int k = 1; k < 6; k++) i += (p >= pre[k]) ? 1 : 0;
-            // select box i without dynamic register indexing
-            int x0 = bx[0].x0, y0 = bx[0].y0, w = bx[0].w, base = pre[0];
-#pragma unroll
-            for (int k = 1; k < 6; k++)
-                if (i == k) x0 = bx[k].x0, y0 = bx[k].y0, w = bx[k].w, base = pre[k];
-            const int o = p - base;
-            const int yy = o / w;
-            dy = y0 + yy, dx = x0 + (o - yy * w);
-        }
-        uint8_t v;
-        if (band_px || !fast_ok) v = eval_pixel(g, fa, fb, view, dy, dx);
-        else v = q.t.max_taps <= 3 ? eval_fast<3>(tabs, q.t, R, rc, dy, dx) : eval_fast<5>(tabs, q.t, R, rc, dy, dx);
-        tl[dy * R + dx] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-
-    // ---- 3. stream the tile out
-    if (vec16) {
-        for (int c = lane; c < chunks; c += 64) out[c] = tl4[c];
-    } else {
-        const uint32_t *tl32 = reinterpret_cast<const uint32_t *>(tl);
-        for (int w = lane; w < (RR >> 2); w += 64) out32[w] = tl32[w];
-    }
-}
-
-#endif  // CRL_ABLATION
-
 // ---------------------------------------------------------------------------------------
 // Production kernel: ONE WAVEFRONT PER (env, plane group), looping over the group's planes
-// and both views.  Compared with the tile-per-wave kernel above (kept for ablation,
-// CRL_GRAY_DEBUG=8) this
+// and both views.  Compared with a tile-per-wave kernel this
 //   * pays the HBM latency of the ring read once per env instead of once per tile (lanes
 //     0..7 fetch the eight frame words, parked in LDS) and stages the tap tables once per
 //     32 tiles instead of once per 4;
@@ -343,7 +153,8 @@ __global__ __launch_bounds__(256) void pong_raster_gray_kernel(const uint64_t *_
 //     through readfirstlane, the first/last maps are int32 so they come in by s_load);
 //   * issues the template loads of a tile before its box arithmetic so their L2 latency is
 //     covered, and decodes patch positions with a reciprocal instead of an integer divide.
-// Separable form of eval_fast.  For the pixel (dy, dx) the source pixel under tap (j, k) is
+// Separable evaluation of a pixel whose footprint lies in source rows without score ink (white bands or court rectangles: a few
+// interval tests instead of a table lookup).  For the pixel (dy, dx) the source pixel under tap (j, k) is
 // lit iff some rectangle (ball a, ball b, view-left bat, view-right bat, white band) holds
 // both source row sy0+j and source col sx0+k.  Row membership depends only on dy and
 // column membership only on dx, so each is computed once per tile into a 5-bit-per-tap
@@ -405,14 +216,6 @@ __device__ inline uint8_t eval_sep(const uint8_t *__restrict__ tabs, const GrayT
     return (uint8_t)min(max(v, 0), 255);
 }
 
-// CRL_GRAY_DEBUG & 128 (instrumented instance): s_memtime stamps around the phases of a tile, summed over all wavefronts
-__device__ unsigned long long g_gray_ticks[1024][8];  // (1 024 rows, one per workgroup index mod 1 024: every wavefront adding to ONE row took 4.7 ms of atomics per launch)
-#define GRAY_TICK(Kk)                                        \
-    if (DBG && (dbg & 128)) {                                \
-        const long long now_ = __builtin_readcyclecounter(); \
-        gtick[Kk] += (unsigned)(now_ - gprev);               \
-        gprev = now_;                                        \
-    }
 // TI = 16-byte chunks per lane per tile: 7 holds R <= 84, 2 holds R <= 45 (the reference's default resized_dim = 42:
 // a quarter of the LDS and 40 fewer registers, so more wavefronts cover the per-tile latency chain)
 // F32: the observation tensor is float32 (DummyVecEnv's buffers, utils/dummy_vec_env.py:37-44): the tile is built in
@@ -431,7 +234,7 @@ __device__ unsigned long long g_gray_ticks[1024][8];  // (1 024 rows, one per wo
 // EPWV (round 6): envs per wavefront of the K = 1 launch (make_envs("cPongDouble-v0")'s own observation: one plane per agent).  A wavefront that
 // draws ONE env's two tiles pays the workgroup's table staging, its ring read and its launch for 14 KB of output; EPWV consecutive envs per
 // wavefront amortise them like the four-plane stack does.
-template <int MAXT, bool DBG, int TI, bool F32, bool STACK = false, bool SF32 = false, int EPWV = 1>
+template <int MAXT, int TI, bool F32, bool STACK = false, bool SF32 = false, int EPWV = 1>
 #ifndef CRL_GRAY_SMALL_LB
 #define CRL_GRAY_SMALL_LB 6  // R <= 45 instances: workgroups per CU the register allocation must allow
 #endif
@@ -468,9 +271,6 @@ __global__ __launch_bounds__(256, TI == 2 ? CRL_GRAY_SMALL_LB : ((STACK || EPWV 
     const uint4 *__restrict__ rest4 = reinterpret_cast<const uint4 *>(q.rest);
     const int zc0 = (q.zero_row0 * R + 15) >> 4, zc1 = (q.zero_row1 * R) >> 4;  // chunks fully inside zero rows
     const bool fast_ok = q.t.fast_ok != 0;
-    const int dbg = DBG ? q.debug : 0;  // ablation switches (profiling instance only)
-    unsigned gtick[6] = {0, 0, 0, 0, 0, 0};
-    long long gprev = (DBG && (dbg & 128)) ? __builtin_readcyclecounter() : 0;
 
     if constexpr (STACK) {
         const int ntiles = min(ppw, jobs - p0);
@@ -521,11 +321,6 @@ __global__ __launch_bounds__(256, TI == 2 ? CRL_GRAY_SMALL_LB : ((STACK || EPWV 
 #include "pong_gray_tile.inc"
         }
     }
-    if (DBG && (dbg & 128) && lane == 0) {
-        unsigned long long *row = g_gray_ticks[blockIdx.x & 1023];
-        for (int i = 0; i < 6; i++) atomicAdd(&row[i], (unsigned long long)gtick[i]);
-        atomicAdd(&row[7], 1ull);
-    }
 }
 
 #ifdef CRL_ABLATION  // bit-exact and slower than the env kernel (lab notes 4.3a): profiling build only, CRL_GRAY_SWEEP=1
@@ -570,8 +365,6 @@ __global__ __launch_bounds__(256) void pong_gray_header_kernel(const uint64_t *_
     memset(&h, 0, sizeof(h));
     if (fa.sl == 255) {  // both blank: plane erased by a done
         hdr[tile] = h;
-        reinterpret_cast<uint2 *>(hdr + n * tiles_per_env)[tile] = make_uint2(h.band_off, h.kind);
-        reinterpret_cast<uint16_t *>(reinterpret_cast<uint2 *>(hdr + n * tiles_per_env) + n * tiles_per_env)[tile] = 0;
         return;
     }
     bool slow = false;
@@ -618,9 +411,6 @@ __global__ __launch_bounds__(256) void pong_gray_header_kernel(const uint64_t *_
     }
     h.chunkmask = mask;
     hdr[tile] = h;
-    reinterpret_cast<uint2 *>(hdr + n * tiles_per_env)[tile] = make_uint2(h.band_off, h.kind);  // dense copy (skeleton experiment)
-    reinterpret_cast<uint16_t *>(reinterpret_cast<uint2 *>(hdr + n * tiles_per_env) + n * tiles_per_env)[tile] =
-        (uint16_t)((h.band_off / (uint32_t)q.band_chunks) | ((uint32_t)h.kind << 12));  // 2-byte record
 }
 
 // One wavefront per 1-KiB-ALIGNED block of the output tensor (chunks [64 b, 64 b + 64) of the whole tensor), NB blocks per
@@ -639,10 +429,7 @@ __device__ inline int opaque_zero() {  // a zero the compiler must treat as per-
     return z;
 }
 
-// Measurement only (CRL_GRAY_SWEEP=2, wrong pixels wherever a ball or bat is): the SKELETON of an address-linear writer with
-// real per-tile metadata -- tile index, one 16-byte header read, the template chunk, an aligned 1-KiB store -- and none of the
-// box path, i.e. what a writer that got its box pixels for free could at best cost.  NB blocks per wavefront, a grid apart.
-// F32OUT (round 6): the same blocks widened to float32 on the way out -- a block is 1 024 pixels either way (one 16-byte chunk of bytes per
+// F32OUT (round 6): the blocks widened to float32 on the way out -- a block is 1 024 pixels either way (one 16-byte chunk of bytes per
 // lane), so the float32 writer pays the per-block bookkeeping once per 4 KiB instead of once per KiB: the block goes through 1 KiB of LDS
 // and leaves as four 1-KiB wave stores (store k, lane l: the float4 of pixels 256 k + 4 l .. + 3).
 __device__ inline void store_block_f32(const uint8_t *tl, float4 *__restrict__ outf, int64_t first_chunk, int lane, int64_t total_chunks) {
@@ -656,53 +443,10 @@ __device__ inline void store_block_f32(const uint8_t *tl, float4 *__restrict__ o
             outf[first_chunk * 4 + 64 * k + lane] = make_float4((float)(px[k] & 255u), (float)((px[k] >> 8) & 255u), (float)((px[k] >> 16) & 255u), (float)(px[k] >> 24));
 }
 
-template <int NB, bool F32OUT = false>
-__global__ __launch_bounds__(256) void pong_gray_sweep_skeleton_kernel(const GrayTileHdr *__restrict__ hdrs, int n_tiles, GrayGeom q,
-                                                                       uint8_t *__restrict__ obs, int stride, int dense) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[F32OUT ? 4 : 1][F32OUT ? 1024 : 16];
-    constexpr int R = 84, chunks = R * R >> 4;
-    const int total = n_tiles * chunks;
-    const int bb = q.band_chunks;
-    const int zc0 = (q.zero_row0 * R + 15) >> 4, zc1 = (q.zero_row1 * R) >> 4;
-    const uint4 *__restrict__ band4 = reinterpret_cast<const uint4 *>(q.band);
-    const uint4 *__restrict__ rest4 = reinterpret_cast<const uint4 *>(q.rest);
-    int gl[NB], c[NB];
-    uint2 h[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++) {
-        gl[i] = ((int)blockIdx.x * 256 + (int)threadIdx.x) + i * stride * 64;
-        const int gg = min(gl[i], total - 1), tile = gg / chunks;
-        c[i] = gg - tile * chunks;
-        if (dense == 2) {  // 2 bytes per tile (1 MB for 524 288 tiles: resident in every L2): band-table row | kind << 12
-            const uint32_t m16 = reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint2 *>(hdrs + n_tiles) + n_tiles)[tile];
-            h[i] = make_uint2((m16 & 4095u) * (uint32_t)bb, m16 >> 12);
-        } else {
-            h[i] = dense ? reinterpret_cast<const uint2 *>(hdrs + n_tiles)[tile] : *reinterpret_cast<const uint2 *>(hdrs + tile);  // band offset, kind
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NB; i++) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if ((h[i].y & 255u) != 0) {
-            if (c[i] < bb) v = band4[h[i].x + c[i]];
-            else if (c[i] < zc0 || c[i] >= zc1) v = rest4[c[i]];
-        }
-        if (F32OUT) {
-            const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-            reinterpret_cast<uint4 *>(lds[wave])[lane] = v;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            store_block_f32(lds[wave], reinterpret_cast<float4 *>(obs), (int64_t)gl[i] - lane, lane, total);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        } else if (gl[i] < total) {
-            reinterpret_cast<uint4 *>(obs)[gl[i]] = v;
-        }
-    }
-}
-
 template <int RT, int NB, bool F32OUT = false>
 __global__ __launch_bounds__(256) void pong_raster_gray_sweep_kernel(const GrayTileHdr *__restrict__ hdrs, int n_tiles, GrayCtx g, GrayGeom q,
-                                                                     uint8_t *__restrict__ obs, int dbg, const uint64_t *__restrict__ ring,
-                                                                     int64_t n, int stride) {
+                                                                     uint8_t *__restrict__ obs, const uint64_t *__restrict__ ring, int64_t n,
+                                                                     int stride) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4][1024];
     __shared__ uint32_t rowpack_[4][16], colpack_[4][kMaxR];
     constexpr int MAXT = 3;
@@ -726,7 +470,7 @@ __global__ __launch_bounds__(256) void pong_raster_gray_sweep_kernel(const GrayT
     for (int i = 0; i < NB; i++) {  // ---- every block's template chunk: score rows from the band table, zeros for the court, ...
         const uint32_t kind = h[i].y & 255u;
         v[i] = make_uint4(0, 0, 0, 0);
-        if (kind != 0 && !(dbg & 4)) {
+        if (kind != 0) {
             if (c[i] < bb) v[i] = band4[h[i].x + c[i]];
             else if (c[i] < zc0 || c[i] >= zc1) v[i] = rest4[c[i]];
         }
@@ -738,7 +482,7 @@ __global__ __launch_bounds__(256) void pong_raster_gray_sweep_kernel(const GrayT
         const uint32_t kind = h[i].y & 255u;
         // bit j of the tile's 64-bit mask: chunks [8 j, 8 j + 8) hold pixels of a box
         const uint32_t mword = (c[i] >> 3) < 32 ? h[i].z : h[i].w;
-        const bool mine = active && (kind == 2 || (kind == 1 && ((mword >> ((c[i] >> 3) & 31)) & 1u) && !(dbg & 1)));
+        const bool mine = active && (kind == 2 || (kind == 1 && ((mword >> ((c[i] >> 3) & 31)) & 1u)));
         if (!__any(mine)) {  // most blocks: the template, stored straight away
             if (F32OUT) {
                 reinterpret_cast<uint4 *>(lds[wave])[lane] = v[i];
@@ -824,17 +568,6 @@ __global__ __launch_bounds__(256) void pong_raster_gray_sweep_kernel(const GrayT
         else if (active) *out = reinterpret_cast<const uint4 *>(tl)[lane];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the LDS block is reused by the wave's next block
     }
-}
-
-void pong_gray_print_ticks() {
-    static unsigned long long rows[1024][8];
-    if (hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_gray_ticks), sizeof(rows)) != hipSuccess) return;
-    unsigned long long t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < 1024; r++)
-        for (int i = 0; i < 8; i++) t[i] += rows[r][i];
-    if (!t[7]) return;
-    fprintf(stderr, "gray env kernel, mean cycles per wavefront (all its tiles) over %llu wavefronts: loop top/ring words %llu | template issue + boxes %llu | "
-            "row/col words %llu | LDS fill %llu | patch %llu | stream-out %llu\n", t[7], t[0] / t[7], t[1] / t[7], t[2] / t[7], t[3] / t[7], t[4] / t[7], t[5] / t[7]);
 }
 
 #endif  // CRL_ABLATION
@@ -924,7 +657,6 @@ struct F32RefGeom {
     int band_rows, bot0;
     const uint8_t *x_first, *x_last, *y_first, *y_last;
     int xtaps, ytaps;  // entries of the x / y tap tables
-    int debug;         // profiling build: 16 = no re-draw, 32 = no table copy (WRONG pixels: what each phase costs)
     int map_row0, map_rows;  // output rows fed by the court's source rows [CRL_PONG_TOP, CRL_PONG_BOTTOM)
 };
 static constexpr int kF32MaxR = 84, kF32MaxTaps = 3 * kF32MaxR + 8;
@@ -938,7 +670,6 @@ __global__ __launch_bounds__(256, CRL_F32REF_LB) void pong_gray_f32ref_kernel(co
     __shared__ float s_xalpha[kF32MaxTaps], s_yalpha[kF32MaxTaps];
     __shared__ __attribute__((aligned(16))) uint8_t s_map[4][kF32MapBytes];  // per wavefront: court pixel -> index of its re-drawn value (255: none)
     __shared__ float s_pval[4][192];
-    if (q.debug & 64) return;
     GrayCtx g = gg;
     if (R <= kF32MaxR && q.xtaps <= kF32MaxTaps && q.ytaps <= kF32MaxTaps) {  // (uniform)
         for (int i = threadIdx.x; i <= R; i += 256) s_xofs[i] = gg.xofs[i], s_yofs[i] = gg.yofs[i];
@@ -947,7 +678,6 @@ __global__ __launch_bounds__(256, CRL_F32REF_LB) void pong_gray_f32ref_kernel(co
         g.xofs = s_xofs, g.yofs = s_yofs, g.xsi = s_xsi, g.ysi = s_ysi, g.xalpha = s_xalpha, g.yalpha = s_yalpha;
     }
     __syncthreads();
-    if (q.debug & 128) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     // jobs of an env: the planes of a bound FrameStackTensor first (GrayStack, pong_device.h), then the observation's tiles
@@ -1027,7 +757,7 @@ __global__ __launch_bounds__(256, CRL_F32REF_LB) void pong_gray_f32ref_kernel(co
 #pragma unroll
     for (int k = 0; k < kRedraw; k++) {
         const int i = lane + 64 * k;
-        if (i >= total || (q.debug & 16)) continue;
+        if (i >= total) continue;
         int o = 0, base = 0;
 #pragma unroll
         for (int m = 0; m < 5; m++)
@@ -1043,7 +773,7 @@ __global__ __launch_bounds__(256, CRL_F32REF_LB) void pong_gray_f32ref_kernel(co
     const float *bot = q.bot + (int64_t)(rounded ? 1 : 0) * (R - q.bot0) * R;
     const int ntop = q.band_rows * R, nbot0 = q.bot0 * R;
     // the map covers output rows [map_row0, map_row0 + map_rows): every row a court rectangle can feed
-    const bool pieces = ((ntop | nbot0 | (R * R) | R) & 3) == 0 && q.map_rows * R <= kF32MapBytes && !(q.debug & (16 | 32));  // (uniform; R = 84: always)
+    const bool pieces = ((ntop | nbot0 | (R * R) | R) & 3) == 0 && q.map_rows * R <= kF32MapBytes;  // (uniform; R = 84: always)
     if (pieces) {
         uint8_t *map = s_map[wave];
         float *pval = s_pval[wave];
@@ -1097,13 +827,10 @@ __global__ __launch_bounds__(256, CRL_F32REF_LB) void pong_gray_f32ref_kernel(co
             out4[i] = v;
         }
     } else {
-        if (!(q.debug & 32)) {
-            for (int i = lane; i < ntop; i += 64) out[i] = top[i];
-            for (int i = ntop + lane; i < nbot0; i += 64) out[i] = 0.0f;
-            for (int i = nbot0 + lane; i < R * R; i += 64) out[i] = bot[i - nbot0];
-        }
+        for (int i = lane; i < ntop; i += 64) out[i] = top[i];
+        for (int i = ntop + lane; i < nbot0; i += 64) out[i] = 0.0f;
+        for (int i = nbot0 + lane; i < R * R; i += 64) out[i] = bot[i - nbot0];
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the re-drawn pixels below overwrite what other lanes have just stored: those stores first
-        if (q.debug & 16) return;
 #pragma unroll
         for (int k = 0; k < kRedraw; k++)
             if (rpos[k] >= 0) out[rpos[k]] = rval[k];
@@ -1139,8 +866,7 @@ void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t 
     if (p.obs_f32 == 2) {  // CRL_OBS_F32_REF
         const int views = p.views > 0 ? p.views : 2;
         const int64_t tiles = p.n * ((p.stack.out ? p.stack.k : 0) + (p.obs ? views * p.K - (p.stack.out && p.stack.alias ? 1 : 0) : 0));
-        static const int dbg = CRL_ABL(getenv("CRL_GRAY_DEBUG") != nullptr) ? atoi(getenv("CRL_GRAY_DEBUG")) : 0;
-        const F32RefGeom fq = {t.f32_top, t.f32_bot, t.band_rows, t.f32_bot0, t.x_first, t.x_last, t.y_first, t.y_last, t.f32_xtaps, t.f32_ytaps, dbg,
+        const F32RefGeom fq = {t.f32_top, t.f32_bot, t.band_rows, t.f32_bot0, t.x_first, t.x_last, t.y_first, t.y_last, t.f32_xtaps, t.f32_ytaps,
                                t.f32_map_row0, t.f32_map_rows};
         hipLaunchKernelGGL(pong_gray_f32ref_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p.ring, p.n, g, fq, t.R, p.K, views,
                            reinterpret_cast<float *>(p.obs), p.stack);
@@ -1151,59 +877,29 @@ void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t 
     q.band = t.band, q.rest = t.rest, q.zero_row0 = t.zero_row0, q.zero_row1 = t.zero_row1;
     q.x_first = t.x_first, q.x_last = t.x_last, q.y_first = t.y_first, q.y_last = t.y_last;
     q.tab_blob = t.tab_blob, q.t = t.tofs;
-    q.debug = 0;
 #ifdef CRL_ABLATION
-    const int64_t tiles = p.n * q.views * p.K;
-    // profiling build only: CRL_GRAY_DEBUG bits skip phases of the env kernel (WRONG pixels) or select the first tile kernel (8);
-    // CRL_GRAY_SWEEP=1 the address-linear writer (bit-exact, slower), 2 | 3 its skeletons (wrong pixels)
-    {
-        static const int dbg = getenv("CRL_GRAY_DEBUG") ? atoi(getenv("CRL_GRAY_DEBUG")) : 0;
-        q.debug = dbg;
-    }
-    if ((q.debug & 8) && !p.obs_f32 && !p.stack.out) {
-        hipLaunchKernelGGL(pong_raster_gray_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p.ring, p.n, g, q,
-                           p.obs);
-        return;
-    }
-    // address-linear writer (uint8 output, 16-byte-aligned tiles, three-tap tables: R = 84 and similar sizes):
-    // bit-exact, but 1.0-2.0 ms against the env kernel's 0.75 ms at 65 536 envs -- every block has to read per-tile metadata
+    // profiling build only, CRL_GRAY_SWEEP=1: the address-linear writer (uint8 output, 16-byte-aligned tiles, three-tap tables: R = 84 and
+    // similar sizes): bit-exact, but 1.0-2.0 ms against the env kernel's 0.75 ms at 65 536 envs -- every block has to read per-tile metadata
     // first, and a dependent read in a store-saturated memory system takes microseconds.
+    const int64_t tiles = p.n * q.views * p.K;
     static const int sweep_env = getenv("CRL_GRAY_SWEEP") ? atoi(getenv("CRL_GRAY_SWEEP")) : 0;
-    if (sweep_env && p.obs_f32 != 2 && (!p.obs_f32 || t.R == 84) && !p.stack.out && !q.debug && p.hdr && (t.R * t.R) % 16 == 0 && t.tofs.max_taps <= 3 && t.tofs.fast_ok && tiles * (t.R * t.R >> 4) < (1ll << 31) && (t.R * t.R >> 4) <= 512) {
+    if (sweep_env && p.obs_f32 != 2 && (!p.obs_f32 || t.R == 84) && !p.stack.out && p.hdr && (t.R * t.R) % 16 == 0 && t.tofs.max_taps <= 3 && t.tofs.fast_ok && tiles * (t.R * t.R >> 4) < (1ll << 31) && (t.R * t.R >> 4) <= 512) {
         GrayTileHdr *hdr = reinterpret_cast<GrayTileHdr *>(p.hdr);
         hipLaunchKernelGGL(pong_gray_header_kernel, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, st, p.ring, p.n, q, hdr);
-        static const int sdbg = getenv("CRL_GRAY_SWEEP_DEBUG") ? atoi(getenv("CRL_GRAY_SWEEP_DEBUG")) : 0;
-        static const int nb_env = getenv("CRL_GRAY_SWEEP_NB") ? atoi(getenv("CRL_GRAY_SWEEP_NB")) : 2;
         const int64_t wblocks = (tiles * (t.R * t.R >> 4) + 63) / 64;   // 1-KiB blocks of the whole tensor
-        const int nb = wblocks < 8192 ? 1 : nb_env;
+        const int nb = wblocks < 8192 ? 1 : 2;
         const int stride = (int)(((wblocks + nb - 1) / nb + 3) / 4 * 4);  // blocks per round, a multiple of the 4 waves of a workgroup
         const dim3 grid((unsigned)(stride / 4));
-        const int sweep_mode = sweep_env;
-        if ((sweep_mode == 2 || sweep_mode == 3 || sweep_mode == 4) && t.R == 84) {  // skeletons: 64-byte headers | dense 8-byte records | dense 2-byte records
-            const int dense = sweep_mode - 2;
-#define CRL_SKEL(NBv) do { if (p.obs_f32) hipLaunchKernelGGL((pong_gray_sweep_skeleton_kernel<NBv, true>), grid, dim3(256), 0, st, hdr, (int)tiles, q, p.obs, stride, dense); \
-                           else hipLaunchKernelGGL((pong_gray_sweep_skeleton_kernel<NBv, false>), grid, dim3(256), 0, st, hdr, (int)tiles, q, p.obs, stride, dense); } while (0)
-            if (nb == 1) CRL_SKEL(1);
-            else if (nb == 2) CRL_SKEL(2);
-            else CRL_SKEL(4);
-#undef CRL_SKEL
-            return;
-        }
+#define CRL_SWEEP(...) hipLaunchKernelGGL((pong_raster_gray_sweep_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, hdr, (int)tiles, g, q, p.obs, p.ring, p.n, stride)
         if (p.obs_f32) {  // float32 output (round 6): R = 84 only
-            if (nb == 1) hipLaunchKernelGGL((pong_raster_gray_sweep_kernel<84, 1, true>), grid, dim3(256), 0, st, hdr, (int)tiles, g, q, p.obs, sdbg, p.ring, p.n, stride);
-            else if (nb == 2) hipLaunchKernelGGL((pong_raster_gray_sweep_kernel<84, 2, true>), grid, dim3(256), 0, st, hdr, (int)tiles, g, q, p.obs, sdbg, p.ring, p.n, stride);
-            else hipLaunchKernelGGL((pong_raster_gray_sweep_kernel<84, 4, true>), grid, dim3(256), 0, st, hdr, (int)tiles, g, q, p.obs, sdbg, p.ring, p.n, stride);
-            return;
-        }
-#define CRL_SWEEP(RTv, NBv) hipLaunchKernelGGL((pong_raster_gray_sweep_kernel<RTv, NBv>), grid, dim3(256), 0, st, hdr, (int)tiles, g, q, p.obs, sdbg, p.ring, p.n, stride)
-        if (t.R == 84) {
+            if (nb == 1) CRL_SWEEP(84, 1, true);
+            else CRL_SWEEP(84, 2, true);
+        } else if (t.R == 84) {
             if (nb == 1) CRL_SWEEP(84, 1);
-            else if (nb == 2) CRL_SWEEP(84, 2);
-            else if (nb == 8) CRL_SWEEP(84, 8);
-            else CRL_SWEEP(84, 4);
+            else CRL_SWEEP(84, 2);
         } else {
             if (nb == 1) CRL_SWEEP(0, 1);
-            else CRL_SWEEP(0, 4);
+            else CRL_SWEEP(0, 4);  // (blocks past the tensor's end are not stored)
         }
 #undef CRL_SWEEP
         return;
@@ -1211,24 +907,18 @@ void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t 
 #endif  // CRL_ABLATION
     // planes per wave: the whole stack of an env per wave once there are enough envs to fill
     // the chip (256 CUs x 16 waves), one plane per wave below that
-    static const int ppw_env = CRL_ABL(getenv("CRL_GRAY_PPW") ? atoi(getenv("CRL_GRAY_PPW")) : 0);  // tuning experiments (profiling build)
-    int ppw = (p.n >= 8192 && !(q.debug & 16)) ? p.K : 1;
-    if (ppw_env > 0 && p.K % ppw_env == 0) ppw = ppw_env;
-    static const bool small_off = CRL_ABL(getenv("CRL_GRAY_SMALL_OFF") != nullptr);  // A/B: the R <= 45 instance off
+    const int ppw = p.n >= 8192 ? p.K : 1;
     const GrayStack &sk = p.stack;
     if (sk.out) {  // FrameStackTensor fused into the draw: the env's jobs = the stack's planes + the observation's tiles
         const int jobs = sk.k + (p.obs ? q.views * p.K - (sk.alias ? 1 : 0) : 0);
-        static const int jpw_env = CRL_ABL(getenv("CRL_GRAY_JPW") != nullptr) ? atoi(getenv("CRL_GRAY_JPW")) : 0;
         // jobs per wavefront: a uint8 stack is fastest with the whole env in one wavefront (497 us; two / three jobs: 655 / 576); a float32
-        // stack with two (five alternating pairs, tools/ab/r06_stack_jpw2.sh: - 1.2 ... - 7.5 % against the whole env, mean - 3 %)
-        int jpw = p.n >= 8192 ? (sk.f32 ? 2 : jobs) : 1;
-        if (jpw_env > 0) jpw = jpw_env;
-        if (jpw_env < 0) jpw = jobs;  // (profiling build: CRL_GRAY_JPW=-1 = all of the env's jobs)
+        // stack with two (five alternating pairs: - 1.2 ... - 7.5 % against the whole env, mean - 3 %)
+        const int jpw = p.n >= 8192 ? (sk.f32 ? 2 : jobs) : 1;
         const int64_t waves = p.n * ((jobs + jpw - 1) / jpw);
         const dim3 grid((unsigned)((waves + 3) / 4));
-        const int ti = t.tofs.max_taps <= 3 ? 0 : (t.R * t.R <= 2048 && !small_off) ? 1 : 2;
+        const int ti = t.tofs.max_taps <= 3 ? 0 : (t.R * t.R <= 2048) ? 1 : 2;
 #define CRL_STACK_LAUNCH(MT, TIv, OF, SF) \
-    hipLaunchKernelGGL((pong_raster_gray_env_kernel<MT, false, TIv, OF, true, SF>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, jpw, sk)
+    hipLaunchKernelGGL((pong_raster_gray_env_kernel<MT, TIv, OF, true, SF>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, jpw, sk)
 #define CRL_STACK_TI(OF, SF)                           \
     do {                                               \
         if (ti == 0) CRL_STACK_LAUNCH(3, 7, OF, SF);   \
@@ -1247,41 +937,33 @@ void launch_pong_raster_gray(const GrayTables &t, const GrayJob &p, hipStream_t 
     const dim3 grid((unsigned)((waves + 3) / 4));
     if (p.obs_f32) {
         if (t.tofs.max_taps <= 3)
-            hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, false, 7, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
-        else if (t.R * t.R <= 2048 && !small_off)
-            hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 2, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+            hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, 7, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+        else if (t.R * t.R <= 2048)
+            hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, 2, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         else
-            hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 7, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+            hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, 7, true>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         return;
     }
-#ifdef CRL_ABLATION
-    if (q.debug & ~16) {  // any ablation switch: the instrumented instance
-        if (t.tofs.max_taps <= 3) hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, true, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
-        else hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, true, 2, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
-        return;
-    }
-#endif
     // one plane per agent (the observation make_envs("cPongDouble-v0") itself returns) in a batch that fills the chip several times over: four
-    // envs per wavefront (CRL_GRAY_EPWV=1 in the profiling build: one)
-    static const int epwv_env = CRL_ABL(getenv("CRL_GRAY_EPWV") ? atoi(getenv("CRL_GRAY_EPWV")) : 0);
+    // envs per wavefront
 #ifndef CRL_GRAY_EPWV_N
 #define CRL_GRAY_EPWV_N 4  // (measured at 65 536 envs, 84 x 84: 1 / 4 envs per wavefront 237 / 221 us)
 #endif
-    if (p.K == 1 && ppw == 1 && p.n >= 8192 * CRL_GRAY_EPWV_N && epwv_env != 1 && (t.tofs.max_taps <= 3 || (t.R * t.R <= 2048 && !small_off))) {
+    if (p.K == 1 && ppw == 1 && p.n >= 8192 * CRL_GRAY_EPWV_N && (t.tofs.max_taps <= 3 || (t.R * t.R <= 2048))) {
         constexpr int E = CRL_GRAY_EPWV_N;
         const dim3 grid4((unsigned)(((p.n + E - 1) / E + 3) / 4));
         if (t.tofs.max_taps <= 3)
-            hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, false, 7, false, false, false, E>), grid4, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+            hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, 7, false, false, false, E>), grid4, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         else
-            hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 2, false, false, false, E>), grid4, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+            hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, 2, false, false, false, E>), grid4, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
         return;
     }
     if (t.tofs.max_taps <= 3)
-        hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, false, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
-    else if (t.R * t.R <= 2048 && !small_off)
-        hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 2, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+        hipLaunchKernelGGL((pong_raster_gray_env_kernel<3, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+    else if (t.R * t.R <= 2048)
+        hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, 2, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
     else
-        hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, false, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
+        hipLaunchKernelGGL((pong_raster_gray_env_kernel<5, 7, false>), grid, dim3(256), 0, st, p.ring, p.n, g, q, p.obs, ppw, nosk);
 }
 
 }  // namespace crl

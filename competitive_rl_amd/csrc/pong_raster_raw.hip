@@ -13,9 +13,7 @@
 //   rows >=194: white.
 // Agent 1's view is rows >= 25 mirrored; since every pixel is achromatic (R=G=B) a
 // mirrored chunk is the byte-reversed chunk (29 - c) of the unmirrored row.
-// Three work splits: pong_raster_raw_sweep_kernel (production: address-linear, a thread's four chunks a whole grid
-// apart), pong_raster_raw_linear_kernel (address-linear, a workgroup's chunks contiguous; CRL_RAW_SWEEP=0) and the
-// original one workgroup per env (thread t writes chunks t, t+256, ...; CRL_RAW_SWEEP=0 CRL_RAW_LINEAR=0), kept for A/B.
+// The work split is pong_raster_raw_sweep_kernel's: address-linear, a thread's four chunks a whole grid apart.
 #include <stdlib.h>
 
 #include "crl_internal.h"
@@ -42,8 +40,8 @@ __device__ inline uint32_t span_bits(int a, int b) {
 __device__ inline uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
 
 // The 16 bytes of chunk q (0 .. views * kFrameChunks - 1) of one env's frames: THE pixel function of this file, shared by
-// the three work splits below.  dbg: 1 = constants only, 2 = no score-band loads (profiling).
-__device__ __forceinline__ uint4 raw_chunk(const Frame &f, int q, const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1, int dbg) {
+// the full draw and the delta draw below.
+__device__ __forceinline__ uint4 raw_chunk(const Frame &f, int q, const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1) {
     const bool blank = f.sl == 255;
     const uint32_t bg = blank ? 0u : 0xFFFFFFFFu;
     const int view = q >= kFrameChunks;
@@ -53,9 +51,9 @@ __device__ __forceinline__ uint4 raw_chunk(const Frame &f, int q, const uint4 *_
     const bool mirror = view && row >= CRL_PONG_MIRROR_ROW;
     const int sc = mirror ? (kRowChunks - 1 - cc) : cc;  // source chunk in the unmirrored row
     uint4 v = make_uint4(bg, bg, bg, bg);
-    if (!blank && !(dbg & 1)) {
+    if (!blank) {
         if (row < CRL_PONG_TOP) {
-            if (row >= ink_row0 && row < ink_row1 && !(dbg & 2)) v = atlas_rgb[(int64_t)((f.sl * 22 + f.sr) * CRL_PONG_TOP + row) * kRowChunks + sc];
+            if (row >= ink_row0 && row < ink_row1) v = atlas_rgb[(int64_t)((f.sl * 22 + f.sr) * CRL_PONG_TOP + row) * kRowChunks + sc];
         } else if (row < CRL_PONG_BOTTOM) {
             const int lo = sc * 16;
             uint32_t m = 0;
@@ -107,61 +105,16 @@ __device__ __forceinline__ uint4 court_chunk(const Frame &f, int row, int sc, bo
                       nibble_to_bytes_perm(m >> 12));
 }
 
-#ifdef CRL_ABLATION  // superseded writers (one workgroup per env; workgroup-contiguous): profiling build only, CRL_RAW_SWEEP=0
-__global__ __launch_bounds__(256) void pong_raster_raw_kernel(const uint64_t *__restrict__ frames,
-                                                              const uint4 *__restrict__ atlas_rgb, int ink_row0,
-                                                              int ink_row1, uint4 *__restrict__ obs, int views, int dbg) {
-    const int64_t env = blockIdx.x;
-    const uint64_t packed = frames[env];  // wave-uniform -> scalar load
-    const Frame f = unpack_frame(packed);
-    uint4 *__restrict__ out = obs + env * (int64_t)(views * kFrameChunks);
-    for (int q = threadIdx.x; q < views * kFrameChunks; q += 256) out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, dbg);
-}
-
-// Address-linear kernel, workgroup-contiguous (production until the sweep variant below): workgroup b writes chunks [b * 512, (b + 1) * 512) of
-// the WHOLE output tensor -- two 16-byte chunks per thread, 8 KiB per workgroup -- whichever envs
-// they belong to (at most two).  Measured on MI355X at 65 536 envs (13.2 GB per launch):
-//   one workgroup per env, 49 chunks per thread            2 250-2 300 us  (5.8 TB/s)
-//   address-linear, 1 / 2 / 4 / 8 chunks per thread    2 550 / 2 030 / 2 120 / 2 180 us
-//   torch.Tensor.fill_ of the same bytes (ceiling)           1 915 us      (6.9 TB/s)
-// With one workgroup per env the ~2 000 resident workgroups write 2 000 separate streams 201 600 B
-// apart, which DRAM sees as that many open pages; here the resident workgroups cover one moving
-// 16 MB window of the tensor, like a plain fill.  One chunk per thread is bound by wave launch
-// plus the frame-descriptor load in front of every wave; more than two widen the window again.
-// The pixel arithmetic itself is off the critical path (removing it changes nothing).
-template <int ITERS, int THREADS, int VIEWS>
-__global__ __launch_bounds__(THREADS) void pong_raster_raw_linear_kernel(const uint64_t *__restrict__ frames,
-                                                                         const uint4 *__restrict__ atlas_rgb, int ink_row0,
-                                                                         int ink_row1, uint4 *__restrict__ obs, int views, int64_t n,
-                                                                         int dbg) {
-    constexpr int per_env = VIEWS * kFrameChunks;
-    const int64_t g0 = (int64_t)blockIdx.x * (THREADS * ITERS);
-    const int64_t total = n * per_env;
-    const int64_t e0 = g0 / per_env;  // first env of this span; the span is shorter than one env
-    const int64_t e1 = e0 + 1 < n ? e0 + 1 : e0;
-    const Frame f0 = unpack_frame(frames[e0]), f1 = unpack_frame(frames[e1]);  // uniform -> scalar loads
-    const int q0 = (int)(g0 - e0 * per_env);
-#pragma unroll
-    for (int i = 0; i < ITERS; i++) {
-        const int64_t g = g0 + i * THREADS + threadIdx.x;
-        if (g >= total) break;
-        int q = q0 + i * THREADS + (int)threadIdx.x;
-        const bool second = q >= per_env;
-        q -= second ? per_env : 0;
-        obs[g] = raw_chunk(pick_frame(f0, f1, second), q, atlas_rgb, ink_row0, ink_row1, dbg);
-    }
-}
-
-#endif  // CRL_ABLATION
-
-// Sweep variant of the address-linear kernel: thread t of workgroup b writes chunks b * 256 + t + i * (gridDim.x * 256),
+// The full draw, address-linear (workgroups write chunks of the WHOLE output tensor, whichever envs they belong to: with one
+// workgroup per env the ~2 000 resident workgroups write 2 000 separate streams 201 600 B apart, which DRAM sees as that many open
+// pages): thread t of workgroup b writes chunks b * 256 + t + i * (gridDim.x * 256),
 // i = 0 .. ITERS-1 -- every "round" i of the whole chip is one dense linear sweep over 1/ITERS of the tensor.  Pure-store
 // probes (tools/store_order_probe.hip): a wavefront that walks through a private contiguous span makes the chip write a
 // comb (one tooth per resident wavefront) and loses 8-20 % of the fill rate; stores a whole grid apart do not, however
 // many a wavefront issues.  Per round a workgroup's 4 KB block touches at most two envs (two scalar descriptor loads).
 template <int ITERS, int VIEWS>
 __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64_t *__restrict__ frames, const uint4 *__restrict__ atlas_rgb,
-                                                                    int ink_row0, int ink_row1, uint4 *__restrict__ obs, int64_t n, int dbg) {
+                                                                    int ink_row0, int ink_row1, uint4 *__restrict__ obs, int64_t n) {
     constexpr int per_env = VIEWS * kFrameChunks;
     const int64_t total = n * per_env;
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -183,7 +136,7 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
         int q = q0[i] + (int)threadIdx.x;
         const bool second = q >= per_env;
         q -= second ? per_env : 0;
-        obs[g] = raw_chunk(pick_frame(f0[i], f1[i], second), q, atlas_rgb, ink_row0, ink_row1, dbg);
+        obs[g] = raw_chunk(pick_frame(f0[i], f1[i], second), q, atlas_rgb, ink_row0, ink_row1);
     }
 }
 
@@ -230,7 +183,7 @@ __global__ __launch_bounds__(256) void pong_raster_raw_sweep_kernel(const uint64
 //   L = 16 / 64, G = 4 ................................ 101 / 108 us on that second box
 // The cost was the partial memory request, not the byte count (G = 4 writes 198 MB against 118.7) and not the lane order.
 // Round 9 (profiles/r09_raw_summary.txt): the mapping above against the one before it (running sums over six rectangles, slot ->
-// rectangle decoded per trip, chunks built by raw_chunk(); CRL_RAW_DELTA_SLOTS=1 in the profiling build), alternating runs on one box:
+// rectangle decoded per trip, chunks built by raw_chunk()), alternating runs on one box:
 //   vector / scalar instructions per wavefront ........ 516 / 295 -> 272 / 148 (SQ counters); no load and no vmcnt wait in the court code
 //   the launch inside the bench's event brackets ....... 96.4 -> 91.3 us; the step 0.1103 -> 0.1051 ms; same requests, same bytes
 // Half the instructions bought a twentieth of the time: the launch is bound by its 3.1 M scattered 64-byte requests, not by issue.
@@ -291,7 +244,7 @@ __device__ __forceinline__ void raw_delta_draw(uint64_t pn, uint64_t po, int vie
     if (blank_n && blank_o) return;  // (two blank frames are equal)
     const int q_view = view * kFrameChunks;
     if (blank_n != blank_o) {  // the whole frame
-        for (int c = lane; c < kFrameChunks; c += L) chunk_store<NT>(out + (q_view + c), raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0));
+        for (int c = lane; c < kFrameChunks; c += L) chunk_store<NT>(out + (q_view + c), raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1));
         return;
     }
     const int j = lane & (G - 1), u = lane >> SH;  // this lane's chunk of a block; its (row, block) place within an object
@@ -306,7 +259,7 @@ __device__ __forceinline__ void raw_delta_draw(uint64_t pn, uint64_t po, int vie
         }
         if (s1 >= kRowChunks) {  // every other pair (a game's end, set_state, a successor outside the atlas): every chunk of the ink rows
             const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
-            for (int c = lane; c < cn; c += L) chunk_store<NT>(out + (c0 + c), raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0));
+            for (int c = lane; c < cn; c += L) chunk_store<NT>(out + (c0 + c), raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1));
         } else if (s0 <= s1) {
             // place = (ink row, block of the row): a row's span touches at most nb blocks (it starts anywhere within its first
             // block), 1 << bs >= nb of them are a row's share of a trip's L / G places, and a trip takes (L / G) >> bs rows
@@ -320,7 +273,7 @@ __device__ __forceinline__ void raw_delta_draw(uint64_t pn, uint64_t po, int vie
                 const int first = (q_row + (mir ? kRowChunks - 1 - s1 : s0)) >> SH, last = (q_row + (mir ? kRowChunks - 1 - s0 : s1)) >> SH;
                 for (int b0 = 0; b0 < nb; b0 += 1 << bs) {
                     const int blk = first + b0 + bu, q = (blk << SH) + j;  // (a block may reach into the neighbouring row: raw_chunk() draws that row's chunk)
-                    if (row < ink_row1 && blk <= last) chunk_store<NT>(out + q, raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0));
+                    if (row < ink_row1 && blk <= last) chunk_store<NT>(out + q, raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1));
                 }
             }
         }
@@ -387,7 +340,8 @@ __global__ __launch_bounds__(256) void pong_raster_raw_delta_kernel(const uint64
 // 0 .. W-1 (every other lane: two blank ones, which the draw skips) and walks them, 64 / kDeltaL / VIEWS per trip as the draw-only
 // kernel's wavefronts do, taking each env's pair out of its lane -- with two views by readlane at the uniform trip index, so the
 // rectangles, trip counts and branches of raw_delta_draw() stay scalar code; with one view each 32-lane group fetches its env's
-// pair by a shuffle.  stepped (profiling build): phase A only reads the descriptors a dynamics launch left.
+// pair by a shuffle.  stepped: phase A only reads the descriptors a dynamics launch left; always 0 (kept: without the argument the
+// unaligned two-view instance allocates two scalar registers more).
 // Measured on MI355X at 65 536 envs, two views, variants alternated inside one process over bench.py's window (r11_raw_summary.txt):
 //   draw-only kernel behind the dynamics kernel ....... 68.6 + 5.4 us in their brackets, the step 0.0825 ms
 //   first design: no LDS, every wavefront steps its own W = 16 envs in 16 lanes and draws them in sequence ... 78.0 us, 0.0826 ms
@@ -440,229 +394,16 @@ __global__ __launch_bounds__(64 * (B / W)) void pong_step_raw_delta_kernel(
     }
 }
 
-#ifdef CRL_ABLATION  // superseded mapping (running sums over six rectangles, a slot decode per trip; every L and G): profiling build only, CRL_RAW_DELTA_SLOTS=1
-static constexpr int kBatLc0 = 3 * CRL_PONG_BATL_X / 16, kBatLc1 = (3 * (CRL_PONG_BATL_X + CRL_PONG_BAT_W) - 1) / 16;
-static constexpr int kBatRc0 = 3 * CRL_PONG_BATR_X / 16, kBatRc1 = (3 * (CRL_PONG_BATR_X + CRL_PONG_BAT_W) - 1) / 16;
-
-// rows [r0, r0 + nr) of the court x output chunks [o0, o1] of each row (at most two), the view's mirroring applied
-struct DeltaRect {
-    int r0, nr, o0, o1;
-};
-
-// (rows [r0, r1) clamped to the court) x (source chunks [c0, c1]): the mirrored view's chunk of source chunk c is 29 - c
-__device__ __forceinline__ DeltaRect delta_rect(int view, int r0, int r1, int c0, int c1) {
-    r0 = max(r0, CRL_PONG_TOP), r1 = min(r1, CRL_PONG_BOTTOM);
-    const bool mirror = view != 0;  // (court rows are all >= CRL_PONG_MIRROR_ROW)
-    DeltaRect r;
-    r.r0 = r0, r.nr = max(r1 - r0, 0);
-    r.o0 = mirror ? kRowChunks - 1 - c1 : c0, r.o1 = mirror ? kRowChunks - 1 - c0 : c1;
-    return r;
-}
-
-// the rows of the symmetric difference of [a, a + h) and [b, b + h): [lo, lo + k) and [hi + h - k, hi + h), k = min(|a - b|, h)
-__device__ __forceinline__ void delta_bat(DeltaRect *r, int view, int a, int b, int c0, int c1) {
-    const int lo = min(a, b), hi = max(a, b), k = min(hi - lo, CRL_PONG_BAT_H);
-    r[0] = delta_rect(view, lo, lo + k, c0, c1);
-    r[1] = delta_rect(view, hi + CRL_PONG_BAT_H - k, hi + CRL_PONG_BAT_H, c0, c1);
-}
-
-__device__ __forceinline__ DeltaRect delta_ball(int view, const Frame &g, bool moved) {
-    const int b0 = max(3 * g.x, 0), b1 = min(3 * (g.x + CRL_PONG_BALL), kRowBytes);  // bytes of the row the ball covers
-    DeltaRect r = delta_rect(view, g.y, g.y + CRL_PONG_BALL, b0 / 16, (max(b1, 1) - 1) / 16);
-    if (!moved || b0 >= b1) r.nr = 0;
-    return r;
-}
-
-// blocks of G = 1 << SH chunks a rectangle's row touches: the block of its first chunk counts from the view's first chunk, and a
-// row starts 0 or 2 chunks into a 4-chunk block, so the larger of the two counts (slots past a row's last block store nothing)
-template <int SH>
-__device__ __forceinline__ int delta_blocks(const DeltaRect &r) {
-    const int n0 = (r.o1 >> SH) - (r.o0 >> SH) + 1, n2 = ((r.o1 + 2) >> SH) - ((r.o0 + 2) >> SH) + 1;
-    return max(n0, n2);
-}
-
-template <int VIEWS, int L, int G>
-__global__ __launch_bounds__(256) void pong_raster_raw_delta_slots_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
-                                                                    const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
-                                                                    uint4 *__restrict__ obs, int64_t n) {
-    static_assert((L == 16 || L == 32 || L == 64) && (G == 1 || G == 2 || G == 4) && (VIEWS == 1 || VIEWS == 2), "");
-    constexpr int per_env = VIEWS * kFrameChunks, SH = G == 4 ? 2 : G == 2 ? 1 : 0;
-    constexpr int GW = 64 / L;  // groups per wavefront
-    const int64_t gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);  // this wavefront, of the grid
-    const int lane = (int)threadIdx.x & (L - 1);
-    int64_t env;
-    int view;
-    if constexpr (GW >= VIEWS) {  // a wavefront holds GW / VIEWS whole envs: one env -> uniform descriptor loads
-        constexpr int E = GW / VIEWS;
-        const int sub = ((int)threadIdx.x & 63) / L;
-        env = gw * E + (E > 1 ? sub / VIEWS : 0), view = sub % VIEWS;
-    } else {  // L = 64, two views: an env is two wavefronts of one workgroup
-        env = gw / VIEWS, view = (int)(gw % VIEWS);
-    }
-    const bool valid = env < n;
-    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
-    if constexpr (GW < VIEWS) __syncthreads();  // both wavefronts of the env have read its record
-    if (valid && view == 0 && lane == 0) drawn[env] = pn;
-    const Frame f = unpack_frame(pn), g = unpack_frame(po);
-    const bool blank_n = f.sl == 255, blank_o = g.sl == 255;
-    if (!valid || (blank_n && blank_o)) return;  // (two blank frames are equal)
-    uint4 *__restrict__ out = obs + env * per_env;
-    const int q_view = view * kFrameChunks;
-    if (blank_n != blank_o) {  // the whole frame
-        for (int c = lane; c < kFrameChunks; c += L) out[q_view + c] = raw_chunk(f, q_view + c, atlas_rgb, ink_row0, ink_row1, 0);
-        return;
-    }
-    if ((f.sl != g.sl || f.sr != g.sr) && ink_row1 > ink_row0) {  // the score band's ink rows
-        const int c0 = q_view + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
-        for (int c = lane; c < cn; c += L) out[c0 + c] = raw_chunk(f, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
-    }
-
-    DeltaRect r[6];
-    const bool moved = f.x != g.x || f.y != g.y;
-    r[0] = delta_ball(view, f, moved), r[1] = delta_ball(view, g, moved);
-    delta_bat(r + 2, view, g.bl, f.bl, kBatLc0, kBatLc1);
-    delta_bat(r + 4, view, g.br, f.br, kBatRc0, kBatRc1);
-    int nb[6], end[6], S = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) nb[i] = delta_blocks<SH>(r[i]), S += r[i].nr * nb[i] * G, end[i] = S;
-    for (int s = lane; s < S; s += L) {
-        int k = 0;  // the rectangle slot s falls into, and its index there
-#pragma unroll
-        for (int i = 0; i < 5; i++) k += s >= end[i];
-        DeltaRect rc = r[0];
-        int t = s, nbk = nb[0];
-#pragma unroll
-        for (int i = 1; i < 6; i++)
-            if (k == i) rc = r[i], t = s - end[i - 1], nbk = nb[i];
-        const int j = t & (G - 1), u = t >> SH;                             // chunk of the block; (row, block) of the rectangle
-        const int dr = nbk == 2 ? u >> 1 : u, b = nbk == 2 ? u & 1 : 0;  // (a rectangle's row touches one or two blocks)
-        const int q_row = q_view + (rc.r0 + dr) * kRowChunks;
-        const int blk = ((q_row + rc.o0) >> SH) + b;
-        if (blk > ((q_row + rc.o1) >> SH)) continue;
-        if (k == 1 && dr + rc.r0 >= r[0].r0 && dr + rc.r0 < r[0].r0 + r[0].nr && blk >= ((q_row + r[0].o0) >> SH) &&
-            blk <= ((q_row + r[0].o1) >> SH))
-            continue;  // the new ball's rectangle stores this block
-        const int q = (blk << SH) + j;
-        out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
-    }
-}
-
-#endif  // CRL_ABLATION
-
-#ifdef CRL_ABLATION  // superseded mapping (one lane per env, one wavefront per (view, object) of 64 envs): profiling build only, CRL_RAW_DELTA_LANES=1
-__device__ __forceinline__ void delta_store(uint4 *__restrict__ out, const Frame &f, const DeltaRect &r, int view, const uint4 *__restrict__ atlas_rgb,
-                                            int ink_row0, int ink_row1) {
-    for (int row = r.r0; row < r.r0 + r.nr; row++)
-        for (int o = r.o0; o <= r.o1; o++) {
-            const int q = view * kFrameChunks + row * kRowChunks + o;
-            out[q] = raw_chunk(f, q, atlas_rgb, ink_row0, ink_row1, 0);
-        }
-}
-
-template <int VIEWS>
-__global__ __launch_bounds__(64 * 3 * VIEWS) void pong_raster_raw_delta_lanes_kernel(const uint64_t *__restrict__ frames, uint64_t *__restrict__ drawn,
-                                                                                   const uint4 *__restrict__ atlas_rgb, int ink_row0, int ink_row1,
-                                                                                   uint4 *__restrict__ obs, int64_t n) {
-    constexpr int per_env = VIEWS * kFrameChunks;
-    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-    const int view = wave / 3, obj = wave - 3 * view;  // obj: 0 ball, 1 left bat, 2 right bat
-    const int64_t env = (int64_t)blockIdx.x * 64 + lane;
-    const bool valid = env < n;
-    const uint64_t pn = valid ? frames[env] : kBlankFrame, po = valid ? drawn[env] : kBlankFrame;
-    __syncthreads();  // every wavefront has read drawn[] of this workgroup's envs
-    if (wave == 0 && valid) drawn[env] = pn;
-    const Frame f = unpack_frame(pn), g = unpack_frame(po);
-    const bool blank_n = f.sl == 255, blank_o = g.sl == 255;
-    const bool whole = blank_n != blank_o;
-    const bool band = !blank_n && !blank_o && (f.sl != g.sl || f.sr != g.sr) && ink_row1 > ink_row0;
-
-    // cooperative part: whole frames, then score bands, of the flagged envs (every wavefront of the view sees the same flags)
-    const int t = obj * 64 + lane;  // 0 .. 191 within the view
-    for (uint64_t m = __ballot(whole); m; m &= m - 1) {
-        const int l = __builtin_ctzll(m);
-        const int64_t e = (int64_t)blockIdx.x * 64 + l;
-        const Frame fe = unpack_frame(frames[e]);
-        uint4 *__restrict__ out = obs + e * per_env;
-        for (int c = t; c < kFrameChunks; c += 192) out[view * kFrameChunks + c] = raw_chunk(fe, view * kFrameChunks + c, atlas_rgb, ink_row0, ink_row1, 0);
-    }
-    for (uint64_t m = __ballot(band); m; m &= m - 1) {
-        const int l = __builtin_ctzll(m);
-        const int64_t e = (int64_t)blockIdx.x * 64 + l;
-        const Frame fe = unpack_frame(frames[e]);
-        uint4 *__restrict__ out = obs + e * per_env;
-        const int c0 = view * kFrameChunks + ink_row0 * kRowChunks, cn = (ink_row1 - ink_row0) * kRowChunks;
-        for (int c = t; c < cn; c += 192) out[c0 + c] = raw_chunk(fe, c0 + c, atlas_rgb, ink_row0, ink_row1, 0);
-    }
-    if (!valid || whole || blank_n) return;  // (a whole frame is drawn above; two blank frames are equal)
-
-    // per-lane part: this env's object in this view
-    uint4 *__restrict__ out = obs + env * per_env;
-    DeltaRect r[2];
-    if (obj == 0) {
-        const bool moved = f.x != g.x || f.y != g.y;
-        r[0] = delta_ball(view, g, moved), r[1] = delta_ball(view, f, moved);
-    } else if (obj == 1) {
-        delta_bat(r, view, g.bl, f.bl, kBatLc0, kBatLc1);
-    } else {
-        delta_bat(r, view, g.br, f.br, kBatRc0, kBatRc1);
-    }
-    delta_store(out, f, r[0], view, atlas_rgb, ink_row0, ink_row1);
-    delta_store(out, f, r[1], view, atlas_rgb, ink_row0, ink_row1);
-}
-#endif  // CRL_ABLATION
-
 void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64_t n, const uint8_t *atlas_rgb, const uint8_t *band_span,
                                   int ink_row0, int ink_row1, uint8_t *obs, int views, hipStream_t st) {
     if (n <= 0 || (views != 1 && views != 2)) return;
     const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
     uint4 *ob = reinterpret_cast<uint4 *>(obs);
-#define CRL_LAUNCH_DELTA(KERNEL, V, L)                                                                                                     \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)((n * V * L + 255) / 256)), dim3(256), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n)
-#ifdef CRL_ABLATION
-    // (profiling build only: CRL_RAW_DELTA_SLOTS=1 selects the superseded running-sum mapping, CRL_RAW_DELTA_L / CRL_RAW_DELTA_G
-    // its lanes per (env, view) and its chunks per block; CRL_RAW_DELTA_LANES=1 the lane-per-env mapping before it)
-    static const int abl_lanes = getenv("CRL_RAW_DELTA_LANES") ? atoi(getenv("CRL_RAW_DELTA_LANES")) : 0;
-    static const int abl_l = getenv("CRL_RAW_DELTA_L") ? atoi(getenv("CRL_RAW_DELTA_L")) : kDeltaL;
-    static const int abl_g = getenv("CRL_RAW_DELTA_G") ? atoi(getenv("CRL_RAW_DELTA_G")) : kDeltaG;
-    static const int abl_slots = getenv("CRL_RAW_DELTA_SLOTS") ? atoi(getenv("CRL_RAW_DELTA_SLOTS")) : 0;
-    if (abl_lanes) {
-        const unsigned blocks = (unsigned)((n + 63) / 64);
-        if (views == 2)
-            hipLaunchKernelGGL((pong_raster_raw_delta_lanes_kernel<2>), dim3(blocks), dim3(384), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
-        else
-            hipLaunchKernelGGL((pong_raster_raw_delta_lanes_kernel<1>), dim3(blocks), dim3(192), 0, st, frames, drawn, at, ink_row0, ink_row1, ob, n);
-        return;
-    }
-    if (abl_slots || abl_l != kDeltaL || abl_g != kDeltaG) {
-        const int g = (uintptr_t)obs % (16 * abl_g) ? 1 : abl_g;
-#define CRL_DELTA_CASE(L, G)                                                                      \
-    if (abl_l == L && g == G) {                                                                   \
-        if (views == 2) CRL_LAUNCH_DELTA((pong_raster_raw_delta_slots_kernel<2, L, G>), 2, L);    \
-        else CRL_LAUNCH_DELTA((pong_raster_raw_delta_slots_kernel<1, L, G>), 1, L);               \
-        return;                                                                                   \
-    }
-        CRL_DELTA_CASE(16, 1) CRL_DELTA_CASE(16, 2) CRL_DELTA_CASE(16, 4) CRL_DELTA_CASE(32, 1) CRL_DELTA_CASE(32, 2) CRL_DELTA_CASE(32, 4)
-        CRL_DELTA_CASE(64, 1) CRL_DELTA_CASE(64, 2) CRL_DELTA_CASE(64, 4)
-#undef CRL_DELTA_CASE
-        return;  // (no such variant: nothing is drawn, which the tests see)
-    }
-#endif
     // a block is a whole memory request only in a buffer aligned to it; crl_draw_raw_delta admits any 16-byte-aligned one: single chunks there
     const bool blocks_ok = (uintptr_t)obs % (16 * kDeltaG) == 0;
-    // (profiling build only: CRL_RAW_BAND_WHOLE=1 stores every chunk of the ink rows at any score change, as before the span table)
-    static const bool band_whole = CRL_ABL(getenv("CRL_RAW_BAND_WHOLE") && atoi(getenv("CRL_RAW_BAND_WHOLE")));
-    const uint8_t *span = band_whole ? nullptr : band_span;
 #define CRL_LAUNCH_DELTA_SPAN(V, G, NT)                                                                                                    \
     hipLaunchKernelGGL((pong_raster_raw_delta_kernel<V, G, NT>), dim3((unsigned)((n * V * kDeltaL + 255) / 256)), dim3(256), 0, st, frames, drawn, at, \
-                       span, ink_row0, ink_row1, ob, n)
-#ifdef CRL_ABLATION
-    // (profiling build only, two views in an aligned buffer: CRL_RAW_NT=1 stores with the non-temporal hint)
-    const bool abl_nt = getenv("CRL_RAW_NT") && atoi(getenv("CRL_RAW_NT"));
-    if (abl_nt != kDeltaNT && views == 2 && blocks_ok) {
-        CRL_LAUNCH_DELTA_SPAN(2, kDeltaG, !kDeltaNT);
-        return;
-    }
-#endif
+                       band_span, ink_row0, ink_row1, ob, n)
     if (views == 2) {
         if (blocks_ok) CRL_LAUNCH_DELTA_SPAN(2, kDeltaG, kDeltaNT);
         else CRL_LAUNCH_DELTA_SPAN(2, 1, kDeltaNT);
@@ -671,38 +412,18 @@ void launch_pong_raster_raw_delta(const uint64_t *frames, uint64_t *drawn, int64
         else CRL_LAUNCH_DELTA_SPAN(1, 1, kDeltaNT);
     }
 #undef CRL_LAUNCH_DELTA_SPAN
-#undef CRL_LAUNCH_DELTA
 }
 
 void launch_pong_step_raw_delta(const PongSoA &s, const ServeSrc &src, const int32_t *actions, int64_t n, float *rew, uint8_t *done,
                                 uint64_t *drawn, const uint8_t *atlas_rgb, const uint8_t *band_span, int ink_row0, int ink_row1, uint8_t *obs,
-                                int views, hipStream_t st, int stepped) {
+                                int views, hipStream_t st) {
     if (n <= 0 || (views != 1 && views != 2)) return;
     const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
     uint4 *ob = reinterpret_cast<uint4 *>(obs);
     const bool blocks_ok = (uintptr_t)obs % (16 * kDeltaG) == 0;  // (as in launch_pong_raster_raw_delta)
 #define CRL_LAUNCH_STEP(V, G, W, B, NT)                                                                                                          \
     hipLaunchKernelGGL((pong_step_raw_delta_kernel<V, G, W, B, NT>), dim3((unsigned)((n + B - 1) / B)), dim3(64 * (B / W)), 0, st, s, src, actions, n, rew, \
-                       done, drawn, at, band_span, ink_row0, ink_row1, ob, stepped)
-#ifdef CRL_ABLATION
-    // (profiling build only, two views in an aligned buffer: CRL_RAW_STEP_W and CRL_RAW_STEP_B select the other candidates, CRL_RAW_NT=1
-    // the non-temporal stores; read at every launch, so that one process can alternate them)
-    const int abl_w = getenv("CRL_RAW_STEP_W") ? atoi(getenv("CRL_RAW_STEP_W")) : kStepW;
-    const int abl_b = getenv("CRL_RAW_STEP_B") ? atoi(getenv("CRL_RAW_STEP_B")) : kStepB;
-    const int abl_nt = getenv("CRL_RAW_NT") ? atoi(getenv("CRL_RAW_NT")) : (int)kStepNT;
-    if (views == 2 && blocks_ok && (abl_w != kStepW || abl_b != kStepB || (abl_nt != 0) != kStepNT)) {
-#define CRL_STEP_CASE(W, B)                                            \
-    if (abl_w == W && abl_b == B) {                                    \
-        if (abl_nt) CRL_LAUNCH_STEP(2, kDeltaG, W, B, true);           \
-        else CRL_LAUNCH_STEP(2, kDeltaG, W, B, false);                 \
-        return;                                                        \
-    }
-        CRL_STEP_CASE(1, 16) CRL_STEP_CASE(2, 16) CRL_STEP_CASE(2, 32) CRL_STEP_CASE(4, 32) CRL_STEP_CASE(4, 64) CRL_STEP_CASE(8, 64) CRL_STEP_CASE(16, 64)
-        CRL_STEP_CASE(32, 64) CRL_STEP_CASE(64, 64) CRL_STEP_CASE(1, 8) CRL_STEP_CASE(1, 4)
-#undef CRL_STEP_CASE
-        return;  // (no such variant: nothing is stepped, which the tests see)
-    }
-#endif
+                       done, drawn, at, band_span, ink_row0, ink_row1, ob, 0)
     constexpr int W1 = kStepW < 2 ? 2 : kStepW;  // (one view: a trip takes two envs)
     if (views == 2) {
         if (blocks_ok) CRL_LAUNCH_STEP(2, kDeltaG, kStepW, kStepB, kStepNT);
@@ -716,55 +437,13 @@ void launch_pong_step_raw_delta(const PongSoA &s, const ServeSrc &src, const int
 
 void launch_pong_raster_raw(const uint64_t *frames, int64_t n, const uint8_t *atlas_rgb, int ink_row0, int ink_row1,
                             uint8_t *obs, int views, hipStream_t st) {
-    if (n <= 0) return;
-    // (profiling build only: CRL_RAW_DEBUG bit 1 = constant chunks, i.e. WRONG pixels, to size the pixel arithmetic; CRL_RAW_SWEEP /
-    // CRL_RAW_LINEAR select the superseded writers)
-    static const int dbg = CRL_ABL(getenv("CRL_RAW_DEBUG") ? atoi(getenv("CRL_RAW_DEBUG")) : 0);
-    static const int sweep = CRL_ABL(getenv("CRL_RAW_SWEEP") != nullptr) ? atoi(getenv("CRL_RAW_SWEEP")) : 4;
-    if (views != 1 && views != 2) return;  // (crl_create admits nothing else)
-    if (sweep > 0) {
-        const int64_t total = n * views * kFrameChunks;
-        const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
-        uint4 *ob = reinterpret_cast<uint4 *>(obs);
-#define CRL_LAUNCH_SWEEP(I, V)                                                                                              \
-    hipLaunchKernelGGL((pong_raster_raw_sweep_kernel<I, V>), dim3((unsigned)((total + 256 * I - 1) / (256 * I))), dim3(256), 0, st, frames, \
-                       at, ink_row0, ink_row1, ob, n, dbg)
-        if (views == 2) {
-#ifdef CRL_ABLATION
-            if (sweep <= 2) CRL_LAUNCH_SWEEP(2, 2);
-            else if (sweep > 4) CRL_LAUNCH_SWEEP(8, 2);
-            else
-#endif
-                CRL_LAUNCH_SWEEP(4, 2);
-        } else {
-            CRL_LAUNCH_SWEEP(4, 1);
-        }
-#undef CRL_LAUNCH_SWEEP
-        return;
-    }
-#ifdef CRL_ABLATION
-    static const int lin = getenv("CRL_RAW_LINEAR") ? atoi(getenv("CRL_RAW_LINEAR")) : 2;
-    if (lin > 0) {
-        const int64_t total = n * views * kFrameChunks;
-        const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
-        uint4 *ob = reinterpret_cast<uint4 *>(obs);
-#define CRL_LAUNCH_LIN(I, V)                                                                                         \
-    hipLaunchKernelGGL((pong_raster_raw_linear_kernel<I, 256, V>), dim3((unsigned)((total + 256 * I - 1) / (256 * I))), dim3(256), 0, \
-                       st, frames, at, ink_row0, ink_row1, ob, views, n, dbg)
-        if (views == 2) {
-            if (lin <= 1) CRL_LAUNCH_LIN(1, 2);
-            else if (lin <= 2) CRL_LAUNCH_LIN(2, 2);
-            else if (lin <= 4) CRL_LAUNCH_LIN(4, 2);
-            else CRL_LAUNCH_LIN(8, 2);
-        } else {
-            CRL_LAUNCH_LIN(2, 1);
-        }
-#undef CRL_LAUNCH_LIN
-        return;
-    }
-    hipLaunchKernelGGL(pong_raster_raw_kernel, dim3((unsigned)n), dim3(256), 0, st, frames,
-                       reinterpret_cast<const uint4 *>(atlas_rgb), ink_row0, ink_row1, reinterpret_cast<uint4 *>(obs), views, dbg);
-#endif
+    if (n <= 0 || (views != 1 && views != 2)) return;  // (crl_create admits nothing else)
+    const int64_t total = n * views * kFrameChunks;
+    const uint4 *at = reinterpret_cast<const uint4 *>(atlas_rgb);
+    uint4 *ob = reinterpret_cast<uint4 *>(obs);
+    const unsigned blocks = (unsigned)((total + 256 * 4 - 1) / (256 * 4));
+    if (views == 2) hipLaunchKernelGGL((pong_raster_raw_sweep_kernel<4, 2>), dim3(blocks), dim3(256), 0, st, frames, at, ink_row0, ink_row1, ob, n);
+    else hipLaunchKernelGGL((pong_raster_raw_sweep_kernel<4, 1>), dim3(blocks), dim3(256), 0, st, frames, at, ink_row0, ink_row1, ob, n);
 }
 
 }  // namespace crl

@@ -104,9 +104,10 @@ def test_c_abi_demo_links_against_the_library():
 
 
 def test_shipped_library_carries_no_debug_switches_or_superseded_kernels():
-    """wrong-output switches (CRL_*_DEBUG, skeleton sweeps, phase skips) and the superseded kernels (round 2's
-    analytic CarRacing raster, the first Pong writers, the packed-FMA opponent network) exist only in the profiling variant
-    (-DCRL_ABLATION -> libcrl_hip_abl.so); the shipped library contains neither their names nor their code objects."""
+    """the shipped library reads only the switches DESIGN.md section 11 lists, every one an alternative correct path.
+    The kernels the profiling variant (-DCRL_ABLATION -> libcrl_hip_abl.so) keeps for A/B tests -- the packed-FMA opponent network, the
+    address-linear gray writer -- are not inside it, and neither are the wrong-output switches (CRL_*_DEBUG, skeleton sweeps, phase
+    skips) and superseded kernels (round 2's analytic CarRacing raster, the first Pong writers) that no build holds any more."""
     import subprocess
 
     from competitive_rl_amd import _native as N

@@ -794,7 +794,8 @@ def test_set_state_that_rewinds_the_episode_does_not_reuse_an_overwritten_walk()
     the track from points partly replaced.  Now the piece that starts overwriting voids the tag first.  Snapshot, let a third of the
     envs reset, run on while their next walks are under way, restore, make them reset again: their tracks must be those of a context
     without walk-ahead (CRL_CAR_NO_OVERLAP=1 walks inline), i.e. a function of (seed, env, episode) alone.
-    (With CRL_LIB_VARIANT=abl CRL_CAR_ABL_KEEP_TAG=1 -- round 4's behaviour -- this test fails: docs/LAB_NOTES_r05.md.)"""
+    (With round 4's behaviour -- the tag kept -- this test fails: docs/LAB_NOTES_r05.md; the switch that demonstrated it,
+    CRL_CAR_ABL_KEEP_TAG of the profiling build, can be read at commit bab01f158452.)"""
     _need_gpu()
     import competitive_rl_amd as crl
 

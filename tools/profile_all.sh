@@ -21,9 +21,5 @@ tail -c 600 "$RES/${RND}_bench_all.json"
 python3 bench.py --workload car --steps 6000 --warmup 5 --no-cpu-baseline > gpurun_out/${RND}_bench_car_long.json 2> gpurun_out/${RND}_bench_car_long.err
 python3 bench.py --workload car_fma --steps 6000 --warmup 5 --no-cpu-baseline > gpurun_out/${RND}_bench_car_fma_long.json 2> gpurun_out/${RND}_bench_car_fma_long.err
 tail -c 300 gpurun_out/${RND}_bench_car_long.json; tail -c 300 gpurun_out/${RND}_bench_car_fma_long.json
-# phase stamps of the touching solve (profiling build), both arithmetics
-for sv in box2d fma; do
-  CRL_LIB_VARIANT=abl CRL_CAR_STAMPS=1 QUICK_SOLVER=$sv PYTHONPATH=. timeout 100 python3 tools/car_quick.py 16384 1500 500 > gpurun_out/${RND}_car_stamps_$sv.txt 2>&1
-done
 [ -x tools/solve_chain_probe ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I include tools/solve_chain_probe.hip -o tools/solve_chain_probe  # (git-ignored binary: built on first use)
 timeout 60 ./tools/solve_chain_probe > gpurun_out/${RND}_solve_chain_probe.txt 2>&1

@@ -1,5 +1,5 @@
 """Kernel time of the fused frame-stack draw (crl_step_stack) by hipEvents on the launch stream: 65 536 envs, 84 x 84, k = 4.
-Usage: python tools/stack_time.py [f32|u8] [steps]   (CRL_LIB_VARIANT=abl CRL_GRAY_JPW=<jobs per wavefront> for the A/B)"""
+Usage: python tools/stack_time.py [f32|u8] [steps]"""
 import os
 import sys
 
@@ -34,5 +34,5 @@ ms, cnt = env.kernel_time_ms(1)
 assert f.fused_updates == steps + 21, f.fused_updates
 stack_b = n * 4 * 7056 * (4 if kind == "f32" else 1)
 obs_b = n * 7056 * (2 if kind == "f32" else 1)
-print(f"{kind} stack, JPW={os.environ.get('CRL_GRAY_JPW', 'default')}: {ms / cnt * 1e3:.1f} us per launch over {cnt} launches; "
+print(f"{kind} stack: {ms / cnt * 1e3:.1f} us per launch over {cnt} launches; "
       f"{(stack_b + obs_b) / (ms / cnt * 1e-3) / 1e12:.2f} TB/s on {(stack_b + obs_b) / 1e9:.2f} GB")
