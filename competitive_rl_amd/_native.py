@@ -74,6 +74,12 @@ class CrlPpoHyper(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("clip", "vf_coef", "ent_coef", "lr", "beta1", "beta2", "eps", "max_grad_norm")]
 
 
+class CrlPpoTeacher(C.Structure):
+    """crl_ppo_teacher (include/crl.h "ppo update, teacher targets")."""
+    _fields_ = [("logits_dev", C.c_void_p), ("labels_dev", C.c_void_p), ("value_targets_dev", C.c_void_p), ("rows", C.c_int64),
+                ("temperature", C.c_float), ("coef", C.c_float), ("policy_term", C.c_int32)]
+
+
 class CrlStackDesc(C.Structure):
     """crl_stack_desc (include/crl.h): a FrameStackTensor drawn by the step."""
     _fields_ = [("stack_dev", C.c_void_p), ("planes", C.c_int32), ("dtype", C.c_int32), ("agent", C.c_int32),
@@ -226,6 +232,9 @@ SIGNATURES = {
     "crl_car_driver_act": (i32, [vp, vp, vp]),
     "crl_car_driver_get_counters": (i32, [vp, P(u64), P(i64)]),
     "crl_car_driver_set_counters": (i32, [vp, u64, i64]),
+    "crl_rule_labels": (i32, [vp, i32, vp, i64, vp]),
+    "crl_ppo_grad_teacher": (i32, [vp, vp, vp, i64, vp, vp, vp]),
+    "crl_ppo_teacher_stats": (i32, [vp, P(f64)]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -534,6 +534,18 @@ static int step_pong(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, flo
     return draw_obs(c, obs_dev, st, stack ? &sk : nullptr);
 }
 
+int crl_rule_labels(crl_ctx *c, int32_t seat, int32_t *labels_dev, int64_t stride, void *stream) {
+    CRL_ENTER(c);
+    if (!c || !labels_dev) return crl_fail(CRL_EINVAL, "crl_rule_labels: null argument");
+    if (c->car) return crl_fail(CRL_EINVAL, "crl_rule_labels: a CarRacing context (the rule is Pong's)");
+    if (seat != 0 && seat != 1) return crl_fail(CRL_EINVAL, "crl_rule_labels: seat must be 0 (the left bat) or 1 (the right), not %d", (int)seat);
+    if (stride < 1) return crl_fail(CRL_EINVAL, "crl_rule_labels: stride must be >= 1, not %lld", (long long)stride);
+    if ((uintptr_t)labels_dev & 3) return crl_fail(CRL_EINVAL, "crl_rule_labels: labels must be 4-byte aligned");
+    launch_pong_rule_labels(c->s, c->n, seat, labels_dev, stride, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
+}
+
 int crl_step(crl_ctx *c, const void *actions_void, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, void *stream) {
     return step_pong(c, actions_void, obs_dev, rew_dev, done_dev, nullptr, stream);
 }

@@ -244,6 +244,9 @@ struct PongMode {
 void launch_pong_reset(const PongSoA &s, const ServeSrc &src, int64_t n, PongMode mode, hipStream_t st);
 void launch_pong_dynamics(const PongSoA &s, const ServeSrc &src, const int32_t *actions, int64_t n, PongMode mode,
                           float *rew, uint8_t *done, hipStream_t st);
+// labels[i * stride] = auto_action + 1 of bat `seat` (0 left, 1 right) in the state env i holds now: what CRL_PONG_CHEAT resolves to on
+// the first frame of the next step (include/crl.h crl_rule_labels).  Reads the state, writes nothing else.
+void launch_pong_rule_labels(const PongSoA &s, int64_t n, int seat, int32_t *labels, int64_t stride, hipStream_t st);
 // out[(6, 7) * count + k] = frames[(0, 1) * n + idx[k]]: the pairs of `count` device-resident env indices as the newest
 // plane of a single-plane ring (planes 0..2 are not written: K = 1 never reads them)
 void launch_pong_gather_frames(const uint64_t *frames, const int64_t *idx_dev, int64_t count, int64_t n, uint64_t *ring_out,

@@ -107,6 +107,21 @@ __global__ __launch_bounds__(256) void pong_gather_frames_kernel(const uint64_t 
     ring_out[7 * count + k] = ok ? frames[n + i] : kBlankFrame;
 }
 
+// RULE_BASED's action as a label, one lane per env: decode_action(CRL_PONG_CHEAT, ...) exactly as frame_step calls it for that bat on
+// the state as it stands (the step re-evaluates the rule on each of its frames; this is the first of them), + 1
+__global__ __launch_bounds__(256) void pong_rule_labels_kernel(PongSoA s, int64_t n, int seat, int32_t *__restrict__ labels, int64_t stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double sx = s.speed_x[i];
+    const int ball_y = s.ball_y[i];
+    const int d = seat == 0 ? decode_action(CRL_PONG_CHEAT, -sx, s.bat_l[i], ball_y) : decode_action(CRL_PONG_CHEAT, sx, s.bat_r[i], ball_y);
+    labels[i * stride] = d + 1;
+}
+
+void launch_pong_rule_labels(const PongSoA &s, int64_t n, int seat, int32_t *labels, int64_t stride, hipStream_t st) {
+    hipLaunchKernelGGL(pong_rule_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s, n, seat, labels, stride);
+}
+
 void launch_pong_gather_frames(const uint64_t *frames, const int64_t *idx_dev, int64_t count, int64_t n, uint64_t *ring_out,
                                hipStream_t st) {
     hipLaunchKernelGGL(pong_gather_frames_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, frames, idx_dev, count, n,

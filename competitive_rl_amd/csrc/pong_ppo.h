@@ -50,10 +50,106 @@ __device__ inline void ppo_sample_terms(const double (&l)[3], const double v, co
     st[3] = olp - logp, st[4] = (ratio < lo || ratio > hi) ? 1.0 : 0.0;
 }
 
+// ---- include/crl.h "ppo update, teacher targets"
+static constexpr int kStatT = 4;                // ce, kl to the teacher, agreement, labelled
+static constexpr int kStatAll = kStatN + kStatT;  // what a teacher gradient's statistics carry
+
+struct PpoTeacherDev {
+    const float *logits;    // [T * N][3] or null
+    const int32_t *labels;  // [T * N] or null: exactly one of the two
+    const float *vtarget;   // [T * N] or null = the stored returns
+    float tau, coef;
+    int32_t policy_term;
+};
+
+// what a teacher instantiation of a heads kernel receives where the plain one receives PpoHyperDev
+struct PpoHyperTeacher : PpoHyperDev {
+    PpoTeacherDev t;
+};
+
+// One sample's teacher row as the kernels stage it: the three logits (or nothing) and the label (-1: none; logits: not read)
+struct TeacherRow {
+    float l[3];
+    int32_t label;
+};
+
+__device__ inline TeacherRow teacher_row(const PpoTeacherDev &t, uint32_t flat) {
+    TeacherRow r{{0.f, 0.f, 0.f}, -1};
+    if (t.logits) r.l[0] = t.logits[3 * (int64_t)flat], r.l[1] = t.logits[3 * (int64_t)flat + 1], r.l[2] = t.logits[3 * (int64_t)flat + 2];
+    else r.label = t.labels[flat];
+    return r;
+}
+
+// ppo_sample_terms with a teacher term: `ret` is the value target the caller chose (the stored return or the teacher's), tr the
+// sample's teacher row.  dl_k = (ppo_sample_terms' expression, the policy part at 0 when policy_term is 0) + coef (p_k - q_k), the
+// teacher term added last; st: the five statistics as always, then ce, kl, agree, labelled.
+__device__ inline void ppo_sample_terms_teacher(const double (&l)[3], const double v, const int act, const double olp, const double ret, const double A,
+                                                const PpoHyperDev &h, const PpoTeacherDev &t, const TeacherRow &tr, float (&dl)[3], float &dv,
+                                                double (&st)[kStatAll]) {
+    const double m = fmax(fmax(l[0], l[1]), l[2]);
+    const double d[3] = {l[0] - m, l[1] - m, l[2] - m};
+    const double ex[3] = {exp(d[0]), exp(d[1]), exp(d[2])};
+    const double S = (ex[0] + ex[1]) + ex[2];
+    const double logS = log(S);
+    const double lp[3] = {d[0] - logS, d[1] - logS, d[2] - logS};
+    const double p[3] = {ex[0] / S, ex[1] / S, ex[2] / S};
+    const double logp = lp[act];
+    const double ratio = exp(logp - olp);
+    const double lo = 1.0 - (double)h.clip, hi = 1.0 + (double)h.clip;
+    const double surr1 = ratio * A, surr2 = fmin(fmax(ratio, lo), hi) * A;
+    const bool active = (A >= 0.0 && ratio < hi) || (A < 0.0 && ratio > lo);
+    const double glp = (active && t.policy_term) ? -(A * ratio) : 0.0;
+    const double H = -((p[0] * lp[0] + p[1] * lp[1]) + p[2] * lp[2]);
+    // the target distribution
+    double q[3] = {0.0, 0.0, 0.0}, qlq[3] = {0.0, 0.0, 0.0};  // q_k and q_k log q_k (a term with q_k = 0 counts as 0)
+    bool labelled;
+    int qtop = 0;
+    if (t.logits) {
+        const double tau = (double)t.tau;
+        const double u[3] = {(double)tr.l[0] / tau, (double)tr.l[1] / tau, (double)tr.l[2] / tau};
+        const double mu = fmax(fmax(u[0], u[1]), u[2]);
+        const double eu[3] = {exp(u[0] - mu), exp(u[1] - mu), exp(u[2] - mu)};
+        const double Su = (eu[0] + eu[1]) + eu[2];
+        const double logSu = log(Su);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            q[k] = eu[k] / Su;
+            qlq[k] = q[k] > 0.0 ? q[k] * ((u[k] - mu) - logSu) : 0.0;
+        }
+        qtop = u[1] > u[0] ? 1 : 0;
+        if (u[2] > u[qtop]) qtop = 2;
+        labelled = true;
+    } else {
+        labelled = (uint32_t)tr.label < 3u;
+        if (labelled) q[tr.label] = 1.0, qtop = tr.label;
+    }
+    double ce = 0.0, Hq = 0.0;
+    if (labelled) {
+        const double c0 = q[0] > 0.0 ? q[0] * lp[0] : 0.0, c1 = q[1] > 0.0 ? q[1] * lp[1] : 0.0, c2 = q[2] > 0.0 ? q[2] * lp[2] : 0.0;
+        ce = -((c0 + c1) + c2);
+        Hq = -((qlq[0] + qlq[1]) + qlq[2]);
+    }
+    const double coef = (double)t.coef;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double base = glp * ((k == act ? 1.0 : 0.0) - p[k]) + (double)h.ent * (p[k] * (lp[k] + H));
+        dl[k] = (float)(labelled ? base + coef * (p[k] - q[k]) : base);
+    }
+    const double dif = v - ret;
+    dv = (float)((double)h.vf * dif);
+    st[0] = -fmin(surr1, surr2), st[1] = 0.5 * (dif * dif), st[2] = H;
+    st[3] = olp - logp, st[4] = (ratio < lo || ratio > hi) ? 1.0 : 0.0;
+    int ptop = l[1] > l[0] ? 1 : 0;
+    if (l[2] > l[ptop]) ptop = 2;
+    st[5] = ce, st[6] = ce - Hq, st[7] = (labelled && ptop == qtop) ? 1.0 : 0.0, st[8] = labelled ? 1.0 : 0.0;
+}
+
 // the full-size learner behind the common entry points of pong_ppo.hip (p->full is set)
 void ppo_full_destroy(PpoFull *f);
 int64_t ppo_full_scratch_rows(const PpoFull *f);  // samples per chunk of a minibatch: part of the summation shape (crl_ppo_get_state)
-int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, hipStream_t st);
+// t: null = the plain gradient (the kernels crl_ppo_grad has always launched), else the teacher instantiations
+int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, const PpoTeacherDev *t,
+                  hipStream_t st);
 
 }  // namespace crl
 
@@ -61,10 +157,11 @@ struct crl_ppo {
     int device = 0;
     int blob_floats = 0;  // the master blob, both moments and the gradient: 8 488 floats (light) or 1 001 784 (full size)
     float *raw = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
-    double *red = nullptr;  // [0]: the gradient's sum of squares, [1 .. 5]: the statistics' means
+    double *red = nullptr;  // [0]: the gradient's sum of squares, [1 .. 5]: the statistics' means, [6 .. 9]: a teacher gradient's four
     float *partials = nullptr;                        // light: [W][blob]
-    double *stat_part = nullptr, *sq_part = nullptr;  // light
+    double *stat_part = nullptr, *sq_part = nullptr;  // light (stat_part: [W][5], a teacher gradient's [W][9])
     crl::PpoFull *full = nullptr;                     // crl_ppo_create_full
     int64_t steps = 0;  // optimiser steps taken (the t of the bias corrections)
     bool have_grad = false;
+    bool teacher_grad = false;  // the last gradient was crl_ppo_grad_teacher's: red[6 .. 9] are its statistics
 };

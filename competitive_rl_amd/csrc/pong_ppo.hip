@@ -20,6 +20,10 @@
 //             Conv2 is 2 x 2 with stride 2, so da1 needs no overlap handling.  gW1 and gW2 are four accumulator tiles each and stay in
 //             registers until the workgroup ends; the bias gradients are per-lane sums beside them.
 // At the end the eight wavefronts' accumulators are added in wavefront order and the workgroup's partial blob leaves once.
+#include <float.h>
+
+#include <type_traits>
+
 #include "crl_internal.h"
 #include "pong_league.h"
 #include "pong_net.h"
@@ -50,6 +54,9 @@ static constexpr int kRedWave = 2048 + 32;  // a wavefront's gW1, gW2, gb1, gb2 
 static_assert(kGWaves == kGE, "the heads phase gives a wavefront to a sample");
 static_assert(kLdsGrad <= 160 * 1024, "the gradient kernel's LDS must fit a CU");
 static_assert(kGWaves * kRedWave * 4 <= kLdsBuf + kLdsA2, "the final reduction reuses the staging buffers");
+// the teacher instantiation: nine statistics per sample, and behind them the samples' teacher rows [kGE][4] (three logits, the label)
+static constexpr int kLdsGradTeacher = kLdsGrad + kGE * kStatT * 8 + kGE * 4 * 4;
+static_assert(kLdsGradTeacher <= 160 * 1024, "the teacher gradient kernel's LDS must fit a CU");
 
 struct GradArgs {
     RolloutView r;
@@ -60,6 +67,9 @@ struct GradArgs {
     double *stat_part;   // [W][kStatN]
     PpoHyperDev h;
 };
+struct GradArgsTeacher : GradArgs {
+    PpoTeacherDev t;
+};
 
 // the wavefront's own LDS traffic in program order (a tile is written by some lanes and read by others)
 __device__ inline void wave_lds_sync() {
@@ -67,14 +77,19 @@ __device__ inline void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a) {
+// TEACHER: include/crl.h "ppo update, teacher targets" -- the staging also fetches the samples' teacher rows and value targets, the
+// heads phase calls ppo_sample_terms_teacher and the statistics are nine.  <false> is the kernel crl_ppo_grad launches, as it was.
+template <bool TEACHER>
+__global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(std::conditional_t<TEACHER, GradArgsTeacher, GradArgs> a) {
+    constexpr int NS = TEACHER ? kStatAll : kStatN;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *sh_buf = smem;                                                  // [kGE][4][kPlanePad]
     float *sh_a2 = reinterpret_cast<float *>(smem + kLdsBuf);               // [kGE][1600]
     float *sh_scr = sh_a2 + kGE * kFeat;                                     // [kGWaves][5][16][17]
     float *sh_dh = sh_scr + kGWaves * kScrWave;                              // [kGE][4]: dlogits, dv
     float *sh_sc = sh_dh + kGE * 4;                                          // [kGE][4]: action, old log-prob, return, advantage
-    double *sh_st = reinterpret_cast<double *>(sh_sc + kGE * 4);             // [kGE][kStatN]
+    double *sh_st = reinterpret_cast<double *>(sh_sc + kGE * 4);             // [kGE][NS]
+    [[maybe_unused]] float *sh_tr = reinterpret_cast<float *>(sh_st + kGE * NS);  // (TEACHER) [kGE][4]: teacher logits, label
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int lj = lane & 15, lk = lane >> 4;
     const int64_t ngroups = (a.count + kGE - 1) / kGE;
@@ -104,7 +119,7 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a)
 #pragma unroll
         for (int i = 0; i < kHeadIter; i++) gWh[k][i] = 0.f;
     float gbh[4] = {0.f, 0.f, 0.f, 0.f};         // (thread 0)
-    double wst[kStatN] = {0, 0, 0, 0, 0};        // (thread 0)
+    double wst[NS] = {};                         // (thread 0)
     float *scr = sh_scr + wave * kScrWave;
 
     // a lane's 6 x 6 patch of plane ic = lk under conv2 position q of the group, as x / 255
@@ -159,6 +174,17 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a)
                 olp = a.r.logp[flat], ret = a.r.ret[flat], adv = a.r.adv[flat];
                 if (a.r.stats) adv = (adv - (float)a.r.stats[0]) / ((float)a.r.stats[1] + 1e-5f);  // as crl_rollout_gather hands it out
             }
+            if constexpr (TEACHER) {  // row s = the sample's flat index, never its place in the batch
+                TeacherRow tr{{0.f, 0.f, 0.f}, -1};
+                if (tid < here) {
+                    const uint32_t raw = (uint32_t)a.idx[b0 + tid];
+                    const uint32_t flat = raw < a.r.last ? raw : a.r.last;
+                    tr = teacher_row(a.t, flat);
+                    if (a.t.vtarget) ret = a.t.vtarget[flat];
+                }
+                sh_tr[tid * 4 + 0] = tr.l[0], sh_tr[tid * 4 + 1] = tr.l[1], sh_tr[tid * 4 + 2] = tr.l[2];
+                reinterpret_cast<int32_t *>(sh_tr)[tid * 4 + 3] = tr.label;
+            }
             sh_sc[tid * 4 + 0] = act, sh_sc[tid * 4 + 1] = olp, sh_sc[tid * 4 + 2] = ret, sh_sc[tid * 4 + 3] = adv;
         }
         __syncthreads();
@@ -198,17 +224,22 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a)
             for (int d = 32; d >= 1; d >>= 1) s0 += __shfl_xor(s0, d), s1 += __shfl_xor(s1, d), s2 += __shfl_xor(s2, d), s3 += __shfl_xor(s3, d);
             if (lane == 0) {
                 float dl[3] = {0.f, 0.f, 0.f}, dv = 0.f;
-                double st[kStatN] = {0, 0, 0, 0, 0};
+                double st[NS] = {};
                 if (e < here) {
                     const double l[3] = {(double)a.raw[kLightBa + 0] + s0, (double)a.raw[kLightBa + 1] + s1, (double)a.raw[kLightBa + 2] + s2};
                     const double v = (double)a.raw[kLightBc] + s3;
                     const int act = (int)sh_sc[e * 4 + 0];
                     const double olp = (double)sh_sc[e * 4 + 1], ret = (double)sh_sc[e * 4 + 2], A = (double)sh_sc[e * 4 + 3];
-                    ppo_sample_terms(l, v, act, olp, ret, A, a.h, dl, dv, st);
+                    if constexpr (TEACHER) {
+                        const TeacherRow tr{{sh_tr[e * 4 + 0], sh_tr[e * 4 + 1], sh_tr[e * 4 + 2]}, reinterpret_cast<const int32_t *>(sh_tr)[e * 4 + 3]};
+                        ppo_sample_terms_teacher(l, v, act, olp, ret, A, a.h, a.t, tr, dl, dv, st);
+                    } else {
+                        ppo_sample_terms(l, v, act, olp, ret, A, a.h, dl, dv, st);
+                    }
                 }
                 sh_dh[e * 4 + 0] = dl[0], sh_dh[e * 4 + 1] = dl[1], sh_dh[e * 4 + 2] = dl[2], sh_dh[e * 4 + 3] = dv;
 #pragma unroll
-                for (int k = 0; k < kStatN; k++) sh_st[e * kStatN + k] = st[k];
+                for (int k = 0; k < NS; k++) sh_st[e * NS + k] = st[k];
             }
         }
         __syncthreads();
@@ -230,7 +261,7 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a)
 #pragma unroll
                 for (int k = 0; k < 4; k++) gbh[k] += sh_dh[e * 4 + k];
 #pragma unroll
-                for (int k = 0; k < kStatN; k++) wst[k] += sh_st[e * kStatN + k];
+                for (int k = 0; k < NS; k++) wst[k] += sh_st[e * NS + k];
             }
         }
         // ---- backward through the convolutions
@@ -333,7 +364,7 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(GradArgs a)
         out[kLightBa + 0] = gbh[0], out[kLightBa + 1] = gbh[1], out[kLightBa + 2] = gbh[2], out[kLightBa + 3] = 0.f;
         out[kLightBc + 0] = gbh[3], out[kLightBc + 1] = 0.f, out[kLightBc + 2] = 0.f, out[kLightBc + 3] = 0.f;
 #pragma unroll
-        for (int k = 0; k < kStatN; k++) a.stat_part[blockIdx.x * kStatN + k] = wst[k];
+        for (int k = 0; k < NS; k++) a.stat_part[blockIdx.x * NS + k] = wst[k];
     }
 }
 
@@ -360,16 +391,18 @@ __global__ __launch_bounds__(256) void pong_ppo_reduce_kernel(const float *__res
     if (threadIdx.x == 0) sq_part[blockIdx.x] = s[0];
 }
 
-// ... and one lane: the 34 sums of squares in order, the W statistics partials in order.  out: [0] the sum of squares, [1 .. 5] the means
+// ... and one lane: the 34 sums of squares in order, the W statistics partials in order.  out: [0] the sum of squares, [1 .. NS] the means
+// (NS = 5, or the 9 of a teacher gradient)
+template <int NS>
 __global__ void pong_ppo_final_kernel(const double *__restrict__ sq_part, const double *__restrict__ stat_part, int groups, int64_t count,
                                       double *__restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double sq = 0.0;
     for (int b = 0; b < kRedBlocks; b++) sq += sq_part[b];
     out[0] = sq;
-    for (int k = 0; k < kStatN; k++) {
+    for (int k = 0; k < NS; k++) {
         double s = 0.0;
-        for (int w = 0; w < groups; w++) s += stat_part[w * kStatN + k];
+        for (int w = 0; w < groups; w++) s += stat_part[w * NS + k];
         out[1 + k] = s / (double)count;
     }
 }
@@ -459,11 +492,15 @@ int crl_ppo_create(int32_t device, const float *conv1_w, const float *conv1_b, c
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->v, kBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->grad, kBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->partials, (size_t)kGMaxGroups * kBlob * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->stat_part, (size_t)kGMaxGroups * kStatN * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->stat_part, (size_t)kGMaxGroups * kStatAll * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->sq_part, kRedBlocks * sizeof(double), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatN) * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
     if (rc == CRL_OK) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_ppo_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsGrad);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_ppo_grad_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsGrad);
+        if (e != hipSuccess) rc = crl_hip_fail(e, who);
+    }
+    if (rc == CRL_OK) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_ppo_grad_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsGradTeacher);
         if (e != hipSuccess) rc = crl_hip_fail(e, who);
     }
     if (rc == CRL_OK) rc = crl_ppo_set_weights(p, conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b, critic_w, critic_b);
@@ -498,29 +535,63 @@ int crl_ppo_weights_dev(crl_ppo *p, const float **blob_dev) {
     return CRL_OK;
 }
 
-int crl_ppo_grad(crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper, void *stream) {
+// crl_ppo_grad (teacher null) and crl_ppo_grad_teacher: everything is looked at before the learner or the GPU is touched
+static int ppo_grad(const char *who, crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper,
+                    const crl_ppo_teacher *teacher, void *stream) {
     crl_fail_no_ctx();
-    if (!p || !rollout || !idx_dev) return crl_fail(CRL_EINVAL, "crl_ppo_grad: null argument");
-    if ((uintptr_t)idx_dev & 7) return crl_fail(CRL_EINVAL, "crl_ppo_grad: idx must be 8-byte aligned");
-    if (count < 1 || count > 0x7fffffff) return crl_fail(CRL_EINVAL, "crl_ppo_grad: the number of samples must be in [1, 2^31)");
-    if (int rc = ppo_hyper_check("crl_ppo_grad", hyper)) return rc;
+    if (!p || !rollout || !idx_dev) return crl_fail(CRL_EINVAL, "%s: null argument", who);
+    if ((uintptr_t)idx_dev & 7) return crl_fail(CRL_EINVAL, "%s: idx must be 8-byte aligned", who);
+    if (count < 1 || count > 0x7fffffff) return crl_fail(CRL_EINVAL, "%s: the number of samples must be in [1, 2^31)", who);
+    if (int rc = ppo_hyper_check(who, hyper)) return rc;
     const RolloutView view = rollout_view(rollout);
-    if (!view.finished) return crl_fail(CRL_EINVAL, "crl_ppo_grad: the rollout is not finished (crl_rollout_finish computes returns and advantages)");
+    if (!view.finished) return crl_fail(CRL_EINVAL, "%s: the rollout is not finished (crl_rollout_finish computes returns and advantages)", who);
+    PpoTeacherDev t{};
+    if (teacher) {
+        if (!teacher->logits_dev == !teacher->labels_dev) return crl_fail(CRL_EINVAL, "%s: a teacher has logits or labels, exactly one of the two", who);
+        if (teacher->rows != (int64_t)view.last + 1)
+            return crl_fail(CRL_EINVAL, "%s: the teacher holds %lld rows, the rollout's T * N is %lld", who, (long long)teacher->rows, (long long)view.last + 1);
+        if (!(teacher->temperature > 0.f && teacher->temperature <= FLT_MAX)) return crl_fail(CRL_EINVAL, "%s: the temperature must be finite and > 0", who);
+        if (!(teacher->coef >= 0.f && teacher->coef <= FLT_MAX)) return crl_fail(CRL_EINVAL, "%s: coef must be finite and >= 0", who);
+        if (teacher->policy_term != 0 && teacher->policy_term != 1)
+            return crl_fail(CRL_EINVAL, "%s: policy_term must be 0 or 1, not %d", who, (int)teacher->policy_term);
+        if (((uintptr_t)teacher->logits_dev | (uintptr_t)teacher->labels_dev | (uintptr_t)teacher->value_targets_dev) & 3)
+            return crl_fail(CRL_EINVAL, "%s: the teacher's arrays must be 4-byte aligned", who);
+        t = PpoTeacherDev{teacher->logits_dev, teacher->labels_dev, teacher->value_targets_dev, teacher->temperature, teacher->coef, teacher->policy_term};
+    }
     hipStream_t st = (hipStream_t)stream;
+    const PpoHyperDev h{hyper->clip, hyper->vf_coef, hyper->ent_coef};
     if (p->full) {
-        if (int rc = ppo_full_grad(p, view, idx_dev, count, PpoHyperDev{hyper->clip, hyper->vf_coef, hyper->ent_coef}, st)) return rc;
-        p->have_grad = true;
+        if (int rc = ppo_full_grad(p, view, idx_dev, count, h, teacher ? &t : nullptr, st)) return rc;
+        p->have_grad = true, p->teacher_grad = teacher != nullptr;
         return CRL_OK;
     }
     const int64_t ngroups = (count + kGE - 1) / kGE;
     const int groups = (int)(ngroups < kGMaxGroups ? ngroups : kGMaxGroups);
-    GradArgs a{view, idx_dev, count, p->raw, p->partials, p->stat_part, PpoHyperDev{hyper->clip, hyper->vf_coef, hyper->ent_coef}};
-    hipLaunchKernelGGL(pong_ppo_grad_kernel, dim3(groups), dim3(kGThreads), kLdsGrad, st, a);
+    GradArgs a{view, idx_dev, count, p->raw, p->partials, p->stat_part, h};
+    if (teacher) {
+        GradArgsTeacher at;
+        static_cast<GradArgs &>(at) = a, at.t = t;
+        hipLaunchKernelGGL(pong_ppo_grad_kernel<true>, dim3(groups), dim3(kGThreads), kLdsGradTeacher, st, at);
+    } else {
+        hipLaunchKernelGGL(pong_ppo_grad_kernel<false>, dim3(groups), dim3(kGThreads), kLdsGrad, st, a);
+    }
     hipLaunchKernelGGL(pong_ppo_reduce_kernel, dim3(kRedBlocks), dim3(256), 0, st, p->partials, groups, (float)count, p->grad, p->sq_part);
-    hipLaunchKernelGGL(pong_ppo_final_kernel, dim3(1), dim3(64), 0, st, p->sq_part, p->stat_part, groups, count, p->red);
+    if (teacher) hipLaunchKernelGGL(pong_ppo_final_kernel<kStatAll>, dim3(1), dim3(64), 0, st, p->sq_part, p->stat_part, groups, count, p->red);
+    else hipLaunchKernelGGL(pong_ppo_final_kernel<kStatN>, dim3(1), dim3(64), 0, st, p->sq_part, p->stat_part, groups, count, p->red);
     HIP_TRY(hipGetLastError());
-    p->have_grad = true;
+    p->have_grad = true, p->teacher_grad = teacher != nullptr;
     return CRL_OK;
+}
+
+int crl_ppo_grad(crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper, void *stream) {
+    return ppo_grad("crl_ppo_grad", p, rollout, idx_dev, count, hyper, nullptr, stream);
+}
+
+int crl_ppo_grad_teacher(crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper,
+                         const crl_ppo_teacher *teacher, void *stream) {
+    crl_fail_no_ctx();
+    if (!teacher) return crl_fail(CRL_EINVAL, "crl_ppo_grad_teacher: null teacher (crl_ppo_grad is the plain gradient)");
+    return ppo_grad("crl_ppo_grad_teacher", p, rollout, idx_dev, count, hyper, teacher, stream);
 }
 
 int crl_ppo_get_grad(crl_ppo *p, const float **grad_dev, float *grad_out_host) {
@@ -566,6 +637,17 @@ int crl_ppo_stats(crl_ppo *p, double *out7_host) {
     return CRL_OK;
 }
 
+int crl_ppo_teacher_stats(crl_ppo *p, double *out4_host) {
+    crl_fail_no_ctx();
+    if (!p || !out4_host) return crl_fail(CRL_EINVAL, "crl_ppo_teacher_stats: null argument");
+    if (!p->have_grad || !p->teacher_grad)
+        return crl_fail(CRL_EINVAL, "crl_ppo_teacher_stats: the last gradient had no teacher (crl_ppo_grad_teacher)");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out4_host, p->red + 1 + kStatN, kStatT * sizeof(double), hipMemcpyDeviceToHost));
+    return CRL_OK;
+}
+
 int crl_ppo_get_state(crl_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t blob_floats, int64_t *steps_out,
                       int64_t *scratch_rows_out, void *stream) {
     crl_fail_no_ctx();
@@ -597,7 +679,7 @@ int crl_ppo_set_state(crl_ppo *p, const float *blob_host, const float *m_host, c
     HIP_TRY(hipMemcpyAsync(p->m, m_host, bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(p->v, v_host, bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    p->steps = steps, p->have_grad = false;
+    p->steps = steps, p->have_grad = false, p->teacher_grad = false;
     return CRL_OK;
 }
 

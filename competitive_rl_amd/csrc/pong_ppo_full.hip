@@ -32,6 +32,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "crl_internal.h"
@@ -73,7 +74,7 @@ struct PpoFull {
     float *a3 = nullptr;     // [rows][256]
     float *dz3 = nullptr;    // [rows][256]
     float *dh = nullptr;     // [rows][4]: dlogits, dv
-    double *st = nullptr;    // [rows][kStatN]
+    double *st = nullptr;    // [rows][kStatN] (a teacher gradient: [rows][kStatAll]; so hsd and stat_acc)
     float *gacc = nullptr;   // [kFullBlob]: the sums over the samples of w3, b3, wa, ba, wc, bc (the rest and the pads stay zero)
     float *partials = nullptr;  // [kBackMax][kBackBlob]
     float *hs = nullptr;     // [ceil(rows / 256)][6 * 256]: the head gradients' slice sums
@@ -277,10 +278,13 @@ __global__ __launch_bounds__(256, 2) void ppo_full_conv3_kernel(const float *__r
     }
 }
 
-// ---- heads: a wavefront per row
+// ---- heads: a wavefront per row.  TEACHER: include/crl.h "ppo update, teacher targets" -- h carries the teacher, the row's teacher row
+// and value target are fetched at its flat index and the statistics are nine per row.  <false> is the kernel crl_ppo_grad launches, as it was.
+template <bool TEACHER>
 __global__ __launch_bounds__(256) void ppo_full_heads_kernel(RolloutView r, const int64_t *__restrict__ idx, int64_t rows, const float *__restrict__ raw,
                                                              const float *__restrict__ a3, float *__restrict__ dz3, float *__restrict__ dh,
-                                                             double *__restrict__ stat, PpoHyperDev h) {
+                                                             double *__restrict__ stat, std::conditional_t<TEACHER, PpoHyperTeacher, PpoHyperDev> h) {
+    constexpr int NS = TEACHER ? kStatAll : kStatN;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -306,12 +310,17 @@ __global__ __launch_bounds__(256) void ppo_full_heads_kernel(RolloutView r, cons
     const double l[3] = {(double)raw[kOffBa + 0] + s0, (double)raw[kOffBa + 1] + s1, (double)raw[kOffBa + 2] + s2};
     const double v = (double)raw[kOffBc] + s3;
     float dl[3], dv;
-    double st[kStatN];
-    ppo_sample_terms(l, v, act, (double)r.logp[flat], (double)r.ret[flat], (double)adv, h, dl, dv, st);
+    double st[NS];
+    if constexpr (TEACHER) {
+        const float target = h.t.vtarget ? h.t.vtarget[flat] : r.ret[flat];
+        ppo_sample_terms_teacher(l, v, act, (double)r.logp[flat], (double)target, (double)adv, h, h.t, teacher_row(h.t, flat), dl, dv, st);
+    } else {
+        ppo_sample_terms(l, v, act, (double)r.logp[flat], (double)r.ret[flat], (double)adv, h, dl, dv, st);
+    }
     if (lane == 0) {
         dh[row * 4 + 0] = dl[0], dh[row * 4 + 1] = dl[1], dh[row * 4 + 2] = dl[2], dh[row * 4 + 3] = dv;
 #pragma unroll
-        for (int k = 0; k < kStatN; k++) stat[row * kStatN + k] = st[k];
+        for (int k = 0; k < NS; k++) stat[row * NS + k] = st[k];
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -345,7 +354,9 @@ __device__ __forceinline__ T walk_rows(int64_t lo, int64_t hi, T acc, Load load,
 // x = 0..2 wa[k][c], 3 wc[c], 4 b3[c], 5 threads 0..3 ba / bc and threads 4..8 the statistics; each thread walks its slice's rows in order
 // from zero into slot [s][256 x + c] (the statistics: [s][k], float64).  Level two, grid 6: the same thread adds the slices' sums in
 // slice order onto the previous chunks' sum (first: onto zero).
+// NS: the statistics per row, 5 or the 9 of a teacher gradient (threads 4 .. 4 + NS - 1 of block 5).
 static constexpr int kHeadSlice = 256, kHeadSlots = 6 * 256;
+template <int NS>
 __global__ __launch_bounds__(256) void ppo_full_headslice_kernel(int64_t rows, const float *__restrict__ dh, const float *__restrict__ a3,
                                                                  const float *__restrict__ dz3, const double *__restrict__ stat, float *__restrict__ hs,
                                                                  double *__restrict__ hsd) {
@@ -360,12 +371,13 @@ __global__ __launch_bounds__(256) void ppo_full_headslice_kernel(int64_t rows, c
         *o = walk_rows(lo, hi, 0.f, [&](int64_t row) { return dz3[row * kC3 + c]; }, plus);
     } else if (c < 4) {
         *o = walk_rows(lo, hi, 0.f, [&](int64_t row) { return dh[row * 4 + c]; }, plus);
-    } else if (c < 4 + kStatN) {
+    } else if (c < 4 + NS) {
         const int k = c - 4;
-        hsd[(int64_t)blockIdx.y * kStatN + k] = walk_rows(lo, hi, 0.0, [&](int64_t row) { return stat[row * kStatN + k]; }, plus);
+        hsd[(int64_t)blockIdx.y * NS + k] = walk_rows(lo, hi, 0.0, [&](int64_t row) { return stat[row * NS + k]; }, plus);
     }
 }
 
+template <int NS>
 __global__ __launch_bounds__(256) void ppo_full_headsum_kernel(int slices, const float *__restrict__ hs, const double *__restrict__ hsd, float *__restrict__ gacc,
                                                                double *__restrict__ stat_acc, int first) {
     const int b = blockIdx.x, c = threadIdx.x;
@@ -373,9 +385,9 @@ __global__ __launch_bounds__(256) void ppo_full_headsum_kernel(int slices, const
     if (b < 5 || c < 4) {
         float *o = gacc + (b < 3 ? kOffWa + b * kC3 + c : b == 3 ? kOffWc + c : b == 4 ? kOffB3 + c : c < 3 ? kOffBa + c : kOffBc);
         *o = walk_rows(0, slices, first ? 0.f : *o, [&](int64_t s) { return hs[s * kHeadSlots + b * 256 + c]; }, plus);
-    } else if (c < 4 + kStatN) {
+    } else if (c < 4 + NS) {
         const int k = c - 4;
-        stat_acc[k] = walk_rows(0, slices, first ? 0.0 : stat_acc[k], [&](int64_t s) { return hsd[s * kStatN + k]; }, plus);
+        stat_acc[k] = walk_rows(0, slices, first ? 0.0 : stat_acc[k], [&](int64_t s) { return hsd[s * NS + k]; }, plus);
     }
 }
 
@@ -611,7 +623,8 @@ __global__ __launch_bounds__(256) void ppo_full_finish_kernel(const float *__res
     if (threadIdx.x == 0) sq_part[blockIdx.x] = s[0];
 }
 
-// ... and one workgroup: thread t adds the block sums t, t + 256, ... in order, then the same tree.  out: [0] the sum of squares, [1 .. 5] the means
+// ... and one workgroup: thread t adds the block sums t, t + 256, ... in order, then the same tree.  out: [0] the sum of squares, [1 .. NS] the means
+template <int NS>
 __global__ __launch_bounds__(256) void ppo_full_final_kernel(const double *__restrict__ sq_part, const double *__restrict__ stat_acc, int64_t count,
                                                              double *__restrict__ out) {
     __shared__ double s[256];
@@ -624,7 +637,7 @@ __global__ __launch_bounds__(256) void ppo_full_final_kernel(const double *__res
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = s[0];
-    if (threadIdx.x < kStatN) out[1 + threadIdx.x] = stat_acc[threadIdx.x] / (double)count;
+    if (threadIdx.x < NS) out[1 + threadIdx.x] = stat_acc[threadIdx.x] / (double)count;
 }
 
 void ppo_full_destroy(PpoFull *f) {
@@ -637,8 +650,11 @@ void ppo_full_destroy(PpoFull *f) {
 
 int64_t ppo_full_scratch_rows(const PpoFull *f) { return f->scratch_rows; }
 
-int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, hipStream_t st) {
+int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, const PpoTeacherDev *t,
+                  hipStream_t st) {
     PpoFull *f = p->full;
+    PpoHyperTeacher ht{};
+    if (t) static_cast<PpoHyperDev &>(ht) = h, ht.t = *t;
     const int64_t S = f->scratch_rows;
     const int64_t first_rows = std::min(S, count);
     const int groups = (int)std::min<int64_t>(kBackMax, first_rows);  // W: a function of B and scratch_rows alone
@@ -649,16 +665,23 @@ int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev,
         const int64_t *idx = idx_dev + c0;
         hipLaunchKernelGGL(ppo_full_front_kernel, dim3((unsigned)std::min<int64_t>(rows, (int64_t)f->cus * 2)), dim3(256), 0, st, view, idx, rows, raw, f->act2);
         hipLaunchKernelGGL(ppo_full_conv3_kernel, dim3((unsigned)((rows + kGM - 1) / kGM), kC3 / kGN), dim3(256), 0, st, f->act2, raw + kOffW3, raw + kOffB3, f->a3, rows);
-        hipLaunchKernelGGL(ppo_full_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, view, idx, rows, raw, f->a3, f->dz3, f->dh, f->st, h);
         const int slices = (int)((rows + kHeadSlice - 1) / kHeadSlice);
-        hipLaunchKernelGGL(ppo_full_headslice_kernel, dim3(6, slices), dim3(256), 0, st, rows, f->dh, f->a3, f->dz3, f->st, f->hs, f->hsd);
-        hipLaunchKernelGGL(ppo_full_headsum_kernel, dim3(6), dim3(256), 0, st, slices, f->hs, f->hsd, f->gacc, f->stat_acc, first);
+        if (t) {
+            hipLaunchKernelGGL(ppo_full_heads_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, view, idx, rows, raw, f->a3, f->dz3, f->dh, f->st, ht);
+            hipLaunchKernelGGL(ppo_full_headslice_kernel<kStatAll>, dim3(6, slices), dim3(256), 0, st, rows, f->dh, f->a3, f->dz3, f->st, f->hs, f->hsd);
+            hipLaunchKernelGGL(ppo_full_headsum_kernel<kStatAll>, dim3(6), dim3(256), 0, st, slices, f->hs, f->hsd, f->gacc, f->stat_acc, first);
+        } else {
+            hipLaunchKernelGGL(ppo_full_heads_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, view, idx, rows, raw, f->a3, f->dz3, f->dh, f->st, h);
+            hipLaunchKernelGGL(ppo_full_headslice_kernel<kStatN>, dim3(6, slices), dim3(256), 0, st, rows, f->dh, f->a3, f->dz3, f->st, f->hs, f->hsd);
+            hipLaunchKernelGGL(ppo_full_headsum_kernel<kStatN>, dim3(6), dim3(256), 0, st, slices, f->hs, f->hsd, f->gacc, f->stat_acc, first);
+        }
         hipLaunchKernelGGL(ppo_full_gw3_kernel, dim3(kK3 / 32, kC3 / 128), dim3(256), 0, st, f->dz3, f->act2, rows, f->gacc + kOffW3, first);
         hipLaunchKernelGGL(ppo_full_dz2_kernel, dim3((unsigned)((rows + 127) / 128), kK3 / 32), dim3(256), 0, st, f->dz3, raw + kOffW3, f->act2, rows);
         hipLaunchKernelGGL(ppo_full_back_kernel, dim3(groups), dim3(256), kBackLds, st, view, idx, rows, raw, f->act2, f->partials, first);
     }
     hipLaunchKernelGGL(ppo_full_finish_kernel, dim3(kSqBlocks), dim3(256), 0, st, f->partials, groups, f->gacc, (float)count, p->grad, f->sq_part);
-    hipLaunchKernelGGL(ppo_full_final_kernel, dim3(1), dim3(256), 0, st, f->sq_part, f->stat_acc, count, p->red);
+    if (t) hipLaunchKernelGGL(ppo_full_final_kernel<kStatAll>, dim3(1), dim3(256), 0, st, f->sq_part, f->stat_acc, count, p->red);
+    else hipLaunchKernelGGL(ppo_full_final_kernel<kStatN>, dim3(1), dim3(256), 0, st, f->sq_part, f->stat_acc, count, p->red);
     HIP_TRY(hipGetLastError());
     return CRL_OK;
 }
@@ -719,18 +742,18 @@ int crl_ppo_create_full(int32_t device, int64_t scratch_rows, const float *conv1
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->m, blob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->v, blob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->grad, blob, who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatN) * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->gacc, blob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->act2, (size_t)S * kK3 * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->a3, (size_t)S * kC3 * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->dz3, (size_t)S * kC3 * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->dh, (size_t)S * 4 * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->st, (size_t)S * kStatN * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->st, (size_t)S * kStatAll * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->partials, (size_t)kBackMax * kBackBlob * sizeof(float), who);
     const size_t slices = (size_t)((S + kHeadSlice - 1) / kHeadSlice);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->hs, slices * kHeadSlots * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->hsd, slices * kStatN * sizeof(double), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->stat_acc, kStatN * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->hsd, slices * kStatAll * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->stat_acc, kStatAll * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->sq_part, kSqBlocks * sizeof(double), who);
     if (rc == CRL_OK) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_full_back_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kBackLds);

@@ -449,6 +449,10 @@ class LeagueEnvWrapper(AgentPool):
         """The last step's done flags on the host, ahead of the observation (HipPongVecEnv.done_host)."""
         return self.env.done_host()
 
+    def rule_labels(self, seat=0, out=None):
+        """RULE_BASED's next action per env as int32 labels on the device (HipPongVecEnv.rule_labels); seat 0 is the learner's bat."""
+        return self.env.rule_labels(seat=seat, out=out)
+
     # ---- VecEnv protocol, agent 0's view
     def _frames(self, obs):
         if isinstance(obs, np.ndarray):

@@ -15,6 +15,30 @@ new weights go into a served ``Policy`` or a league / arena slot by a device-to-
 ``FullPPO(weights_or_checkpoint, scratch_rows=None, ...)`` is the same for ``Policy(use_light_model=False)`` and a pool's full-size slots;
 a minibatch runs in chunks of ``scratch_rows`` samples (17.6 KB of device scratch each, 16 384 by default).
 
+Teacher targets (include/crl.h "ppo update, teacher targets") add ``coef * CE(teacher, learner)`` to either learner's loss.
+Distilling a full-size agent into a light one -- the student acts and is recorded, the teacher sees the same frames and resets:
+
+    student, teacher = Policy(light_ckpt, n), Policy(full_ckpt, n, use_light_model=False)
+    logits = torch.empty((T, n, 3), device="cuda")
+    for t in range(T):
+        values, actions, logp = student.act_rollout(frame, reset)          # as in rollout.py; storage.record(...)
+        teacher.act_rollout(frame, reset, want_logits=True)
+        logits[t] = teacher.logits()
+        ...                                                                # env step, storage.outcome(...)
+    storage.finish(...)
+    learner.update(storage, 4, 32, teacher=Teacher(logits=logits, temperature=2.0, coef=1.0, policy_term=False))
+    print(learner.teacher_stats())                                         # ce, kl, agreement, labelled (synchronises)
+
+Cloning RULE_BASED as a warm start -- the labels are what the cheat code 999 would play in the state the frame shows:
+
+    labels = torch.empty((T, n), dtype=torch.int32, device="cuda")
+    for t in range(T):
+        envs.rule_labels(seat=0, out=labels[t])                            # before the step that consumes the action
+        ...
+    learner.update(storage, 4, 32, teacher=Teacher(labels=labels, policy_term=False))
+
+``Teacher(logits=..., coef=0.1)`` with the policy term left on is PPO regularised towards the teacher.
+
 The reference ships no trainer: the loss, its summation shape and the optimiser step are the header's written rule;
 ``rules.ppo_loss_reference`` / ``rules.ppo_full_loss_reference`` (autograd, float64) and ``rules.adam_reference`` (numpy float32) restate them.  There is no CPU path.
 """
@@ -28,9 +52,56 @@ from . import _native as N
 from . import checkpoint as K
 from .checkpoint import BLOB_FLOATS, BLOB_LAYOUT, FULL_BLOB_FLOATS, FULL_BLOB_LAYOUT  # noqa: F401  (the blobs' layouts; re-exported)
 from .policy_serving import _CRITIC_KEYS, _FULL_KEYS, _KEYS, _SHAPES, Policy, check_full_weights, critic_of, load_full_weights, load_light_weights
-from .rules import PPO_DEFAULTS, PPO_FULL_KEYS, PPO_KEYS, adam_reference, ppo_full_loss_reference, ppo_loss_reference  # noqa: F401  (re-exported)
+from .rules import (PPO_DEFAULTS, PPO_FULL_KEYS, PPO_KEYS, adam_reference, check_teacher, ppo_full_loss_reference,  # noqa: F401  (re-exported)
+                    ppo_full_teacher_loss_reference, ppo_loss_reference, ppo_teacher_loss_reference)
 
 PPOStats = collections.namedtuple("PPOStats", ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "grad_norm", "steps"))
+TeacherStats = collections.namedtuple("TeacherStats", ("ce", "kl", "agreement", "labelled"))
+
+
+class Teacher:
+    """Teacher targets for ``grad`` / ``update`` (include/crl.h "ppo update, teacher targets"): a small value object over the CALLER's
+    tensors -- they are not learner state, and the learner keeps no reference beyond the call.  Exactly one of
+      logits         float32 (T*N, 3) or (T, N, 3): the teacher's logits of every stored sample, softened by ``temperature``
+      labels         int32 (T*N,) or (T, N): an action in 0..2 per sample; any other value = no teacher term for that sample
+    and optionally ``value_targets`` float32 (T*N,) or (T, N) in place of the stored returns (a teacher's critic).  All contiguous, on
+    the learner's device, row ``t * N + e`` the sample ``storage.gather`` calls so.  The loss per sample becomes
+    ``policy_term * policy + coef * CE(q, p) + vf * value - ent * entropy``: ``policy_term=False`` is pure imitation, ``coef=0`` with
+    ``policy_term=True`` the plain PPO loss.  A wrong dtype, shape or both / neither of logits and labels raise a ``ValueError`` here;
+    the device and the row count are checked against the learner and the storage by ``grad``, before any native call."""
+
+    def __init__(self, logits=None, labels=None, value_targets=None, temperature=1.0, coef=1.0, policy_term=True):
+        if (logits is None) == (labels is None):
+            raise ValueError("a Teacher has logits or labels, exactly one of the two")
+        self.temperature, self.coef, self.policy_term = check_teacher(temperature, coef, policy_term)
+        self.logits, self.labels, self.value_targets = logits, labels, value_targets
+        rows = set()
+        for name, t, dtype, tail in (("logits", logits, torch.float32, (3,)), ("labels", labels, torch.int32, ()),
+                                     ("value_targets", value_targets, torch.float32, ())):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+                raise ValueError(f"Teacher: {name} must be a {dtype} tensor")
+            lead = t.shape[:t.dim() - len(tail)]
+            if tuple(t.shape[t.dim() - len(tail):]) != tail or len(lead) not in (1, 2) or not t.is_contiguous():
+                raise ValueError(f"Teacher: {name} must be contiguous (T*N, ...) or (T, N, ...) with trailing shape {tail}, not {tuple(t.shape)}")
+            rows.add(int(np.prod(lead)))
+        if len(rows) != 1:
+            raise ValueError(f"Teacher: the tensors hold different numbers of samples ({sorted(rows)})")
+        self.rows = rows.pop()
+
+    def _tensors(self):
+        return [t for t in (self.logits, self.labels, self.value_targets) if t is not None]
+
+    def _native(self, device, total):
+        """the crl_ppo_teacher of this teacher for a learner on ``device`` and a storage of ``total`` samples"""
+        for t in self._tensors():
+            if t.device != device:
+                raise ValueError(f"Teacher: a tensor lives on {t.device}, the learner on {device}")
+        if self.rows != total:
+            raise ValueError(f"Teacher: {self.rows} rows, but the storage holds T * N = {total} samples")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return N.CrlPpoTeacher(ptr(self.logits), ptr(self.labels), ptr(self.value_targets), self.rows, self.temperature, self.coef, self.policy_term)
 
 
 def blob_views(blob):
@@ -115,17 +186,27 @@ class _PPOLearner:
         holder = type("_Blob", (), {"__cuda_array_interface__": iface, "_keep": self})()
         return torch.as_tensor(holder, device=self.device)
 
-    def grad(self, storage, idx):
+    def grad(self, storage, idx, teacher=None):
         """The gradient of the loss over the samples ``idx`` (int64 on the device, flat ``t * num_envs + e``, as ``storage.gather`` takes
         them) of a finished ``RolloutStorage``, at the learner's weights: a dict of device VIEWS of the gradient tensors, for
-        callers with their own optimiser; the next ``grad`` overwrites them.  No synchronisation."""
+        callers with their own optimiser; the next ``grad`` overwrites them.  ``teacher``: a ``Teacher`` adds its term to the loss
+        (``teacher_stats()`` then has its statistics); None is the plain PPO loss.  No synchronisation."""
         assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1, "idx: int64 (B,) on the learner's device"
         assert storage.device == self.device, "the storage lives on another device"
         idx = idx.contiguous()
         hyper = self._hyper()
+        if teacher is not None:
+            if not isinstance(teacher, Teacher):
+                raise ValueError(f"teacher must be a Teacher or None, not {type(teacher).__name__}")
+            native = teacher._native(self.device, storage.num_steps * storage.num_envs)
         with torch.cuda.device(self.device):
-            N.check(self._L.crl_ppo_grad(self._h, storage._h, C.c_void_p(idx.data_ptr()) if idx.numel() else None, idx.numel(), C.byref(hyper),
-                                         self._stream()))
+            ip = C.c_void_p(idx.data_ptr()) if idx.numel() else None
+            if teacher is None:
+                N.check(self._L.crl_ppo_grad(self._h, storage._h, ip, idx.numel(), C.byref(hyper), self._stream()))
+            else:
+                N.check(self._L.crl_ppo_grad_teacher(self._h, storage._h, ip, idx.numel(), C.byref(hyper), C.byref(native), self._stream()))
+                for t in teacher._tensors():  # (the launches read them: a caching allocator must not hand them out before that)
+                    t.record_stream(torch.cuda.current_stream(self.device))
             p = C.c_void_p()
             N.check(self._L.crl_ppo_get_grad(self._h, C.byref(p), None))
         return blob_views(self._dev_blob(p.value))
@@ -136,18 +217,27 @@ class _PPOLearner:
         with torch.cuda.device(self.device):
             N.check(self._L.crl_ppo_step(self._h, C.byref(hyper), self._stream()))
 
-    def update(self, storage, num_epochs, num_mini_batch, generator=None):
+    def update(self, storage, num_epochs, num_mini_batch, generator=None, teacher=None):
         """``num_epochs`` passes over the finished ``storage``: per pass one ``torch.randperm`` on the device (``generator``: a device
         generator, for a reproducible order) cut into ``num_mini_batch`` batches of T * N // num_mini_batch samples, ``grad`` and ``step``
-        per batch.  Nothing synchronises."""
+        per batch; ``teacher`` goes to every ``grad``.  Nothing synchronises."""
         total = storage.num_steps * storage.num_envs
         size = total // int(num_mini_batch)
         assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
         for _ in range(int(num_epochs)):
             perm = torch.randperm(total, device=self.device, generator=generator)
             for k in range(int(num_mini_batch)):
-                self.grad(storage, perm[k * size:(k + 1) * size])
+                self.grad(storage, perm[k * size:(k + 1) * size], teacher)
                 self.step()
+
+    def teacher_stats(self):
+        """``TeacherStats`` of the last ``grad`` with a teacher: the means over the batch of the cross-entropy to the target, of
+        KL(teacher || learner), of the samples whose greedy action is the target's, and the share of samples that had a teacher term.
+        Refuses after a plain ``grad``.  Synchronises the device: logging and tests."""
+        out = (C.c_double * 4)()
+        with torch.cuda.device(self.device):
+            N.check(self._L.crl_ppo_teacher_stats(self._h, out))
+        return TeacherStats(*out)
 
     def _blob_dev(self, target):
         p = C.c_void_p()

@@ -175,8 +175,45 @@ def _full_forward(F, torch, w, x):
     return a3, dict(z1=z1, z2=z2, z3=z3)
 
 
-def _ppo_loss(keys, forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype):
-    """The loss of include/crl.h "ppo update" behind the features of ``forward``: shared by the two references below."""
+def check_teacher(temperature, coef, policy_term):
+    """What ``crl_ppo_grad_teacher`` accepts beside its arrays, as the values it receives: a finite float32 temperature > 0, a finite
+    float32 coef >= 0 and a policy_term of 0 or 1 (a bool).  Returns (temperature, coef, policy_term) as floats and an int."""
+    with np.errstate(over="ignore"):
+        t, k = np.float32(temperature), np.float32(coef)
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError(f"temperature must be finite and > 0, not {temperature}")
+    if not (np.isfinite(k) and k >= 0):
+        raise ValueError(f"coef must be finite and >= 0, not {coef}")
+    if isinstance(policy_term, (bool, np.bool_)):
+        policy_term = int(policy_term)
+    if not isinstance(policy_term, (int, np.integer)) or int(policy_term) not in (0, 1):
+        raise ValueError(f"policy_term must be 0 or 1, not {policy_term!r}")
+    return float(t), float(k), int(policy_term)
+
+
+def _teacher_targets(torch, teacher, count, dtype):
+    """(q [B, 3], q log q with the zero terms as 0 [B, 3], labelled [B] bool, what argmax q is taken over [B, 3]) of a per-sample
+    teacher dict"""
+    logits, labels = teacher.get("logits"), teacher.get("labels")
+    if (logits is None) == (labels is None):
+        raise ValueError("a teacher has logits or labels, exactly one of the two")
+    if logits is not None:
+        tau = float(np.float32(teacher.get("temperature", 1.0)))
+        u = torch.tensor(np.asarray(logits, np.float32).reshape(count, 3), dtype=dtype) / tau
+        logq = torch.log_softmax(u, dim=1)
+        q = logq.exp()
+        return q, q * logq, torch.ones(count, dtype=torch.bool), u
+    lab = np.asarray(labels, np.int64).reshape(count)
+    ok = (lab >= 0) & (lab <= 2)
+    q = np.zeros((count, 3))
+    q[np.nonzero(ok)[0], lab[ok]] = 1.0
+    q = torch.tensor(q, dtype=dtype)
+    return q, torch.zeros_like(q), torch.tensor(ok), q
+
+
+def _ppo_loss(keys, forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype, teacher=None):
+    """The loss of include/crl.h "ppo update" behind the features of ``forward``: shared by the references below.  ``teacher``: the
+    per-sample teacher dict of ``ppo_teacher_loss_reference`` ("ppo update, teacher targets"), None = the loss as it stands."""
     import torch
     import torch.nn.functional as F
 
@@ -186,6 +223,8 @@ def _ppo_loss(keys, forward, weights, stacks, actions, old_logp, returns, adv, h
     w = {k: torch.tensor(np.asarray(weights[k], np.float32), dtype=dtype, requires_grad=True) for k in keys}
     x = torch.tensor(np.asarray(stacks, np.uint8).astype(np.float32), dtype=dtype) / 255
     a = torch.tensor(np.asarray(actions, np.int64))
+    if teacher is not None and teacher.get("value_targets") is not None:
+        returns = np.asarray(teacher["value_targets"], np.float32).reshape(len(a))
     olp, ret, A = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (old_logp, returns, adv))
     feat, pre = forward(F, torch, w, x)
     logits = feat @ w["actor_w"].t() + w["actor_b"]
@@ -196,16 +235,26 @@ def _ppo_loss(keys, forward, weights, stacks, actions, old_logp, returns, adv, h
     policy = -torch.minimum(ratio * A, torch.clamp(ratio, 1 - c, 1 + c) * A)
     value = 0.5 * (ret - v) ** 2
     entropy = -(lp_all.exp() * lp_all).sum(1)
-    loss = (policy + vf * value - ent * entropy).mean()
+    n = lambda t: t.detach().numpy()  # noqa: E731
+    s = lambda t: float(t.detach())  # noqa: E731
+    extra = {}
+    if teacher is None:
+        loss = (policy + vf * value - ent * entropy).mean()
+    else:
+        _, coef, policy_term = check_teacher(teacher.get("temperature", 1.0), teacher.get("coef", 1.0), teacher.get("policy_term", 1))
+        q, qlogq, labelled, order = _teacher_targets(torch, teacher, len(a), dtype)
+        ce = -torch.where(q > 0, q * lp_all, torch.zeros_like(lp_all)).sum(1)  # (terms with q_k = 0 count as 0; no label: no term)
+        kl_t = ce + qlogq.sum(1)
+        loss = (policy_term * policy + coef * ce + vf * value - ent * entropy).mean()
+        agree = (np.argmax(n(logits), axis=1) == np.argmax(n(order), axis=1)) & n(labelled)  # (the lowest index among equals)
+        extra = dict(ce=s(ce.mean()), kl_teacher=s(kl_t.mean()), agree=float(agree.mean()), labelled=float(n(labelled).mean()), q=n(q))
     loss.backward()
     r = ratio.detach()
     active = ((A >= 0) & (r < 1 + c)) | ((A < 0) & (r > 1 - c))
-    n = lambda t: t.detach().numpy()  # noqa: E731
-    s = lambda t: float(t.detach())  # noqa: E731
     return dict(loss=s(loss), policy=s(policy.mean()), value=s(value.mean()), entropy=s(entropy.mean()),
                 kl=s((olp - logp).mean()), clipped=float(((r < 1 - c) | (r > 1 + c)).to(dtype).mean()),
                 grads={k: n(w[k].grad) for k in keys}, logits=n(logits), v=n(v), logp=n(logp), ratio=n(r),
-                active=n(active), **{k: n(z) for k, z in pre.items()})
+                active=n(active), **{k: n(z) for k, z in pre.items()}, **extra)
 
 
 def ppo_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None):
@@ -228,6 +277,38 @@ def ppo_full_loss_reference(weights, stacks, actions, old_logp, returns, adv, hy
     ``weights``: the ten tensors of ``PPO_FULL_KEYS`` in torch layout.  The same return dict, with ``z2`` [B, 32, 11, 11] and, beside it,
     ``z3`` [B, 256].  Host code for tests; the kernels do not use it."""
     return _ppo_loss(PPO_FULL_KEYS, _full_forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype)
+
+
+def ppo_teacher_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None, teacher=None):
+    """The loss of include/crl.h "ppo update, teacher targets" with torch autograd on the CPU: ``ppo_loss_reference`` plus
+    ``coef * ce`` towards a per-sample target distribution, with the policy term switched by ``policy_term``.  ``teacher``: None (then
+    this IS ``ppo_loss_reference``) or a dict of PER-SAMPLE rows, already taken at the samples' flat indices: ``logits`` float32
+    [B, 3] at ``temperature``, or ``labels`` int [B] (a value outside 0..2: no teacher term for that sample); optionally
+    ``value_targets`` float32 [B] in place of the returns; ``temperature`` (1), ``coef`` (1), ``policy_term`` (1).  The return dict
+    gains the means ``ce``, ``kl_teacher``, ``agree``, ``labelled`` and the targets ``q`` [B, 3].  Host code for tests."""
+    return _ppo_loss(PPO_KEYS, _light_forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype, teacher)
+
+
+def ppo_full_teacher_loss_reference(weights, stacks, actions, old_logp, returns, adv, hyper=None, dtype=None, teacher=None):
+    """``ppo_teacher_loss_reference`` for the full-size ActorCritic; without a teacher it is ``ppo_full_loss_reference``."""
+    return _ppo_loss(PPO_FULL_KEYS, _full_forward, weights, stacks, actions, old_logp, returns, adv, hyper, dtype, teacher)
+
+
+def pong_rule_label_reference(state, seat):
+    """The labels of ``crl_rule_labels`` in numpy over a ``get_state()`` record (``_native.STATE_DT``): the action in 0..2 that the
+    cheat code 999 would resolve to for ``seat`` (0 the left bat, 1 the right) on the FIRST frame of the next step.  ``auto_action``
+    (pong/base_pong_env.py:457-471) on the ball's speed towards that side (seat 0: ``-speed_x``), the bat's centre ``bat_y + 7`` and
+    the ball's centre ``ball_y + 2`` (as the step's decode forms them): a ball moving away sends the bat towards the arena's centre
+    line (y = 114), a ball coming is followed, a ball at rest leaves the bat; + 1.  Returns int32 [N].  Host code for tests."""
+    if seat not in (0, 1):
+        raise ValueError(f"seat must be 0 (left) or 1 (right), not {seat!r}")
+    sx = np.asarray(state["speed_x"], np.float64) * (-1.0 if seat == 0 else 1.0)
+    bat = np.asarray(state["bat_l_y" if seat == 0 else "bat_r_y"], np.int64) + 7
+    ball = np.asarray(state["ball_y"], np.int64) + 2
+    centre = 34 + 80
+    away = np.where(bat < centre, 1, np.where(bat > centre, -1, 0))
+    coming = np.where(bat < ball, 1, -1)
+    return (np.where(sx < 0, away, np.where(sx > 0, coming, 0)) + 1).astype(np.int32)
 
 
 def adam_reference(params, m, v, grad, grad_norm, step, hyper=None):

@@ -86,6 +86,10 @@ class TournamentEnvWrapper:
         """The last step's done flags on the host, ahead of the observation (HipPongVecEnv.done_host)."""
         return self.env.done_host()
 
+    def rule_labels(self, seat=0, out=None):
+        """RULE_BASED's next action per env as int32 labels on the device (HipPongVecEnv.rule_labels); seat 0 is the caller's bat."""
+        return self.env.rule_labels(seat=seat, out=out)
+
     # ---- opponent
     def _select(self, name):
         self.current_agent_name, self.current_agent = name, self.agents[name]

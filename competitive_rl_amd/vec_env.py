@@ -670,6 +670,22 @@ class HipPongVecEnv(VecEnv):
         N.check(self._L.crl_get_state(self._h, st.ctypes.data_as(C.c_void_p), 0, self.num_envs, self._stream()))
         return st
 
+    def rule_labels(self, seat=0, out=None):
+        """RULE_BASED's action as a label (include/crl.h ``crl_rule_labels``): int32 (N,) on the device, per env the action in 0..2 that
+        the cheat code 999 would resolve to for bat ``seat`` (0 left, 1 right) on the first frame of the next step, in the state the env
+        holds now.  ``out``: a contiguous int32 tensor of N elements on the env's device (e.g. a row of a (T, N) label tensor).  One
+        small launch on the current stream; nothing in the env changes, nothing synchronises.
+        ``rules.pong_rule_label_reference(envs.get_state(), seat)`` restates it."""
+        self._check_open()
+        if seat not in (0, 1):
+            raise ValueError(f"seat must be 0 (left) or 1 (right), not {seat!r}")
+        if out is None:
+            out = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+        if not (out.is_contiguous() and out.dtype == torch.int32 and out.device == self.device and out.numel() == self.num_envs):
+            raise ValueError("out must be a contiguous int32 tensor of num_envs elements on the env's device")
+        N.check(self._L.crl_rule_labels(self._h, int(seat), C.c_void_p(out.data_ptr()), 1, self._stream()))
+        return out
+
     def set_state(self, st):
         st = np.ascontiguousarray(st, N.STATE_DT)
         assert len(st) == self.num_envs

@@ -291,6 +291,15 @@ int crl_terminal_observation_dev(crl_ctx *ctx, const int64_t *env_idx_dev, int64
 /* Synchronises `stream` and reports (then clears) a pending CRL_EACTION. */
 int crl_check(crl_ctx *ctx, void *stream);
 
+/* RULE_BASED's action as a label (a teacher's labels for "ppo update, teacher targets").  labels_dev[i * stride], int32, = the action
+ * in 0..2 that the cheat code CRL_PONG_CHEAT would resolve to for bat `seat` (0 the left, 1 the right) of env i on the FIRST frame of
+ * the next step, in the state the context holds now: auto_action (base_pong_env.py:457-471) + 1, on the ball's speed towards that side
+ * (seat 0: -speed_x), the bat's centre bat_y + 7 and the ball's centre ball_y + 2, as the step's decode forms them.  A wrapped step
+ * re-evaluates the rule on each of its four frames; the label is the first of them.  One small launch, one lane per env, ordered on
+ * `stream` behind the step that committed the state; reads the state and changes nothing in the env.  Refuses (CRL_EINVAL, before
+ * any GPU call) a null argument, a CarRacing context, a seat outside {0, 1}, a stride < 1 and a labels_dev that is not 4-byte aligned. */
+int crl_rule_labels(crl_ctx *ctx, int32_t seat, int32_t *labels_dev, int64_t stride, void *stream);
+
 /* Parity tests + checkpoint/resume: whole-state copy, host AoS <-> device SoA.
  * Synchronises `stream`. */
 int crl_get_state(crl_ctx *ctx, crl_pong_env_state *state_host, int64_t first, int64_t count,
@@ -1004,6 +1013,51 @@ int crl_ppo_get_weights_full(crl_ppo *p, float *conv1_w_host, float *conv1_b_hos
  * crl_policy_load_weights_dev keeps refusing a full-size policy: its blob is the light learner's. */
 int crl_policy_load_full_dev(crl_policy *p, const float *blob_dev, void *stream);
 int crl_pool_load_full_dev(crl_league *l, int32_t agent, const float *blob_dev, void *stream);
+
+/* ---- ppo update, teacher targets: imitation and KL-to-teacher on either learner ----------------
+ * Extends "ppo update" (and "ppo update, full size"); nothing in those sections changes.  One term is added to d loss / d logits in the
+ * heads; everything behind the heads -- backward passes, summation shapes, reduce, optimiser step, push, resume -- is untouched.  Serves
+ * distilling one network into another (teacher logits), cloning a rule (labels, e.g. crl_rule_labels) and PPO regularised towards a teacher.
+ *
+ * Target distribution q of sample b, from row s = idx[b] (the flat t * N + e index; never row b) of one of two device arrays:
+ *   logits  float32 [T * N][3], at temperature tau, in float64:  u_k = (double) l_k / (double) tau,  m = max u,  e_k = exp(u_k - m),
+ *           S = (e0 + e1) + e2,  q_k = e_k / S,  logq_k = (u_k - m) - log S;
+ *   labels  int32 [T * N]: a value in 0..2 gives the one-hot q (a term with q_k = 0 counts as 0); any other value means the sample has
+ *           no teacher: its teacher term and its teacher statistics are 0.
+ * Learner side: logp_k, p_k exactly as "ppo update" forms them (the learner's temperature stays fixed at 1), and
+ *   ce = -((q0 logp0 + q1 logp1) + q2 logp2),   Hq = -((q0 logq0 + q1 logq1) + q2 logq2),   kl = ce - Hq   (= KL(q || p)).
+ * Loss, per sample:   loss_b = policy_term * policy + coef * ce + vf * value - ent * entropy,
+ *   policy_term in {0, 1}: at 0 the rule sets d policy / d logp = 0 -- pure imitation; the stored advantage and old log-prob then play
+ *   no part in the gradient (they still enter the five statistics);  coef >= 0;
+ *   value = 0.5 (target - v)^2 with target = the stored return, or row s of an optional float32 array value_targets [T * N] (a teacher's critic).
+ * Closed form, float64, rounded once to float32:   d loss_b / d logit_k = (the expression of "ppo update") + coef (p_k - q_k), the
+ * teacher term added last;  d loss_b / d v = vf (v - target).  With coef = 0, policy_term = 1 and no value targets the gradient
+ * therefore equals crl_ppo_grad's as numbers.
+ * Statistics: the five of "ppo update" as always, and four more, float64 sums over the samples / B: ce, kl, agree = 1[argmax p ==
+ * argmax q] (the lowest index among equals on both sides; taken over the logits and over u), labelled = the share of samples with a
+ * teacher term.  They use the summation shape the five have on each learner: per workgroup then over workgroups (light); rows, then
+ * slices, then chunks (full size).
+ * The kernels: the teacher instantiations of the gradient kernel (light) and of the heads, head-slice, head-sum and final kernels (full
+ * size); the plain instantiations are what crl_ppo_grad launches, unchanged.  The same launches, no floating-point atomics, the same call
+ * gives the same bits on every run, nothing synchronises, all work is ordered on the caller's stream. */
+typedef struct crl_ppo_teacher {
+    const float *logits_dev;          /* [rows][3] or null */
+    const int32_t *labels_dev;        /* [rows] or null; exactly one of the two */
+    const float *value_targets_dev;   /* [rows] or null = the stored returns */
+    int64_t rows;                     /* must equal T * N of the rollout */
+    float temperature, coef;
+    int32_t policy_term;
+} crl_ppo_teacher;
+/* crl_ppo_grad with a teacher, on either kind of learner; crl_ppo_step, _stats, _get_grad and _weights_dev work behind it as behind
+ * crl_ppo_grad.  The teacher's arrays are the caller's and must stay valid until the launches have run.  Refuses (CRL_EINVAL, before any
+ * GPU call, the learner as it was): everything crl_ppo_grad refuses; a null teacher; both of logits and labels, or neither; rows != T * N;
+ * a temperature that is not finite and > 0; a coef that is not finite and >= 0; policy_term outside {0, 1}; a teacher array that is
+ * not 4-byte aligned. */
+int crl_ppo_grad_teacher(crl_ppo *p, const crl_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper,
+                         const crl_ppo_teacher *teacher, void *stream);
+/* out4_host: ce, kl, agree, labelled of the last crl_ppo_grad_teacher.  Synchronises the device, like crl_ppo_stats.  Refuses
+ * (CRL_EINVAL) when the learner's last gradient was a plain crl_ppo_grad's, or when it has none. */
+int crl_ppo_teacher_stats(crl_ppo *p, double *out4_host);
 
 /* ---- checkpoint / resume: what a training loop needs to stop and go on, bit for bit ----------------
  * The reference's trainers checkpoint the model's state_dict and the optimiser's (torch.save); a loop that never leaves the device
