@@ -1,9 +1,21 @@
-// pong_policy_full.h -- the full-size ActorCritic opponent (pong_policy_full.hip) as seen from pong_policy.hip.
+// pong_policy_full.h -- the full-size ActorCritic (pong_policy_full.hip) as seen from pong_policy.hip and pong_league.hip, and the
+// network's shapes and weight blob layout, which its learner (pong_ppo_full.hip) shares.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace crl {
+
+static constexpr int kC1 = 16, kP1 = 400;  // conv1: 16 channels x 20 x 20
+static constexpr int kC2 = 32, kP2 = 121;  // conv2: 32 channels x 11 x 11
+static constexpr int kK3 = kC2 * kP2;      // 3872 = conv3's receptive field: the whole of act2
+static constexpr int kC3 = 256;
+// the packed blob, torch layouts: w1 | b1 | w2 | b2 | w3 | b3 | wa | ba + 1 pad (policy_full_pack), and behind it a crl_policy's and a
+// learner's critic tail: wc | bc + 3 pad (policy_full_pack_critic)
+static constexpr int kOffW1 = 0, kOffB1 = kOffW1 + 1024, kOffW2 = kOffB1 + 16, kOffB2 = kOffW2 + kC2 * 256, kOffW3 = kOffB2 + 32;
+static constexpr int kOffB3 = kOffW3 + kC3 * kK3, kOffWa = kOffB3 + kC3, kOffBa = kOffWa + 3 * kC3, kFullRawFloats = kOffBa + 4;
+static constexpr int kOffWc = kFullRawFloats, kOffBc = kOffWc + kC3, kFullCriticFloats = kC3 + 4;
+static constexpr int kFullBlob = kFullRawFloats + kFullCriticFloats;  // 1 001 784
 
 struct SampleArgs;  // pong_sample.h
 struct HeadArgs;    // pong_sample.h

@@ -26,6 +26,8 @@
 // scratch belongs to env env_list[r]; ring, frame, action and logits are addressed by the env, act2 and feat by the row.  All three
 // grids are persistent and sized from an upper bound of the count; a workgroup without a row returns before it touches LDS or
 // reaches a barrier.  The arithmetic of a row is the dense kernels', operation for operation, and does not depend on the row's place.
+//
+// The network's shapes (kC1 .. kC3, kP1, kP2, kK3) and the weight blob's offsets (kOff*) are pong_policy_full.h's: the learner shares them.
 #include "pong_policy_full.h"
 
 #include <string.h>
@@ -40,15 +42,7 @@
 
 namespace crl {
 
-static constexpr int kC1 = 16, kP1 = 400;        // conv1: 16 channels x 20 x 20
-static constexpr int kC2 = 32, kP2 = 121;        // conv2: 32 channels x 11 x 11
-static constexpr int kK3 = kC2 * kP2;            // 3872 = conv3's receptive field: the whole of act2
-static constexpr int kC3 = 256;
 static constexpr int64_t kChunk = 65536;         // envs per pass (scratch: 42 KB per env)
-
-static constexpr int kOffW1 = 0, kOffB1 = kOffW1 + 1024, kOffW2 = kOffB1 + 16, kOffB2 = kOffW2 + kC2 * 256, kOffW3 = kOffB2 + 32;
-static constexpr int kOffB3 = kOffW3 + kC3 * kK3, kOffWa = kOffB3 + kC3, kOffBa = kOffWa + 3 * kC3, kBlob = kOffBa + 4;
-static constexpr int kOffWc = kBlob, kOffBc = kOffWc + kC3, kCritic = kC3 + 4;  // a crl_policy's blob: the critic row and its bias behind the actor
 
 struct PolicyFull {
     int64_t n = 0, chunk = 0;
@@ -350,10 +344,10 @@ __global__ __launch_bounds__(256) void policy_full_actor_kernel(const float *__r
     }
 }
 
-int64_t policy_full_blob_floats() { return kBlob; }
+int64_t policy_full_blob_floats() { return kFullRawFloats; }
 int64_t policy_full_act2_floats() { return kK3; }
 int64_t policy_full_feat_floats() { return kC3; }
-int64_t policy_full_critic_floats() { return kCritic; }
+int64_t policy_full_critic_floats() { return kFullCriticFloats; }
 float *policy_full_blob(PolicyFull *f) { return f->w; }
 void policy_full_pack_critic(float *critic_part, const float *critic_w, const float *critic_b) {
     memcpy(critic_part, critic_w, kC3 * sizeof(float)), critic_part[kOffBc - kOffWc] = critic_b[0];
@@ -376,7 +370,7 @@ hipError_t policy_full_create(PolicyFull **out, int64_t num_envs, const float *c
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         f->cus <= 0)
         f->cus = 256;
-    std::vector<float> blob(kBlob + kCritic, 0.f);  // (the critic part stays zero until crl_policy_set_critic / _load_weights)
+    std::vector<float> blob(kFullBlob, 0.f);  // (the critic part stays zero until crl_policy_set_critic / _load_weights)
     policy_full_pack(blob.data(), conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b);
     hipError_t e = hipMalloc(&f->w, blob.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(f->w, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);

@@ -1,6 +1,8 @@
 // pong_ppo.hip -- the learner's PPO update for the LightActorCritic on the device (include/crl.h "ppo update"): the gradient of the
 // clipped-surrogate loss over a minibatch of a crl_rollout, read from the stored uint8 planes, and the clip + Adam step on a master blob
 // in the layout of pong_league.h.  Three launches per gradient (gradient, reduce, final) and one per step; nothing touches the host.
+// What the full-size learner (pong_ppo_full.hip) shares lives here too: the blobs' host side (ppo_alloc_blobs, ppo_upload, ppo_download),
+// and the step kernel; the sample fetch, the loss terms and the reduce kernel of both are pong_ppo.h's.
 //
 // The reference ships no trainer (utils/network.py has only the networks): the loss is the written rule of the header.
 //
@@ -67,7 +69,7 @@ struct GradArgs {
     double *stat_part;   // [W][kStatN]
     PpoHyperDev h;
 };
-struct GradArgsTeacher : GradArgs {
+struct GradArgsTeacher : GradArgs {  // (built as GradArgsTeacher{a, t})
     PpoTeacherDev t;
 };
 
@@ -77,11 +79,13 @@ __device__ inline void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// TEACHER: include/crl.h "ppo update, teacher targets" -- the staging also fetches the samples' teacher rows and value targets, the
-// heads phase calls ppo_sample_terms_teacher and the statistics are nine.  <false> is the kernel crl_ppo_grad launches, as it was.
+// TEACHER: include/crl.h "ppo update, teacher targets" -- the staging also keeps the samples' teacher rows (the value target is the
+// teacher's where it has one), the heads phase forms the teacher term and the statistics are nine.  <false> is what crl_ppo_grad launches.
 template <bool TEACHER>
 __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(std::conditional_t<TEACHER, GradArgsTeacher, GradArgs> a) {
     constexpr int NS = TEACHER ? kStatAll : kStatN;
+    const PpoTeacherDev *teacher = nullptr;
+    if constexpr (TEACHER) teacher = &a.t;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *sh_buf = smem;                                                  // [kGE][4][kPlanePad]
     float *sh_a2 = reinterpret_cast<float *>(smem + kLdsBuf);               // [kGE][1600]
@@ -156,36 +160,19 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(std::condit
             const int j = rem / kPlaneChunks, c = rem - j * kPlaneChunks;
             uint4 v{0u, 0u, 0u, 0u};
             if (fe < here) {
-                const uint32_t raw = (uint32_t)a.idx[b0 + fe];
-                const uint32_t flat = raw < a.r.last ? raw : a.r.last;  // (a bad index only reads inside the arrays, as in the gather)
-                const uint32_t t = flat / a.r.n, e = flat - t * a.r.n;
-                if (CRL_POLICY_STACK - 1 - j < (int)a.r.depth[flat])
-                    v = reinterpret_cast<const uint4 *>(a.r.planes)[((int64_t)(t + j) * a.r.n + e) * kPlaneChunks + c];
+                const uint32_t flat = sample_of(a.r, a.idx, b0 + fe);
+                if (CRL_POLICY_STACK - 1 - j < (int)a.r.depth[flat]) v = *plane_of(a.r, sample_at(a.r, flat), j, c);
             }
             reinterpret_cast<uint4 *>(sh_buf)[(fe * CRL_POLICY_STACK + j) * kPlaneChunks + c] = v;
         }
         if (tid < kGE) {
-            float act = 0.f, olp = 0.f, ret = 0.f, adv = 0.f;
-            if (tid < here) {
-                const uint32_t raw = (uint32_t)a.idx[b0 + tid];
-                const uint32_t flat = raw < a.r.last ? raw : a.r.last;
-                const int32_t ai = a.r.actions[flat];
-                act = (float)(ai < 0 ? 0 : ai > 2 ? 2 : ai);
-                olp = a.r.logp[flat], ret = a.r.ret[flat], adv = a.r.adv[flat];
-                if (a.r.stats) adv = (adv - (float)a.r.stats[0]) / ((float)a.r.stats[1] + 1e-5f);  // as crl_rollout_gather hands it out
+            PpoSample sm;
+            if (tid < here) sm = sample_scalars(a.r, sample_of(a.r, a.idx, b0 + tid), teacher);
+            sh_sc[tid * 4 + 0] = (float)sm.act, sh_sc[tid * 4 + 1] = sm.olp, sh_sc[tid * 4 + 2] = sm.target, sh_sc[tid * 4 + 3] = sm.adv;
+            if constexpr (TEACHER) {
+                sh_tr[tid * 4 + 0] = sm.tr.l[0], sh_tr[tid * 4 + 1] = sm.tr.l[1], sh_tr[tid * 4 + 2] = sm.tr.l[2];
+                reinterpret_cast<int32_t *>(sh_tr)[tid * 4 + 3] = sm.tr.label;
             }
-            if constexpr (TEACHER) {  // row s = the sample's flat index, never its place in the batch
-                TeacherRow tr{{0.f, 0.f, 0.f}, -1};
-                if (tid < here) {
-                    const uint32_t raw = (uint32_t)a.idx[b0 + tid];
-                    const uint32_t flat = raw < a.r.last ? raw : a.r.last;
-                    tr = teacher_row(a.t, flat);
-                    if (a.t.vtarget) ret = a.t.vtarget[flat];
-                }
-                sh_tr[tid * 4 + 0] = tr.l[0], sh_tr[tid * 4 + 1] = tr.l[1], sh_tr[tid * 4 + 2] = tr.l[2];
-                reinterpret_cast<int32_t *>(sh_tr)[tid * 4 + 3] = tr.label;
-            }
-            sh_sc[tid * 4 + 0] = act, sh_sc[tid * 4 + 1] = olp, sh_sc[tid * 4 + 2] = ret, sh_sc[tid * 4 + 3] = adv;
         }
         __syncthreads();
         // ---- forward: the features
@@ -230,12 +217,9 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(std::condit
                     const double v = (double)a.raw[kLightBc] + s3;
                     const int act = (int)sh_sc[e * 4 + 0];
                     const double olp = (double)sh_sc[e * 4 + 1], ret = (double)sh_sc[e * 4 + 2], A = (double)sh_sc[e * 4 + 3];
-                    if constexpr (TEACHER) {
-                        const TeacherRow tr{{sh_tr[e * 4 + 0], sh_tr[e * 4 + 1], sh_tr[e * 4 + 2]}, reinterpret_cast<const int32_t *>(sh_tr)[e * 4 + 3]};
-                        ppo_sample_terms_teacher(l, v, act, olp, ret, A, a.h, a.t, tr, dl, dv, st);
-                    } else {
-                        ppo_sample_terms(l, v, act, olp, ret, A, a.h, dl, dv, st);
-                    }
+                    TeacherRow tr;
+                    if constexpr (TEACHER) tr = TeacherRow{{sh_tr[e * 4 + 0], sh_tr[e * 4 + 1], sh_tr[e * 4 + 2]}, reinterpret_cast<const int32_t *>(sh_tr)[e * 4 + 3]};
+                    ppo_sample_terms<TEACHER>(l, v, act, olp, ret, A, a.h, teacher, tr, dl, dv, st);
                 }
                 sh_dh[e * 4 + 0] = dl[0], sh_dh[e * 4 + 1] = dl[1], sh_dh[e * 4 + 2] = dl[2], sh_dh[e * 4 + 3] = dv;
 #pragma unroll
@@ -368,29 +352,7 @@ __global__ __launch_bounds__(kGThreads, 1) void pong_ppo_grad_kernel(std::condit
     }
 }
 
-// Reduce: a lane per blob element adds the W partial blobs in workgroup order (float32) and divides by B; the workgroup's 256 squares
-// go through a binary tree in float64.
 static constexpr int kRedBlocks = (kBlob + 255) / 256;  // 34
-__global__ __launch_bounds__(256) void pong_ppo_reduce_kernel(const float *__restrict__ partials, int groups, float count_f, float *__restrict__ grad,
-                                                             double *__restrict__ sq_part) {
-    __shared__ double s[256];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    float g = 0.f;
-    if (i < kBlob) {
-        float sum = partials[i];
-        for (int w = 1; w < groups; w++) sum += partials[(int64_t)w * kBlob + i];
-        g = sum / count_f;
-        grad[i] = g;
-    }
-    s[threadIdx.x] = (double)g * (double)g;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sq_part[blockIdx.x] = s[0];
-}
-
 // ... and one lane: the 34 sums of squares in order, the W statistics partials in order.  out: [0] the sum of squares, [1 .. NS] the means
 // (NS = 5, or the 9 of a teacher gradient)
 template <int NS>
@@ -429,6 +391,34 @@ __global__ __launch_bounds__(256) void pong_ppo_step_kernel(StepArgs a) {
     a.raw[i] = a.raw[i] - a.step_size * (m / denom);
 }
 
+int ppo_alloc_blobs(::crl_ppo *p, int blob_floats, const char *who) {
+    p->blob_floats = blob_floats;
+    int rc = CRL_OK;
+    for (float **q : {&p->raw, &p->m, &p->v, &p->grad})
+        if (rc == CRL_OK) rc = crl_dev_zalloc(q, (size_t)blob_floats * sizeof(float), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
+    return rc;
+}
+
+int ppo_upload(::crl_ppo *p, const float *blob) {
+    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(p->raw, blob, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(p->m, 0, bytes));
+    HIP_TRY(hipMemset(p->v, 0, bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    p->steps = 0;
+    return CRL_OK;
+}
+
+int ppo_download(::crl_ppo *p, float *blob) {
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(blob, p->raw, (size_t)p->blob_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CRL_OK;
+}
+
 }  // namespace crl
 
 using namespace crl;
@@ -444,6 +434,18 @@ static int ppo_hyper_check(const char *who, const crl_ppo_hyper *h) {
     if (!(h->clip >= 0.f) || !(h->lr >= 0.f) || !(h->beta1 >= 0.f && h->beta1 < 1.f) || !(h->beta2 >= 0.f && h->beta2 < 1.f) || !(h->eps > 0.f) ||
         !(h->max_grad_norm > 0.f) || !(h->vf_coef == h->vf_coef) || !(h->ent_coef == h->ent_coef))
         return crl_fail(CRL_EINVAL, "%s: clip >= 0, lr >= 0, betas in [0, 1), eps > 0, max_grad_norm > 0, no NaN", who);
+    return CRL_OK;
+}
+
+// the light learner's three launches; TEACHER chooses the instantiations, their LDS and the statistics' count
+template <bool TEACHER>
+static int ppo_light_grad(crl_ppo *p, const std::conditional_t<TEACHER, GradArgsTeacher, GradArgs> &a, hipStream_t st) {
+    const int64_t ngroups = (a.count + kGE - 1) / kGE;
+    const int groups = (int)(ngroups < kGMaxGroups ? ngroups : kGMaxGroups);
+    hipLaunchKernelGGL(pong_ppo_grad_kernel<TEACHER>, dim3(groups), dim3(kGThreads), TEACHER ? kLdsGradTeacher : kLdsGrad, st, a);
+    hipLaunchKernelGGL((ppo_reduce_kernel<kBlob, kBlob>), dim3(kRedBlocks), dim3(256), 0, st, p->partials, groups, nullptr, (float)a.count, p->grad, p->sq_part);
+    hipLaunchKernelGGL(pong_ppo_final_kernel<TEACHER ? kStatAll : kStatN>, dim3(1), dim3(64), 0, st, p->sq_part, p->stat_part, groups, a.count, p->red);
+    HIP_TRY(hipGetLastError());
     return CRL_OK;
 }
 
@@ -464,17 +466,10 @@ int crl_ppo_set_weights(crl_ppo *p, const float *conv1_w, const float *conv1_b, 
     if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b || !critic_w || !critic_b)
         return crl_fail(CRL_EINVAL, "crl_ppo_set_weights: null argument (a learner needs its critic)");
     if (p->full) return crl_fail(CRL_EINVAL, "crl_ppo_set_weights: a full-size learner (crl_ppo_set_weights_full)");
-    HIP_TRY(hipSetDevice(p->device));
     std::vector<float> blob(kBlob);
     const float *const t[8] = {conv1_w, conv1_b, conv2_w, conv2_b, actor_w, actor_b, critic_w, critic_b};
     ppo_pack(blob.data(), t);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(p->raw, blob.data(), kBlob * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(p->m, 0, kBlob * sizeof(float)));
-    HIP_TRY(hipMemset(p->v, 0, kBlob * sizeof(float)));
-    HIP_TRY(hipDeviceSynchronize());
-    p->steps = 0;
-    return CRL_OK;
+    return ppo_upload(p, blob.data());
 }
 
 int crl_ppo_create(int32_t device, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *actor_w,
@@ -485,16 +480,12 @@ int crl_ppo_create(int32_t device, const float *conv1_w, const float *conv1_b, c
     *out = nullptr;
     HIP_TRY(hipSetDevice(device));
     crl_ppo *p = new crl_ppo();
-    p->device = device, p->blob_floats = kBlob;
+    p->device = device;
     const char *who = "crl_ppo_create";
-    int rc = crl_dev_zalloc(&p->raw, kBlob * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->m, kBlob * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->v, kBlob * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->grad, kBlob * sizeof(float), who);
+    int rc = ppo_alloc_blobs(p, kBlob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->partials, (size_t)kGMaxGroups * kBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->stat_part, (size_t)kGMaxGroups * kStatAll * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->sq_part, kRedBlocks * sizeof(double), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
     if (rc == CRL_OK) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pong_ppo_grad_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsGrad);
         if (e != hipSuccess) rc = crl_hip_fail(e, who);
@@ -518,10 +509,8 @@ int crl_ppo_get_weights(crl_ppo *p, float *conv1_w, float *conv1_b, float *conv2
     if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !actor_w || !actor_b || !critic_w || !critic_b)
         return crl_fail(CRL_EINVAL, "crl_ppo_get_weights: null argument");
     if (p->full) return crl_fail(CRL_EINVAL, "crl_ppo_get_weights: a full-size learner (crl_ppo_get_weights_full)");
-    HIP_TRY(hipSetDevice(p->device));
     std::vector<float> blob(kBlob);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(blob.data(), p->raw, kBlob * sizeof(float), hipMemcpyDeviceToHost));
+    if (int rc = ppo_download(p, blob.data())) return rc;
     memcpy(conv1_w, &blob[kLightW1], 1024 * 4), memcpy(conv1_b, &blob[kLightB1], 16 * 4), memcpy(conv2_w, &blob[kLightW2], 1024 * 4);
     memcpy(conv2_b, &blob[kLightB2], 16 * 4), memcpy(actor_w, &blob[kLightWa], 4800 * 4), memcpy(actor_b, &blob[kLightBa], 3 * 4);
     memcpy(critic_w, &blob[kLightWc], 1600 * 4), critic_b[0] = blob[kLightBc];
@@ -560,25 +549,14 @@ static int ppo_grad(const char *who, crl_ppo *p, const crl_rollout *rollout, con
     }
     hipStream_t st = (hipStream_t)stream;
     const PpoHyperDev h{hyper->clip, hyper->vf_coef, hyper->ent_coef};
+    int rc;
     if (p->full) {
-        if (int rc = ppo_full_grad(p, view, idx_dev, count, h, teacher ? &t : nullptr, st)) return rc;
-        p->have_grad = true, p->teacher_grad = teacher != nullptr;
-        return CRL_OK;
-    }
-    const int64_t ngroups = (count + kGE - 1) / kGE;
-    const int groups = (int)(ngroups < kGMaxGroups ? ngroups : kGMaxGroups);
-    GradArgs a{view, idx_dev, count, p->raw, p->partials, p->stat_part, h};
-    if (teacher) {
-        GradArgsTeacher at;
-        static_cast<GradArgs &>(at) = a, at.t = t;
-        hipLaunchKernelGGL(pong_ppo_grad_kernel<true>, dim3(groups), dim3(kGThreads), kLdsGradTeacher, st, at);
+        rc = ppo_full_grad(p, view, idx_dev, count, h, teacher ? &t : nullptr, st);
     } else {
-        hipLaunchKernelGGL(pong_ppo_grad_kernel<false>, dim3(groups), dim3(kGThreads), kLdsGrad, st, a);
+        const GradArgs a{view, idx_dev, count, p->raw, p->partials, p->stat_part, h};
+        rc = teacher ? ppo_light_grad<true>(p, GradArgsTeacher{a, t}, st) : ppo_light_grad<false>(p, a, st);
     }
-    hipLaunchKernelGGL(pong_ppo_reduce_kernel, dim3(kRedBlocks), dim3(256), 0, st, p->partials, groups, (float)count, p->grad, p->sq_part);
-    if (teacher) hipLaunchKernelGGL(pong_ppo_final_kernel<kStatAll>, dim3(1), dim3(64), 0, st, p->sq_part, p->stat_part, groups, count, p->red);
-    else hipLaunchKernelGGL(pong_ppo_final_kernel<kStatN>, dim3(1), dim3(64), 0, st, p->sq_part, p->stat_part, groups, count, p->red);
-    HIP_TRY(hipGetLastError());
+    if (rc) return rc;
     p->have_grad = true, p->teacher_grad = teacher != nullptr;
     return CRL_OK;
 }

@@ -1,7 +1,7 @@
 // pong_ppo_full.hip -- the learner's PPO update for the full-size ActorCritic on the device (include/crl.h "ppo update, full size"): the
 // gradient of the clipped-surrogate loss over a minibatch of a crl_rollout, read from the stored uint8 planes, on a master blob in the
-// layout of a full-size crl_policy (pong_policy_full.hip).  The loss, the statistics and the optimiser step are pong_ppo.hip's; the
-// step kernel is its kernel, over 1 001 784 floats.
+// layout of a full-size crl_policy (pong_policy_full.h).  The sample fetch, the loss and the statistics are pong_ppo.h's; the blobs'
+// host side and the optimiser step are pong_ppo.hip's, over 1 001 784 floats; the reduce kernel is pong_ppo.h's.
 //
 // A minibatch is cut into chunks of at most scratch_rows samples (scratch per row: act2 / dz2 3872 floats, a3 256, dz3 256, dlogits and
 // dv 4, the statistics 5 doubles); the chunks run in order, eight launches each, and every gradient element accumulates over the chunks
@@ -28,7 +28,8 @@
 //               dz1 = da1 * (a1 > 0) into LDS, then gW1[oc][ic, tap] += dz1[oc][pos] x[ic][pos + tap]   M 16, N 64, K = 400
 //             with gW1 / gW2 in matrix accumulators for the whole launch and the biases as per-thread sums beside them; the workgroup's
 //             partial blob (9 264 floats: w1 | b1 | w2 | b2) is written by the first chunk and added to by the later ones.
-// Then finish (partials in workgroup order, / float32(B), sums of squares per block of 256) and final (the block sums, the statistics).
+// Then pong_ppo.h's reduce (the back kernel's partials in workgroup order for w1 .. b2, the accumulated sums for the rest, / float32(B),
+// sums of squares per block of 256) and final (the block sums, the statistics).
 #include <string.h>
 
 #include <algorithm>
@@ -44,20 +45,11 @@
 
 namespace crl {
 
-static constexpr int kC1 = 16, kP1 = 400;  // conv1: 16 channels x 20 x 20
-static constexpr int kC2 = 32, kP2 = 121;  // conv2: 32 channels x 11 x 11
-static constexpr int kK3 = kC2 * kP2;      // 3872
-static constexpr int kC3 = 256;
-// the blob of a full-size crl_policy (pong_policy_full.hip), critic tail included
-static constexpr int kOffW1 = 0, kOffB1 = kOffW1 + 1024, kOffW2 = kOffB1 + 16, kOffB2 = kOffW2 + kC2 * 256, kOffW3 = kOffB2 + 32;
-static constexpr int kOffB3 = kOffW3 + kC3 * kK3, kOffWa = kOffB3 + kC3, kOffBa = kOffWa + 3 * kC3, kOffWc = kOffBa + 4, kOffBc = kOffWc + kC3;
-static constexpr int kFullBlob = kOffBc + 4;  // 1 001 784
-static constexpr int kBackBlob = kOffW3;      // 9 264: what the back kernel's partials hold
+static constexpr int kBackBlob = kOffW3;      // 9 264: what the back kernel's partials hold (w1 | b1 | w2 | b2 of pong_policy_full.h's blob)
 static constexpr int kBackMax = 256;          // W <= 256
 static constexpr int kSqBlocks = (kFullBlob + 255) / 256;  // 3 914
 static constexpr int64_t kDefaultRows = 16384;            // scratch: 17.6 KB per row = 288 MB
 static constexpr int64_t kMinRows = 64, kMaxRows = 1 << 20;  // (eight launches per chunk: a smaller chunk only queues launches)
-static_assert(kFullBlob == 1001784 && kBackBlob == 9264, "the blob of include/crl.h");
 
 static constexpr int kS1Rows = 24, kS1Pitch = 580;  // a1: padded plane 24 x 24 = 576 floats + 4 (pong_policy_full.hip)
 static constexpr int kW2Pitch = 260;                // W2 in LDS, floats per output channel
@@ -84,12 +76,6 @@ struct PpoFull {
 
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-// the flat sample index of row `row` (a bad index only reads inside the arrays, as in the gather)
-__device__ inline uint32_t sample_of(const RolloutView &r, const int64_t *idx, int64_t row) {
-    const uint32_t raw = (uint32_t)idx[row];
-    return raw < r.last ? raw : r.last;
-}
-
 // conv1's B operands of a lane: channel li, k order 32 h + 8 lk + j = torch's own, each weight / 255 as three bf16 terms
 __device__ __forceinline__ void conv1_weights(const float *__restrict__ w1, int li, int lk, bf8 (&wB)[3][2]) {
 #pragma unroll
@@ -106,7 +92,7 @@ __device__ __forceinline__ void conv1_weights(const float *__restrict__ w1, int 
 // of 25, as policy_full_front_kernel forms them; the spare turns repeat tile 24 (same values, same addresses).
 __device__ __forceinline__ void conv1_to_lds(const RolloutView &r, uint32_t flat, const bf8 (&wB)[3][2], const f4 bias1, float *s1, int wave, int li,
                                              int lk) {
-    const uint32_t t = flat / r.n, e = flat - t * r.n;
+    const SampleAt at = sample_at(r, flat);
     const int depth = r.depth[flat];
     const uint8_t *pl[2];
     bool live[2];
@@ -114,7 +100,7 @@ __device__ __forceinline__ void conv1_to_lds(const RolloutView &r, uint32_t flat
     for (int h = 0; h < 2; h++) {  // plane 2 h + (lk >> 1), window rows 2 (lk & 1) + {0, 1}
         const int j = 2 * h + (lk >> 1);
         live[h] = CRL_POLICY_STACK - 1 - j < depth;
-        pl[h] = r.planes + ((int64_t)(t + j) * r.n + e) * kPlanePad + (2 * (lk & 1)) * kDim;
+        pl[h] = reinterpret_cast<const uint8_t *>(plane_of(r, at, j)) + (2 * (lk & 1)) * kDim;
     }
 #pragma unroll
     for (int it = 0; it < 7; it++) {
@@ -278,8 +264,8 @@ __global__ __launch_bounds__(256, 2) void ppo_full_conv3_kernel(const float *__r
     }
 }
 
-// ---- heads: a wavefront per row.  TEACHER: include/crl.h "ppo update, teacher targets" -- h carries the teacher, the row's teacher row
-// and value target are fetched at its flat index and the statistics are nine per row.  <false> is the kernel crl_ppo_grad launches, as it was.
+// ---- heads: a wavefront per row.  TEACHER: include/crl.h "ppo update, teacher targets" -- the row's teacher row and value target are
+// fetched at its flat index and the statistics are nine per row.  <false> is what crl_ppo_grad launches, and receives no teacher.
 template <bool TEACHER>
 __global__ __launch_bounds__(256) void ppo_full_heads_kernel(RolloutView r, const int64_t *__restrict__ idx, int64_t rows, const float *__restrict__ raw,
                                                              const float *__restrict__ a3, float *__restrict__ dz3, float *__restrict__ dh,
@@ -302,21 +288,14 @@ __global__ __launch_bounds__(256) void ppo_full_heads_kernel(RolloutView r, cons
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s0 += __shfl_xor(s0, d), s1 += __shfl_xor(s1, d), s2 += __shfl_xor(s2, d), s3 += __shfl_xor(s3, d);
     // (a + b and b + a are the same bits: every lane holds the same four sums and forms the same terms)
-    const uint32_t flat = sample_of(r, idx, row);
-    const int32_t ai = r.actions[flat];
-    const int act = ai < 0 ? 0 : ai > 2 ? 2 : ai;
-    float adv = r.adv[flat];
-    if (r.stats) adv = (adv - (float)r.stats[0]) / ((float)r.stats[1] + 1e-5f);  // as crl_rollout_gather hands it out
+    const PpoTeacherDev *teacher = nullptr;
+    if constexpr (TEACHER) teacher = &h.t;
+    const PpoSample sm = sample_scalars(r, sample_of(r, idx, row), teacher);
     const double l[3] = {(double)raw[kOffBa + 0] + s0, (double)raw[kOffBa + 1] + s1, (double)raw[kOffBa + 2] + s2};
     const double v = (double)raw[kOffBc] + s3;
     float dl[3], dv;
     double st[NS];
-    if constexpr (TEACHER) {
-        const float target = h.t.vtarget ? h.t.vtarget[flat] : r.ret[flat];
-        ppo_sample_terms_teacher(l, v, act, (double)r.logp[flat], (double)target, (double)adv, h, h.t, teacher_row(h.t, flat), dl, dv, st);
-    } else {
-        ppo_sample_terms(l, v, act, (double)r.logp[flat], (double)r.ret[flat], (double)adv, h, dl, dv, st);
-    }
+    ppo_sample_terms<TEACHER>(l, v, sm.act, (double)sm.olp, (double)sm.target, (double)sm.adv, h, teacher, sm.tr, dl, dv, st);
     if (lane == 0) {
         dh[row * 4 + 0] = dl[0], dh[row * 4 + 1] = dl[1], dh[row * 4 + 2] = dl[2], dh[row * 4 + 3] = dv;
 #pragma unroll
@@ -513,12 +492,12 @@ __global__ __launch_bounds__(256, 1) void ppo_full_back_kernel(RolloutView r, co
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
         const uint32_t flat = sample_of(r, idx, row);
         {  // the planes by the stack rule, the row's dz2
-            const uint32_t t = flat / r.n, e = flat - t * r.n;
+            const SampleAt at = sample_at(r, flat);
             const int depth = r.depth[flat];
             for (int i = tid; i < CRL_POLICY_STACK * kPlaneChunks; i += 256) {
                 const int j = i / kPlaneChunks, c = i - j * kPlaneChunks;
                 uint4 v{0u, 0u, 0u, 0u};
-                if (CRL_POLICY_STACK - 1 - j < depth) v = reinterpret_cast<const uint4 *>(r.planes)[((int64_t)(t + j) * r.n + e) * kPlaneChunks + c];
+                if (CRL_POLICY_STACK - 1 - j < depth) v = *plane_of(r, at, j, c);
                 reinterpret_cast<uint4 *>(spl)[i] = v;
             }
             const float *src = dz2g + row * kK3;
@@ -596,33 +575,7 @@ __global__ __launch_bounds__(256, 1) void ppo_full_back_kernel(RolloutView r, co
     if ((tid & 15) == 0) put(kOffB1 + (tid >> 4), accB1);
 }
 
-// ---- finish: element i of the gradient = (the W partials in workgroup order | the accumulated sum) / float32(B); the block's 256
-// squares through a binary tree in float64
-__global__ __launch_bounds__(256) void ppo_full_finish_kernel(const float *__restrict__ partials, int groups, const float *__restrict__ gacc, float count_f,
-                                                              float *__restrict__ grad, double *__restrict__ sq_part) {
-    __shared__ double s[256];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    float g = 0.f;
-    if (i < kFullBlob) {
-        float sum;
-        if (i < kBackBlob) {
-            sum = partials[i];
-            for (int w = 1; w < groups; w++) sum += partials[(int64_t)w * kBackBlob + i];
-        } else {
-            sum = gacc[i];
-        }
-        g = sum / count_f;
-        grad[i] = g;
-    }
-    s[threadIdx.x] = (double)g * (double)g;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sq_part[blockIdx.x] = s[0];
-}
-
+// ---- finish: pong_ppo.h's reduce (elements below kBackBlob from the W partials, the rest from the accumulated sum)
 // ... and one workgroup: thread t adds the block sums t, t + 256, ... in order, then the same tree.  out: [0] the sum of squares, [1 .. NS] the means
 template <int NS>
 __global__ __launch_bounds__(256) void ppo_full_final_kernel(const double *__restrict__ sq_part, const double *__restrict__ stat_acc, int64_t count,
@@ -650,11 +603,12 @@ void ppo_full_destroy(PpoFull *f) {
 
 int64_t ppo_full_scratch_rows(const PpoFull *f) { return f->scratch_rows; }
 
-int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, const PpoTeacherDev *t,
-                  hipStream_t st) {
+// TEACHER chooses the instantiations and the statistics' count
+template <bool TEACHER>
+static int full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count,
+                     const std::conditional_t<TEACHER, PpoHyperTeacher, PpoHyperDev> &h, hipStream_t st) {
+    constexpr int NS = TEACHER ? kStatAll : kStatN;
     PpoFull *f = p->full;
-    PpoHyperTeacher ht{};
-    if (t) static_cast<PpoHyperDev &>(ht) = h, ht.t = *t;
     const int64_t S = f->scratch_rows;
     const int64_t first_rows = std::min(S, count);
     const int groups = (int)std::min<int64_t>(kBackMax, first_rows);  // W: a function of B and scratch_rows alone
@@ -666,24 +620,22 @@ int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev,
         hipLaunchKernelGGL(ppo_full_front_kernel, dim3((unsigned)std::min<int64_t>(rows, (int64_t)f->cus * 2)), dim3(256), 0, st, view, idx, rows, raw, f->act2);
         hipLaunchKernelGGL(ppo_full_conv3_kernel, dim3((unsigned)((rows + kGM - 1) / kGM), kC3 / kGN), dim3(256), 0, st, f->act2, raw + kOffW3, raw + kOffB3, f->a3, rows);
         const int slices = (int)((rows + kHeadSlice - 1) / kHeadSlice);
-        if (t) {
-            hipLaunchKernelGGL(ppo_full_heads_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, view, idx, rows, raw, f->a3, f->dz3, f->dh, f->st, ht);
-            hipLaunchKernelGGL(ppo_full_headslice_kernel<kStatAll>, dim3(6, slices), dim3(256), 0, st, rows, f->dh, f->a3, f->dz3, f->st, f->hs, f->hsd);
-            hipLaunchKernelGGL(ppo_full_headsum_kernel<kStatAll>, dim3(6), dim3(256), 0, st, slices, f->hs, f->hsd, f->gacc, f->stat_acc, first);
-        } else {
-            hipLaunchKernelGGL(ppo_full_heads_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, view, idx, rows, raw, f->a3, f->dz3, f->dh, f->st, h);
-            hipLaunchKernelGGL(ppo_full_headslice_kernel<kStatN>, dim3(6, slices), dim3(256), 0, st, rows, f->dh, f->a3, f->dz3, f->st, f->hs, f->hsd);
-            hipLaunchKernelGGL(ppo_full_headsum_kernel<kStatN>, dim3(6), dim3(256), 0, st, slices, f->hs, f->hsd, f->gacc, f->stat_acc, first);
-        }
+        hipLaunchKernelGGL(ppo_full_heads_kernel<TEACHER>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, view, idx, rows, raw, f->a3, f->dz3, f->dh, f->st, h);
+        hipLaunchKernelGGL(ppo_full_headslice_kernel<NS>, dim3(6, slices), dim3(256), 0, st, rows, f->dh, f->a3, f->dz3, f->st, f->hs, f->hsd);
+        hipLaunchKernelGGL(ppo_full_headsum_kernel<NS>, dim3(6), dim3(256), 0, st, slices, f->hs, f->hsd, f->gacc, f->stat_acc, first);
         hipLaunchKernelGGL(ppo_full_gw3_kernel, dim3(kK3 / 32, kC3 / 128), dim3(256), 0, st, f->dz3, f->act2, rows, f->gacc + kOffW3, first);
         hipLaunchKernelGGL(ppo_full_dz2_kernel, dim3((unsigned)((rows + 127) / 128), kK3 / 32), dim3(256), 0, st, f->dz3, raw + kOffW3, f->act2, rows);
         hipLaunchKernelGGL(ppo_full_back_kernel, dim3(groups), dim3(256), kBackLds, st, view, idx, rows, raw, f->act2, f->partials, first);
     }
-    hipLaunchKernelGGL(ppo_full_finish_kernel, dim3(kSqBlocks), dim3(256), 0, st, f->partials, groups, f->gacc, (float)count, p->grad, f->sq_part);
-    if (t) hipLaunchKernelGGL(ppo_full_final_kernel<kStatAll>, dim3(1), dim3(256), 0, st, f->sq_part, f->stat_acc, count, p->red);
-    else hipLaunchKernelGGL(ppo_full_final_kernel<kStatN>, dim3(1), dim3(256), 0, st, f->sq_part, f->stat_acc, count, p->red);
+    hipLaunchKernelGGL((ppo_reduce_kernel<kBackBlob, kFullBlob>), dim3(kSqBlocks), dim3(256), 0, st, f->partials, groups, f->gacc, (float)count, p->grad, f->sq_part);
+    hipLaunchKernelGGL(ppo_full_final_kernel<NS>, dim3(1), dim3(256), 0, st, f->sq_part, f->stat_acc, count, p->red);
     HIP_TRY(hipGetLastError());
     return CRL_OK;
+}
+
+int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, const PpoTeacherDev *t,
+                  hipStream_t st) {
+    return t ? full_grad<true>(p, view, idx_dev, count, PpoHyperTeacher{h, *t}, st) : full_grad<false>(p, view, idx_dev, count, h, st);
 }
 
 static void ppo_full_pack(float *blob, const float *const t[10]) {
@@ -704,17 +656,10 @@ int crl_ppo_set_weights_full(crl_ppo *p, const float *conv1_w, const float *conv
     if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !conv3_w || !conv3_b || !actor_w || !actor_b || !critic_w || !critic_b)
         return crl_fail(CRL_EINVAL, "crl_ppo_set_weights_full: null argument (a learner needs its critic)");
     if (!p->full) return crl_fail(CRL_EINVAL, "crl_ppo_set_weights_full: a LightActorCritic learner (crl_ppo_set_weights)");
-    HIP_TRY(hipSetDevice(p->device));
     std::vector<float> blob(kFullBlob);
     const float *const t[10] = {conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, actor_w, actor_b, critic_w, critic_b};
     ppo_full_pack(blob.data(), t);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(p->raw, blob.data(), (size_t)kFullBlob * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(p->m, 0, (size_t)kFullBlob * sizeof(float)));
-    HIP_TRY(hipMemset(p->v, 0, (size_t)kFullBlob * sizeof(float)));
-    HIP_TRY(hipDeviceSynchronize());
-    p->steps = 0;
-    return CRL_OK;
+    return ppo_upload(p, blob.data());
 }
 
 int crl_ppo_create_full(int32_t device, int64_t scratch_rows, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b,
@@ -728,22 +673,15 @@ int crl_ppo_create_full(int32_t device, int64_t scratch_rows, const float *conv1
         return crl_fail(CRL_EINVAL, "crl_ppo_create_full: scratch_rows must be 0 (%lld) or in [%lld, %lld], not %lld", (long long)kDefaultRows, (long long)kMinRows,
                         (long long)kMaxRows,
                         (long long)scratch_rows);
-    if (policy_full_blob_floats() + policy_full_critic_floats() != kFullBlob || policy_full_act2_floats() != kK3 || policy_full_feat_floats() != kC3)
-        return crl_fail(CRL_EINVAL, "crl_ppo_create_full: the learner's blob is not the served policy's");
     HIP_TRY(hipSetDevice(device));
     crl_ppo *p = new crl_ppo();
     PpoFull *f = p->full = new PpoFull();
-    p->device = device, p->blob_floats = kFullBlob;
+    p->device = device;
     const int64_t S = f->scratch_rows = scratch_rows ? scratch_rows : kDefaultRows;
     if (hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || f->cus <= 0) f->cus = 256;
     const char *who = "crl_ppo_create_full";
-    const size_t blob = (size_t)kFullBlob * sizeof(float);
-    int rc = crl_dev_zalloc(&p->raw, blob, who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->m, blob, who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->v, blob, who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->grad, blob, who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->gacc, blob, who);
+    int rc = ppo_alloc_blobs(p, kFullBlob, who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&f->gacc, (size_t)kFullBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->act2, (size_t)S * kK3 * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->a3, (size_t)S * kC3 * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->dz3, (size_t)S * kC3 * sizeof(float), who);
@@ -774,10 +712,8 @@ int crl_ppo_get_weights_full(crl_ppo *p, float *conv1_w, float *conv1_b, float *
     if (!p || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !conv3_w || !conv3_b || !actor_w || !actor_b || !critic_w || !critic_b)
         return crl_fail(CRL_EINVAL, "crl_ppo_get_weights_full: null argument");
     if (!p->full) return crl_fail(CRL_EINVAL, "crl_ppo_get_weights_full: a LightActorCritic learner (crl_ppo_get_weights)");
-    HIP_TRY(hipSetDevice(p->device));
     std::vector<float> blob(kFullBlob);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(blob.data(), p->raw, (size_t)kFullBlob * sizeof(float), hipMemcpyDeviceToHost));
+    if (int rc = ppo_download(p, blob.data())) return rc;
     memcpy(conv1_w, &blob[kOffW1], 1024 * 4), memcpy(conv1_b, &blob[kOffB1], 16 * 4), memcpy(conv2_w, &blob[kOffW2], (size_t)kC2 * 256 * 4);
     memcpy(conv2_b, &blob[kOffB2], kC2 * 4), memcpy(conv3_w, &blob[kOffW3], (size_t)kC3 * kK3 * 4), memcpy(conv3_b, &blob[kOffB3], kC3 * 4);
     memcpy(actor_w, &blob[kOffWa], (size_t)3 * kC3 * 4), memcpy(actor_b, &blob[kOffBa], 3 * 4), memcpy(critic_w, &blob[kOffWc], kC3 * 4);
