@@ -379,6 +379,12 @@ __device__ __forceinline__ void car_obs_third(const CarSoA &s, uint8_t *__restri
     const int lane = threadIdx.x & 63;
     const int64_t t = env * s.players + viewer;
     const int dx00 = vp[0], dy00 = vp[1], isin = vp[2], icos = vp[3], rx = vp[4], ry = vp[5], flags = vp[6];
+    // (the indicator rectangles are read here, with the view's other words, and not where they are painted: read behind the gather, the
+    // upper thirds' wavefronts waited for them -- the big launch 267-273 us against the parent's 255-262; read here 256-260 against 250-256,
+    // five alternating pairs each, docs/LAB_NOTES_car_obs_edges.md)
+    uint32_t rects[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) rects[r] = reinterpret_cast<const uint32_t *>(vp)[8 + r];
     const int r0 = 32 * third;
     const uint8_t *map = env_map(s, env);
     uint8_t *tile8 = reinterpret_cast<uint8_t *>(tile);
@@ -406,13 +412,15 @@ __device__ __forceinline__ void car_obs_third(const CarSoA &s, uint8_t *__restri
             for (int x = xl; x <= xr; x++) tile8[y * (kPitch * 4) + x] = (uint8_t)gray;
         }
     }
-    if (third == 2) {  // (the indicator strip and the read-out live in rows 86 .. 95)
-        const uint32_t *rects = reinterpret_cast<const uint32_t *>(vp) + 8;
+    // ---- indicator bars: the rows of each rectangle that fall into this third.  The strip lives in rows 86 .. 95, but a bar grows with
+    // its input (a wheel beyond +-1250 rad/s, a speed above 625: above row 64), and every form must draw one state the same way.
+    // The eight words are wavefront-uniform: the upper thirds skip them with scalar compares.
+    {
         const int rgray[8] = {0, G_BLUE, G_BLUE, G_BLUE, G_ABS_REAR, G_ABS_REAR, G_GREEN, G_RED};
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const uint32_t q = rects[r];
-            const int x0 = (int)(q & 0xFFu), x1 = (int)((q >> 8) & 0xFFu), y0 = max((int)((q >> 16) & 0xFFu), r0), y1 = (int)(q >> 24);
+            const int x0 = (int)(q & 0xFFu), x1 = (int)((q >> 8) & 0xFFu), y0 = max((int)((q >> 16) & 0xFFu), r0), y1 = min((int)(q >> 24), r0 + 31);
             const int w = x1 - x0 + 1, h = y1 - y0 + 1;
             if (w <= 0 || h <= 0) continue;
             for (int p = lane; p < w * h; p += 64) {
@@ -420,6 +428,8 @@ __device__ __forceinline__ void car_obs_third(const CarSoA &s, uint8_t *__restri
                 tile8[(y0 - r0 + yy) * (kPitch * 4) + x0 + xx] = (uint8_t)rgray[r];
             }
         }
+    }
+    if (third == 2) {  // (the read-out lives in rows 91 .. 95)
         if (s.text_bits && lane < 32) {
             const double rw = s.reward[(int64_t)viewer * s.n + env];
             const double rr = rint(rw);  // "%.0f" rounds half to even
