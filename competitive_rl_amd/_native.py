@@ -30,6 +30,8 @@ CRL_ARENA_DOMAIN_PAIR = 0x4C475550
 CRL_CAR_DRIVER_DOMAIN = 0x43524430  # "CRD0": car c draws under CRL_CAR_DRIVER_DOMAIN + c (include/crl.h "car drivers")
 CRL_CAR_DRIVER_RANDOM, CRL_CAR_DRIVER_RULE_BASED = 0, 1
 CRL_CAR_DRIVER_SLOTS = 16
+CRL_CAR_POLICY_DOMAIN = 0x43525030  # "CRP0": car c draws under CRL_CAR_POLICY_DOMAIN + c (include/crl.h "car policy")
+CRL_CAR_POLICY_SLOTS, CRL_CAR_OBS_FEATURES, CRL_CAR_POLICY_HIDDEN, CRL_CAR_POLICY_BLOB_FLOATS = 8, 21, 100, 2508
 CRL_ARENA_COUNTERS = 6  # planes of the counters tensor, in this order (enum crl_arena_counter); each plane is [left][right]
 CRL_ARENA_COUNTER_NAMES = ("episodes", "left_wins", "right_wins", "draws", "return_sum", "length_sum")
 
@@ -232,6 +234,17 @@ SIGNATURES = {
     "crl_car_driver_act": (i32, [vp, vp, vp]),
     "crl_car_driver_get_counters": (i32, [vp, P(u64), P(i64)]),
     "crl_car_driver_set_counters": (i32, [vp, u64, i64]),
+    "crl_car_policy_create": (i32, [vp, u64, P(vp)]),
+    "crl_car_policy_destroy": (None, [vp]),
+    "crl_car_policy_set_weights": (i32, [vp, i32, vp, i32, vp]),
+    "crl_car_policy_get_weights": (i32, [vp, i32, vp, P(i32), vp]),
+    "crl_car_policy_set_sampling": (i32, [vp, i32, i32]),
+    "crl_car_policy_set_assignment": (i32, [vp, vp, vp]),
+    "crl_car_policy_get_assignment": (i32, [vp, vp, vp]),
+    "crl_car_policy_act": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "crl_car_policy_observe": (i32, [vp, vp, vp]),
+    "crl_car_policy_get_counters": (i32, [vp, P(u64), P(i64)]),
+    "crl_car_policy_set_counters": (i32, [vp, u64, i64]),
     "crl_rule_labels": (i32, [vp, i32, vp, i64, vp]),
     "crl_ppo_grad_teacher": (i32, [vp, vp, vp, i64, vp, vp, vp]),
     "crl_ppo_teacher_stats": (i32, [vp, P(f64)]),

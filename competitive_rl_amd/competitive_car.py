@@ -16,12 +16,17 @@ forwarded to the envs.
 ``opponent_policy`` may also be the NAME of a built-in driver (``get_builtin_car_driver_names()``: "RANDOM", "RULE_BASED") or of a style
 given in ``styles``: car 1 is then driven by ``CarDrivers.act`` on the device from the env's own state, with the same timing -- its action
 for step t + 1 is formed right after step t (or after the reset) -- and nothing touches the host.
+
+It may also be the weights of a learned driver -- a dict (a torch ``MLP(21, 2)`` state dict as it is) or the path of a checkpoint file,
+whatever ``CarPolicy.add_network`` takes: car 1 is then driven by ``CarPolicy.act`` with them, deterministically, with that timing.
 """
 import numpy as np
 import torch
 
 from . import spaces
 from .car_drivers import CarDrivers
+from .car_policy import CarPolicy, is_car_policy_weights
+from .rules import CAR_DRIVER_KINDS
 from .vec_env import VecEnv, _EnvList
 from .vec_env_car import HipCarVecEnv
 
@@ -54,7 +59,7 @@ class _Agent0Infos:
 class HipCompetitiveCarVecEnv(VecEnv):
     def __init__(self, opponent_policy, num_envs, seed=0, frame_stack=4, dones="dummy", batched=False, device=None, output="torch",
                  env_id_base=0, styles=None):
-        assert callable(opponent_policy) or isinstance(opponent_policy, str)
+        assert callable(opponent_policy) or isinstance(opponent_policy, str) or is_car_policy_weights(opponent_policy)
         self.opponent_policy, self.batched = opponent_policy, bool(batched)
         self.env = HipCarVecEnv(num_envs, seed=seed, device=device, env_id_base=env_id_base, output="torch", dones=dones,
                                 action_repeat=None, frame_stack=frame_stack, players=2, done_policy="car0")
@@ -65,8 +70,13 @@ class HipCompetitiveCarVecEnv(VecEnv):
         self._act = torch.zeros((num_envs, 2, 2), dtype=torch.float32, device=self.device)
         self.opponent_action = None
         self.envs = _EnvList(self)
-        self.drivers = None
-        if isinstance(opponent_policy, str):  # a built-in driver: served on the device, keyed by the env's seed
+        self.drivers = self.policy = None
+        known = tuple(styles or {}) + CAR_DRIVER_KINDS  # (a name that is also a file's stays a name)
+        if is_car_policy_weights(opponent_policy) and opponent_policy not in known:  # a learned driver: its mean, served on the device
+            self.policy = CarPolicy(self.env, seed=seed)
+            self.policy.add_network("opponent", opponent_policy, deterministic=True)
+            self.policy.assign(1, "opponent")
+        elif isinstance(opponent_policy, str):  # a built-in driver: served on the device, keyed by the env's seed
             self.drivers = CarDrivers(self.env, seed=seed)
             for name, params in (styles or {}).items():
                 self.drivers.set_style(name, **params)
@@ -75,6 +85,9 @@ class HipCompetitiveCarVecEnv(VecEnv):
     def _opponent(self, obs):
         if self.drivers is not None:  # car 1's rows of the action tensor, filled in place from the state the call before committed
             self.drivers.act(self._act)
+            return
+        if self.policy is not None:
+            self.policy.act(self._act)
             return
         theirs = obs[:, self.K:]
         if self.batched:
@@ -96,7 +109,7 @@ class HipCompetitiveCarVecEnv(VecEnv):
     def step_async(self, actions):
         a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float32))
         self._act[:, 0] = a.to(self.device, torch.float32).reshape(self.num_envs, -1)[:, :2]
-        if self.drivers is None:
+        if self.drivers is None and self.policy is None:
             self._act[:, 1] = self.opponent_action
 
     def step_wait(self):
@@ -109,8 +122,9 @@ class HipCompetitiveCarVecEnv(VecEnv):
         return self.env.seed(seed)
 
     def close(self):
-        if self.drivers is not None:
-            self.drivers.close()
+        for server in (self.drivers, self.policy):
+            if server is not None:
+                server.close()
         self.env.close()
 
     def get_attr(self, attr_name, indices=None):
@@ -128,7 +142,7 @@ class HipCompetitiveCarVecEnv(VecEnv):
 
 def make_competitive_car_racing(opponent_policy, seed=0, num_envs=3, asynchronous=False, frame_stack=4, action_repeat=None, *,
                                 batched=False, device=None, output="torch", env_id_base=0, styles=None):
-    assert callable(opponent_policy) or isinstance(opponent_policy, str)
+    assert callable(opponent_policy) or isinstance(opponent_policy, str) or is_car_policy_weights(opponent_policy)
     asynchronous = asynchronous and num_envs > 1
     return HipCompetitiveCarVecEnv(opponent_policy, num_envs, seed=seed, frame_stack=frame_stack,
                                    dones="subproc" if asynchronous else "dummy", batched=batched, device=device, output=output,

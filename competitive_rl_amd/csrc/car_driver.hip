@@ -7,13 +7,12 @@
 // the reference ships none) and is CarRacing's counterpart of pong/builtin_policies.py:44-58.
 //
 // One launch per act call: ONE WAVEFRONT PER ENV.  The 64 lanes walk the env's n <= 512 boxes of tile_aabb_em ([n][512] float4: 16
-// bytes per lane, 1 KiB per load, at most 8 loads), each box read once for both cars; every lane keeps the smallest (distance, index)
-// per car as one 64-bit key -- the distance's bit pattern above the index: distances are >= +0 or +inf, so the keys order as the rule
-// does, the lowest index among equals included -- and six butterfly steps of cross-lane moves give every lane the wave's minimum.  No LDS,
-// no barrier.  What follows the search is wave-uniform arithmetic; lane 0 stores the car's two floats.
+// bytes per lane, 1 KiB per load, at most 8 loads), each box read once for both cars (car_search.h: car_nearest2).  No LDS, no barrier.
+// What follows the search is wave-uniform arithmetic; lane 0 stores the car's two floats.
 #include <math.h>
 
 #include "car_device.h"
+#include "car_search.h"
 #include "crl_internal.h"
 
 #pragma clang fp contract(off)
@@ -43,29 +42,8 @@ struct DriverArgs {
     DriverStyle style[CRL_CAR_DRIVER_SLOTS];
 };
 
-// the generator of "league draws" (pong_device.h, car_track.hip)
-__device__ inline void driver_philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0, c[1] = n1, c[2] = n2, c[3] = n3;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-}
-
 __device__ inline float driver_unit(uint32_t x) { return (float)((int32_t)(x >> 8) - 8388608) * 0x1p-23f; }
 __device__ inline float driver_clamp(float x) { return x < -1.0f ? -1.0f : x > 1.0f ? 1.0f : x; }
-
-__device__ inline uint64_t wave_min_u64(uint64_t k) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), m, 64), lo = (uint32_t)__shfl_xor((int)(uint32_t)k, m, 64);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        k = o < k ? o : k;
-    }
-    return k;
-}
 
 static constexpr int kDriverWaves = 4;  // envs per workgroup
 
@@ -141,23 +119,7 @@ __global__ __launch_bounds__(64 * kDriverWaves) void car_driver_kernel(const Dri
     // rule 2: the nearest tile of each car that needs one
     int near0 = 0, near1 = 0;
     const float4 *__restrict__ boxes = A.tile_aabb_em + env * kCarMaxTiles;
-    if (P0.search || P1.search) {
-        uint64_t best0 = ~0ull, best1 = ~0ull;
-        for (int t = lane; t < n; t += 64) {
-            const float4 b = boxes[t];
-            const float tx = (b.x + b.z) * 0.5f, ty = (b.y + b.w) * 0.5f;
-            const float dx0 = tx - P0.cx, dy0 = ty - P0.cy, dx1 = tx - P1.cx, dy1 = ty - P1.cy;
-            float d0 = dx0 * dx0 + dy0 * dy0, d1 = dx1 * dx1 + dy1 * dy1;
-            if (!(d0 == d0)) d0 = INFINITY;
-            if (!(d1 == d1)) d1 = INFINITY;
-            const uint64_t k0 = ((uint64_t)__float_as_uint(d0) << 32) | (uint32_t)t, k1 = ((uint64_t)__float_as_uint(d1) << 32) | (uint32_t)t;
-            best0 = k0 < best0 ? k0 : best0;
-            best1 = k1 < best1 ? k1 : best1;
-        }
-        near0 = (int)(uint32_t)wave_min_u64(best0), near1 = (int)(uint32_t)wave_min_u64(best1);
-        near0 = (near0 >= 0 && near0 < n) ? near0 : 0;
-        near1 = (near1 >= 0 && near1 < n) ? near1 : 0;
-    }
+    if (P0.search || P1.search) car_nearest2(boxes, n, lane, P0.cx, P0.cy, P1.cx, P1.cy, near0, near1);
     driver_finish(A, P0, env, n, 0, near0, boxes, lane, actions);
     driver_finish(A, P1, env, n, 1, near1, boxes, lane, actions);
 }

@@ -446,3 +446,235 @@ def car_driver_reference(hull, wheels, done, boxes, n, style, seed, gid, car, ca
     ruled = np.stack([steer, gas], axis=1).astype(f)
     out[live] = np.where(explore[:, None], rnd, ruled)[live]
     return out
+
+
+# ---- include/crl.h "car policy": the state observation, the reference's MLP on it and the Gaussian draw
+CAR_OBS_FEATURES = N.CRL_CAR_OBS_FEATURES
+CAR_OBS_SPEED_SCALE, CAR_OBS_DIST_SCALE = 2.0 ** -6, 2.0 ** -5  # CRL_CAR_OBS_SPEED_SCALE, CRL_CAR_OBS_DIST_SCALE
+CAR_OBS_OFFSETS = (0, 2, 4, 8, 16)  # tiles ahead of the nearest one whose centres features 6..15 hold
+CAR_POLICY_HIDDEN = N.CRL_CAR_POLICY_HIDDEN
+CAR_POLICY_SHAPES = dict(fc1_w=(CAR_POLICY_HIDDEN, CAR_OBS_FEATURES), fc1_b=(CAR_POLICY_HIDDEN,), policy_w=(2, CAR_POLICY_HIDDEN), policy_b=(2,),
+                         value_w=(1, CAR_POLICY_HIDDEN), value_b=(1,), log_std=(2,))
+CAR_POLICY_KEYS = tuple(CAR_POLICY_SHAPES)
+_CAR_POLICY_TORCH_KEYS = {"fc1.weight": "fc1_w", "fc1.bias": "fc1_b", "policy.weight": "policy_w", "policy.bias": "policy_b",
+                          "value.weight": "value_w", "value.bias": "value_b"}
+CAR_POLICY_TWO_PI = np.float32(2 * np.pi)        # CRL_CAR_POLICY_TWO_PI
+CAR_POLICY_LN_2PI = np.float32(np.log(2 * np.pi))  # CRL_CAR_POLICY_LN_2PI
+
+
+def car_policy_weights(weights):
+    """The seven arrays of ``CAR_POLICY_KEYS`` as float32, from a dict under those keys or under the keys of a torch ``MLP(21, 2)``
+    state dict (``fc1.weight``, ``policy.bias``, ...; numpy arrays or torch tensors), or from the path of a checkpoint holding one
+    (``.npz``, or anything ``torch.load`` reads; a ``{"model": state_dict}`` wrapping is looked through).  ``log_std`` is 0 where it is
+    missing.  A missing key, a wrong shape or a value that is not finite raises ``ValueError``."""
+    import os
+
+    if isinstance(weights, (str, os.PathLike)):
+        path = os.fspath(weights)
+        if path.endswith(".npz"):
+            with np.load(path) as z:
+                weights = {k: z[k] for k in z.files}
+        else:
+            import torch
+
+            weights = torch.load(path, map_location="cpu")
+            if isinstance(weights, dict) and isinstance(weights.get("model"), dict):
+                weights = weights["model"]
+    if not isinstance(weights, dict):
+        raise ValueError(f"car policy weights: a dict or a checkpoint path is needed, not {type(weights).__name__}")
+    out = {}
+    for k, v in weights.items():
+        k = _CAR_POLICY_TORCH_KEYS.get(k, k)
+        if k in CAR_POLICY_SHAPES:
+            v = v.detach().cpu().numpy() if hasattr(v, "detach") else v
+            out[k] = np.ascontiguousarray(v, np.float32)
+    out.setdefault("log_std", np.zeros(2, np.float32))
+    for k, s in CAR_POLICY_SHAPES.items():
+        if k not in out:
+            raise ValueError(f"car policy weights: {k} is missing")
+        if out[k].shape != s:
+            raise ValueError(f"car policy weights: {k} has shape {out[k].shape}, the MLP's is {s}")
+        if not np.isfinite(out[k]).all():
+            raise ValueError(f"car policy weights: {k} holds values that are not finite")
+    return {k: out[k] for k in CAR_POLICY_KEYS}
+
+
+def car_policy_pack(weights):
+    """A slot's blob (include/crl.h "car policy": CRL_CAR_POLICY_BLOB_FLOATS float32) from anything ``car_policy_weights`` takes:
+    fc1_w transposed, fc1_b, policy_w, value_w, then policy_b, value_b, log_std, std = float32(exp(float64(log_std))) and a pad."""
+    w = car_policy_weights(weights)
+    std = np.exp(w["log_std"].astype(np.float64)).astype(np.float32)
+    blob = np.concatenate([w["fc1_w"].T.reshape(-1), w["fc1_b"], w["policy_w"].reshape(-1), w["value_w"].reshape(-1), w["policy_b"],
+                           w["value_b"], w["log_std"], std, np.zeros(1, np.float32)]).astype(np.float32)
+    assert blob.size == N.CRL_CAR_POLICY_BLOB_FLOATS
+    return blob
+
+
+def car_policy_unpack(blob):
+    """The seven arrays of a blob in torch layout (copies)."""
+    b = np.asarray(blob, np.float32).reshape(-1)
+    if b.size != N.CRL_CAR_POLICY_BLOB_FLOATS:
+        raise ValueError(f"a car policy blob has {N.CRL_CAR_POLICY_BLOB_FLOATS} floats, not {b.size}")
+    H, K = CAR_POLICY_HIDDEN, CAR_OBS_FEATURES
+    t = K * H + 4 * H
+    return dict(fc1_w=b[:K * H].reshape(K, H).T.copy(), fc1_b=b[K * H:K * H + H].copy(), policy_w=b[K * H + H:K * H + 3 * H].reshape(2, H).copy(),
+                policy_b=b[t:t + 2].copy(), value_w=b[K * H + 3 * H:t].reshape(1, H).copy(), value_b=b[t + 2:t + 3].copy(), log_std=b[t + 3:t + 5].copy())
+
+
+def car_obs_reference(hull, wheels, done, visited_count, touch, boxes, n, other_hull=None, other_done=None):
+    """The observation of include/crl.h "car policy" in numpy float32, one rounding per operation, bit for bit what
+    ``car_policy_kernel`` writes for one car of E envs:
+      hull           float32 [E, 6]     the car's hull body: cx, cy, a, vx, vy, w
+      wheels         float32 [E, 4, 3]  its wheel bodies 0..3: cx, cy, a
+      done           [E]                its done flag
+      visited_count  int [E]            tiles it has visited
+      touch          bool [E, 4]        wheel k touches at least one tile
+      boxes, n                          as ``car_driver_reference`` takes them
+      other_hull, other_done            the other car's hull [E, 6] and done flag [E]; None for players == 1
+    Returns float32 [E, 21].  Host code for tests and for driving the CPU checker; the kernels do not use it."""
+    f = np.float32
+    hull, wheels, boxes = np.asarray(hull, f), np.asarray(wheels, f), np.asarray(boxes, f)
+    E = hull.shape[0]
+    if hull.shape != (E, 6) or wheels.shape != (E, 4, 3) or boxes.ndim != 3 or boxes.shape[0] != E or boxes.shape[2] != 4:
+        raise ValueError("hull [E, 6], wheels [E, 4, 3], boxes [E, T, 4]")
+    n = np.broadcast_to(np.asarray(n, np.int64), (E,))
+    done = np.broadcast_to(np.asarray(done), (E,)) != 0
+    touch = np.asarray(touch).reshape(E, 4) != 0
+    visited = np.broadcast_to(np.asarray(visited_count, np.int64), (E,))
+    if n.max(initial=0) > boxes.shape[1]:
+        raise ValueError("n exceeds the rows of boxes")
+    half, one, zero = f(0.5), f(1), f(0)
+    speed, dist = f(CAR_OBS_SPEED_SCALE), f(CAR_OBS_DIST_SCALE)
+    x = np.zeros((E, CAR_OBS_FEATURES), f)
+    with np.errstate(all="ignore"):
+        live = ~done & (n > 0)
+        nn = np.maximum(n, 1)
+        cx, cy, a, vx, vy, w = (hull[:, k] for k in range(6))
+        hx = (wheels[:, 0, 0] + wheels[:, 1, 0]) * half - (wheels[:, 2, 0] + wheels[:, 3, 0]) * half
+        hy = (wheels[:, 0, 1] + wheels[:, 1, 1]) * half - (wheels[:, 2, 1] + wheels[:, 3, 1]) * half
+        length = np.sqrt(hx * hx + hy * hy)
+        ok = length > zero
+        safe = np.where(ok, length, one)
+        fx, fy = np.where(ok, hx / safe, one).astype(f), np.where(ok, hy / safe, zero).astype(f)
+        lx, ly = -fy, fx
+
+        def frame(px, py, k, scale):
+            x[:, k], x[:, k + 1] = (px * fx + py * fy) * scale, (px * lx + py * ly) * scale
+
+        frame(vx, vy, 0, speed)
+        x[:, 2] = w * f(0.25)
+        x[:, 3] = (wheels[:, 0, 2] - a) * f(2)
+        x[:, 4] = touch.sum(axis=1).astype(f) * f(0.25)
+        x[:, 5] = visited.astype(f) / nn.astype(f)
+        tx = (boxes[..., 0] + boxes[..., 2]) * half
+        ty = (boxes[..., 1] + boxes[..., 3]) * half
+        dx, dy = tx - cx[:, None], ty - cy[:, None]
+        d2 = dx * dx + dy * dy
+        d2 = np.where(d2 == d2, d2, f(np.inf))
+        d2 = np.where(np.arange(boxes.shape[1])[None, :] < nn[:, None], d2, f(np.inf))
+        near = np.argmin(d2, axis=1)  # (the first index among equals)
+        rows = np.arange(E)
+        for m, o in enumerate(CAR_OBS_OFFSETS):
+            g = (near + o) % nn
+            frame(tx[rows, g] - cx, ty[rows, g] - cy, 6 + 2 * m, dist)
+        if other_hull is not None:
+            oh = np.asarray(other_hull, f)
+            if oh.shape != (E, 6):
+                raise ValueError("other_hull [E, 6]")
+            frame(oh[:, 0] - cx, oh[:, 1] - cy, 16, dist)
+            frame(oh[:, 3] - vx, oh[:, 4] - vy, 18, speed)
+            x[:, 20] = np.where(np.broadcast_to(np.asarray(other_done), (E,)) != 0, zero, one)
+    x[~live] = 0
+    return x
+
+
+def car_mlp_reference(weights, obs):
+    """Mean and value of the MLP of include/crl.h "car policy" on observations float32 [E, 21], in numpy float32 with the header's
+    summation shape -- bit for bit the kernel's.  Returns (mean float32 [E, 2], value float32 [E])."""
+    f = np.float32
+    w = car_policy_weights(weights)
+    x = np.asarray(obs, f)
+    E = x.shape[0]
+    if x.shape != (E, CAR_OBS_FEATURES):
+        raise ValueError(f"obs [E, {CAR_OBS_FEATURES}]")
+    H, second = CAR_POLICY_HIDDEN, CAR_POLICY_HIDDEN - 64
+    with np.errstate(all="ignore"):
+        a = np.broadcast_to(w["fc1_b"], (E, H)).astype(f)
+        for k in range(CAR_OBS_FEATURES):
+            a = a + w["fc1_w"][None, :, k] * x[:, k, None]
+        h = np.where(a > 0, a, f(0)).astype(f)
+        lanes = np.arange(64)
+        outs = []
+        for r, b in ((w["policy_w"][0], w["policy_b"][0]), (w["policy_w"][1], w["policy_b"][1]), (w["value_w"][0], w["value_b"][0])):
+            p = h[:, :64] * r[None, :64]
+            p[:, :second] = p[:, :second] + h[:, 64:] * r[None, 64:]
+            for m in (32, 16, 8, 4, 2, 1):
+                p = p + p[:, lanes ^ m]
+            outs.append(p[:, 0] + b)
+    return np.stack(outs[:2], axis=1).astype(f), outs[2].astype(f)
+
+
+def car_policy_draws(seed, gid, car, call):
+    """The Philox call of "car policy": as ``car_driver_draws`` under CRL_CAR_POLICY_DOMAIN + car."""
+    return _philox4x32_10(gid, call, N.CRL_CAR_POLICY_DOMAIN + int(car), seed)
+
+
+def car_policy_uniforms(x):
+    """(u1 [E, 2] in (0, 1], u2 [E, 2] in [0, 1)) of the four words of ``car_policy_draws``: float32, every step exact."""
+    q = [(np.asarray(w, np.uint64) >> np.uint64(8)).astype(np.int64) for w in x]
+    s = np.float32(2.0 ** -24)
+    return (np.stack([(q[0] + 1).astype(np.float32) * s, (q[2] + 1).astype(np.float32) * s], axis=-1),
+            np.stack([q[1].astype(np.float32) * s, q[3].astype(np.float32) * s], axis=-1))
+
+
+def car_policy_noise(seed, gid, car, call):
+    """z float32 [E, 2] of "car policy": Box-Muller of the uniforms in float32, with the float64 logarithm and the float64 cosine of
+    the float32 argument each rounded to float32 (the device takes its library's logf, within 1 ulp, and crl_sincosf): z agrees with
+    the device's within the header's bound, not bit for bit."""
+    f = np.float32
+    u1, u2 = car_policy_uniforms(car_policy_draws(seed, gid, car, call))
+    with np.errstate(all="ignore"):
+        L = np.log(u1.astype(np.float64)).astype(f)
+        r = np.sqrt(f(-2) * L)
+        t = CAR_POLICY_TWO_PI * u2
+        return (r * np.cos(t.astype(np.float64)).astype(f)).astype(f)
+
+
+def car_policy_noise_bound(seed, gid, car, call):
+    """(Z float64 [E, 2], bound float64 [E, 2]): Box-Muller of the same uniforms in float64 and the header's bound on
+    |z - Z| = R * 2^-23 * (2 pi + 2), R = sqrt(-2 ln u1)."""
+    u1, u2 = car_policy_uniforms(car_policy_draws(seed, gid, car, call))
+    R = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    return R * np.cos(2 * np.pi * u2.astype(np.float64)), R * 2.0 ** -23 * (2 * np.pi + 2)
+
+
+def car_policy_sample(mean, log_std, z):
+    """(u float32 [E, 2], log_prob float32 [E]) of a sampling slot given its noise z, in the header's written order."""
+    f = np.float32
+    mean, z, ls = np.asarray(mean, f), np.asarray(z, f), np.asarray(log_std, f).reshape(2)
+    std = np.exp(ls.astype(np.float64)).astype(f)
+    with np.errstate(all="ignore"):
+        u = mean + std[None, :] * z
+        t = [(f(-0.5) * z[:, d]) * z[:, d] - ls[d] for d in range(2)]
+        return u.astype(f), ((t[0] + t[1]) - CAR_POLICY_LN_2PI).astype(f)
+
+
+def car_policy_reference(weights, obs, live, deterministic, seed=0, gid=0, car=0, call=0, z=None):
+    """What ``crl_car_policy_act`` writes for one served car of E envs: a dict ``u`` [E, 2], ``value`` [E], ``log_prob`` [E], ``z``
+    [E, 2], ``mean`` [E, 2].  ``obs`` as ``car_obs_reference`` returns it, ``live`` [E] = not done and n > 0 (the others get zeros);
+    ``z``: the noise to use in place of ``car_policy_noise`` (the device's own, for a bit-for-bit comparison of u and log_prob)."""
+    f = np.float32
+    w = car_policy_weights(weights)
+    mean, value = car_mlp_reference(w, obs)
+    E = mean.shape[0]
+    live = np.broadcast_to(np.asarray(live, bool), (E,))
+    if deterministic:
+        u, lp, z = mean.copy(), np.zeros(E, f), np.zeros((E, 2), f)
+    else:
+        gid = np.broadcast_to(np.asarray(gid, np.uint64), (E,))
+        z = car_policy_noise(seed, gid, car, np.broadcast_to(np.asarray(call, np.uint64), (E,))) if z is None else np.asarray(z, f).copy()
+        u, lp = car_policy_sample(mean, w["log_std"], z)
+    out = dict(u=u, value=value.copy(), log_prob=lp, z=z, mean=mean)
+    for k in ("u", "value", "log_prob", "z"):
+        out[k][~live] = 0
+    return out

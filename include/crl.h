@@ -1202,6 +1202,105 @@ int crl_car_driver_act(crl_car_driver *d, float *actions_dev, void *stream);
 int crl_car_driver_get_counters(crl_car_driver *d, uint64_t *seed, int64_t *calls);
 int crl_car_driver_set_counters(crl_car_driver *d, uint64_t seed, int64_t calls);
 
+/* ---- car policy: a state observation and the reference's MLP, served per env and per car ---------
+ * What "serve a learner" is for Pong, for CarRacing: the reference's MLP(input_size, output_size) (utils/network.py:59-70: fc1 -> 100,
+ * ReLU, policy, value) on a per-car STATE observation computed from the context's committed state, served per env and per car from
+ * CRL_CAR_POLICY_SLOTS weight sets, with Gaussian actions, values and log-probabilities for a trainer.  An object beside a CarRacing
+ * context, as the car drivers are: it READS the state and writes the caller's tensors.  One launch per crl_car_policy_act /
+ * _observe on the caller's stream; nothing synchronises with the host.  rules.car_obs_reference, rules.car_mlp_reference and
+ * rules.car_policy_reference (with car_policy_noise and car_policy_sample) restate this section in numpy.
+ *
+ * As in "car drivers": everything is float32 with ONE rounding per operation, no contraction, no fast-math intrinsic, / and sqrt
+ * correctly rounded; every sum has two terms or the shape written here.
+ * Inputs of car c of env i: its hull body (cx, cy, a, vx, vy, w); its wheel bodies k = 0..3 (wx_k, wy_k, wa_k; 0, 1 front, 2, 3 rear);
+ * its done flag and visited_count; touch_k = wheel k touches at least one tile; the env's tile count n and tile boxes; for
+ * players == 2 the other car's hull (ocx, ocy, ovx, ovy) and done flag.
+ *
+ * Observation: CRL_CAR_OBS_FEATURES = 21 float32.  done != 0 or n <= 0: all 21 are +0 and nothing below is evaluated.  Otherwise
+ *   frame: (hx, hy) exactly as rule 4 of "car drivers";  len = sqrt((hx * hx) + (hy * hy));  forward f = (hx / len, hy / len) if
+ *     len > 0, otherwise (zero, or NaN) (1, 0);  left l = (-f.y, f.x);  car(v) = ((v.x * f.x) + (v.y * f.y), (v.x * l.x) + (v.y * l.y)).
+ *   [0], [1]   car((vx, vy)) * CRL_CAR_OBS_SPEED_SCALE, componentwise
+ *   [2]        w * 2^-2
+ *   [3]        (wa_0 - a) * 2
+ *   [4]        (the number of k with touch_k, as float32) * 0.25
+ *   [5]        float32(visited_count) / float32(n)
+ *   [6 + 2 m], [7 + 2 m], m = 0..4: with nearest = rule 2 of "car drivers" and o_m = (0, 2, 4, 8, 16)[m]: g = (nearest + o_m) mod n,
+ *              car((tx_g - cx, ty_g - cy)) * CRL_CAR_OBS_DIST_SCALE  (tx, ty: the box centres of rule 2)
+ *   [16], [17] car((ocx - cx, ocy - cy)) * CRL_CAR_OBS_DIST_SCALE
+ *   [18], [19] car((ovx - vx, ovy - vy)) * CRL_CAR_OBS_SPEED_SCALE
+ *   [20]       1 if the other car is not done, else 0
+ *   players == 1: [16..20] are +0.
+ * Every scale is a power of two: the scaling is exact.
+ *
+ * Network.  Weights of one slot: fc1_w (100, 21), fc1_b (100), policy_w (2, 100), policy_b (2), value_w (1, 100), value_b (1) -- the
+ * reference's MLP(21, 2) -- and log_std (2), which the reference's class lacks (0 where a checkpoint has none).  With x the observation:
+ *   hidden_j = relu(a_j), j < 100:  a_j starts as fc1_b[j]; then for k = 0, 1, .., 20 IN THIS ORDER a_j = a_j + (fc1_w[j][k] * x[k]);
+ *     relu(a) = a if a > 0, else +0.
+ *   each output o of (mean_0, mean_1, value), with row r_o = policy_w[0], policy_w[1], value_w[0] and bias policy_b[0], policy_b[1],
+ *     value_b[0]: the 64 partial sums p_L = hidden_L * r_o[L] for L < 64, and for L < 36 p_L = p_L + (hidden_{L+64} * r_o[L + 64]);
+ *     then the butterfly: for m = 32, 16, 8, 4, 2, 1 IN THIS ORDER every p_L = p_L + p_{L xor m} (all 64 at once; float addition
+ *     commutes, so all 64 hold the same bits);  o = p_0 + bias.
+ *   std_d = float32(exp(float64(log_std_d))), computed by whoever packs the blob, on the host: the kernel evaluates no exp.
+ * The blob of one slot, CRL_CAR_POLICY_BLOB_FLOATS float32: fc1_w TRANSPOSED [21][100] at 0 (a lane reads its hidden unit's weight
+ * of input k beside its neighbours'), fc1_b at 2100, policy_w [2][100] at 2200, value_w [100] at 2400, then at 2500: policy_b[0],
+ * policy_b[1], value_b[0], log_std_0, log_std_1, std_0, std_1, one pad.  rules.car_policy_pack / car_policy_unpack.
+ *
+ * Action.  The env clips actions itself (process_action, car_racing_multi_players.py:528-540): u is written unclipped.
+ *   done != 0 or n <= 0: u = (0, 0), value 0, log_prob 0, z = (0, 0).
+ *   deterministic slot: u = mean, log_prob = 0, z = (0, 0).
+ *   sampling slot: ONE call x = Philox4x32-10(counter = (gid & 0xFFFFFFFF, gid >> 32, call, CRL_CAR_POLICY_DOMAIN + c), key = (seed &
+ *     0xFFFFFFFF, seed >> 32)), gid and call as rule 1 of "car drivers" (call counts crl_car_policy_act calls; _observe does not move
+ *     it).  Component d = 0, 1 takes (x_{2d}, x_{2d+1}):
+ *       u1 = float32((x_{2d} >> 8) + 1) * 2^-24, in (0, 1], exact;   u2 = float32(x_{2d+1} >> 8) * 2^-24, in [0, 1), exact;
+ *       L = log(u1): a float32 natural logarithm with an error of at most 1 ulp (the kernel: the device library's logf; rules: the
+ *         float64 logarithm rounded to float32);   r = sqrt(-2 * L)  (-2 * L is exact);
+ *       t = CRL_CAR_POLICY_TWO_PI * u2;   cs = the cosine of include/crl_rot.h's crl_sincosf(t) (correctly rounded);   z_d = r * cs.
+ *     u_d = mean_d + (std_d * z_d);
+ *     log_prob = ((((-0.5 * z_0) * z_0) - log_std_0) + (((-0.5 * z_1) * z_1) - log_std_1)) - CRL_CAR_POLICY_LN_2PI.
+ *   Against Z_d = sqrt(-2 ln u1) cos(2 pi u2) in exact arithmetic, with R = sqrt(-2 ln u1) <= 5.77: 1 ulp of L and the square root's
+ *   rounding move r by at most R * 2^-23; the rounded 2 pi and the product move t by at most 2 pi * 2^-23, the cosine's rounding adds
+ *   2^-25; the last product adds R * 2^-24:  |z_d - Z_d| <= R * 2^-23 * (2 pi + 2)  (the 0.25 beyond 2 pi + 1.75 covers the
+ *   second-order terms).  Only z differs between evaluations of L; given z, u and log_prob follow bit for bit.
+ * A draw depends on (seed, global env id, car, call) alone and the rest on the env's state: shards act as the whole batch. */
+#define CRL_CAR_OBS_FEATURES 21
+#define CRL_CAR_OBS_SPEED_SCALE 0x1p-6f
+#define CRL_CAR_OBS_DIST_SCALE 0x1p-5f
+#define CRL_CAR_POLICY_SLOTS 8
+#define CRL_CAR_POLICY_HIDDEN 100
+#define CRL_CAR_POLICY_BLOB_FLOATS 2508
+#define CRL_CAR_POLICY_DOMAIN 0x43525030u /* "CRP0"; car 1 draws under "CRP1" */
+#define CRL_CAR_POLICY_TWO_PI 0x1.921fb6p+2f
+#define CRL_CAR_POLICY_LN_2PI 0x1.d67f1cp+0f /* float32(ln(2 pi)) */
+typedef struct crl_car_policy crl_car_policy;
+/* A policy server for the envs of CarRacing context `ctx`, which must outlive it; seed = the key of the draws.  Every slot is empty
+ * and every car unassigned (-1).  Refuses (CRL_EINVAL, before any GPU call) a null argument and a Pong context. */
+int crl_car_policy_create(crl_ctx *ctx, uint64_t seed, crl_car_policy **out);
+void crl_car_policy_destroy(crl_car_policy *p);
+/* The blob of slot `slot` (host or device memory, CRL_CAR_POLICY_BLOB_FLOATS floats), copied on `stream`: no device synchronisation,
+ * and launches enqueued on `stream` after this call see the new weights.  deterministic: 0 = sampling, 1 = u = mean; it holds for
+ * the launches enqueued after the call.  The argument checks are those of crl_car_driver_*: the values first (slot outside [0,
+ * CRL_CAR_POLICY_SLOTS), deterministic outside {0, 1}), then the handle and the pointer; CRL_EINVAL before any GPU call. */
+int crl_car_policy_set_weights(crl_car_policy *p, int32_t slot, const float *blob_host_or_dev, int32_t deterministic, void *stream);
+/* What the device holds: the blob (to host or device memory, on `stream`; the caller synchronises `stream` before reading a host
+ * buffer; optional) and the flag (optional).  An empty slot is refused. */
+int crl_car_policy_get_weights(crl_car_policy *p, int32_t slot, float *blob_out_host_or_dev, int32_t *deterministic_out, void *stream);
+/* The flag of a loaded slot alone (host value, no GPU call). */
+int crl_car_policy_set_sampling(crl_car_policy *p, int32_t slot, int32_t deterministic);
+/* int32 [N][players] on the device: the car's slot; a value outside [0, CRL_CAR_POLICY_SLOTS) -- -1 by convention -- or an empty slot
+ * means nobody: the car's floats of the action tensor stay as they are. */
+int crl_car_policy_set_assignment(crl_car_policy *p, const int32_t *ids_dev, void *stream);
+int crl_car_policy_get_assignment(crl_car_policy *p, int32_t *ids_out_dev, void *stream);
+/* One launch: u into actions_dev float32 [N][players][2] for the served cars (the others are left as written); optionally (null =
+ * not wanted) values [N][players], log_probs [N][players], noise z [N][players][2] -- each 0 for a car nobody serves -- and the
+ * observation [N][players][21] of EVERY car.  Sees the state the last crl_step / crl_reset on `stream` committed. */
+int crl_car_policy_act(crl_car_policy *p, float *actions_dev, float *values_dev, float *log_probs_dev, float *noise_dev, float *obs_dev,
+                       void *stream);
+/* The observation [N][players][21] of every car; no network runs and the call counter does not move. */
+int crl_car_policy_observe(crl_car_policy *p, float *obs_dev, void *stream);
+/* Resume: the key and the act-call counter (host values; calls in [0, 2^32)). */
+int crl_car_policy_get_counters(crl_car_policy *p, uint64_t *seed, int64_t *calls);
+int crl_car_policy_set_counters(crl_car_policy *p, uint64_t seed, int64_t calls);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
