@@ -614,6 +614,52 @@ def car_mlp_reference(weights, obs):
     return np.stack(outs[:2], axis=1).astype(f), outs[2].astype(f)
 
 
+CAR_TRACK_DOMAIN = 0x43415253  # "CARS"
+CAR_TRACK_ATTEMPTS = 256  # attempts of one reset (car_track.hip: kMaxAttempts)
+
+
+def car_track_counter(episode, attempt, k):
+    """Counter word 2 of call ``k`` (0..12) of attempt ``attempt`` (< 256) of episode ``episode`` in "car track draws":
+    (episode << 12 | attempt << 4 | k) mod 2^32 -- episode e and e + 2^20 share their counters."""
+    episode, attempt, k = int(episode), int(attempt), int(k)
+    if not (episode >= 0 and 0 <= attempt < CAR_TRACK_ATTEMPTS and 0 <= k < 13):
+        raise ValueError("episode >= 0, attempt in [0, 256), k in [0, 13)")
+    return ((episode << 12) | (attempt << 4) | k) & 0xFFFFFFFF
+
+
+def car_track_uniform(hi, lo):
+    """((hi << 32 | lo) >> 11) * 2^-53 of two 32-bit words: a multiple of 2^-53 in [0, 1), exact in float64."""
+    x = (np.asarray(hi, np.uint64) << np.uint64(32)) | np.asarray(lo, np.uint64)
+    return (x >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def car_track_words(seed, gid, episode, attempts):
+    """The four result words, each uint64 [A, 13], of the 13 Philox4x32-10 calls of every attempt in the sequence ``attempts`` of
+    "car track draws": counter (gid lo, gid hi, car_track_counter(episode, attempt, k), "CARS") under key (seed lo, seed hi)."""
+    ctr = np.array([[car_track_counter(episode, a, k) for k in range(13)] for a in attempts], np.uint64)
+    return _philox4x32_10(np.full(ctr.shape, int(gid) & (2 ** 64 - 1), np.uint64), ctr, CAR_TRACK_DOMAIN, seed)
+
+
+def car_track_attempts(seed, gid, episode, attempts):
+    """``car_track_draws`` of several attempts at once: (u float64 [A, 24], swap int64 [A])."""
+    w = car_track_words(seed, gid, episode, attempts)
+    u = np.empty((w[0].shape[0], 24), np.float64)
+    u[:, 0::2] = car_track_uniform(w[0][:, :12], w[1][:, :12])
+    u[:, 1::2] = car_track_uniform(w[2][:, :12], w[3][:, :12])
+    return u, (w[0][:, 12] & np.uint64(1)).astype(np.int64)
+
+
+def car_track_draws(seed, gid, episode, attempt):
+    """The draws of one _create_track attempt of a seeded CarRacing context in numpy (include/crl.h "car track draws"): 13
+    Philox4x32-10 calls k = 0..12 with counter (gid lo, gid hi, car_track_counter(episode, attempt, k), "CARS") under key
+    (seed lo, seed hi); for k < 12 u[2k] = car_track_uniform(w0, w1) and u[2k + 1] = car_track_uniform(w2, w3); swap = w0 & 1 of
+    call 12.  ``gid`` = env_id_base + the env's index, ``episode`` = the env's resets so far.  Returns (u float64 [24], swap int):
+    a reset takes the track of its first attempt that closes a lap and THAT attempt's swap.  Host code for tests and for callers
+    that want to predict a track; the kernels do not use it."""
+    u, swap = car_track_attempts(seed, gid, episode, [attempt])
+    return u[0], int(swap[0])
+
+
 def car_policy_draws(seed, gid, car, call):
     """The Philox call of "car policy": as ``car_driver_draws`` under CRL_CAR_POLICY_DOMAIN + car."""
     return _philox4x32_10(gid, call, N.CRL_CAR_POLICY_DOMAIN + int(car), seed)

@@ -266,7 +266,7 @@ class HipCarVecEnv(VecEnv):
     def state_dict(self):
         """Checkpoint of the whole batch in torch's idiom: the structured per-env state (bodies, joints, wheel model, tile books,
         manifolds, TimeLimit and episode counters) as a plain dict.  The current TRACKS are not part of it: they are a function of
-        (seed, global env id, episode) and are rebuilt by the next reset; restore into a context that is on the same episodes (or
+        (seed, global env id, episode) (include/crl.h "car track draws", rules.car_track_draws) and are rebuilt by the next reset; restore into a context that is on the same episodes (or
         push tracks with set_track) when the cars' positions matter."""
         return {"kind": "cCarRacing", "num_envs": self.num_envs, "players": self.P, "solver": self.solver, "env_state": self.get_state()}
 

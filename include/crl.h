@@ -402,8 +402,26 @@ int crl_car_get_map(crl_ctx *ctx, int64_t env, uint8_t *palette_host, int32_t *o
  * tile is not recorded), [1] = more than CRL_CAR_MAX_CONTACTS manifolds between the two cars of an env (the rest are dropped),
  * [2], [3] reserved.  Zero on every track of the tests and of a 10^7 env-step soak: a non-zero count means a deviation. */
 int crl_car_cap_hits(crl_ctx *ctx, int32_t *out4_host, void *stream);
-/* Replay mode for CarRacing.reset's randomness: per env `attempts` rows of 24 uniforms (the
- * np_random.uniform draws of one _create_track attempt) and one birth-place swap bit each. */
+/* Car track draws (rules.car_track_draws restates this in numpy; the generator and key of "league draws" below; it does not depend
+ * on how a batch is cut into shards).  CarRacing.reset tries _create_track until a lap closes (car_racing_multi_players.py:454-525);
+ * attempt a = 0, 1, ... of a reset takes 24 uniforms u[0..23] -- checkpoint c reads u[2c] for its angle's noise and u[2c + 1] for its
+ * radius -- and one swap bit for np.random.shuffle of the two birth places.  In a seeded context they are 13 Philox4x32-10 calls:
+ *   for k = 0..12:  w = Philox4x32-10(counter = (gid & 0xFFFFFFFF, gid >> 32, (episode << 12 | a << 4 | k) mod 2^32, 0x43415253 "CARS"),
+ *                                    key = (seed & 0xFFFFFFFF, seed >> 32)), words w0..w3;
+ *   k < 12:   u[2k] = ((w0 << 32 | w1) >> 11) * 2^-53,  u[2k + 1] = ((w2 << 32 | w3) >> 11) * 2^-53: multiples of 2^-53 in [0, 1), exact;
+ *   k = 12:   swap = w0 & 1 (w1..w3 unused).  swap = 1: car 0 starts from birth place 1, car 1 from place 0; a one-car context's car
+ *             starts from place 0 whatever the bit.
+ * gid = env_id_base + i, the env's GLOBAL id; seed = crl_opts.seed or the last crl_seed; episode = the env's count of resets so far
+ * (uint32: 0 for the track of the first crl_reset, the `episode` field of crl_car_env_state, which a reset increments); a < 256: a
+ * reset whose 256 attempts all fail leaves an empty track.  The track is that of the FIRST attempt that closes a lap, and the swap
+ * bit is THAT attempt's, not attempt 0's.  The counter keeps the low 20 bits of the episode: episodes e and e + 2^20 draw the same.
+ * Nothing else enters: a track is a function of (seed, gid, episode), whether the reset walks it itself or takes the walk laid
+ * ahead beside the steps; crl_seed and crl_car_set_replay void every walk laid ahead under the old key or stream.
+ *
+ * Replay mode for CarRacing.reset's randomness: per env `attempts` rows of 24 uniforms (the
+ * np_random.uniform draws of one _create_track attempt) and one birth-place swap bit each;
+ * attempt a of episode `episode` reads row (16 * episode + a) mod attempts of its env.
+ * attempts = 0 (null arrays) returns to the Philox draws above. */
 int crl_car_set_replay(crl_ctx *ctx, const double *u_host, const uint8_t *swap_host, int64_t attempts);
 
 /* CarRacing.step's per-car returns that the VecEnv folds away, as device arrays valid until the
