@@ -248,6 +248,28 @@ SIGNATURES = {
     "crl_rule_labels": (i32, [vp, i32, vp, i64, vp]),
     "crl_ppo_grad_teacher": (i32, [vp, vp, vp, i64, vp, vp, vp]),
     "crl_ppo_teacher_stats": (i32, [vp, P(f64)]),
+    "crl_car_rollout_create": (i32, [vp, i64, i32, P(vp)]),
+    "crl_car_rollout_destroy": (None, [vp]),
+    "crl_car_rollout_begin": (i32, [vp]),
+    "crl_car_rollout_record": (i32, [vp, i64, vp, i32, vp, vp, vp, vp, vp]),
+    "crl_car_rollout_outcome": (i32, [vp, i64, vp, vp, vp]),
+    "crl_car_rollout_finish": (i32, [vp, vp, f64, f64, i32, vp]),
+    "crl_car_rollout_gather": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "crl_car_rollout_stats": (i32, [vp, P(f64)]),
+    "crl_car_rollout_get_info": (i32, [vp, P(i32)]),
+    "crl_car_rollout_get_state": (i32, [vp, i64, vp, vp, vp]),
+    "crl_car_rollout_set_state": (i32, [vp, P(i32), i64, vp, vp, vp]),
+    "crl_car_ppo_create": (i32, [i32, vp, P(vp)]),
+    "crl_car_ppo_destroy": (None, [vp]),
+    "crl_car_ppo_set_weights": (i32, [vp, vp]),
+    "crl_car_ppo_get_weights": (i32, [vp, vp]),
+    "crl_car_ppo_weights_dev": (i32, [vp, P(vp)]),
+    "crl_car_ppo_grad": (i32, [vp, vp, vp, i64, vp, vp]),
+    "crl_car_ppo_get_grad": (i32, [vp, P(vp), vp]),
+    "crl_car_ppo_step": (i32, [vp, vp, vp]),
+    "crl_car_ppo_stats": (i32, [vp, P(f64)]),
+    "crl_car_ppo_get_state": (i32, [vp, vp, vp, vp, P(i64), vp]),
+    "crl_car_ppo_set_state": (i32, [vp, vp, vp, vp, i64, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -2,19 +2,27 @@
 reference's ``MLP(input_size, output_size)`` (utils/network.py:59-70) on it, assignable per env and per car from a pool of weight sets,
 with Gaussian actions, values and log-probabilities -- for CarRacing what ``Policy`` with a critic is for Pong.
 
-A trainer's torch loop handles (B, 21) float tensors only; the env loop stays on the device:
+The env loop stays on the device, and so does the learner's: ``CarRolloutStorage`` keeps what ``act_rollout`` wrote and ``CarPPO``
+updates the weights from it (car_learner.py); a trainer with its own torch network takes (B, 21) minibatches from the storage's
+``gather`` / ``minibatches`` instead:
 
     env = HipCarVecEnv(n)
     policy = CarPolicy(env, seed=0)
     policy.add_network("learner", mlp.state_dict())     # a torch MLP(21, 2), a dict of arrays, or a checkpoint path
     policy.assign(0, "learner")
+    storage = CarRolloutStorage(env, steps, cars=(0,))
     actions = torch.zeros((n, 2, 2), device=env.device)
+    obs = torch.empty((n, 2, 21), device=env.device)
     env.reset()
-    for _ in range(steps):
-        obs = policy.observe()[:, 0].clone()            # what the learner's update will see
-        values, log_probs = policy.act_rollout(actions)
-        env.step_device(actions)
-    policy.update_network("learner", mlp.state_dict())  # on the stream, no device synchronisation
+    storage.begin()
+    values, log_probs = policy.act_rollout(actions, obs_out=obs)
+    for t in range(steps):
+        storage.record(t, policy, "learner", obs, actions, values, log_probs)   # what the learner's update will see
+        _, rewards, done = env.step_device(actions, render=False)
+        storage.outcome(t, rewards, done)
+        values, log_probs = policy.act_rollout(actions, obs_out=obs)
+    storage.finish(values)
+    policy.update_network("learner", mlp.state_dict())  # on the stream, no device synchronisation (CarPPO.push: no host blob either)
 
 It composes with ``CarDrivers`` on one action tensor: ``drivers.act(a); policy.act(a)``, each writing only the cars assigned to it.
 """

@@ -724,3 +724,55 @@ def car_policy_reference(weights, obs, live, deterministic, seed=0, gid=0, car=0
     for k in ("u", "value", "log_prob", "z"):
         out[k][~live] = 0
     return out
+
+
+# ---- include/crl.h "car ppo update": the loss of the car policy's learner
+CAR_PPO_DEFAULTS = dict(clip=0.2, vf_coef=0.5, ent_coef=0.0, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5)
+CAR_PPO_STAT_KEYS = ("policy", "value", "entropy", "kl", "clipped")
+
+
+def car_ppo_loss_reference(weights, obs, actions, old_logp, returns, adv, live, hyper=None, dtype=None):
+    """The loss of include/crl.h "car ppo update" with torch autograd on the CPU; ``dtype=torch.float64`` (the default) is the
+    yardstick of the device's gradient.  ``weights``: anything ``car_policy_weights`` takes; ``obs`` float32 [B, 21]; ``actions``
+    float32 [B, 2]; ``old_logp``, ``returns``, ``adv`` float [B] (``adv`` as the gather hands it out); ``live`` [B]: a dead sample
+    contributes nothing, and the sums are divided by max(L, 1) with L the live count; ``hyper``: ``clip``, ``vf_coef``, ``ent_coef``
+    (missing ones from ``CAR_PPO_DEFAULTS``).  Returns a dict: ``loss``, the five statistics ``policy``, ``value``, ``entropy``,
+    ``kl``, ``clipped`` (means over the live samples), ``live`` (L), ``grads`` (the seven gradient arrays by key) and, per sample,
+    ``a`` [B, 100] (the pre-activations), ``mean`` [B, 2], ``v``, ``logp``, ``ratio``, ``active`` (the branch with
+    d policy / d logp = -A r).  Host code for tests; the kernels do not use it."""
+    import math
+
+    import torch
+
+    dtype = torch.float64 if dtype is None else dtype
+    h = dict(CAR_PPO_DEFAULTS, **(hyper or {}))
+    c, vf, ent = (float(np.float32(h[k])) for k in ("clip", "vf_coef", "ent_coef"))
+    w0 = car_policy_weights(weights)
+    w = {k: torch.tensor(w0[k], dtype=dtype, requires_grad=True) for k in CAR_POLICY_KEYS}
+    x, u = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (obs, actions))
+    olp, ret, A = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (old_logp, returns, adv))
+    lv = torch.tensor(np.asarray(live) != 0)
+    a = x @ w["fc1_w"].t() + w["fc1_b"]
+    hid = torch.where(a > 0, a, torch.zeros_like(a))
+    mean = hid @ w["policy_w"].t() + w["policy_b"]
+    v = (hid @ w["value_w"].t() + w["value_b"]).reshape(-1)
+    ls = w["log_std"]
+    zz = (u - mean) / torch.exp(ls)
+    logp = (-0.5 * zz ** 2 - ls).sum(1) - math.log(2 * math.pi)
+    ratio = torch.exp(logp - olp)
+    policy = -torch.minimum(ratio * A, torch.clamp(ratio, 1 - c, 1 + c) * A)
+    value = 0.5 * (ret - v) ** 2
+    entropy = (ls[0] + ls[1] + (1 + math.log(2 * math.pi))) * torch.ones_like(v)
+    L = max(int(lv.sum()), 1)
+    zero = torch.zeros_like(v)
+    over = lambda t: torch.where(lv, t, zero).sum() / L  # noqa: E731
+    loss = over(policy + vf * value - ent * entropy)
+    loss.backward()
+    n = lambda t: t.detach().numpy()  # noqa: E731
+    s = lambda t: float(t.detach())  # noqa: E731
+    r = ratio.detach()
+    active = ((A >= 0) & (r < 1 + c)) | ((A < 0) & (r > 1 - c))
+    return dict(loss=s(loss), policy=s(over(policy)), value=s(over(value)), entropy=s(over(entropy)), kl=s(over(olp - logp)),
+                clipped=s(over(((r < 1 - c) | (r > 1 + c)).to(dtype))), live=int(lv.sum()),
+                grads={k: (n(w[k].grad) if w[k].grad is not None else np.zeros(CAR_POLICY_SHAPES[k])) for k in CAR_POLICY_KEYS},
+                a=n(a), mean=n(mean), v=n(v), logp=n(logp), ratio=n(r), active=n(active))

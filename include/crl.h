@@ -1319,6 +1319,111 @@ int crl_car_policy_observe(crl_car_policy *p, float *obs_dev, void *stream);
 int crl_car_policy_get_counters(crl_car_policy *p, uint64_t *seed, int64_t *calls);
 int crl_car_policy_set_counters(crl_car_policy *p, uint64_t seed, int64_t calls);
 
+/* ---- car rollout storage: T steps of a CarRacing learner's rollout on the device, GAE, minibatch gather ----------
+ * What "rollout storage" is for Pong, for the car policy: an object beside a CarRacing context, as crl_car_policy is.  It stores what
+ * crl_car_policy_act wrote for the chosen cars and READS the context's committed per-car done flags and tile counts, and crl_car_info's
+ * done_car, itself.  The whole learner loop stays on the device: act -> record -> crl_step (no frame drawn) -> outcome -> finish ->
+ * crl_car_ppo_grad / _step -> crl_car_policy_set_weights; no call below synchronises with the host but _stats and _get/_set_state's
+ * callers.  rules.gae_reference restates the GAE rule.
+ *
+ * Rows.  cars_mask: bit c = car c is stored (1, 2 or 3).  C = the number of stored cars, rows R = N * C, row = e * C + j (j-th stored
+ * car of env e), flat sample index = t * R + row; T * R < 2^31.
+ * Layout: ONE SAMPLE = ONE ALIGNED 128-BYTE LINE of 32 words: obs[21], u[2], log-prob, value, reward, return, advantage, a flags word
+ * (bit 0 live, bit 1 done), three words of padding.  The update fetches samples by random index: a gradient lane touches exactly one
+ * line per sample (128 bytes moved per sample, all of them used but 12); GAE's strided walk over t costs T * R lines once per rollout.
+ *
+ * live(t, row) = the car's assignment in `policy` on the device equals `slot`, and the car's done flag is 0, and the env's tile count
+ * is > 0, all as crl_car_policy_act of step t saw them: the conditions under which that call served a real sample.  A dead sample (an
+ * all-zero observation, log-prob 0) is stored but is not training material: it takes no part in the statistics or in the gradient.
+ * done(t, row) = done[e] != 0 || done_car[e][c] != 0 after the step: the second term covers CRL_CAR_DONE_CAR0, where a finished car 1
+ * stays frozen in the world while car 0 drives on.
+ * GAE: the rule of "rollout storage", unchanged, one lane per row, with done(t, row) and last_values[e][c].
+ * Statistics (normalize != 0): mean and unbiased deviation of the LIVE samples' advantages in float64, in the summation shape of
+ * "rollout storage" over the flat index, a dead sample contributing 0; divisors L and L - 1 with L the live count; the mean is 0 where
+ * L = 0 and the deviation 0 where L < 2.  A gathered advantage is (adv - float32(mean)) / (float32(std) + 1e-5f).
+ * State machine: as crl_rollout_*: record(t) needs t == the steps recorded so far, outcome(t) a record of t and t == the outcomes so
+ * far, finish all T outcomes, gather / the gradient a finish; begin rewinds (there is no frame history to carry).  Every out-of-order
+ * call is refused with CRL_EINVAL before any GPU call. */
+typedef struct crl_car_rollout crl_car_rollout;
+/* A storage of num_steps steps for the cars of cars_mask of CarRacing context `ctx`, which must outlive it, on the current device.
+ * Refuses a Pong context, a mask outside 1..3 or naming a car the context lacks, num_steps < 1, T * R >= 2^31. */
+int crl_car_rollout_create(crl_ctx *ctx, int64_t num_steps, int32_t cars_mask, crl_car_rollout **out);
+void crl_car_rollout_destroy(crl_car_rollout *r);
+int crl_car_rollout_begin(crl_car_rollout *r);
+/* Step t: the full contiguous tensors the crl_car_policy_act call of this step just wrote on `stream` -- obs [N][players][21], actions
+ * [N][players][2], values and log_probs [N][players] -- of which the stored cars' columns are kept, and `live` for network `slot` of
+ * `policy` (a policy of the SAME context; its assignment is copied on `stream`).  A deterministic or empty slot is refused. */
+int crl_car_rollout_record(crl_car_rollout *r, int64_t t, crl_car_policy *policy, int32_t slot, const float *obs_dev, const float *actions_dev,
+                           const float *values_dev, const float *log_probs_dev, void *stream);
+/* What crl_step answered to step t: rewards float32 [N][players] and done u8 [N] as the step wrote them. */
+int crl_car_rollout_outcome(crl_car_rollout *r, int64_t t, const float *rewards_dev, const uint8_t *done_dev, void *stream);
+/* last_values float32 [N][players] (the values of the act call that opens the next rollout) or null = zeros. */
+int crl_car_rollout_finish(crl_car_rollout *r, const float *last_values_dev, double gamma, double lam, int32_t normalize, void *stream);
+/* The samples idx_dev (int64 flat indices, any order, duplicates allowed; a bad index only READS inside the storage): obs [B][21],
+ * actions [B][2], old log-probs, values, returns, advantages (normalised if the finish was) float32 [B], live u8 [B]; each optional. */
+int crl_car_rollout_gather(crl_car_rollout *r, const int64_t *idx_dev, int64_t count, float *obs_out_dev, float *actions_out_dev, float *logp_out_dev,
+                           float *values_out_dev, float *returns_out_dev, float *adv_out_dev, uint8_t *live_out_dev, void *stream);
+/* mean, std, live count L after a normalising finish (synchronises the device). */
+int crl_car_rollout_stats(crl_car_rollout *r, double *out3_host);
+/* Resume.  out8: state (0 fresh, 1 active, 2 finished), steps recorded, outcomes, whether the finish normalised, T, C, cars_mask, words
+ * per line.  _get_state copies the lines of the first `steps` steps ([steps * R][32] float32 words, bits as they are) and the three
+ * statistics to device buffers on `stream` (each optional); _set_state puts them back together with the first four info words. */
+int crl_car_rollout_get_info(crl_car_rollout *r, int32_t *out8_host);
+int crl_car_rollout_get_state(crl_car_rollout *r, int64_t steps, float *lines_out_dev, double *stats_out_dev, void *stream);
+int crl_car_rollout_set_state(crl_car_rollout *r, const int32_t *info4_host, int64_t steps, const float *lines_dev, const double *stats_dev, void *stream);
+
+/* ---- car ppo update: the gradient and optimiser step for the car policy's MLP on the device ----------------
+ * What "ppo update" is for the LightActorCritic, for the MLP(21, 2) of "car policy" with its Gaussian head.  The MASTER WEIGHTS ARE A
+ * CAR POLICY BLOB (CRL_CAR_POLICY_BLOB_FLOATS floats in the layout of "car policy"): handing them to a served policy is
+ * crl_car_policy_set_weights(policy, slot, crl_car_ppo_weights_dev(..), 0, stream), a device-to-device copy.  The blob holds 2505
+ * parameters (fc1_w, fc1_b, policy_w, value_w, policy_b, value_b, log_std); the two std floats are derived, not trained -- their
+ * gradient and Adam moments stay 0 -- and the pad stays 0.  rules.car_ppo_loss_reference (torch float64 autograd) restates the loss,
+ * rules.adam_reference the step.
+ *
+ * Loss.  Per LIVE sample b of the minibatch, with x, u, old_logp, ret as stored and A the advantage as the gather hands it out:
+ *   a = fc1(x);  h = max(a, 0) with derivative (a > 0 ? 1 : 0);  mean = policy(h);  v = value(h);
+ *   std_d = exp(log_std_d);  zz_d = (u_d - mean_d) / std_d;  logp = sum_d (-0.5 zz_d^2 - log_std_d) - ln(2 pi);  r = exp(logp - old_logp);
+ *   policy = -min(r A, clamp(r, 1 - c, 1 + c) A), with g = d policy / d logp = -(A r) if (A >= 0 and r < 1 + c) or (A < 0 and r > 1 - c),
+ *     else 0 -- exactly the clipped surrogate of "ppo update", the same branch conditions;
+ *   value = 0.5 (ret - v)^2;  entropy = log_std_0 + log_std_1 + (1 + ln(2 pi));
+ *   loss = (sum over the LIVE samples of policy + vf * value - ent * entropy) / max(L, 1), L the minibatch's live count.
+ * A dead sample contributes nothing to the gradient or to the statistics.  Closed forms:
+ *   d loss_b / d mean_d = g zz_d / std_d;   d loss_b / d log_std_d = g (zz_d^2 - 1) - ent;   d loss_b / d v = vf (v - ret).
+ * Precision: the hidden layer is float32 (the serving kernel's order: fc1_b[j], then inputs 0..20); from h on, mean, v, logp, r and the
+ * three derivative heads are formed in float64 and rounded once to float32; the backward pass through the two layers is float32,
+ * da_j = (a_j > 0) ? ((d0 wp0_j + d1 wp1_j) + dv wv_j) : 0.
+ * Summation shape, a function of B alone: groups of G = 64 consecutive idx entries, W = min(1024, ceil(B / 64)) workgroups of one
+ * wavefront, workgroup w taking groups w, w + W, ... in order.  fc1_w, fc1_b, policy_w and value_w are sums over the samples on
+ * v_mfma_f32_16x16x4_f32, the samples as its K dimension: four consecutive samples per instruction (the instruction's own order within
+ * the four), the instructions of a group in sample order, a workgroup's groups in order into the same accumulators.  policy_b, value_b
+ * and log_std: the UNROUNDED float64 closed forms; lane l adds its samples (entry l of each of the workgroup's groups) in order in
+ * float64, then the butterfly of "car policy" over the 64 lanes in float64.  The workgroups' partial sums are added in workgroup
+ * order and divided by float32(max(L, 1)) (the five float64 sums: added in float64, divided by L in float64, rounded once).  No
+ * floating-point atomics: the same idx gives the same bits on every run.
+ * Statistics: the means over the live samples of policy, value, entropy, old_logp - logp and the clipped share (r outside [1 - c,
+ * 1 + c]) in float64, the gradient's norm before clipping, the optimiser steps taken, and L.
+ * Step: clip by the global norm and Adam by the rule of "ppo update", unchanged, over the 2505 parameters; then
+ * std_d = float32(exp(float64(log_std_d))) is rewritten in the master blob on the device (the serving kernel evaluates no exp).
+ * Default hyper-parameters of the Python side are common continuous-control practice: clip 0.2, vf 0.5, ent 0.0, lr 3e-4, betas (0.9,
+ * 0.999), eps 1e-5, max_grad_norm 0.5. */
+typedef struct crl_car_ppo crl_car_ppo;
+/* blob_host: a car policy blob; the std floats and the pad are recomputed.  Both moments and the step count start at 0. */
+int crl_car_ppo_create(int32_t device, const float *blob_host, crl_car_ppo **out);
+void crl_car_ppo_destroy(crl_car_ppo *p);
+int crl_car_ppo_set_weights(crl_car_ppo *p, const float *blob_host); /* zeroes the moments and the step count (synchronises) */
+int crl_car_ppo_get_weights(crl_car_ppo *p, float *blob_out_host);   /* (synchronises) */
+int crl_car_ppo_weights_dev(crl_car_ppo *p, const float **blob_dev);
+/* The gradient over the samples idx_dev [count] of a finished storage, at the master weights, on `stream`. */
+int crl_car_ppo_grad(crl_car_ppo *p, const crl_car_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper, void *stream);
+/* The last gradient, a blob in the weights' layout: its device address and / or a host copy (synchronises). */
+int crl_car_ppo_get_grad(crl_car_ppo *p, const float **grad_dev, float *grad_out_host);
+int crl_car_ppo_step(crl_car_ppo *p, const crl_ppo_hyper *hyper, void *stream);
+/* out8: policy loss, value loss, entropy, approximate KL, clipped share, gradient norm, steps, L (synchronises the device). */
+int crl_car_ppo_stats(crl_car_ppo *p, double *out8_host);
+/* Resume: the master blob, Adam's moments and the step count, behind / ordered on `stream` (both synchronise with it). */
+int crl_car_ppo_get_state(crl_car_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t *steps_out, void *stream);
+int crl_car_ppo_set_state(crl_car_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t steps, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
