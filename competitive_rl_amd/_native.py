@@ -32,6 +32,10 @@ CRL_CAR_DRIVER_RANDOM, CRL_CAR_DRIVER_RULE_BASED = 0, 1
 CRL_CAR_DRIVER_SLOTS = 16
 CRL_CAR_POLICY_DOMAIN = 0x43525030  # "CRP0": car c draws under CRL_CAR_POLICY_DOMAIN + c (include/crl.h "car policy")
 CRL_CAR_POLICY_SLOTS, CRL_CAR_OBS_FEATURES, CRL_CAR_POLICY_HIDDEN, CRL_CAR_POLICY_BLOB_FLOATS = 8, 21, 100, 2508
+CRL_CAR_LEAGUE_DOMAIN = 0x43524C47  # "CRLG" (include/crl.h "car league")
+CRL_CAR_LEAGUE_COUNTERS = 7  # planes of the counters tensor, in this order (enum crl_car_league_counter)
+CRL_CAR_LEAGUE_COUNTER_NAMES = ("episodes", "wins", "losses", "draws", "return_sum", "opponent_return_sum", "length_sum")
+CRL_CAR_LEAGUE_NETWORK, CRL_CAR_LEAGUE_STYLE = 0, 1
 CRL_ARENA_COUNTERS = 6  # planes of the counters tensor, in this order (enum crl_arena_counter); each plane is [left][right]
 CRL_ARENA_COUNTER_NAMES = ("episodes", "left_wins", "right_wins", "draws", "return_sum", "length_sum")
 
@@ -270,6 +274,23 @@ SIGNATURES = {
     "crl_car_ppo_stats": (i32, [vp, P(f64)]),
     "crl_car_ppo_get_state": (i32, [vp, vp, vp, vp, P(i64), vp]),
     "crl_car_ppo_set_state": (i32, [vp, vp, vp, vp, i64, vp]),
+    "crl_car_league_create": (i32, [vp, vp, vp, u64, P(vp)]),
+    "crl_car_league_destroy": (None, [vp]),
+    "crl_car_league_add_agent": (i32, [vp, i32, i32, P(i32), vp]),
+    "crl_car_league_get_pool": (i32, [vp, P(i32), vp, vp]),
+    "crl_car_league_draw_all": (i32, [vp, vp]),
+    "crl_car_league_seed": (i32, [vp, u64, vp]),
+    "crl_car_league_reset": (i32, [vp, vp]),
+    "crl_car_league_reset_agent": (i32, [vp, i32, vp]),
+    "crl_car_league_set_weights": (i32, [vp, vp, i32, vp]),
+    "crl_car_league_get_weights": (i32, [vp, vp, vp]),
+    "crl_car_league_pfsp_weights": (i32, [vp, vp, i32, i32, u32, vp]),
+    "crl_car_league_get_counters": (i32, [vp, vp, vp]),
+    "crl_car_league_set_counters": (i32, [vp, vp, vp]),
+    "crl_car_league_get_env_state": (i32, [vp, vp, vp, vp, vp, vp]),
+    "crl_car_league_set_env_state": (i32, [vp, vp, vp, vp, vp, vp]),
+    "crl_car_league_get_assignment": (i32, [vp, vp, vp]),
+    "crl_car_league_step": (i32, [vp, vp, vp, i32, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

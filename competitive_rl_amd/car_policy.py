@@ -141,6 +141,8 @@ class CarPolicy:
         self._check_open()
         if not 0 <= int(car) < self.players:
             raise ValueError(f"car must lie in [0, {self.players})")
+        # the mirror takes what the device holds first (a copy on the stream): a CarLeague writes column 1 there on its own
+        N.check(self._L.crl_car_policy_get_assignment(self._h, C.c_void_p(self._assign.data_ptr()), self._stream()))
         if isinstance(who, torch.Tensor):
             if who.dtype != torch.int32 or who.device != self.device or tuple(who.shape) != (self.num_envs,):
                 raise ValueError(f"a per-env assignment is an int32 tensor of shape ({self.num_envs},) on the env's device")

@@ -140,6 +140,9 @@ struct crl_car_driver {
     float epsilon[CRL_CAR_DRIVER_SLOTS];
 };
 
+crl_car_ctx *crl_car_driver_ctx(crl_car_driver *d) { return d->car; }
+int32_t *crl_car_driver_assign_dev(crl_car_driver *d) { return d->assign; }
+
 static uint32_t driver_eps_q(float epsilon) {
     const double q = floor((double)epsilon * 4294967296.0);
     return q >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)q;

@@ -201,6 +201,9 @@ struct crl_car_policy {
     int8_t flag[CRL_CAR_POLICY_SLOTS];
 };
 
+crl_car_ctx *crl_car_policy_ctx(crl_car_policy *p) { return p->car; }
+int32_t *crl_car_policy_assign_dev(crl_car_policy *p) { return p->assign; }
+
 static int policy_launch(crl_car_policy *p, bool act, float *actions, float *values, float *logp, float *noise, float *obs, void *stream) {
     const CarSoA *s = crl_car_soa(p->car);
     PolicyArgs A;

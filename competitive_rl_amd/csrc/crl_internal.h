@@ -74,6 +74,12 @@ struct CarSoA;
 crl_car_ctx *crl_ctx_car(crl_ctx *c);
 const crl::CarSoA *crl_car_soa(const crl_car_ctx *c);
 int64_t crl_car_env_id_base(const crl_car_ctx *c);
+// what crl_car_league (car_league.hip) needs of the two objects it writes into: the context each was made for and its device
+// assignment array [n][players]
+crl_car_ctx *crl_car_policy_ctx(crl_car_policy *p);
+int32_t *crl_car_policy_assign_dev(crl_car_policy *p);
+crl_car_ctx *crl_car_driver_ctx(crl_car_driver *d);
+int32_t *crl_car_driver_assign_dev(crl_car_driver *d);
 int crl_car_step(crl_car_ctx *c, const float *actions_dev, uint8_t *obs_dev, float *rew_dev, uint8_t *done_dev, hipStream_t st,
                  crl_timer *tm);
 int crl_car_get_state_impl(crl_car_ctx *c, crl_car_env_state *out, int64_t first, int64_t count, hipStream_t st);

@@ -776,3 +776,120 @@ def car_ppo_loss_reference(weights, obs, actions, old_logp, returns, adv, live, 
                 clipped=s(over(((r < 1 - c) | (r > 1 + c)).to(dtype))), live=int(lv.sum()),
                 grads={k: (n(w[k].grad) if w[k].grad is not None else np.zeros(CAR_POLICY_SHAPES[k])) for k in CAR_POLICY_KEYS},
                 a=n(a), mean=n(mean), v=n(v), logp=n(logp), ratio=n(r), active=n(active))
+
+
+# ---- include/crl.h "car league": the draw of car 1's driver and the race books
+CAR_LEAGUE_KINDS = ("NETWORK", "STYLE")  # enum crl_car_league_kind
+CAR_LEAGUE_COUNTER_NAMES = N.CRL_CAR_LEAGUE_COUNTER_NAMES
+_CL_A = N.CRL_LEAGUE_MAX_AGENTS
+
+
+def _car_league_table(weights):
+    """``weights`` as the device's table: uint64 (16,), zero beyond the entries given."""
+    w = np.asarray(weights)
+    if w.ndim != 1 or len(w) > _CL_A or (w < 0).any() or (w > 0xFFFFFFFF).any():
+        raise ValueError(f"at most {_CL_A} weights in [0, 2^32)")
+    table = np.zeros(_CL_A, np.uint64)
+    table[:len(w)] = w.astype(np.uint64)
+    return table
+
+
+def car_league_draw_reference(seed, gid, counter, weights):
+    """The car league's weighted draw in numpy: the rule of include/crl.h "ledger draws" (``ledger.ledger_draw_reference``) with
+    CRL_CAR_LEAGUE_DOMAIN as the counter's fourth word.  ``gid`` and ``counter`` broadcast; ``weights`` must sum to a value in
+    [1, 2^32).  Returns int64.  Host code for tests and for callers that want to predict a draw; the kernels do not use it."""
+    table = _car_league_table(weights)
+    total = int(table.sum())
+    if not 0 < total < 2 ** 32:
+        raise ValueError(f"the weights must sum to a value in [1, 2^32), not {total}")
+    r = league_draw_reference(seed, gid, counter, N.CRL_CAR_LEAGUE_DOMAIN, total)  # (x * T) >> 32
+    return np.searchsorted(np.cumsum(table.astype(np.int64)), r, side="right").astype(np.int64)
+
+
+def car_league_q(x):
+    """q of "car league": a float32 return in units of 1/256 as an int64 -- rint(clamp(float64(x) * 256, -2^62, 2^62)) (ties to even)
+    for a finite x, 0 otherwise."""
+    x = np.asarray(x, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.clip(x.astype(np.float64) * np.float64(256.0), -2.0 ** 62, 2.0 ** 62)
+        return np.where(np.isfinite(x), np.rint(np.where(np.isfinite(x), v, 0.0)), 0.0).astype(np.int64)
+
+
+def car_league_columns(pool, agent):
+    """What serving pool entry ``agent[e]`` writes into column 1 of the policy's and of the driver's assignment: (policy column, driver
+    column), int32 each.  ``pool``: a sequence of (kind, slot), kind "NETWORK" / "STYLE" (or its enum value).  Entries of ``agent``
+    outside the pool give -1 in both (the device leaves such a row as it is)."""
+    agent = np.asarray(agent, np.int64)
+    net, style = np.full(len(pool) + 1, -1, np.int32), np.full(len(pool) + 1, -1, np.int32)
+    for a, (kind, slot) in enumerate(pool):
+        kind = CAR_LEAGUE_KINDS[kind] if not isinstance(kind, str) else kind
+        if kind not in CAR_LEAGUE_KINDS:
+            raise ValueError(f"kind must be one of {CAR_LEAGUE_KINDS}")
+        (net if kind == "NETWORK" else style)[a] = int(slot)
+    idx = np.where((agent >= 0) & (agent < len(pool)), agent, len(pool))
+    return net[idx], style[idx]
+
+
+def car_league_state(num_envs):
+    """A fresh league's state as the replay keeps it: ``agent`` int32 (N,) = -1, ``ret`` float32 (N, 2), ``len`` int32 (N,),
+    ``draw_ctr`` uint32 (N,), ``counters`` int64 (7, 16) in the order of ``CAR_LEAGUE_COUNTER_NAMES``."""
+    n = int(num_envs)
+    return dict(agent=np.full(n, -1, np.int32), ret=np.zeros((n, 2), np.float32), len=np.zeros(n, np.int32), draw_ctr=np.zeros(n, np.uint32),
+                counters=np.zeros((N.CRL_CAR_LEAGUE_COUNTERS, _CL_A), np.int64))
+
+
+def _car_league_redraw(state, where, agents, weights, seed, env_id_base):
+    table = _car_league_table(weights)
+    table[int(agents):] = 0
+    if not 0 < int(table.sum()) < 2 ** 32 or not where.any():
+        return  # a table without a draw keeps agent and counter
+    e = np.nonzero(where)[0]
+    state["agent"][e] = car_league_draw_reference(seed, e.astype(np.uint64) + np.uint64(env_id_base), state["draw_ctr"][e], table).astype(np.int32)
+    state["draw_ctr"][e] += np.uint32(1)
+
+
+def car_league_draw_all_reference(state, agents, weights, seed, env_id_base=0):
+    """``crl_car_league_draw_all`` on a copy of ``state``: a fresh draw for every env."""
+    state = {k: v.copy() for k, v in state.items()}
+    _car_league_redraw(state, np.ones(len(state["agent"]), bool), agents, weights, seed, env_id_base)
+    return state
+
+
+def car_league_reset_agent_reference(state, agent):
+    """``crl_car_league_reset_agent`` on a copy of ``state``: the counter column of one pool entry back to zero."""
+    state = {k: v.copy() for k, v in state.items()}
+    state["counters"][:, int(agent)] = 0
+    return state
+
+
+def car_league_reference(state, rewards, dones, agents, weights, seed, env_id_base=0, redraw=True):
+    """The replay of include/crl.h "car league": ``crl_car_league_step`` for every recorded step, in numpy.  ``state``: a dict as
+    ``car_league_state`` makes it (not modified); ``rewards`` float32 (T, N, 2) and ``dones`` (T, N) as ``step_device`` returned them;
+    ``agents``: the pool's size; ``weights``: the table (one sequence for all steps); ``redraw``: a bool, or one per step.  Returns
+    (the state after the last step, int32 (T, N): the agent array after every step).  Host code for tests; the kernels do not use it."""
+    rewards, dones = np.asarray(rewards, np.float32), np.asarray(dones) != 0
+    steps, n = dones.shape
+    if rewards.shape != (steps, n, 2) or len(state["agent"]) != n:
+        raise ValueError("rewards (T, N, 2), dones (T, N) and a state of N envs")
+    state = {k: v.copy() for k, v in state.items()}
+    flags = [bool(redraw)] * steps if isinstance(redraw, (bool, np.bool_, int)) else [bool(x) for x in redraw]
+    after = np.zeros((steps, n), np.int32)
+    c = state["counters"]
+    for t in range(steps):
+        ret = (state["ret"] + rewards[t]).astype(np.float32)  # one float32 rounding per add
+        length = state["len"] + np.int32(1)
+        d = dones[t]
+        booked = d & (state["agent"] >= 0) & (state["agent"] < int(agents))
+        key = state["agent"][booked].astype(np.int64)
+        r0, r1 = ret[booked, 0], ret[booked, 1]
+        won, lost = r0 > r1, r0 < r1  # a NaN on either side is neither: a draw
+        for plane, value in ((0, np.ones(len(key), np.int64)), (1, won.astype(np.int64)), (2, lost.astype(np.int64)),
+                             (3, (~won & ~lost).astype(np.int64)), (4, car_league_q(r0)), (5, car_league_q(r1)),
+                             (6, length[booked].astype(np.int64))):
+            np.add.at(c[plane], key, value)
+        ret[d], length[d] = 0, 0
+        state["ret"], state["len"] = ret, length
+        if flags[t]:
+            _car_league_redraw(state, d, agents, weights, seed, env_id_base)
+        after[t] = state["agent"]
+    return state, after

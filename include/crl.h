@@ -1424,6 +1424,85 @@ int crl_car_ppo_stats(crl_car_ppo *p, double *out8_host);
 int crl_car_ppo_get_state(crl_car_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t *steps_out, void *stream);
 int crl_car_ppo_set_state(crl_car_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t steps, void *stream);
 
+/* ---- car league: per-env opponents for car 1 and race books on the device --------------
+ * What "league" and "league ledger" are for cPongTournament, for a two-car CarRacing context: a pool of opponents, a per-env draw of
+ * who drives car 1, and books of how car 0 (the caller's car, the seat make_competitive_car_racing gives its agent,
+ * car_racing/make_competitive_car_racing.py:10-58) fares against each of them.  An object beside the context, a crl_car_policy and a
+ * crl_car_driver of that context: it reads the step's rewards and done flags and WRITES column 1 of both objects' device assignment
+ * arrays, nothing else of them; column 0 is never touched.  All work is ordered on the caller's stream; no call synchronises with the
+ * host, the getters hand over device memory (crl_car_league_get_pool returns host values and makes no GPU call).
+ * rules.car_league_reference and rules.car_league_draw_reference restate this section in numpy.
+ *
+ * Pool.  Up to CRL_LEAGUE_MAX_AGENTS entries (kind, slot), append-only: kind CRL_CAR_LEAGUE_NETWORK names a network slot of the
+ * policy, kind CRL_CAR_LEAGUE_STYLE a style slot of the driver.  Serving agent a means: policy assignment[e][1] = slot and driver
+ * assignment[e][1] = -1 for a network, the other way round for a style.
+ *
+ * State.  Per env: agent int32 (the pool entry that drives car 1; -1 until the first draw), ret float32 [2] (the running episode's
+ * summed step rewards of car 0 and car 1), len int32 (its steps), draw_ctr uint32.  Per agent: CRL_CAR_LEAGUE_COUNTERS int64 counters,
+ * laid out [counter][CRL_LEAGUE_MAX_AGENTS] in the order of enum crl_car_league_counter.  A weight table uint32
+ * w[CRL_LEAGUE_MAX_AGENTS]: 1 for an entry when it enters the pool, 0 beyond the pool.
+ *
+ * crl_car_league_step, one launch with one lane per env, enqueued behind the crl_step that wrote rewards and done:
+ *   1. ret[c] = ret[c] + reward[e][c] for c = 0, 1 in float32, one rounding per add, in step order; len += 1;
+ *   2. where done[e] != 0 the episode is credited to agent[e], the entry that DROVE it: episodes += 1; one of wins (ret[0] > ret[1]) /
+ *      losses (ret[0] < ret[1]) / draws (otherwise: equal, or a NaN on either side) += 1; return_sum += q(ret[0]);
+ *      opponent_return_sum += q(ret[1]); length_sum += len; then ret = len = 0.  q(x) = llrint(clamp((double)x * 256.0, -2^62, 2^62))
+ *      (round to nearest, ties to even) for a finite x and 0 otherwise: returns in units of 1/256.  An agent outside [0, agents) (-1:
+ *      no draw yet) is credited nowhere.  All sums are 64-bit integer atomics, reduced per wavefront by the keys present: the totals do
+ *      not depend on the order in which wavefronts arrive;
+ *   3. where done[e] != 0 and redraw != 0: a weighted draw by the rule of "ledger draws" with CRL_CAR_LEAGUE_DOMAIN in place of
+ *      CRL_LEDGER_DOMAIN_OPPONENT (key = the league's seed, gid = the context's env_id_base + e, n = draw_ctr[e]); then agent[e] = the
+ *      drawn entry, draw_ctr[e] += 1, and column 1 of row e of both assignment arrays is written as above.  A table that sums to 0
+ *      (or past 2^32 - 1) keeps the env's agent, counter and assignments.  The next crl_car_policy_act / crl_car_driver_act on the
+ *      stream serves the new opponent from the first step of the new episode (crl_step has reset the env already).
+ * A draw depends on (seed, global env id, counter, table) alone: shards that hold the same table draw what the whole batch would.
+ * PFSP weights: the rule of "PFSP weights" over the planes episodes, wins and draws. */
+#define CRL_CAR_LEAGUE_DOMAIN 0x43524C47u /* "CRLG" */
+#define CRL_CAR_LEAGUE_COUNTERS 7
+enum crl_car_league_counter { CRL_CAR_LEAGUE_EPISODES = 0, CRL_CAR_LEAGUE_WINS = 1, CRL_CAR_LEAGUE_LOSSES = 2, CRL_CAR_LEAGUE_DRAWS = 3,
+                              CRL_CAR_LEAGUE_RETURN_SUM = 4, CRL_CAR_LEAGUE_OPPONENT_RETURN_SUM = 5, CRL_CAR_LEAGUE_LENGTH_SUM = 6 };
+enum crl_car_league_kind { CRL_CAR_LEAGUE_NETWORK = 0, CRL_CAR_LEAGUE_STYLE = 1 };
+typedef struct crl_car_league crl_car_league;
+/* A league for the envs of the two-car CarRacing context `ctx` and a policy and a driver of THAT context; all three must outlive it.
+ * The pool is empty.  Refuses (CRL_EINVAL, before any GPU call) a null argument, a Pong context, a one-car context and a policy or
+ * driver of another context. */
+int crl_car_league_create(crl_ctx *ctx, crl_car_policy *policy, crl_car_driver *driver, uint64_t seed, crl_car_league **out);
+void crl_car_league_destroy(crl_car_league *l);
+/* Appends (kind, slot) to the pool; its id goes to *id_out (optional) and its weight becomes 1 in stream order.  Refuses a kind
+ * outside the enum, a slot outside [0, CRL_CAR_POLICY_SLOTS) / [0, CRL_CAR_DRIVER_SLOTS) and a 17th entry. */
+int crl_car_league_add_agent(crl_car_league *l, int32_t kind, int32_t slot, int32_t *id_out, void *stream);
+/* The pool (host values, no GPU call): its size, and kinds / slots as int32 [CRL_LEAGUE_MAX_AGENTS] (-1 beyond the pool); each optional. */
+int crl_car_league_get_pool(crl_car_league *l, int32_t *agents_out, int32_t *kinds_out, int32_t *slots_out);
+/* A fresh draw (step 3) for EVERY env, e.g. after crl_reset. */
+int crl_car_league_draw_all(crl_car_league *l, void *stream);
+/* New key for the draws, every draw_ctr back to 0 (results, weights and assignments stay). */
+int crl_car_league_seed(crl_car_league *l, uint64_t seed, void *stream);
+/* Zeroes the counters and every env's ret / len (weights, key, draw counters and assignments stay). */
+int crl_car_league_reset(crl_car_league *l, void *stream);
+/* Zeroes the counter column of pool entry `agent` (a slot that took a newer snapshot starts its record over). */
+int crl_car_league_reset_agent(crl_car_league *l, int32_t agent, void *stream);
+/* w_host: uint32 [count] on the HOST, count == the pool's size, summing to a value in [1, 2^32) (read before the call returns). */
+int crl_car_league_set_weights(crl_car_league *l, const uint32_t *w_host, int32_t count, void *stream);
+/* w_out_dev: uint32 [CRL_LEAGUE_MAX_AGENTS] on the device. */
+int crl_car_league_get_weights(crl_car_league *l, uint32_t *w_out_dev, void *stream);
+/* The PFSP table from counters_dev (int64 [CRL_CAR_LEAGUE_COUNTERS][CRL_LEAGUE_MAX_AGENTS] on the device, e.g. all-reduced over the
+ * shards) or from the league's own counters when NULL; mode, exponent and floor as crl_ledger_pfsp_weights takes and refuses them. */
+int crl_car_league_pfsp_weights(crl_car_league *l, const int64_t *counters_dev, int32_t mode, int32_t exponent, uint32_t floor, void *stream);
+/* Counters as int64 [CRL_CAR_LEAGUE_COUNTERS][CRL_LEAGUE_MAX_AGENTS], device memory. */
+int crl_car_league_get_counters(crl_car_league *l, int64_t *counters_out_dev, void *stream);
+int crl_car_league_set_counters(crl_car_league *l, const int64_t *counters_dev, void *stream);
+/* Checkpoints / tests: the per-env values on the device, each optional: agent int32 [N], ret float32 [N][2], len int32 [N], draw_ctr
+ * uint32 [N].  _set_env_state with an agent array also writes column 1 of both assignment arrays for every env whose agent lies in the
+ * pool, so that the opponent served is the one the books will credit. */
+int crl_car_league_get_env_state(crl_car_league *l, int32_t *agent_out_dev, float *ret_out_dev, int32_t *len_out_dev, uint32_t *draw_ctr_out_dev,
+                                 void *stream);
+int crl_car_league_set_env_state(crl_car_league *l, const int32_t *agent_dev, const float *ret_dev, const int32_t *len_dev,
+                                 const uint32_t *draw_ctr_dev, void *stream);
+/* The agent array: int32 [N] on the device. */
+int crl_car_league_get_assignment(crl_car_league *l, int32_t *agent_out_dev, void *stream);
+/* The per-step call described above: rewards_dev float32 [N][2] and done_dev uint8 [N] as crl_step wrote them. */
+int crl_car_league_step(crl_car_league *l, const float *rewards_dev, const uint8_t *done_dev, int32_t redraw, void *stream);
+
 /* Text of the most recent failing call: of the calling thread (any call, crl_create included), or of one context. */
 const char *crl_last_error(void);
 const char *crl_ctx_last_error(const crl_ctx *ctx);
