@@ -1,7 +1,11 @@
 """DeviceBooks: what ``LeagueLedger`` (ledger.py) and ``ArenaBooks`` (arena.py) share -- the same device object with another key
 (csrc/pong_books.h): an opponent's id in the ledger, a (left, right) cell in the arena.  A subclass names its C prefix, its counters and
 the shape of one counter plane; its weight table is that plane cut to the pool.  The handle, the checks of ``update``, the copies of
-counters, per-env state and weights, seed / reset / ``state_dict`` / ``load_state_dict`` and the lifetime live here.
+counters and per-env state, ``state_dict`` / ``load_state_dict`` and the lifetime live here.
+
+``WeightTable`` is the part that ``CarLeague`` (car_league.py) shares as well, an object with per-env state of its own: the weight
+table of a pool behind a C prefix -- its check, ``set_weights`` / ``weights_device`` / ``weights``, ``seed`` / ``reset`` and the checks
+of a PFSP fill.
 """
 import ctypes as C
 
@@ -17,7 +21,76 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class DeviceBooks:
+PFSP_MODES = {"hard": N.CRL_LEDGER_PFSP_HARD, "variance": N.CRL_LEDGER_PFSP_VARIANCE}
+
+
+class WeightTable:
+    """The weight table of a pool of ``self.agents`` agents behind ``self._C`` + set_weights / get_weights / seed / reset (and
+    pfsp_weights where the table holds one weight per agent).  The host object has ``_L``, ``_h``, ``device``, ``_stream()``, the shape
+    ``_PLANE`` of the device's table and the shape ``_COUNTERS`` of its counter planes."""
+
+    _C = None
+    _PLANE = (_A,)
+    _COUNTERS = ()
+
+    def _c(self, name):
+        return getattr(self._L, self._C + name)
+
+    def _check_open(self):
+        """Raises where a call would write into something closed (``CarLeague``); the Pong books have no such check."""
+
+    def _weight_table(self, weights, what):
+        w = np.asarray(weights)
+        shape = (self.agents,) * len(self._PLANE)
+        if w.shape != shape or not w.size or (w < 0).any() or (w > 0xFFFFFFFF).any():
+            raise ValueError(f"{what}: {shape} integers in [0, 2^32)")
+        return np.ascontiguousarray(w, np.uint32)
+
+    def set_weights(self, weights):
+        """``weights``: one non-negative integer per agent / per [left][right] cell of the pool (host values); their sum must lie in
+        [1, 2^32).  Weight 0: never drawn."""
+        self._check_open()
+        w = self._weight_table(weights, "set_weights")
+        N.check(self._c("set_weights")(self._h, w.ctypes.data_as(C.c_void_p), w.size, self._stream()))
+
+    def weights_device(self):
+        """int64 device tensor of the shape of a counter plane holding the uint32 table (entries beyond the pool are 0): a copy, no
+        synchronisation."""
+        self._check_open()
+        raw = torch.empty(self._PLANE, dtype=torch.int32, device=self.device)
+        N.check(self._c("get_weights")(self._h, _p(raw), self._stream()))
+        return raw.to(torch.int64) & 0xFFFFFFFF
+
+    def weights(self):
+        """The table of the pool as a host uint32 array (synchronises)."""
+        return self.weights_device()[(slice(0, self.agents),) * len(self._PLANE)].cpu().numpy().astype(np.uint32)
+
+    def _check_counters(self, counters, what):
+        if counters is not None and (not isinstance(counters, torch.Tensor) or counters.dtype != torch.int64 or tuple(counters.shape) != self._COUNTERS
+                                     or not counters.is_contiguous() or counters.device != self.device):
+            raise ValueError(f"{what}: counters must be a contiguous int64 {self._COUNTERS} tensor on {self.device}")
+
+    def _pfsp_weights(self, mode, exponent, floor, counters):
+        """``pfsp_weights`` of a table of one weight per agent, behind the checks of ``mode`` and ``counters``."""
+        self._check_open()
+        if mode not in PFSP_MODES:
+            raise ValueError(f"pfsp_weights: mode must be one of {sorted(PFSP_MODES)}")
+        self._check_counters(counters, "pfsp_weights")
+        N.check(self._c("pfsp_weights")(self._h, _p(counters), PFSP_MODES[mode], int(exponent), int(floor), self._stream()))
+
+    def seed(self, seed):
+        """New key for the draws; every env's draw counter starts over.  Results, weights and what the envs hold stay."""
+        self._check_open()
+        self._seed = int(seed or 0) & (2 ** 64 - 1)
+        N.check(self._c("seed")(self._h, self._seed, self._stream()))
+
+    def reset(self):
+        """Zeroes the counters and the running returns / lengths (weights, key, draw counters and assignments stay)."""
+        self._check_open()
+        N.check(self._c("reset")(self._h, self._stream()))
+
+
+class DeviceBooks(WeightTable):
     """Results of ``num_envs`` envs over a pool of ``agents`` agents and the weighted draw of an env's next ids.  ``env_id_base``: the
     global id of env 0 (a shard passes its own, so that its draws are those of the whole batch); ``seed``: the key of the draws."""
 
@@ -37,14 +110,12 @@ class DeviceBooks:
         self.env_id_base = int(env_id_base)
         self._seed = int(seed) & (2 ** 64 - 1)
         self._L = N.load()
-        self._words = len(self._NAMES) * int(np.prod(self._PLANE))  # int64 counter words; `ignored` follows them
+        self._COUNTERS = (len(self._NAMES),) + self._PLANE
+        self._words = int(np.prod(self._COUNTERS))  # int64 counter words; `ignored` follows them
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             N.check(self._c("create")(self.device.index, self.num_envs, self.env_id_base, self._seed, self.agents, C.byref(h)))
         self._h = h
-
-    def _c(self, name):
-        return getattr(self._L, self._C + name)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -87,12 +158,6 @@ class DeviceBooks:
         d["ignored"] = int(host[-1])
         return d
 
-    def _check_counters(self, counters, what):
-        shape = (len(self._NAMES),) + self._PLANE
-        if counters is not None and (counters.dtype != torch.int64 or tuple(counters.shape) != shape or not counters.is_contiguous()
-                                     or counters.device != self.device):
-            raise ValueError(f"{what}: counters must be a contiguous int64 {shape} tensor on {self.device}")
-
     def env_state(self):
         """Device tensors (ret int32, len int32, draw_ctr as int32 bits) of the running episodes: copies, no synchronisation."""
         t = [torch.empty((self.num_envs,), dtype=torch.int32, device=self.device) for _ in range(3)]
@@ -106,40 +171,7 @@ class DeviceBooks:
         N.check(self._c("set_agents")(self._h, int(agents), self._stream()))
         self.agents = int(agents)
 
-    def _weight_table(self, weights, what):
-        w = np.asarray(weights)
-        shape = (self.agents,) * len(self._PLANE)
-        if w.shape != shape or (w < 0).any() or (w > 0xFFFFFFFF).any():
-            raise ValueError(f"{what}: {shape} integers in [0, 2^32)")
-        return np.ascontiguousarray(w, np.uint32)
-
-    def set_weights(self, weights):
-        """``weights``: one non-negative integer per agent / per [left][right] cell of the pool (host values); their sum must lie in
-        [1, 2^32).  Weight 0: never drawn."""
-        w = self._weight_table(weights, "set_weights")
-        N.check(self._c("set_weights")(self._h, w.ctypes.data_as(C.c_void_p), w.size, self._stream()))
-
-    def weights_device(self):
-        """int64 device tensor of the shape of a counter plane holding the uint32 table (entries beyond the pool are 0): a copy, no
-        synchronisation."""
-        raw = torch.empty(self._PLANE, dtype=torch.int32, device=self.device)
-        N.check(self._c("get_weights")(self._h, _p(raw), self._stream()))
-        return raw.to(torch.int64) & 0xFFFFFFFF
-
-    def weights(self):
-        """The table of the pool as a host uint32 array (synchronises)."""
-        return self.weights_device()[self._pool()].cpu().numpy().astype(np.uint32)
-
-    # ---- lifetime
-    def seed(self, s):
-        """New key for the draws; every env's draw counter starts over.  Results and weights stay."""
-        self._seed = int(s or 0) & (2 ** 64 - 1)
-        N.check(self._c("seed")(self._h, self._seed, self._stream()))
-
-    def reset(self):
-        """Zeroes the counters and the running returns / lengths (weights, key and draw counters stay)."""
-        N.check(self._c("reset")(self._h, self._stream()))
-
+    # ---- lifetime (the table, ``seed`` and ``reset`` are ``WeightTable``'s)
     def state_dict(self):
         """Everything a continuation needs, as host arrays (synchronises)."""
         both = self._counters_and_ignored().cpu().numpy()

@@ -34,19 +34,21 @@ import torch
 
 from . import _native as N
 from . import checkpoint as ck
-from .books import _p
+from .books import WeightTable, _p
 from .rules import CAR_LEAGUE_KINDS
 
 __all__ = ["CarLeague"]
 
-_MODES = {"hard": N.CRL_LEDGER_PFSP_HARD, "variance": N.CRL_LEDGER_PFSP_VARIANCE}
 _A = N.CRL_LEAGUE_MAX_AGENTS
 _NAMES = N.CRL_CAR_LEAGUE_COUNTER_NAMES
 
 
-class CarLeague:
+class CarLeague(WeightTable):
     """A pool of up to 16 opponents for car 1 of ``env`` -- networks of ``policy`` and styles of ``drivers`` -- with per-env draws and
-    per-agent books.  ``seed``: the key of the draws; the env's ``env_id_base`` makes a shard draw what the whole batch would."""
+    per-agent books.  ``seed``: the key of the draws; the env's ``env_id_base`` makes a shard draw what the whole batch would.  The
+    weight table (``set_weights``, ``weights_device``, ``weights``), ``seed`` and ``reset`` are ``books.WeightTable``'s."""
+
+    _C, _COUNTERS = "crl_car_league_", (len(_NAMES), _A)
 
     def __init__(self, env, policy, drivers, seed=0):
         env = getattr(env, "env", env)  # (a HipCompetitiveCarVecEnv wraps its HipCarVecEnv)
@@ -181,54 +183,13 @@ class CarLeague:
         return agent, ret, length, ctr
 
     # ---- weights
-    def _weight_table(self, weights, what):
-        w = np.asarray(weights)
-        if w.shape != (self.agents,) or self.agents < 1 or (w < 0).any() or (w > 0xFFFFFFFF).any():
-            raise ValueError(f"{what}: {self.agents} integers in [0, 2^32), one per agent of the pool")
-        return np.ascontiguousarray(w, np.uint32)
-
-    def set_weights(self, weights):
-        """One non-negative integer per agent of the pool (host values) whose sum lies in [1, 2^32).  Weight 0: never drawn."""
-        self._check_open()
-        w = self._weight_table(weights, "set_weights")
-        N.check(self._L.crl_car_league_set_weights(self._h, w.ctypes.data_as(C.c_void_p), w.size, self._stream()))
-
-    def weights_device(self):
-        """int64 (16,) device tensor holding the uint32 table (0 beyond the pool): a copy, no synchronisation."""
-        self._check_open()
-        raw = torch.empty((_A,), dtype=torch.int32, device=self.device)
-        N.check(self._L.crl_car_league_get_weights(self._h, _p(raw), self._stream()))
-        return raw.to(torch.int64) & 0xFFFFFFFF
-
-    def weights(self):
-        """The table of the pool as a host uint32 array (synchronises)."""
-        return self.weights_device()[:self.agents].cpu().numpy().astype(np.uint32)
-
     def pfsp_weights(self, mode="hard", exponent=2, floor=1, counters=None):
         """Fills the table on the device by the rule of ``LeagueLedger.pfsp_weights`` over this league's episodes, wins and draws:
         agents car 0 loses to are drawn more often.  ``counters``: an int64 (7, 16) device tensor in place of the league's own (a
         sharded caller passes the all-reduced ``counters_device()``).  No synchronisation."""
-        self._check_open()
-        if mode not in _MODES:
-            raise ValueError(f"pfsp_weights: mode must be one of {sorted(_MODES)}")
-        shape = (len(_NAMES), _A)
-        if counters is not None and (not isinstance(counters, torch.Tensor) or counters.dtype != torch.int64 or tuple(counters.shape) != shape
-                                     or not counters.is_contiguous() or counters.device != self.device):
-            raise ValueError(f"pfsp_weights: counters must be a contiguous int64 {shape} tensor on {self.device}")
-        N.check(self._L.crl_car_league_pfsp_weights(self._h, _p(counters), _MODES[mode], int(exponent), int(floor), self._stream()))
+        self._pfsp_weights(mode, exponent, floor, counters)
 
     # ---- lifetime
-    def seed(self, seed):
-        """New key for the draws; every env's draw counter starts over.  Results, weights and assignments stay."""
-        self._check_open()
-        self._seed = int(seed or 0) & (2 ** 64 - 1)
-        N.check(self._L.crl_car_league_seed(self._h, self._seed, self._stream()))
-
-    def reset(self):
-        """Zeroes the counters and the running returns / lengths (weights, key, draw counters and assignments stay)."""
-        self._check_open()
-        N.check(self._L.crl_car_league_reset(self._h, self._stream()))
-
     def reset_agent(self, name):
         """Zeroes the counters of agent ``name``: its slot took a newer snapshot, the record starts over."""
         self._check_open()

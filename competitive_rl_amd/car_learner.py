@@ -37,6 +37,7 @@ import torch
 from . import _native as N
 from . import checkpoint as K
 from .car_policy import CarPolicy
+from .ppo import _PPOLearner
 from .rules import (CAR_POLICY_KEYS, CAR_POLICY_SHAPES, CAR_PPO_DEFAULTS, adam_reference, car_policy_pack, car_policy_unpack,  # noqa: F401  (re-exported)
                     car_ppo_loss_reference, gae_reference)
 
@@ -253,20 +254,19 @@ class CarRolloutStorage:
         torch.cuda.current_stream(self.device).synchronize()  # the staging tensors above are this call's own
 
 
-class CarPPO:
+class CarPPO(_PPOLearner):
+    """``ppo._PPOLearner`` over ``crl_car_ppo_*``: hyper-parameters, ``step``, ``close`` and the optimiser half of the state dict are
+    the base's; here is what the MLP(21, 2) and its line storage make different."""
+    _C, _DEFAULTS, _FLOATS, _SIZED = "crl_car_ppo_", CAR_PPO_DEFAULTS, N.CRL_CAR_POLICY_BLOB_FLOATS, False
+    _views = staticmethod(car_blob_views)
+    _samples = staticmethod(lambda s: s.num_steps * s.rows)
+    _split = staticmethod(car_policy_unpack)
+
     def __init__(self, weights, device=None, **hyper):
         """``weights``: anything ``rules.car_policy_weights`` takes (a dict of the seven arrays, a torch ``MLP(21, 2)`` state dict, a
         checkpoint path).  ``hyper``: ``clip``, ``vf_coef``, ``ent_coef``, ``lr``, ``betas``, ``eps``, ``max_grad_norm``
         (``rules.CAR_PPO_DEFAULTS``, common continuous-control practice); the dict ``hyper`` may be changed between calls."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("competitive_rl_amd.CarPPO needs a ROCm GPU; there is no CPU fallback")
-        unknown = set(hyper) - set(CAR_PPO_DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown hyper-parameters {sorted(unknown)}; CarPPO takes {sorted(CAR_PPO_DEFAULTS)}")
-        self.hyper = dict(CAR_PPO_DEFAULTS, **hyper)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._open(device, hyper)
         blob = car_policy_pack(weights)
         self._L = N.load()
         h = C.c_void_p()
@@ -274,38 +274,12 @@ class CarPPO:
             N.check(self._L.crl_car_ppo_create(self.device.index or 0, blob.ctypes.data_as(C.c_void_p), C.byref(h)))
         self._h = h
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _hyper(self):
-        h = self.hyper
-        return N.CrlPpoHyper(h["clip"], h["vf_coef"], h["ent_coef"], h["lr"], h["betas"][0], h["betas"][1], h["eps"], h["max_grad_norm"])
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.crl_car_ppo_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _dev_blob(self, ptr):
-        """A float32 (2508,) tensor over the learner's own device memory at ``ptr`` (valid while the learner lives)."""
-        iface = {"shape": (N.CRL_CAR_POLICY_BLOB_FLOATS,), "typestr": "<f4", "data": (ptr, False), "version": 2}
-        holder = type("_Blob", (), {"__cuda_array_interface__": iface, "_keep": self})()
-        return torch.as_tensor(holder, device=self.device)
-
     def grad(self, storage, idx):
         """The gradient of the loss over the samples ``idx`` (int64 on the device, as ``storage.gather`` takes them) of a finished
         ``CarRolloutStorage``, at the learner's weights: a dict of device VIEWS of the seven gradient tensors in torch layout, for
         callers with their own optimiser (``grad_blob()``: the same memory as one flat blob); the next ``grad`` overwrites them.  No
         synchronisation."""
-        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1, "idx: int64 (B,) on the learner's device"
-        assert storage.device == self.device, "the storage lives on another device"
-        idx = idx.contiguous()
-        hyper = self._hyper()
-        with torch.cuda.device(self.device):
-            N.check(self._L.crl_car_ppo_grad(self._h, storage._h, _ptr(idx) if idx.numel() else None, idx.numel(), C.byref(hyper), self._stream()))
-        return car_blob_views(self.grad_blob())
+        return super().grad(storage, idx)
 
     def grad_blob(self):
         """The last gradient as a device VIEW of the learner's own memory: float32 (2508,) in the weights' layout (include/crl.h "car
@@ -318,33 +292,23 @@ class CarPPO:
     def step(self):
         """Clips the last gradient to ``max_grad_norm`` and takes one Adam step on the master weights, in place; the two std floats of
         the blob follow the new log_std.  No synchronisation."""
-        hyper = self._hyper()
-        with torch.cuda.device(self.device):
-            N.check(self._L.crl_car_ppo_step(self._h, C.byref(hyper), self._stream()))
+        super().step()
 
     def update(self, storage, num_epochs, num_mini_batch, generator=None):
         """``num_epochs`` passes over the finished ``storage``: per pass one ``torch.randperm`` on the device cut into
         ``num_mini_batch`` batches of T * R // num_mini_batch samples, ``grad`` and ``step`` per batch.  Nothing synchronises."""
-        total = storage.num_steps * storage.rows
-        size = total // int(num_mini_batch)
-        assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
-        for _ in range(int(num_epochs)):
-            perm = torch.randperm(total, device=self.device, generator=generator)
-            for k in range(int(num_mini_batch)):
-                self.grad(storage, perm[k * size:(k + 1) * size])
-                self.step()
+        super().update(storage, num_epochs, num_mini_batch, generator)
 
     def push(self, policy, name):
         """The master weights into network ``name`` of a ``CarPolicy``: one device-to-device copy ordered on the current stream, the
         host is not touched; the network's sampling flag stays."""
         assert policy.device == self.device, "the policy lives on another device"
-        p = C.c_void_p()
-        N.check(self._L.crl_car_ppo_weights_dev(self._h, C.byref(p)))
+        p = self._blob_dev(policy)
         with torch.cuda.device(self.device):
             N.check(self._L.crl_car_policy_set_weights(policy._h, policy.slot_of(name), p, int(policy.is_deterministic(name)), self._stream()))
 
     def _blob(self):
-        blob = np.empty(N.CRL_CAR_POLICY_BLOB_FLOATS, np.float32)
+        blob = np.empty(self._FLOATS, np.float32)
         with torch.cuda.device(self.device):
             N.check(self._L.crl_car_ppo_get_weights(self._h, blob.ctypes.data_as(C.c_void_p)))
         return blob
@@ -368,26 +332,13 @@ class CarPPO:
             N.check(self._L.crl_car_ppo_stats(self._h, out))
         return CarPPOStats(*out[:6], int(out[6]), int(out[7]))
 
-    # ---- checkpoint / resume
+    # ---- checkpoint / resume: ``state_dict()`` -- the master ``weights`` by key, Adam's moments ``m`` and ``v`` by key (the blob's std
+    # floats, which are derived, are not state), ``steps`` and ``hyper`` -- and ``load_state_dict`` are the base's over these tensors
     def _get_state(self):
-        blobs = [np.empty(N.CRL_CAR_POLICY_BLOB_FLOATS, np.float32) for _ in range(3)]
-        steps = C.c_int64()
-        with torch.cuda.device(self.device):
-            N.check(self._L.crl_car_ppo_get_state(self._h, *[b.ctypes.data_as(C.c_void_p) for b in blobs], C.byref(steps), self._stream()))
-        return blobs, steps.value
+        w, m, v, steps, _ = self._state()
+        return [w, m, v], steps
 
-    def state_dict(self):
-        """Everything a continuation needs, as host arrays (SYNCHRONISES with the current stream): the master ``weights`` by key,
-        Adam's moments ``m`` and ``v`` by key (the blob's std floats, which are derived, are not state), ``steps`` and ``hyper``."""
-        (w, m, v), steps = self._get_state()
-        return {"kind": "CarPPO", "weights": car_policy_unpack(w), "m": car_policy_unpack(m), "v": car_policy_unpack(v), "steps": steps,
-                "hyper": {k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in self.hyper.items()}}
-
-    def load_state_dict(self, sd):
-        """Puts a ``state_dict()`` back: weights, both moments and the step count together, and ``hyper``.  Everything is looked at
-        before anything is written; a refused load raises ``ValueError`` and leaves the learner as it was.  SYNCHRONISES with the
-        current stream.  Afterwards the learner has no gradient until the next ``grad``."""
-        K.check_header(sd, "CarPPO", "CarPPO")
+    def _state_blobs(self, sd):
         blobs = []
         for part in ("weights", "m", "v"):
             try:
@@ -403,10 +354,4 @@ class CarPPO:
                     blobs.append(np.ascontiguousarray(b))
             except (KeyError, TypeError, ValueError) as e:
                 raise K.refuse(f"CarPPO {part}: {e}") from None
-        steps = K.check_counter(sd.get("steps"), 63, "steps", "CarPPO")
-        hyper = sd.get("hyper", self.hyper)
-        if not isinstance(hyper, dict) or set(hyper) - set(CAR_PPO_DEFAULTS):
-            raise K.refuse(f"CarPPO: hyper must be a dict with keys of {sorted(CAR_PPO_DEFAULTS)}")
-        with torch.cuda.device(self.device):
-            N.check(self._L.crl_car_ppo_set_state(self._h, *[b.ctypes.data_as(C.c_void_p) for b in blobs], steps, self._stream()))
-        self.hyper = dict(CAR_PPO_DEFAULTS, **{k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in hyper.items()})
+        return blobs

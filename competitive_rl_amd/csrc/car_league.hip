@@ -7,8 +7,9 @@
 // opponent_policy for the env's life) does on the host: summing both cars' rewards per episode, booking the result under the opponent
 // that drove, and handing the env another opponent when it resets.  Here that is one launch per step with one lane per env, in the
 // shape of books_step_kernel (pong_books.h): a wavefront without an episode end leaves after its loads and stores; one with some
-// reduces them by the keys present and the key's first lane adds with 64-bit integer atomics.  What differs from the Pong books and
-// makes this a kernel of its own: two float32 returns per env, quantised when booked, and the two assignment writes of a redraw.
+// books them by the keys present with books_book_wave, the loop of the Pong books.  What differs from the Pong books and makes this a
+// kernel of its own: two float32 returns per env, quantised when booked, and the two assignment writes of a redraw.  The table of one
+// weight per agent is the ledger's: its draw and its two writers are pong_books.h's.
 #include <math.h>
 
 #include "car_device.h"
@@ -28,27 +29,6 @@ struct CarLeaguePool {
     int8_t net[kCLAgents];    // the policy's slot, -1 for a style
     int8_t style[kCLAgents];  // the driver's slot, -1 for a network
 };
-
-struct CarLeagueTable {
-    uint32_t w[kCLAgents];
-};
-
-// include/crl.h "ledger draws" under CRL_CAR_LEAGUE_DOMAIN; -1 when the table sums to 0 (or past 2^32 - 1)
-__device__ inline int car_league_draw(const uint32_t *__restrict__ w, uint64_t seed, uint64_t gid, uint32_t n) {
-    uint64_t total = 0;
-#pragma unroll
-    for (int a = 0; a < kCLAgents; a++) total += w[a];
-    if (total - 1 >= 0xFFFFFFFFull) return -1;
-    const uint64_t r = league_draw(seed, gid, n, CRL_CAR_LEAGUE_DOMAIN, (uint32_t)total);
-    uint64_t cum = 0;
-    int drawn = -1;
-#pragma unroll
-    for (int a = 0; a < kCLAgents; a++) {
-        cum += w[a];
-        if (drawn < 0 && cum > r) drawn = a;
-    }
-    return drawn;
-}
 
 // q of "car league": a return in units of 1/256
 __device__ inline long long car_league_q(float x) {
@@ -83,14 +63,13 @@ __device__ inline void car_league_serve(const CarLeagueArgs &A, int64_t i, int a
 // step 3 of "car league" for env i: a table without a draw keeps agent, counter and assignments
 __device__ inline void car_league_redraw(const CarLeagueArgs &A, int64_t i) {
     const uint32_t ctr = A.draw_ctr[i];
-    const int drawn = car_league_draw(A.w, A.seed, (uint64_t)(A.id_base + i), ctr);
+    const int drawn = books_draw16(A.w, A.seed, (uint64_t)(A.id_base + i), ctr, CRL_CAR_LEAGUE_DOMAIN);
     if (drawn >= 0 && drawn < A.agents) car_league_serve(A, i, drawn), A.draw_ctr[i] = ctr + 1;
 }
 
 __global__ __launch_bounds__(kBThreads) void car_league_step_kernel(const CarLeagueArgs A, const float *__restrict__ reward,
                                                                    const uint8_t *__restrict__ done, int redraw) {
     const int64_t i = (int64_t)blockIdx.x * kBThreads + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int key = -1;  // the entry this lane's finished episode goes to; -1: no episode ended here, or its agent lies outside the pool
     float r0 = 0.f, r1 = 0.f;
     int steps = 0;
@@ -105,26 +84,9 @@ __global__ __launch_bounds__(kBThreads) void car_league_step_kernel(const CarLea
         }
         A.ret[2 * i] = d ? 0.f : r0, A.ret[2 * i + 1] = d ? 0.f : r1, A.len[i] = d ? 0 : steps;
     }
-    unsigned long long rest = __ballot(key >= 0);
-    while (rest) {  // (uniform) one round per key present in this wavefront; none in the usual case
-        const int c = __shfl(key, __ffsll(rest) - 1);
-        const bool mine = key == c;
-        const unsigned long long m = __ballot(mine);
-        const unsigned long long won = __ballot(mine && r0 > r1), lost = __ballot(mine && r0 < r1);
-        const long long sum0 = wave_sum(mine ? car_league_q(r0) : 0ll), sum1 = wave_sum(mine ? car_league_q(r1) : 0ll);
-        const long long len_sum = wave_sum(mine ? (long long)steps : 0ll);
-        if (lane == __ffsll(m) - 1) {
-            const unsigned long long e = (unsigned long long)__popcll(m), nw = (unsigned long long)__popcll(won), nl = (unsigned long long)__popcll(lost);
-            atomicAdd(&A.counters[CRL_CAR_LEAGUE_EPISODES * kCLAgents + c], e);
-            if (nw) atomicAdd(&A.counters[CRL_CAR_LEAGUE_WINS * kCLAgents + c], nw);
-            if (nl) atomicAdd(&A.counters[CRL_CAR_LEAGUE_LOSSES * kCLAgents + c], nl);
-            if (e - nw - nl) atomicAdd(&A.counters[CRL_CAR_LEAGUE_DRAWS * kCLAgents + c], e - nw - nl);
-            atomicAdd(&A.counters[CRL_CAR_LEAGUE_RETURN_SUM * kCLAgents + c], (unsigned long long)sum0);
-            atomicAdd(&A.counters[CRL_CAR_LEAGUE_OPPONENT_RETURN_SUM * kCLAgents + c], (unsigned long long)sum1);
-            atomicAdd(&A.counters[CRL_CAR_LEAGUE_LENGTH_SUM * kCLAgents + c], (unsigned long long)len_sum);
-        }
-        rest &= ~m;
-    }
+    long long sums[3] = {0ll, 0ll, (long long)steps};  // both returns in units of 1/256, the length
+    if (key >= 0) sums[0] = car_league_q(r0), sums[1] = car_league_q(r1);
+    books_book_wave(key, r0 > r1, r0 < r1, sums, A.counters, kCLAgents);
 }
 
 __global__ __launch_bounds__(kBThreads) void car_league_draw_all_kernel(const CarLeagueArgs A) {
@@ -138,30 +100,6 @@ __global__ __launch_bounds__(kBThreads) void car_league_apply_kernel(const CarLe
     if (i >= A.n) return;
     const int a = A.agent[i];
     if (a >= 0 && a < A.agents) car_league_serve(A, i, a);
-}
-
-// include/crl.h "PFSP weights" over this object's planes: lane a of one wavefront, float64 with one rounding per operation
-__global__ __launch_bounds__(64) void car_league_pfsp_kernel(const long long *__restrict__ counters, int agents, int mode, int exponent,
-                                                            uint32_t floor_w, uint32_t *__restrict__ w) {
-    const int a = threadIdx.x;
-    if (a >= kCLAgents) return;
-    uint32_t out = 0;
-    if (a < agents) {
-        const double episodes = (double)counters[CRL_CAR_LEAGUE_EPISODES * kCLAgents + a], wins = (double)counters[CRL_CAR_LEAGUE_WINS * kCLAgents + a];
-        const double draws = (double)counters[CRL_CAR_LEAGUE_DRAWS * kCLAgents + a];
-        const double p = ((wins + 0.5 * draws) + 1.0) / (episodes + 2.0);
-        const double q = 1.0 - p;
-        double f = q;
-        if (mode == CRL_LEDGER_PFSP_VARIANCE) f = p * q;
-        else
-            for (int j = 1; j < exponent; j++) f = f * q;
-        out = floor_w + (uint32_t)floor(f * 65535.0);
-    }
-    w[a] = out;
-}
-
-__global__ void car_league_set_weights_kernel(CarLeagueTable t, uint32_t *__restrict__ w) {
-    if (threadIdx.x < kCLAgents) w[threadIdx.x] = t.w[threadIdx.x];
 }
 
 __global__ void car_league_set_weight_kernel(int a, uint32_t value, uint32_t *__restrict__ w) {
@@ -315,15 +253,7 @@ int crl_car_league_reset_agent(crl_car_league *l, int32_t agent, void *stream) {
 int crl_car_league_set_weights(crl_car_league *l, const uint32_t *w_host, int32_t count, void *stream) {
     crl_fail_no_ctx();
     if (!l || !w_host) return crl_fail(CRL_EINVAL, "crl_car_league_set_weights: null argument");
-    if (count != l->agents || count < 1) return crl_fail(CRL_EINVAL, "crl_car_league_set_weights: %d weights for a pool of %d agents", count, l->agents);
-    CarLeagueTable t{};
-    uint64_t total = 0;
-    for (int a = 0; a < count; a++) t.w[a] = w_host[a], total += w_host[a];
-    if (total == 0 || total >= (1ull << 32))
-        return crl_fail(CRL_EINVAL, "crl_car_league_set_weights: the weights must sum to a value in [1, 2^32), not %llu", (unsigned long long)total);
-    hipLaunchKernelGGL(car_league_set_weights_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t, l->w);  // (the table travels as kernel arguments)
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return books_set_weights16("crl_car_league_set_weights", l->w, l->agents, w_host, count, (hipStream_t)stream);
 }
 
 int crl_car_league_get_weights(crl_car_league *l, uint32_t *w_out_dev, void *stream) {
@@ -335,15 +265,7 @@ int crl_car_league_get_weights(crl_car_league *l, uint32_t *w_out_dev, void *str
 int crl_car_league_pfsp_weights(crl_car_league *l, const int64_t *counters_dev, int32_t mode, int32_t exponent, uint32_t floor, void *stream) {
     crl_fail_no_ctx();
     if (!l) return crl_fail(CRL_EINVAL, "crl_car_league_pfsp_weights: null league");
-    if (mode != CRL_LEDGER_PFSP_HARD && mode != CRL_LEDGER_PFSP_VARIANCE)
-        return crl_fail(CRL_EINVAL, "crl_car_league_pfsp_weights: mode must be CRL_LEDGER_PFSP_HARD or CRL_LEDGER_PFSP_VARIANCE");
-    if (mode == CRL_LEDGER_PFSP_HARD && (exponent < 1 || exponent > 64)) return crl_fail(CRL_EINVAL, "crl_car_league_pfsp_weights: exponent must be in [1, 64]");
-    if ((uint64_t)l->agents * ((uint64_t)floor + 65535u) >= (1ull << 32))
-        return crl_fail(CRL_EINVAL, "crl_car_league_pfsp_weights: floor %u lets the weights of %d agents sum past 2^32", floor, l->agents);
-    const long long *src = counters_dev ? reinterpret_cast<const long long *>(counters_dev) : reinterpret_cast<const long long *>(l->counters);
-    hipLaunchKernelGGL(car_league_pfsp_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, l->agents, mode, exponent, floor, l->w);
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return books_pfsp16("crl_car_league_pfsp_weights", l->w, l->agents, l->counters, counters_dev, mode, exponent, floor, (hipStream_t)stream);
 }
 
 int crl_car_league_get_counters(crl_car_league *l, int64_t *counters_out_dev, void *stream) {

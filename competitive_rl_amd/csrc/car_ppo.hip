@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "car_learner.h"
+#include "ppo_optim.h"
 
 #pragma clang fp contract(off)
 
@@ -269,10 +270,9 @@ __global__ __launch_bounds__(256) void car_ppo_reduce_kernel(const float *__rest
 }
 
 struct CarStepArgs {
-    float *raw, *m, *v;
-    const float *grad;
+    AdamBlobs b;
     const double *sq_part;
-    float max_norm, b1, b2, omb1, omb2, step_size, bc2_sqrt, eps;
+    AdamArgs h;
 };
 
 // include/crl.h "ppo update", optimiser step, unchanged, over the 2505 trained floats; the lane of log_std_d then rewrites std_d
@@ -281,45 +281,27 @@ __global__ __launch_bounds__(256) void car_ppo_step_kernel(CarStepArgs a) {
     if (i >= kParams) return;
     double sq = a.sq_part[0];
     for (int k = 1; k < kRedBlocks; k++) sq += a.sq_part[k];
-    const float norm = (float)sqrt(sq);
-    const float coef = fminf(1.0f, a.max_norm / (norm + 1e-6f));
-    const float g = a.grad[i] * coef;
-    const float m = a.b1 * a.m[i] + a.omb1 * g;
-    const float v = a.b2 * a.v[i] + a.omb2 * (g * g);
-    a.m[i] = m, a.v[i] = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    const float p = a.raw[i] - a.step_size * (m / denom);
-    a.raw[i] = p;
-    if (i >= kOffTail + 3) a.raw[i + 2] = (float)exp((double)p);  // the serving kernel evaluates no exp
+    const float p = adam_lane(a.h, a.b, i, sq);
+    a.b.raw[i] = p;
+    if (i >= kOffTail + 3) a.b.raw[i + 2] = (float)exp((double)p);  // the serving kernel evaluates no exp
 }
 
 }  // namespace crl
 
 using namespace crl;
 
-struct crl_car_ppo {
-    int device = 0;
-    float *raw = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
+struct crl_car_ppo : PpoBlobs {  // blob_floats is kBlob
     float *partials = nullptr;
     double *stat_part = nullptr, *sq_part = nullptr, *red = nullptr;  // red[1 .. 5]: the statistics' means, red[6]: L
-    int64_t steps = 0;
-    bool have_grad = false;
 };
-
-static int car_ppo_hyper_check(const char *who, const crl_ppo_hyper *h) {
-    if (!h) return crl_fail(CRL_EINVAL, "%s: null hyper-parameters", who);
-    if (!(h->clip >= 0.f) || !(h->lr >= 0.f) || !(h->beta1 >= 0.f && h->beta1 < 1.f) || !(h->beta2 >= 0.f && h->beta2 < 1.f) || !(h->eps > 0.f) ||
-        !(h->max_grad_norm > 0.f) || !(h->vf_coef == h->vf_coef) || !(h->ent_coef == h->ent_coef))
-        return crl_fail(CRL_EINVAL, "%s: clip >= 0, lr >= 0, betas in [0, 1), eps > 0, max_grad_norm > 0, no NaN", who);
-    return CRL_OK;
-}
 
 extern "C" {
 
 void crl_car_ppo_destroy(crl_car_ppo *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    for (void *q : {(void *)p->raw, (void *)p->m, (void *)p->v, (void *)p->grad, (void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red})
+    ppo_free_blobs(p);
+    for (void *q : {(void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red})
         if (q) (void)hipFree(q);
     delete p;
 }
@@ -332,15 +314,7 @@ int crl_car_ppo_set_weights(crl_car_ppo *p, const float *blob_host) {
         if (!(fabsf(blob[i]) <= FLT_MAX)) return crl_fail(CRL_EINVAL, "crl_car_ppo_set_weights: float %d of the blob is not finite", i);
     for (int d = 0; d < 2; d++) blob[kOffTail + 5 + d] = (float)exp((double)blob[kOffTail + 3 + d]);  // derived, not trained
     blob[kBlob - 1] = 0.f;
-    const size_t bytes = kBlob * sizeof(float);
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(p->raw, blob.data(), bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(p->m, 0, bytes));
-    HIP_TRY(hipMemset(p->v, 0, bytes));
-    HIP_TRY(hipDeviceSynchronize());
-    p->steps = 0;
-    return CRL_OK;
+    return ppo_upload(p, blob.data());
 }
 
 int crl_car_ppo_create(int32_t device, const float *blob_host, crl_car_ppo **out) {
@@ -351,9 +325,7 @@ int crl_car_ppo_create(int32_t device, const float *blob_host, crl_car_ppo **out
     crl_car_ppo *p = new crl_car_ppo();
     p->device = device;
     const char *who = "crl_car_ppo_create";
-    int rc = CRL_OK;
-    for (float **q : {&p->raw, &p->m, &p->v, &p->grad})
-        if (rc == CRL_OK) rc = crl_dev_zalloc(q, kBlob * sizeof(float), who);
+    int rc = ppo_alloc_blobs(p, kBlob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->partials, (size_t)kMaxW * kBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->stat_part, (size_t)kMaxW * kStatRow * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->sq_part, kRedBlocks * sizeof(double), who);
@@ -370,10 +342,7 @@ int crl_car_ppo_create(int32_t device, const float *blob_host, crl_car_ppo **out
 int crl_car_ppo_get_weights(crl_car_ppo *p, float *blob_out_host) {
     crl_fail_no_ctx();
     if (!p || !blob_out_host) return crl_fail(CRL_EINVAL, "crl_car_ppo_get_weights: null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(blob_out_host, p->raw, kBlob * sizeof(float), hipMemcpyDeviceToHost));
-    return CRL_OK;
+    return ppo_download(p, blob_out_host);
 }
 
 int crl_car_ppo_weights_dev(crl_car_ppo *p, const float **blob_dev) {
@@ -389,7 +358,7 @@ int crl_car_ppo_grad(crl_car_ppo *p, const crl_car_rollout *rollout, const int64
     if (!p || !rollout || !idx_dev) return crl_fail(CRL_EINVAL, "%s: null argument", who);
     if ((uintptr_t)idx_dev & 7) return crl_fail(CRL_EINVAL, "%s: idx must be 8-byte aligned", who);
     if (count < 1 || count > 0x7fffffff) return crl_fail(CRL_EINVAL, "%s: the number of samples must be in [1, 2^31)", who);
-    if (int rc = car_ppo_hyper_check(who, hyper)) return rc;
+    if (int rc = ppo_hyper_check(who, hyper)) return rc;
     const CarRolloutView view = car_rollout_view(rollout);
     if (!view.finished) return crl_fail(CRL_EINVAL, "%s: the rollout is not finished (crl_car_rollout_finish computes returns and advantages)", who);
     hipStream_t st = (hipStream_t)stream;
@@ -408,25 +377,16 @@ int crl_car_ppo_get_grad(crl_car_ppo *p, const float **grad_dev, float *grad_out
     crl_fail_no_ctx();
     if (!p || (!grad_dev && !grad_out_host)) return crl_fail(CRL_EINVAL, "crl_car_ppo_get_grad: null argument");
     if (!p->have_grad) return crl_fail(CRL_EINVAL, "crl_car_ppo_get_grad: no gradient yet (crl_car_ppo_grad)");
-    if (grad_dev) *grad_dev = p->grad;
-    if (grad_out_host) {
-        HIP_TRY(hipSetDevice(p->device));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(grad_out_host, p->grad, kBlob * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return CRL_OK;
+    return ppo_read_grad(p, grad_dev, grad_out_host);
 }
 
 int crl_car_ppo_step(crl_car_ppo *p, const crl_ppo_hyper *hyper, void *stream) {
     crl_fail_no_ctx();
     if (!p) return crl_fail(CRL_EINVAL, "crl_car_ppo_step: null learner");
-    if (int rc = car_ppo_hyper_check("crl_car_ppo_step", hyper)) return rc;
+    if (int rc = ppo_hyper_check("crl_car_ppo_step", hyper)) return rc;
     if (!p->have_grad) return crl_fail(CRL_EINVAL, "crl_car_ppo_step: no gradient yet (crl_car_ppo_grad)");
     const int64_t t = p->steps + 1;
-    const double b1 = (double)hyper->beta1, b2 = (double)hyper->beta2;
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    CarStepArgs a{p->raw, p->m, p->v, p->grad, p->sq_part, hyper->max_grad_norm, hyper->beta1, hyper->beta2, (float)(1.0 - b1), (float)(1.0 - b2),
-                  (float)((double)hyper->lr / bc1), (float)sqrt(bc2), hyper->eps};
+    const CarStepArgs a{p->adam(), p->sq_part, adam_args(hyper, t)};
     hipLaunchKernelGGL(car_ppo_step_kernel, dim3((kParams + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     p->steps = t;
@@ -454,30 +414,14 @@ int crl_car_ppo_stats(crl_car_ppo *p, double *out8_host) {
 int crl_car_ppo_get_state(crl_car_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t *steps_out, void *stream) {
     crl_fail_no_ctx();
     if (!p) return crl_fail(CRL_EINVAL, "crl_car_ppo_get_state: null learner");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = kBlob * sizeof(float);
-    HIP_TRY(hipSetDevice(p->device));
-    if (blob_out_host) HIP_TRY(hipMemcpyAsync(blob_out_host, p->raw, bytes, hipMemcpyDeviceToHost, st));
-    if (m_out_host) HIP_TRY(hipMemcpyAsync(m_out_host, p->m, bytes, hipMemcpyDeviceToHost, st));
-    if (v_out_host) HIP_TRY(hipMemcpyAsync(v_out_host, p->v, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (steps_out) *steps_out = p->steps;
-    return CRL_OK;
+    return ppo_read_state(p, blob_out_host, m_out_host, v_out_host, steps_out, (hipStream_t)stream);
 }
 
 int crl_car_ppo_set_state(crl_car_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t steps, void *stream) {
     crl_fail_no_ctx();
     if (!p || !blob_host || !m_host || !v_host) return crl_fail(CRL_EINVAL, "crl_car_ppo_set_state: null argument (weights and both moments are set together)");
     if (steps < 0) return crl_fail(CRL_EINVAL, "crl_car_ppo_set_state: steps must be >= 0, not %lld", (long long)steps);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = kBlob * sizeof(float);
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemcpyAsync(p->raw, blob_host, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(p->m, m_host, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(p->v, v_host, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    p->steps = steps, p->have_grad = false;
-    return CRL_OK;
+    return ppo_write_state(p, blob_host, m_host, v_host, steps, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,10 @@
 //       static __device__ void put(int key, int32_t *ids);                                   // the ids of a drawn key
 //   };
 //
+// Beside them, what every table of one weight per agent shares (the ledger's, and the CarRacing league's of car_league.hip, which keeps
+// its own per-env state): the draw over 16 weights, the table's two writers (pong_ledger.hip) and the booking of a wavefront's finished
+// episodes, books_book_wave, which is the loop of both step kernels.
+//
 // The counter planes have one order in both (include/crl.h crl_ledger_counter / crl_arena_counter): episodes, wins of the first
 // party (the learner; the left agent), wins of the second, draws, return sum, length sum; word kBPlanes * kKeys is `ignored`.
 #pragma once
@@ -28,11 +32,64 @@ static_assert(CRL_LEDGER_EPISODES == kBEpisodes && CRL_LEDGER_WINS == kBWins && 
 static_assert(CRL_ARENA_EPISODES == kBEpisodes && CRL_ARENA_LEFT_WINS == kBWins && CRL_ARENA_RIGHT_WINS == kBLosses && CRL_ARENA_DRAWS == kBDraws &&
                   CRL_ARENA_RETURN_SUM == kBReturnSum && CRL_ARENA_LENGTH_SUM == kBLengthSum && CRL_ARENA_COUNTERS == kBPlanes,
               "the arena's counter planes");
+// the CarRacing league books a third sum: its planes from kBReturnSum on are books_book_wave's sums[0 .. 2]
+static_assert(CRL_CAR_LEAGUE_EPISODES == kBEpisodes && CRL_CAR_LEAGUE_WINS == kBWins && CRL_CAR_LEAGUE_LOSSES == kBLosses && CRL_CAR_LEAGUE_DRAWS == kBDraws &&
+                  CRL_CAR_LEAGUE_RETURN_SUM == kBReturnSum && CRL_CAR_LEAGUE_RETURN_SUM == 4 && CRL_CAR_LEAGUE_OPPONENT_RETURN_SUM == kBReturnSum + 1 &&
+                  CRL_CAR_LEAGUE_LENGTH_SUM == kBReturnSum + 2 && CRL_CAR_LEAGUE_COUNTERS == kBReturnSum + 3,
+              "the car league's counter planes");
 
 __device__ inline long long wave_sum(long long v) {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
     return v;
+}
+
+// include/crl.h "ledger draws" over a table of one weight per agent: the smallest a whose cumulative weight exceeds (x0 * T) >> 32, x0
+// drawn under `domain`; -1 when the table sums to 0 (or past 2^32 - 1)
+__device__ inline int books_draw16(const uint32_t *__restrict__ w, uint64_t seed, uint64_t gid, uint32_t n, uint32_t domain) {
+    uint64_t total = 0;
+#pragma unroll
+    for (int a = 0; a < kBAgents; a++) total += w[a];
+    if (total - 1 >= 0xFFFFFFFFull) return -1;
+    const uint64_t r = league_draw(seed, gid, n, domain, (uint32_t)total);
+    uint64_t cum = 0;
+    int drawn = -1;
+#pragma unroll
+    for (int a = 0; a < kBAgents; a++) {
+        cum += w[a];
+        if (drawn < 0 && cum > r) drawn = a;
+    }
+    return drawn;
+}
+
+// Books a wavefront's finished episodes, all lanes of the wavefront together: `key` >= 0 where this lane's episode ended and goes to
+// that key, `won` / `lost` its result, `sums` what it adds to the planes kBReturnSum .. kBReturnSum + NSUM - 1; `keys` is the width of a
+// counter plane.  One round per key present: the first remaining lane's key, a ballot of the lanes on it, popcounts and a shuffle tree
+// per sum, and the key's first lane adds with 64-bit atomics.  Integer sums: the totals do not depend on arrival order, nor on the order
+// in which a wavefront's keys are visited.
+template <int NSUM>
+__device__ inline void books_book_wave(int key, bool won, bool lost, const long long (&sums)[NSUM], unsigned long long *__restrict__ counters, int keys) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long rest = __ballot(key >= 0);
+    while (rest) {  // (uniform) none in the usual case
+        const int c = __shfl(key, __ffsll(rest) - 1);
+        const bool mine = key == c;
+        const unsigned long long m = __ballot(mine);
+        const unsigned long long mw = __ballot(mine && won), ml = __ballot(mine && lost);
+        long long total[NSUM];
+#pragma unroll
+        for (int k = 0; k < NSUM; k++) total[k] = wave_sum(mine ? sums[k] : 0ll);
+        if (lane == __ffsll(m) - 1) {
+            const unsigned long long e = (unsigned long long)__popcll(m), nw = (unsigned long long)__popcll(mw), nl = (unsigned long long)__popcll(ml);
+            atomicAdd(&counters[kBEpisodes * keys + c], e);
+            if (nw) atomicAdd(&counters[kBWins * keys + c], nw);
+            if (nl) atomicAdd(&counters[kBLosses * keys + c], nl);
+            if (e - nw - nl) atomicAdd(&counters[kBDraws * keys + c], e - nw - nl);
+#pragma unroll
+            for (int k = 0; k < NSUM; k++) atomicAdd(&counters[(kBReturnSum + k) * keys + c], (unsigned long long)total[k]);
+        }
+        rest &= ~m;
+    }
 }
 
 // a fresh draw for env i: a table without a draw (Traits::draw < 0) keeps the ids and the counter
@@ -44,9 +101,7 @@ __device__ inline void books_redraw(int32_t *ids, uint32_t *__restrict__ draw_ct
 }
 
 // One launch per step with one lane per env.  Episode ends are rare (one step in several hundred per env), so a wavefront without one
-// leaves after its loads and stores; one with some reduces them by the keys actually present (the first remaining lane's key, a ballot
-// of the lanes on it, popcounts and a shuffle tree for the two sums) and the key's first lane adds with six 64-bit atomics.  Integer
-// sums: the totals do not depend on arrival order, nor on the order in which a wavefront's keys are visited.
+// leaves after its loads and stores; one with some books them by the keys actually present (books_book_wave).
 // `ids_in` are the ids that PLAYED the step; `ids_out` (it may be `ids_in`) the same, redrawn where `done` is set and `redraw` is.
 template <class T>
 __global__ __launch_bounds__(kBThreads) void books_step_kernel(int agents, const int32_t *ids_in, const float *__restrict__ reward, int64_t reward_stride,
@@ -55,7 +110,6 @@ __global__ __launch_bounds__(kBThreads) void books_step_kernel(int agents, const
                                                               unsigned long long *__restrict__ counters, const uint32_t *__restrict__ w, uint64_t seed,
                                                               int64_t env_id_base, int64_t n, int32_t *ids_out) {
     const int64_t i = (int64_t)blockIdx.x * kBThreads + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int key = -1;  // the key this lane's finished episode goes to; -2: an id outside the pool; -1: no episode ended here
     int r = 0, steps = 0;
     if (i < n) {
@@ -74,26 +128,10 @@ __global__ __launch_bounds__(kBThreads) void books_step_kernel(int agents, const
         for (int k = 0; k < T::kIds; k++) ids_out[T::kIds * i + k] = ids[k];
     }
     if (!__ballot(key != -1)) return;  // (uniform) the usual case: no episode of this wavefront ended
-    unsigned long long rest = __ballot(key >= 0);
-    while (rest) {  // (uniform) one round per key present in this wavefront
-        const int c = __shfl(key, __ffsll(rest) - 1);
-        const bool mine = key == c;
-        const unsigned long long m = __ballot(mine);
-        const unsigned long long won = __ballot(mine && r > 0), lost = __ballot(mine && r < 0);
-        const long long ret_sum = wave_sum(mine ? (long long)r : 0ll), len_sum = wave_sum(mine ? (long long)steps : 0ll);
-        if (lane == __ffsll(m) - 1) {
-            const unsigned long long e = (unsigned long long)__popcll(m), nw = (unsigned long long)__popcll(won), nl = (unsigned long long)__popcll(lost);
-            atomicAdd(&counters[kBEpisodes * T::kKeys + c], e);
-            if (nw) atomicAdd(&counters[kBWins * T::kKeys + c], nw);
-            if (nl) atomicAdd(&counters[kBLosses * T::kKeys + c], nl);
-            if (e - nw - nl) atomicAdd(&counters[kBDraws * T::kKeys + c], e - nw - nl);
-            atomicAdd(&counters[kBReturnSum * T::kKeys + c], (unsigned long long)ret_sum);
-            atomicAdd(&counters[kBLengthSum * T::kKeys + c], (unsigned long long)len_sum);
-        }
-        rest &= ~m;
-    }
+    const long long sums[2] = {(long long)r, (long long)steps};
+    books_book_wave(key, r > 0, r < 0, sums, counters, T::kKeys);
     const unsigned long long stray = __ballot(key == -2);
-    if (stray && lane == __ffsll(stray) - 1) atomicAdd(&counters[kBPlanes * T::kKeys], (unsigned long long)__popcll(stray));
+    if (stray && (int)(threadIdx.x & 63) == __ffsll(stray) - 1) atomicAdd(&counters[kBPlanes * T::kKeys], (unsigned long long)__popcll(stray));
 }
 
 // ---- the host object: crl_ledger and crl_arena derive from it
@@ -198,6 +236,14 @@ inline int books_set_env_state(Books *b, const int32_t *ret_dev, const int32_t *
     if (rc == CRL_OK) rc = books_copy(b->len, len_dev, bytes, st);
     return rc != CRL_OK ? rc : books_copy(b->draw_ctr, draw_ctr_dev, bytes, st);
 }
+
+// ---- the table of one weight per agent behind crl_ledger_* and crl_car_league_* (pong_ledger.hip).  `who`: the C function's name;
+// `w`: the table's kBAgents words on the device; `agents`: the pool's size; the null checks are the caller's.
+// crl_*_set_weights: `count` host weights, one per agent of the pool, whose sum lies in [1, 2^32)
+int books_set_weights16(const char *who, uint32_t *w, int agents, const uint32_t *w_host, int32_t count, hipStream_t st);
+// crl_*_pfsp_weights (include/crl.h "PFSP weights") from `counters_dev`, or from the object's `own` counters where that is null
+int books_pfsp16(const char *who, uint32_t *w, int agents, const unsigned long long *own, const int64_t *counters_dev, int32_t mode, int32_t exponent,
+                 uint32_t floor, hipStream_t st);
 
 template <class T>
 int books_step(Books *b, const int32_t *ids_dev, const float *reward_dev, int64_t reward_stride, const uint8_t *done_dev, int redraw, int32_t *ids_out_dev,

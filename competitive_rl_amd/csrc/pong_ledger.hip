@@ -4,8 +4,9 @@
 //
 // Stands in for the bookkeeping a league trainer around the reference's TournamentEnvWrapper does on the host (episode returns per
 // current_agent, competitive_pong_env.py:27-41 has no such record itself): here it is one launch per step with one lane per env,
-// books_step_kernel of pong_books.h keyed by the opponent's id.  This file holds what knows that key: the draw over the 16 weights,
-// the kernels that write them (PFSP among them) and the entry points; lifetime, seed, reset and the copies are the shared Books'.
+// books_step_kernel of pong_books.h keyed by the opponent's id.  This file holds what knows that key and the entry points; lifetime,
+// seed, reset and the copies are the shared Books'.  The writers of a table of one weight per agent (set weights, PFSP) are defined here
+// for the CarRacing league's table as well (pong_books.h declares them).
 #include "pong_books.h"
 
 namespace crl {
@@ -13,41 +14,29 @@ namespace crl {
 static constexpr int kGAgents = kBAgents;
 static constexpr int kGCounters = kBPlanes * kGAgents;  // int64 words; `ignored` is word kGCounters
 
-struct LedgerTable {
+struct Table16 {
     uint32_t w[kGAgents];
 };
 
 struct LedgerTraits {
     static constexpr int kIds = 1, kKeys = kGAgents;
     static __device__ int key(const int32_t *ids, int agents) { return (ids[0] >= 0 && ids[0] < agents) ? ids[0] : -2; }
-    // include/crl.h "ledger draws": the smallest a whose cumulative weight exceeds (x0 * T) >> 32; -1 when the table sums to 0 (or past 2^32)
     static __device__ int draw(const uint32_t *__restrict__ w, uint64_t seed, uint64_t gid, uint32_t n) {
-        uint64_t total = 0;
-#pragma unroll
-        for (int a = 0; a < kGAgents; a++) total += w[a];
-        if (total - 1 >= 0xFFFFFFFFull) return -1;
-        const uint64_t r = league_draw(seed, gid, n, CRL_LEDGER_DOMAIN_OPPONENT, (uint32_t)total);
-        uint64_t cum = 0;
-        int drawn = -1;
-#pragma unroll
-        for (int a = 0; a < kGAgents; a++) {
-            cum += w[a];
-            if (drawn < 0 && cum > r) drawn = a;
-        }
-        return drawn;
+        return books_draw16(w, seed, gid, n, CRL_LEDGER_DOMAIN_OPPONENT);
     }
     static __device__ void put(int key, int32_t *ids) { ids[0] = key; }
 };
 
-// include/crl.h "PFSP weights": lane a of one wavefront, float64 with one rounding per operation (-ffp-contract=off)
-__global__ __launch_bounds__(64) void ledger_pfsp_kernel(const long long *__restrict__ counters, int agents, int mode, int exponent, uint32_t floor_w,
-                                                        uint32_t *__restrict__ w) {
+// include/crl.h "PFSP weights" over counter planes of kGAgents words (the ledger's, the car league's: episodes, wins and draws are
+// planes 0, 1, 3 of both): lane a of one wavefront, float64 with one rounding per operation (-ffp-contract=off)
+__global__ __launch_bounds__(64) void books_pfsp16_kernel(const long long *__restrict__ counters, int agents, int mode, int exponent, uint32_t floor_w,
+                                                         uint32_t *__restrict__ w) {
     const int a = threadIdx.x;
     if (a >= kGAgents) return;
     uint32_t out = 0;
     if (a < agents) {
-        const double episodes = (double)counters[CRL_LEDGER_EPISODES * kGAgents + a], wins = (double)counters[CRL_LEDGER_WINS * kGAgents + a];
-        const double draws = (double)counters[CRL_LEDGER_DRAWS * kGAgents + a];
+        const double episodes = (double)counters[kBEpisodes * kGAgents + a], wins = (double)counters[kBWins * kGAgents + a];
+        const double draws = (double)counters[kBDraws * kGAgents + a];
         const double p = ((wins + 0.5 * draws) + 1.0) / (episodes + 2.0);
         const double q = 1.0 - p;
         double f = q;
@@ -59,7 +48,7 @@ __global__ __launch_bounds__(64) void ledger_pfsp_kernel(const long long *__rest
     w[a] = out;
 }
 
-__global__ void ledger_set_weights_kernel(LedgerTable t, uint32_t *__restrict__ w) {
+__global__ void books_set_weights16_kernel(Table16 t, uint32_t *__restrict__ w) {
     if (threadIdx.x < kGAgents) w[threadIdx.x] = t.w[threadIdx.x];
 }
 
@@ -69,6 +58,31 @@ __global__ void ledger_resize_kernel(int before, int after, uint32_t *__restrict
     if (a >= kGAgents) return;
     if (a >= after) w[a] = 0;
     else if (a >= before) w[a] = 1;
+}
+
+int books_set_weights16(const char *who, uint32_t *w, int agents, const uint32_t *w_host, int32_t count, hipStream_t st) {
+    if (count != agents || count < 1) return crl_fail(CRL_EINVAL, "%s: %d weights for a pool of %d agents", who, count, agents);
+    Table16 t{};
+    uint64_t total = 0;
+    for (int a = 0; a < count; a++) t.w[a] = w_host[a], total += w_host[a];
+    if (total == 0 || total >= (1ull << 32))
+        return crl_fail(CRL_EINVAL, "%s: the weights must sum to a value in [1, 2^32), not %llu", who, (unsigned long long)total);
+    hipLaunchKernelGGL(books_set_weights16_kernel, dim3(1), dim3(64), 0, st, t, w);  // (the table travels as kernel arguments)
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
+}
+
+int books_pfsp16(const char *who, uint32_t *w, int agents, const unsigned long long *own, const int64_t *counters_dev, int32_t mode, int32_t exponent,
+                 uint32_t floor, hipStream_t st) {
+    if (mode != CRL_LEDGER_PFSP_HARD && mode != CRL_LEDGER_PFSP_VARIANCE)
+        return crl_fail(CRL_EINVAL, "%s: mode must be CRL_LEDGER_PFSP_HARD or CRL_LEDGER_PFSP_VARIANCE", who);
+    if (mode == CRL_LEDGER_PFSP_HARD && (exponent < 1 || exponent > 64)) return crl_fail(CRL_EINVAL, "%s: exponent must be in [1, 64]", who);
+    if ((uint64_t)agents * ((uint64_t)floor + 65535u) >= (1ull << 32))
+        return crl_fail(CRL_EINVAL, "%s: floor %u lets the weights of %d agents sum past 2^32", who, floor, agents);
+    const long long *src = counters_dev ? reinterpret_cast<const long long *>(counters_dev) : reinterpret_cast<const long long *>(own);
+    hipLaunchKernelGGL(books_pfsp16_kernel, dim3(1), dim3(64), 0, st, src, agents, mode, exponent, floor, w);
+    HIP_TRY(hipGetLastError());
+    return CRL_OK;
 }
 
 }  // namespace crl
@@ -113,15 +127,7 @@ int crl_ledger_set_agents(crl_ledger *l, int32_t agents, void *stream) {
 int crl_ledger_set_weights(crl_ledger *l, const uint32_t *w_host, int32_t count, void *stream) {
     crl_fail_no_ctx();
     if (!l || !w_host) return crl_fail(CRL_EINVAL, "crl_ledger_set_weights: null argument");
-    if (count != l->agents) return crl_fail(CRL_EINVAL, "crl_ledger_set_weights: %d weights for a pool of %d agents", count, l->agents);
-    LedgerTable t{};
-    uint64_t total = 0;
-    for (int a = 0; a < count; a++) t.w[a] = w_host[a], total += w_host[a];
-    if (total == 0 || total >= (1ull << 32))
-        return crl_fail(CRL_EINVAL, "crl_ledger_set_weights: the weights must sum to a value in [1, 2^32), not %llu", (unsigned long long)total);
-    hipLaunchKernelGGL(ledger_set_weights_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t, l->w);  // (the table travels as kernel arguments)
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return books_set_weights16("crl_ledger_set_weights", l->w, l->agents, w_host, count, (hipStream_t)stream);
 }
 
 int crl_ledger_get_weights(crl_ledger *l, uint32_t *w_out_dev, void *stream) {
@@ -133,15 +139,7 @@ int crl_ledger_get_weights(crl_ledger *l, uint32_t *w_out_dev, void *stream) {
 int crl_ledger_pfsp_weights(crl_ledger *l, const int64_t *counters_dev, int32_t mode, int32_t exponent, uint32_t floor, void *stream) {
     crl_fail_no_ctx();
     if (!l) return crl_fail(CRL_EINVAL, "crl_ledger_pfsp_weights: null ledger");
-    if (mode != CRL_LEDGER_PFSP_HARD && mode != CRL_LEDGER_PFSP_VARIANCE)
-        return crl_fail(CRL_EINVAL, "crl_ledger_pfsp_weights: mode must be CRL_LEDGER_PFSP_HARD or CRL_LEDGER_PFSP_VARIANCE");
-    if (mode == CRL_LEDGER_PFSP_HARD && (exponent < 1 || exponent > 64)) return crl_fail(CRL_EINVAL, "crl_ledger_pfsp_weights: exponent must be in [1, 64]");
-    if ((uint64_t)l->agents * ((uint64_t)floor + 65535u) >= (1ull << 32))
-        return crl_fail(CRL_EINVAL, "crl_ledger_pfsp_weights: floor %u lets the weights of %d agents sum past 2^32", floor, l->agents);
-    const long long *src = counters_dev ? reinterpret_cast<const long long *>(counters_dev) : reinterpret_cast<const long long *>(l->counters);
-    hipLaunchKernelGGL(ledger_pfsp_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, l->agents, mode, exponent, floor, l->w);
-    HIP_TRY(hipGetLastError());
-    return CRL_OK;
+    return books_pfsp16("crl_ledger_pfsp_weights", l->w, l->agents, l->counters, counters_dev, mode, exponent, floor, (hipStream_t)stream);
 }
 
 int crl_ledger_get_counters(crl_ledger *l, int64_t *counters_out_dev, int64_t *ignored_out_dev, void *stream) {

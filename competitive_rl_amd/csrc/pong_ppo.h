@@ -1,7 +1,7 @@
 // pong_ppo.h -- what the two learners (pong_ppo.hip: the LightActorCritic, pong_ppo_full.hip: the full-size ActorCritic) share: the
 // crl_ppo object and its host helpers (the four blobs), the reduce kernel, the sample fetch (which sample is row i of idx, its
 // scalars, its planes by the stack rule), the per-sample closed forms of include/crl.h "ppo update" with or without a teacher, and the
-// byte / 255 of the gradient kernels.
+// byte / 255 of the gradient kernels.  The blobs' helpers, the hyper-parameter check and the optimiser step are ppo_optim.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +9,7 @@
 #include "crl_internal.h"
 #include "pong_ring.h"
 #include "pong_rollout.h"
+#include "ppo_optim.h"
 
 namespace crl {
 
@@ -201,25 +202,15 @@ int64_t ppo_full_scratch_rows(const PpoFull *f);  // samples per chunk of a mini
 int ppo_full_grad(::crl_ppo *p, const RolloutView &view, const int64_t *idx_dev, int64_t count, const PpoHyperDev &h, const PpoTeacherDev *t,
                   hipStream_t st);
 
-// ---- either learner's host side (pong_ppo.hip)
-// raw, m, v, grad of blob_floats floats and red, zeroed
-int ppo_alloc_blobs(::crl_ppo *p, int blob_floats, const char *who);
-// a packed host blob becomes the master weights; both moments and the step count go to zero (synchronises)
-int ppo_upload(::crl_ppo *p, const float *blob);
-// the master blob on the host (synchronises)
-int ppo_download(::crl_ppo *p, float *blob);
+// either learner's four blobs (ppo_alloc_blobs) and red, zeroed (pong_ppo.hip)
+int ppo_alloc(::crl_ppo *p, int blob_floats, const char *who);
 
 }  // namespace crl
 
-struct crl_ppo {
-    int device = 0;
-    int blob_floats = 0;  // the master blob, both moments and the gradient: 8 488 floats (light) or 1 001 784 (full size)
-    float *raw = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
+struct crl_ppo : crl::PpoBlobs {
     double *red = nullptr;  // [0]: the gradient's sum of squares, [1 .. 5]: the statistics' means, [6 .. 9]: a teacher gradient's four
     float *partials = nullptr;                        // light: [W][blob]
     double *stat_part = nullptr, *sq_part = nullptr;  // light (stat_part: [W][5], a teacher gradient's [W][9])
     crl::PpoFull *full = nullptr;                     // crl_ppo_create_full
-    int64_t steps = 0;  // optimiser steps taken (the t of the bias corrections)
-    bool have_grad = false;
     bool teacher_grad = false;  // the last gradient was crl_ppo_grad_teacher's: red[6 .. 9] are its statistics
 };

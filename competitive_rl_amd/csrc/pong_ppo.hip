@@ -1,8 +1,9 @@
 // pong_ppo.hip -- the learner's PPO update for the LightActorCritic on the device (include/crl.h "ppo update"): the gradient of the
 // clipped-surrogate loss over a minibatch of a crl_rollout, read from the stored uint8 planes, and the clip + Adam step on a master blob
 // in the layout of pong_league.h.  Three launches per gradient (gradient, reduce, final) and one per step; nothing touches the host.
-// What the full-size learner (pong_ppo_full.hip) shares lives here too: the blobs' host side (ppo_alloc_blobs, ppo_upload, ppo_download),
-// and the step kernel; the sample fetch, the loss terms and the reduce kernel of both are pong_ppo.h's.
+// What the other learners share lives here too: the host side of ppo_optim.h (the hyper-parameter check and the blobs' helpers, the
+// CarRacing learner's as well) and, with pong_ppo_full.hip, the step kernel; the sample fetch, the loss terms and the reduce kernel of
+// both Pong learners are pong_ppo.h's.
 //
 // The reference ships no trainer (utils/network.py has only the networks): the loss is the written rule of the header.
 //
@@ -370,37 +371,79 @@ __global__ void pong_ppo_final_kernel(const double *__restrict__ sq_part, const 
 }
 
 struct StepArgs {
-    float *raw, *m, *v;
-    const float *grad;
+    AdamBlobs b;
     const double *red;  // [0]: the gradient's sum of squares
-    float max_norm, b1, b2, omb1, omb2, step_size, bc2_sqrt, eps;
+    AdamArgs h;
     int n;  // the blob's floats
 };
 
-// include/crl.h "ppo update", optimiser step, over a blob of a.n floats (either learner's): float32, one rounding per operation (-ffp-contract=off; sqrtf and / correctly rounded)
+// include/crl.h "ppo update", optimiser step, over a blob of a.n floats (either learner's)
 __global__ __launch_bounds__(256) void pong_ppo_step_kernel(StepArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
-    const float norm = (float)sqrt(a.red[0]);
-    const float coef = fminf(1.0f, a.max_norm / (norm + 1e-6f));
-    const float g = a.grad[i] * coef;
-    const float m = a.b1 * a.m[i] + a.omb1 * g;
-    const float v = a.b2 * a.v[i] + a.omb2 * (g * g);
-    a.m[i] = m, a.v[i] = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.raw[i] = a.raw[i] - a.step_size * (m / denom);
+    a.b.raw[i] = adam_lane(a.h, a.b, i, a.red[0]);
 }
 
-int ppo_alloc_blobs(::crl_ppo *p, int blob_floats, const char *who) {
+// ---- ppo_optim.h's host side, every learner's
+int ppo_hyper_check(const char *who, const crl_ppo_hyper *h) {
+    if (!h) return crl_fail(CRL_EINVAL, "%s: null hyper-parameters", who);
+    if (!(h->clip >= 0.f) || !(h->lr >= 0.f) || !(h->beta1 >= 0.f && h->beta1 < 1.f) || !(h->beta2 >= 0.f && h->beta2 < 1.f) || !(h->eps > 0.f) ||
+        !(h->max_grad_norm > 0.f) || !(h->vf_coef == h->vf_coef) || !(h->ent_coef == h->ent_coef))
+        return crl_fail(CRL_EINVAL, "%s: clip >= 0, lr >= 0, betas in [0, 1), eps > 0, max_grad_norm > 0, no NaN", who);
+    return CRL_OK;
+}
+
+int ppo_alloc_blobs(PpoBlobs *p, int blob_floats, const char *who) {
     p->blob_floats = blob_floats;
     int rc = CRL_OK;
     for (float **q : {&p->raw, &p->m, &p->v, &p->grad})
         if (rc == CRL_OK) rc = crl_dev_zalloc(q, (size_t)blob_floats * sizeof(float), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
     return rc;
 }
 
-int ppo_upload(::crl_ppo *p, const float *blob) {
+void ppo_free_blobs(PpoBlobs *p) {
+    for (float *q : {p->raw, p->m, p->v, p->grad})
+        if (q) (void)hipFree(q);
+}
+
+int ppo_alloc(::crl_ppo *p, int blob_floats, const char *who) {
+    const int rc = ppo_alloc_blobs(p, blob_floats, who);
+    return rc != CRL_OK ? rc : crl_dev_zalloc(&p->red, (1 + kStatAll) * sizeof(double), who);
+}
+
+int ppo_read_grad(PpoBlobs *p, const float **grad_dev, float *grad_out_host) {
+    if (grad_dev) *grad_dev = p->grad;
+    if (grad_out_host) {
+        HIP_TRY(hipSetDevice(p->device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(grad_out_host, p->grad, (size_t)p->blob_floats * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return CRL_OK;
+}
+
+int ppo_read_state(PpoBlobs *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t *steps_out, hipStream_t st) {
+    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
+    HIP_TRY(hipSetDevice(p->device));
+    if (blob_out_host) HIP_TRY(hipMemcpyAsync(blob_out_host, p->raw, bytes, hipMemcpyDeviceToHost, st));
+    if (m_out_host) HIP_TRY(hipMemcpyAsync(m_out_host, p->m, bytes, hipMemcpyDeviceToHost, st));
+    if (v_out_host) HIP_TRY(hipMemcpyAsync(v_out_host, p->v, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (steps_out) *steps_out = p->steps;
+    return CRL_OK;
+}
+
+int ppo_write_state(PpoBlobs *p, const float *blob_host, const float *m_host, const float *v_host, int64_t steps, hipStream_t st) {
+    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemcpyAsync(p->raw, blob_host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->m, m_host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->v, v_host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    p->steps = steps, p->have_grad = false;
+    return CRL_OK;
+}
+
+int ppo_upload(PpoBlobs *p, const float *blob) {
     const size_t bytes = (size_t)p->blob_floats * sizeof(float);
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -412,7 +455,7 @@ int ppo_upload(::crl_ppo *p, const float *blob) {
     return CRL_OK;
 }
 
-int ppo_download(::crl_ppo *p, float *blob) {
+int ppo_download(PpoBlobs *p, float *blob) {
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(blob, p->raw, (size_t)p->blob_floats * sizeof(float), hipMemcpyDeviceToHost));
@@ -427,14 +470,6 @@ static void ppo_pack(float *blob, const float *const t[8]) {
     for (int i = 0; i < kBlob; i++) blob[i] = 0.f;
     policy_light_pack(blob, t[0], t[1], t[2], t[3], t[4], t[5]);
     policy_light_pack_critic(blob + kLightWc, t[6], t[7]);
-}
-
-static int ppo_hyper_check(const char *who, const crl_ppo_hyper *h) {
-    if (!h) return crl_fail(CRL_EINVAL, "%s: null hyper-parameters", who);
-    if (!(h->clip >= 0.f) || !(h->lr >= 0.f) || !(h->beta1 >= 0.f && h->beta1 < 1.f) || !(h->beta2 >= 0.f && h->beta2 < 1.f) || !(h->eps > 0.f) ||
-        !(h->max_grad_norm > 0.f) || !(h->vf_coef == h->vf_coef) || !(h->ent_coef == h->ent_coef))
-        return crl_fail(CRL_EINVAL, "%s: clip >= 0, lr >= 0, betas in [0, 1), eps > 0, max_grad_norm > 0, no NaN", who);
-    return CRL_OK;
 }
 
 // the light learner's three launches; TEACHER chooses the instantiations, their LDS and the statistics' count
@@ -455,7 +490,8 @@ void crl_ppo_destroy(crl_ppo *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     ppo_full_destroy(p->full);
-    for (void *q : {(void *)p->raw, (void *)p->m, (void *)p->v, (void *)p->grad, (void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red})
+    ppo_free_blobs(p);
+    for (void *q : {(void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red})
         if (q) (void)hipFree(q);
     delete p;
 }
@@ -482,7 +518,7 @@ int crl_ppo_create(int32_t device, const float *conv1_w, const float *conv1_b, c
     crl_ppo *p = new crl_ppo();
     p->device = device;
     const char *who = "crl_ppo_create";
-    int rc = ppo_alloc_blobs(p, kBlob, who);
+    int rc = ppo_alloc(p, kBlob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->partials, (size_t)kGMaxGroups * kBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->stat_part, (size_t)kGMaxGroups * kStatAll * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->sq_part, kRedBlocks * sizeof(double), who);
@@ -576,13 +612,7 @@ int crl_ppo_get_grad(crl_ppo *p, const float **grad_dev, float *grad_out_host) {
     crl_fail_no_ctx();
     if (!p || (!grad_dev && !grad_out_host)) return crl_fail(CRL_EINVAL, "crl_ppo_get_grad: null argument");
     if (!p->have_grad) return crl_fail(CRL_EINVAL, "crl_ppo_get_grad: no gradient yet (crl_ppo_grad)");
-    if (grad_dev) *grad_dev = p->grad;
-    if (grad_out_host) {
-        HIP_TRY(hipSetDevice(p->device));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(grad_out_host, p->grad, (size_t)p->blob_floats * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return CRL_OK;
+    return ppo_read_grad(p, grad_dev, grad_out_host);
 }
 
 int crl_ppo_step(crl_ppo *p, const crl_ppo_hyper *hyper, void *stream) {
@@ -591,10 +621,7 @@ int crl_ppo_step(crl_ppo *p, const crl_ppo_hyper *hyper, void *stream) {
     if (int rc = ppo_hyper_check("crl_ppo_step", hyper)) return rc;
     if (!p->have_grad) return crl_fail(CRL_EINVAL, "crl_ppo_step: no gradient yet (crl_ppo_grad)");
     const int64_t t = p->steps + 1;
-    const double b1 = (double)hyper->beta1, b2 = (double)hyper->beta2;
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    StepArgs a{p->raw, p->m, p->v, p->grad, p->red, hyper->max_grad_norm, hyper->beta1, hyper->beta2, (float)(1.0 - b1), (float)(1.0 - b2),
-               (float)((double)hyper->lr / bc1), (float)sqrt(bc2), hyper->eps, p->blob_floats};
+    const StepArgs a{p->adam(), p->red, adam_args(hyper, t), p->blob_floats};
     hipLaunchKernelGGL(pong_ppo_step_kernel, dim3((p->blob_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     p->steps = t;
@@ -632,14 +659,7 @@ int crl_ppo_get_state(crl_ppo *p, float *blob_out_host, float *m_out_host, float
     if (!p) return crl_fail(CRL_EINVAL, "crl_ppo_get_state: null learner");
     if ((blob_out_host || m_out_host || v_out_host) && blob_floats != p->blob_floats)
         return crl_fail(CRL_EINVAL, "crl_ppo_get_state: blob_floats %lld, but this learner's blob holds %d", (long long)blob_floats, p->blob_floats);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
-    HIP_TRY(hipSetDevice(p->device));
-    if (blob_out_host) HIP_TRY(hipMemcpyAsync(blob_out_host, p->raw, bytes, hipMemcpyDeviceToHost, st));
-    if (m_out_host) HIP_TRY(hipMemcpyAsync(m_out_host, p->m, bytes, hipMemcpyDeviceToHost, st));
-    if (v_out_host) HIP_TRY(hipMemcpyAsync(v_out_host, p->v, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (steps_out) *steps_out = p->steps;
+    if (int rc = ppo_read_state(p, blob_out_host, m_out_host, v_out_host, steps_out, (hipStream_t)stream)) return rc;
     if (scratch_rows_out) *scratch_rows_out = p->full ? ppo_full_scratch_rows(p->full) : 0;
     return CRL_OK;
 }
@@ -650,14 +670,8 @@ int crl_ppo_set_state(crl_ppo *p, const float *blob_host, const float *m_host, c
     if (blob_floats != p->blob_floats)
         return crl_fail(CRL_EINVAL, "crl_ppo_set_state: blob_floats %lld, but this learner's blob holds %d", (long long)blob_floats, p->blob_floats);
     if (steps < 0) return crl_fail(CRL_EINVAL, "crl_ppo_set_state: steps must be >= 0, not %lld", (long long)steps);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)p->blob_floats * sizeof(float);
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemcpyAsync(p->raw, blob_host, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(p->m, m_host, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(p->v, v_host, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    p->steps = steps, p->have_grad = false, p->teacher_grad = false;
+    if (int rc = ppo_write_state(p, blob_host, m_host, v_host, steps, (hipStream_t)stream)) return rc;
+    p->teacher_grad = false;
     return CRL_OK;
 }
 

@@ -680,7 +680,7 @@ int crl_ppo_create_full(int32_t device, int64_t scratch_rows, const float *conv1
     const int64_t S = f->scratch_rows = scratch_rows ? scratch_rows : kDefaultRows;
     if (hipDeviceGetAttribute(&f->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || f->cus <= 0) f->cus = 256;
     const char *who = "crl_ppo_create_full";
-    int rc = ppo_alloc_blobs(p, kFullBlob, who);
+    int rc = ppo_alloc(p, kFullBlob, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->gacc, (size_t)kFullBlob * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->act2, (size_t)S * kK3 * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&f->a3, (size_t)S * kC3 * sizeof(float), who);

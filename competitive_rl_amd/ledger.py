@@ -16,10 +16,10 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .books import DeviceBooks, _p
-from .rules import league_draw_reference
+from .books import PFSP_MODES as _MODES
+from .books import DeviceBooks
+from .rules import weighted_draw_reference
 
-_MODES = {"hard": N.CRL_LEDGER_PFSP_HARD, "variance": N.CRL_LEDGER_PFSP_VARIANCE}
 _A = N.CRL_LEAGUE_MAX_AGENTS
 
 
@@ -56,10 +56,7 @@ class LeagueLedger(DeviceBooks):
         ``"variance"``: p (1 - p); weight = floor + int(f * 65535).  ``counters``: an int64 (6, 16) device tensor in place of the
         ledger's own (a sharded caller passes the all-reduced ``counters_device()`` so that every rank holds the same table).  No
         synchronisation."""
-        if mode not in _MODES:
-            raise ValueError(f"pfsp_weights: mode must be one of {sorted(_MODES)}")
-        self._check_counters(counters, "pfsp_weights")
-        N.check(self._L.crl_ledger_pfsp_weights(self._h, _p(counters), _MODES[mode], int(exponent), int(floor), self._stream()))
+        self._pfsp_weights(mode, exponent, floor, counters)
 
 
 def ledger_draw_reference(seed, gid, counter, weights):
@@ -70,11 +67,7 @@ def ledger_draw_reference(seed, gid, counter, weights):
     w = np.asarray(weights)
     if w.ndim != 1 or not 1 <= len(w) <= _A or (w < 0).any():
         raise ValueError(f"1 to {_A} non-negative weights")
-    total = int(w.astype(np.uint64).sum())
-    if not 0 < total < 2 ** 32:
-        raise ValueError(f"the weights must sum to a value in [1, 2^32), not {total}")
-    r = league_draw_reference(seed, gid, counter, N.CRL_LEDGER_DOMAIN_OPPONENT, total)  # (x * T) >> 32
-    return np.searchsorted(np.cumsum(w.astype(np.int64)), r, side="right").astype(np.int64)
+    return weighted_draw_reference(seed, gid, counter, N.CRL_LEDGER_DOMAIN_OPPONENT, w)
 
 
 def pfsp_weights_reference(counters, agents, mode="hard", exponent=2, floor=1):

@@ -146,25 +146,42 @@ def _full_learner_weights(source):
     return {**{k: w[k] for k in _FULL_KEYS}, **{k: critic[k] for k in _CRITIC_KEYS}}
 
 
-class _PPOLearner:
-    """What the two learners share: everything but the network's tensors, its create / weight calls and its push targets."""
-    _KEYS, _LAYOUT, _FLOATS = PPO_KEYS, BLOB_LAYOUT, BLOB_FLOATS
-    _weights_of = staticmethod(_learner_weights)
+def _plain(hyper):
+    return {k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in hyper.items()}
 
-    def _setup(self, weights_or_checkpoint, device, hyper):
+
+class _PPOLearner:
+    """What the learners share (the two of Pong here, ``car_learner.CarPPO``): everything but the network's tensors, its create /
+    weight calls, its statistics and its push targets.  A subclass names what differs as class attributes."""
+    _C = "crl_ppo_"              # the C prefix of the learner's calls
+    _DEFAULTS = PPO_DEFAULTS     # the hyper-parameters and their defaults
+    _KEYS, _LAYOUT, _FLOATS = PPO_KEYS, BLOB_LAYOUT, BLOB_FLOATS
+    _SIZED = True                # crl_ppo_get_state / set_state carry the blob's size and scratch_rows: one C object, two networks
+    _weights_of = staticmethod(_learner_weights)
+    _views = staticmethod(blob_views)                                  # a flat blob as the tensors' views by key
+    _samples = staticmethod(lambda s: s.num_steps * s.num_envs)        # the samples a finished storage holds
+
+    def _open(self, device, hyper):
+        """What every constructor starts with: the GPU, the hyper-parameters, the device."""
         name = type(self).__name__
         if not torch.cuda.is_available():
             raise RuntimeError(f"competitive_rl_amd.{name} needs a ROCm GPU; there is no CPU fallback")
-        unknown = set(hyper) - set(PPO_DEFAULTS)
+        unknown = set(hyper) - set(self._DEFAULTS)
         if unknown:
-            raise TypeError(f"unknown hyper-parameters {sorted(unknown)}; {name} takes {sorted(PPO_DEFAULTS)}")
-        self.hyper = dict(PPO_DEFAULTS, **hyper)
+            raise TypeError(f"unknown hyper-parameters {sorted(unknown)}; {name} takes {sorted(self._DEFAULTS)}")
+        self.hyper = dict(self._DEFAULTS, **hyper)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def _setup(self, weights_or_checkpoint, device, hyper):
+        self._open(device, hyper)
         w = self._weights_of(weights_or_checkpoint)
         self._L = N.load()
         return [w[k].ctypes.data_as(C.c_void_p) for k in self._KEYS]
+
+    def _c(self, name):
+        return getattr(self._L, self._C + name)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -175,7 +192,7 @@ class _PPOLearner:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.crl_ppo_destroy(self._h)
+            self._c("destroy")(self._h)
             self._h = None
 
     __del__ = close
@@ -198,36 +215,37 @@ class _PPOLearner:
         if teacher is not None:
             if not isinstance(teacher, Teacher):
                 raise ValueError(f"teacher must be a Teacher or None, not {type(teacher).__name__}")
-            native = teacher._native(self.device, storage.num_steps * storage.num_envs)
+            native = teacher._native(self.device, self._samples(storage))
         with torch.cuda.device(self.device):
             ip = C.c_void_p(idx.data_ptr()) if idx.numel() else None
             if teacher is None:
-                N.check(self._L.crl_ppo_grad(self._h, storage._h, ip, idx.numel(), C.byref(hyper), self._stream()))
+                N.check(self._c("grad")(self._h, storage._h, ip, idx.numel(), C.byref(hyper), self._stream()))
             else:
-                N.check(self._L.crl_ppo_grad_teacher(self._h, storage._h, ip, idx.numel(), C.byref(hyper), C.byref(native), self._stream()))
+                N.check(self._c("grad_teacher")(self._h, storage._h, ip, idx.numel(), C.byref(hyper), C.byref(native), self._stream()))
                 for t in teacher._tensors():  # (the launches read them: a caching allocator must not hand them out before that)
                     t.record_stream(torch.cuda.current_stream(self.device))
             p = C.c_void_p()
-            N.check(self._L.crl_ppo_get_grad(self._h, C.byref(p), None))
-        return blob_views(self._dev_blob(p.value))
+            N.check(self._c("get_grad")(self._h, C.byref(p), None))
+        return self._views(self._dev_blob(p.value))
 
     def step(self):
         """Clips the last gradient to ``max_grad_norm`` and takes one Adam step on the master weights, in place.  No synchronisation."""
         hyper = self._hyper()
         with torch.cuda.device(self.device):
-            N.check(self._L.crl_ppo_step(self._h, C.byref(hyper), self._stream()))
+            N.check(self._c("step")(self._h, C.byref(hyper), self._stream()))
 
     def update(self, storage, num_epochs, num_mini_batch, generator=None, teacher=None):
         """``num_epochs`` passes over the finished ``storage``: per pass one ``torch.randperm`` on the device (``generator``: a device
         generator, for a reproducible order) cut into ``num_mini_batch`` batches of T * N // num_mini_batch samples, ``grad`` and ``step``
         per batch; ``teacher`` goes to every ``grad``.  Nothing synchronises."""
-        total = storage.num_steps * storage.num_envs
+        total = self._samples(storage)
         size = total // int(num_mini_batch)
         assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
+        extra = () if teacher is None else (teacher,)  # (a learner without a teacher term takes none)
         for _ in range(int(num_epochs)):
             perm = torch.randperm(total, device=self.device, generator=generator)
             for k in range(int(num_mini_batch)):
-                self.grad(storage, perm[k * size:(k + 1) * size], teacher)
+                self.grad(storage, perm[k * size:(k + 1) * size], *extra)
                 self.step()
 
     def teacher_stats(self):
@@ -236,12 +254,12 @@ class _PPOLearner:
         Refuses after a plain ``grad``.  Synchronises the device: logging and tests."""
         out = (C.c_double * 4)()
         with torch.cuda.device(self.device):
-            N.check(self._L.crl_ppo_teacher_stats(self._h, out))
+            N.check(self._c("teacher_stats")(self._h, out))
         return TeacherStats(*out)
 
     def _blob_dev(self, target):
         p = C.c_void_p()
-        N.check(self._L.crl_ppo_weights_dev(self._h, C.byref(p)))
+        N.check(self._c("weights_dev")(self._h, C.byref(p)))
         assert target.device == self.device, "the target lives on another device"
         return p
 
@@ -267,22 +285,34 @@ class _PPOLearner:
         return PPOStats(*out[:6], int(out[6]))
 
     # ---- checkpoint / resume (include/crl.h "checkpoint / resume")
-    def _get_state(self, want_blobs=True):
+    def _state(self, want_blobs=True):
         """(weights blob, m blob, v blob, steps, scratch_rows) as the device holds them, behind the work enqueued on the current stream"""
         blobs = [np.empty(self._FLOATS, np.float32) if want_blobs else None for _ in range(3)]
         steps, rows = C.c_int64(), C.c_int64()
+        tail = (self._FLOATS, C.byref(steps), C.byref(rows)) if self._SIZED else (C.byref(steps),)
         with torch.cuda.device(self.device):
-            N.check(self._L.crl_ppo_get_state(self._h, *[b.ctypes.data_as(C.c_void_p) if want_blobs else None for b in blobs], self._FLOATS,
-                                              C.byref(steps), C.byref(rows), self._stream()))
+            N.check(self._c("get_state")(self._h, *[b.ctypes.data_as(C.c_void_p) if want_blobs else None for b in blobs], *tail, self._stream()))
         return blobs[0], blobs[1], blobs[2], steps.value, rows.value
+
+    def _split(self, blob):
+        """A host blob as the dict of arrays by key that ``state_dict`` carries."""
+        return K.split_blob(blob, self._LAYOUT)
+
+    def _state_blobs(self, sd):
+        """The tensor half of ``load_state_dict``: the three host blobs of ``sd``'s weights, m and v, or a refusal."""
+        name = type(self).__name__
+        rows = self._state(want_blobs=False)[4]
+        if rows and int(sd.get("scratch_rows", -1)) != rows:
+            raise K.refuse(f"{name}: scratch_rows is {sd.get('scratch_rows')} in the state dict and {rows} here (it is part of the summation shape)")
+        return [K.join_blob(sd.get(k), self._LAYOUT, self._FLOATS, f"{name} {k}") for k in ("weights", "m", "v")]
 
     def state_dict(self):
         """Everything a continuation needs, as host arrays (SYNCHRONISES with the current stream): ``kind``, the master ``weights`` by
         key, Adam's moments ``m`` and ``v`` by key in the same layout, the optimiser ``steps`` taken, ``hyper`` and, for ``FullPPO``,
         ``scratch_rows`` (part of the summation shape).  The last gradient and its statistics are not state."""
-        w, m, v, steps, rows = self._get_state()
-        sd = {"kind": type(self).__name__, "weights": K.split_blob(w, self._LAYOUT), "m": K.split_blob(m, self._LAYOUT),
-              "v": K.split_blob(v, self._LAYOUT), "steps": steps, "hyper": {k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in self.hyper.items()}}
+        w, m, v, steps, rows = self._state()
+        sd = {"kind": type(self).__name__, "weights": self._split(w), "m": self._split(m), "v": self._split(v), "steps": steps,
+              "hyper": _plain(self.hyper)}
         if rows:
             sd["scratch_rows"] = rows
         return sd
@@ -295,17 +325,15 @@ class _PPOLearner:
         the next ``grad``, as on a fresh learner."""
         name = type(self).__name__
         K.check_header(sd, name, name)
-        rows = self._get_state(want_blobs=False)[4]
-        if rows and int(sd.get("scratch_rows", -1)) != rows:
-            raise K.refuse(f"{name}: scratch_rows is {sd.get('scratch_rows')} in the state dict and {rows} here (it is part of the summation shape)")
-        blobs = [K.join_blob(sd.get(k), self._LAYOUT, self._FLOATS, f"{name} {k}") for k in ("weights", "m", "v")]
+        blobs = self._state_blobs(sd)
         steps = K.check_counter(sd.get("steps"), 63, "steps", name)
         hyper = sd.get("hyper", self.hyper)
-        if not isinstance(hyper, dict) or set(hyper) - set(PPO_DEFAULTS):
-            raise K.refuse(f"{name}: hyper must be a dict with keys of {sorted(PPO_DEFAULTS)}")
+        if not isinstance(hyper, dict) or set(hyper) - set(self._DEFAULTS):
+            raise K.refuse(f"{name}: hyper must be a dict with keys of {sorted(self._DEFAULTS)}")
+        tail = (self._FLOATS, steps) if self._SIZED else (steps,)
         with torch.cuda.device(self.device):
-            N.check(self._L.crl_ppo_set_state(self._h, *[b.ctypes.data_as(C.c_void_p) for b in blobs], self._FLOATS, steps, self._stream()))
-        self.hyper = dict(PPO_DEFAULTS, **{k: (tuple(x) if isinstance(x, (tuple, list)) else x) for k, x in hyper.items()})
+            N.check(self._c("set_state")(self._h, *[b.ctypes.data_as(C.c_void_p) for b in blobs], *tail, self._stream()))
+        self.hyper = dict(self._DEFAULTS, **_plain(hyper))
 
 
 class LightPPO(_PPOLearner):

@@ -103,6 +103,18 @@ def league_draw_reference(seed, gid, counter, domain, m):
     return ((c[0] * np.uint64(m)) >> np.uint64(32)).astype(np.int64)
 
 
+def weighted_draw_reference(seed, gid, counter, domain, weights):
+    """The weighted draw over a table of one weight per agent in numpy (include/crl.h "ledger draws"): r = ``league_draw_reference``
+    under ``domain`` scaled to the sum T of the weights, which must lie in [1, 2^32); the smallest agent whose cumulative weight exceeds
+    r.  ``weights``: non-negative integers, checked by the caller (``ledger.ledger_draw_reference``, ``car_league_draw_reference``)."""
+    w = np.asarray(weights)
+    total = int(w.astype(np.uint64).sum())
+    if not 0 < total < 2 ** 32:
+        raise ValueError(f"the weights must sum to a value in [1, 2^32), not {total}")
+    r = league_draw_reference(seed, gid, counter, domain, total)  # (x * T) >> 32
+    return np.searchsorted(np.cumsum(w.astype(np.int64)), r, side="right").astype(np.int64)
+
+
 def rollout_stack_reference(rows, reset, depth_before=3):
     """The stack rule of include/crl.h "rollout storage" in numpy.  ``rows``: uint8 [T + 3, N, 42, 42] -- rows 0..2 the three frames before
     step 0 (oldest first), row t + 3 the frame pushed at step t; ``reset``: [T, N], non-zero where the stack was masked before the push;
@@ -798,12 +810,7 @@ def car_league_draw_reference(seed, gid, counter, weights):
     """The car league's weighted draw in numpy: the rule of include/crl.h "ledger draws" (``ledger.ledger_draw_reference``) with
     CRL_CAR_LEAGUE_DOMAIN as the counter's fourth word.  ``gid`` and ``counter`` broadcast; ``weights`` must sum to a value in
     [1, 2^32).  Returns int64.  Host code for tests and for callers that want to predict a draw; the kernels do not use it."""
-    table = _car_league_table(weights)
-    total = int(table.sum())
-    if not 0 < total < 2 ** 32:
-        raise ValueError(f"the weights must sum to a value in [1, 2^32), not {total}")
-    r = league_draw_reference(seed, gid, counter, N.CRL_CAR_LEAGUE_DOMAIN, total)  # (x * T) >> 32
-    return np.searchsorted(np.cumsum(table.astype(np.int64)), r, side="right").astype(np.int64)
+    return weighted_draw_reference(seed, gid, counter, N.CRL_CAR_LEAGUE_DOMAIN, _car_league_table(weights))
 
 
 def car_league_q(x):

@@ -53,6 +53,20 @@ def test_a_draw_depends_on_seed_gid_counter_and_table_alone():
                                            N.CRL_CAR_DRIVER_DOMAIN, N.CRL_CAR_DRIVER_DOMAIN + 1, N.CRL_CAR_POLICY_DOMAIN, N.CRL_CAR_POLICY_DOMAIN + 1)
 
 
+def test_the_shared_draw_under_each_domain_is_what_the_two_named_references_return():
+    from competitive_rl_amd.ledger import ledger_draw_reference
+
+    w = np.array([7, 0, 3, 900, 1, 0, 0, 40, 2, 2, 65535, 1, 9, 0, 5, 11], np.uint32)  # 16 weights, zeros among them
+    gid = np.uint64(2 ** 32) + np.arange(300, dtype=np.uint64) * np.uint64(0x1_0000_0007)  # above 2^32: the counter's second word counts
+    ctr = np.arange(300, dtype=np.uint64) % np.uint64(5)
+    ledger, car = ledger_draw_reference(9, gid, ctr, w), R.car_league_draw_reference(9, gid, ctr, w)
+    assert (R.weighted_draw_reference(9, gid, ctr, N.CRL_LEDGER_DOMAIN_OPPONENT, w) == ledger).all()
+    assert (R.weighted_draw_reference(9, gid, ctr, N.CRL_CAR_LEAGUE_DOMAIN, w) == car).all()
+    assert (ledger != car).any() and not set(np.unique(np.concatenate([ledger, car]))) & {1, 5, 6, 13}
+    # the high word of gid reaches the draw
+    assert (R.weighted_draw_reference(9, gid - np.uint64(2 ** 32), ctr, N.CRL_CAR_LEAGUE_DOMAIN, w) != car).any()
+
+
 def test_q_rounds_to_nearest_even_in_units_of_1_256_and_books_zero_for_non_finite_returns():
     x = np.array([0.0, 1.0, -1.0, 1.5 / 256, 2.5 / 256, -0.5 / 256, 900.25, np.nan, np.inf, -np.inf, 3e38, -3e38], np.float32)
     assert R.car_league_q(x).tolist() == [0, 256, -256, 2, 2, 0, 230464, 0, 0, 0, 2 ** 62, -2 ** 62]
