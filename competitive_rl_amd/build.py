@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libcrl_hip.so")
 SOURCES = ["crl_api.hip", "pong_dynamics.hip", "pong_raster_raw.hip", "pong_raster_gray.hip",
            "crl_car_api.hip", "car_step.hip", "car_contact.hip", "car_track.hip", "car_obs.hip", "car_driver.hip", "car_policy.hip", "car_rollout.hip", "car_ppo.hip", "car_league.hip", "pong_policy.hip", "pong_policy_full.hip", "pong_league.hip", "pong_ledger.hip", "pong_arena.hip", "pong_rollout.hip", "pong_ppo.hip", "pong_ppo_full.hip", "frame_stack.hip", "crl_selftest.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("pong_device.h", "pong_band_span.h", "car_device.h", "car_solver.h", "car_obs_tile.h", "car_search.h", "car_learner.h", "crl_internal.h", "pong_policy_full.h", "pong_league.h", "pong_books.h", "pong_sample.h", "pong_ring.h", "pong_rollout.h", "pong_ppo.h", "ppo_optim.h", "pong_net.h", "pong_policy_packed.inc", "pong_gray_tile.inc")] + [os.path.join(ROOT, "include", "crl.h"), os.path.join(ROOT, "include", "crl_rot.h"), os.path.join(ROOT, "include", "crl_f64.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("pong_device.h", "pong_band_span.h", "car_device.h", "car_solver.h", "car_obs_tile.h", "car_search.h", "car_learner.h", "crl_internal.h", "pong_policy_full.h", "pong_league.h", "pong_books.h", "pong_sample.h", "pong_ring.h", "pong_rollout.h", "rollout_core.h", "pong_ppo.h", "ppo_optim.h", "pong_net.h", "pong_policy_packed.inc", "pong_gray_tile.inc")] + [os.path.join(ROOT, "include", "crl.h"), os.path.join(ROOT, "include", "crl_rot.h"), os.path.join(ROOT, "include", "crl_f64.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 

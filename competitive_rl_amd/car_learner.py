@@ -38,6 +38,7 @@ from . import _native as N
 from . import checkpoint as K
 from .car_policy import CarPolicy
 from .ppo import _PPOLearner
+from .rollout import _ptr, _RolloutBase
 from .rules import (CAR_POLICY_KEYS, CAR_POLICY_SHAPES, CAR_PPO_DEFAULTS, adam_reference, car_policy_pack, car_policy_unpack,  # noqa: F401  (re-exported)
                     car_ppo_loss_reference, gae_reference)
 
@@ -47,7 +48,6 @@ CarRolloutBatch = collections.namedtuple("CarRolloutBatch", ("obs", "actions", "
 CarPPOStats = collections.namedtuple("CarPPOStats", ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "grad_norm", "steps", "live"))
 LINE_WORDS = 32  # one sample = one aligned 128-byte line
 _CARS = {(0,): 1, (1,): 2, (0, 1): 3}
-_STATES = ("fresh", "active", "finished")
 
 
 def car_blob_views(blob):
@@ -60,11 +60,10 @@ def car_blob_views(blob):
                 policy_b=blob[t:t + 2], value_w=blob[K * H + 3 * H:t].reshape(1, H), value_b=blob[t + 2:t + 3], log_std=blob[t + 3:t + 5])
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+class CarRolloutStorage(_RolloutBase):
+    _C, _NSTATS = "crl_car_rollout_", 3
+    _total = lambda self: self.num_steps * self.rows  # noqa: E731  (the samples a finished storage holds)
 
-
-class CarRolloutStorage:
     def __init__(self, env, num_steps, cars=(0,), gamma=0.99, gae_lambda=0.95, normalize_advantage=True):
         """``cars``: which cars' samples are kept, one of (0,), (1,), (0, 1).  Rows R = N * len(cars), row = e * len(cars) + j; the
         flat index of a sample is t * R + row."""
@@ -84,12 +83,6 @@ class CarRolloutStorage:
         with torch.cuda.device(self.device):
             N.check(self._L.crl_car_rollout_create(env._h, self.num_steps, _CARS[cars], C.byref(h)))
         self._h = h
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _on_device(self):
-        return torch.cuda.device(self.device)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -145,17 +138,12 @@ class CarRolloutStorage:
         """Returns and advantages by GAE (``rules.gae_reference`` with the rows' dones) and, with ``normalize_advantage``, the mean and
         the unbiased deviation of the LIVE samples' advantages.  ``last_values``: (N, P), the values of the ``act_rollout`` call that
         opens the next rollout; None: zeros."""
-        if last_values is not None:
-            self._full(last_values, (), "last_values")
-        with self._on_device():
-            N.check(self._L.crl_car_rollout_finish(self._h, _ptr(last_values), self.gamma, self.gae_lambda, int(self.normalize_advantage), self._stream()))
+        self._finish(None if last_values is None else self._full(last_values, (), "last_values"))
 
     def stats(self):
         """(mean, std, live count) of the advantages as the device computed them.  Synchronises the device: logging and tests."""
-        out = (C.c_double * 3)()
-        with self._on_device():
-            N.check(self._L.crl_car_rollout_stats(self._h, out))
-        return out[0], out[1], int(out[2])
+        mean, std, live = super().stats()
+        return mean, std, int(live)
 
     # ---- minibatches
     def empty_batch(self, batch_size, fields=None):
@@ -183,19 +171,9 @@ class CarRolloutStorage:
 
     def minibatches(self, num_mini_batch, generator=None):
         """``num_mini_batch`` batches of T * R // num_mini_batch samples each, drawn without replacement by ``torch.randperm``."""
-        total = self.num_steps * self.rows
-        size = total // int(num_mini_batch)
-        assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
-        perm = torch.randperm(total, device=self.device, generator=generator)
-        for k in range(int(num_mini_batch)):
-            yield self.gather(perm[k * size:(k + 1) * size])
+        return super().minibatches(num_mini_batch, generator)
 
     # ---- checkpoint / resume
-    def _info(self):
-        out = (C.c_int32 * 8)()
-        N.check(self._L.crl_car_rollout_get_info(self._h, out))
-        return _STATES[out[0]], out[1], out[2], bool(out[3])
-
     def state_dict(self, contents=True):
         """Everything a continuation needs, as host arrays (SYNCHRONISES with the current stream): the sizes, ``gamma``, ``gae_lambda``,
         ``normalize_advantage``, ``state`` (fresh / active / finished), ``step`` and ``outcomes``.  ``contents=True`` adds, under
@@ -203,9 +181,7 @@ class CarRolloutStorage:
         the three statistics: a checkpoint taken in the middle of a rollout, or between ``finish`` and ``update``, continues exactly.
         ``contents=False`` is the small form for a checkpoint BETWEEN iterations -- nothing carries over from one rollout to the next,
         so it holds no array; loaded, the storage stands in front of ``begin()``.  In the middle of a rollout it is refused."""
-        state, recorded, outcomes, normalized = self._info()
-        if not contents and state == "active" and recorded:
-            raise ValueError("state_dict(contents=False) in the middle of a rollout would drop the steps recorded so far: pass contents=True")
+        state, recorded, outcomes, normalized = self._info(contents)
         sd = {"kind": "CarRolloutStorage", "num_steps": self.num_steps, "num_envs": self.num_envs, "players": self.players, "cars": self.cars,
               "gamma": self.gamma, "gae_lambda": self.gae_lambda, "normalize_advantage": self.normalize_advantage, "state": state, "step": recorded,
               "outcomes": outcomes, "contents": None}
@@ -222,30 +198,17 @@ class CarRolloutStorage:
         ``step`` outside [0, T] or arrays of the wrong shape raise a ``ValueError`` and leave the storage as it was.  Ordered on the
         current stream and SYNCHRONISES with it."""
         what, T = "CarRolloutStorage", self.num_steps
-        K.check_header(sd, what, what, num_steps=T, num_envs=self.num_envs, players=self.players)
+        state, step, outcomes, gamma, lam, norm, c = self._check_state_header(sd, players=self.players)
         if tuple(sd.get("cars", ())) != self.cars:
             raise K.refuse(f"{what}: cars is {sd.get('cars')!r} in the state dict and {self.cars!r} here")
-        state = sd.get("state")
-        if state not in _STATES:
-            raise K.refuse(f"{what}: state must be fresh, active or finished, not {state!r}")
-        step, outcomes = K.check_counter(sd.get("step"), 31, "step", what), K.check_counter(sd.get("outcomes"), 31, "outcomes", what)
-        if step > T or outcomes > step or (state == "finished" and (outcomes != T or step != T)) or (state == "fresh" and step):
-            raise K.refuse(f"{what}: step {step} and {outcomes} outcomes do not fit a {state} rollout of {T} steps")
-        try:
-            gamma, lam, norm = float(sd["gamma"]), float(sd["gae_lambda"]), bool(sd["normalize_advantage"])
-        except (KeyError, TypeError, ValueError):
-            raise K.refuse(f"{what}: gamma, gae_lambda and normalize_advantage are needed") from None
-        c = sd.get("contents")
+        if state == "finished" and step != T:
+            raise K.refuse(f"{what}: step {step} and {outcomes} outcomes do not fit a finished rollout of {T} steps")
         if c is None:
-            if state == "active" and step:
-                raise K.refuse(f"{what}: a state dict without contents cannot continue in the middle of a rollout (step {step})")
             info, lines, stats, step = (C.c_int32 * 4)(0, 0, 0, 0), None, None, 0
         else:
-            if not isinstance(c, dict):
-                raise K.refuse(f"{what}: contents must be a dict")
             lines = K.check_array(c, "lines", (step * self.rows, LINE_WORDS), 4, what)
             stats = K.check_array(c, "stats", (3,), 8, what)
-            info = (C.c_int32 * 4)(_STATES.index(state), step, outcomes, int(bool(c.get("normalized"))))
+            info = (C.c_int32 * 4)(self._STATES.index(state), step, outcomes, int(bool(c.get("normalized"))))
             lines = torch.from_numpy(np.ascontiguousarray(lines).view(np.float32).copy()).to(self.device)
             stats = torch.from_numpy(np.ascontiguousarray(stats).view(np.float64).copy()).to(self.device)
         with self._on_device():
@@ -259,7 +222,6 @@ class CarPPO(_PPOLearner):
     the base's; here is what the MLP(21, 2) and its line storage make different."""
     _C, _DEFAULTS, _FLOATS, _SIZED = "crl_car_ppo_", CAR_PPO_DEFAULTS, N.CRL_CAR_POLICY_BLOB_FLOATS, False
     _views = staticmethod(car_blob_views)
-    _samples = staticmethod(lambda s: s.num_steps * s.rows)
     _split = staticmethod(car_policy_unpack)
 
     def __init__(self, weights, device=None, **hyper):

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "crl_internal.h"
+#include "rollout_core.h"  // adv_out: the advantage as crl_car_rollout_gather hands it out
 
 namespace crl {
 
@@ -27,11 +28,6 @@ struct CarRolloutView {
     uint32_t last;        // T * R - 1
     bool finished;
 };
-
-// the advantage as crl_car_rollout_gather hands it out
-__device__ inline float car_adv_out(float adv, const double *stats) {
-    return stats ? (adv - (float)stats[0]) / ((float)stats[1] + 1e-5f) : adv;
-}
 
 CarRolloutView car_rollout_view(const ::crl_car_rollout *r);
 

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(64) void car_ppo_grad_kernel(CarGradArgs a) {
         if (live) {
             const double mean0 = m0 + bp0, mean1 = m1 + bp1, v = vv + bv;
             const double olp = (double)q[kCarLineLogp], ret = (double)q[kCarLineReturn];
-            const double A = (double)car_adv_out(q[kCarLineAdv], a.view.stats);
+            const double A = (double)adv_out(q[kCarLineAdv], a.view.stats);
             const double zz0 = ((double)q[kCarLineU] - mean0) / sd0, zz1 = ((double)q[kCarLineU + 1] - mean1) / sd1;
             const double logp = ((-0.5 * (zz0 * zz0) - ls0) + (-0.5 * (zz1 * zz1) - ls1)) - CRL_LN_2PI_F64;
             const double ratio = exp(logp - olp);

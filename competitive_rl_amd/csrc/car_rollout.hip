@@ -13,9 +13,6 @@
 
 namespace crl {
 
-static constexpr int kRedBlock = 256;  // the statistics' fixed shape, that of pong_rollout.hip: at most kRedGroups workgroups of kRedBlock lanes, then one
-static constexpr int kRedGroups = 256;
-
 struct CarRecordArgs {
     const float *obs, *actions, *values, *logp;  // [N][P][21], [N][P][2], [N][P], [N][P]
     const int32_t *assign;                       // [N][P]: the policy's assignment
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(256) void car_rollout_outcome_kernel(const float *_
     line[kCarLineFlags] = __uint_as_float(fl | (d ? kCarFlagDone : 0u));
 }
 
-// include/crl.h "GAE rule", unchanged: a lane per row walks t = T-1 .. 0; float32, one rounding per operation
+// include/crl.h "GAE rule" (rollout_core.h): a lane per row walks t = T-1 .. 0 over the rows' lines
 __global__ __launch_bounds__(256) void car_rollout_gae_kernel(float *__restrict__ lines, const float *__restrict__ last_values, float g, float gl, int64_t n,
                                                              int players, int cars, int first, int steps) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -74,66 +71,17 @@ __global__ __launch_bounds__(256) void car_rollout_gae_kernel(float *__restrict_
     float vnext = last_values ? last_values[e * players + c] : 0.0f;
     for (int t = steps - 1; t >= 0; t--) {
         float *line = lines + ((int64_t)t * rows + row) * kCarLineWords;
-        const float nd = (__float_as_uint(line[kCarLineFlags]) & kCarFlagDone) ? 0.0f : 1.0f;
-        const float v = line[kCarLineValue];
-        const float delta = (line[kCarLineReward] + (g * vnext) * nd) - v;
-        acc = delta + (gl * nd) * acc;
-        line[kCarLineAdv] = acc;
-        line[kCarLineReturn] = acc + v;
-        vnext = v;
+        const bool done = (__float_as_uint(line[kCarLineFlags]) & kCarFlagDone) != 0;
+        gae_step(line[kCarLineReward], line[kCarLineValue], done, g, gl, acc, vnext, line[kCarLineAdv], line[kCarLineReturn]);
     }
 }
 
-// The statistics' partial sums, float64, in the shape of "rollout storage": workgroup w of `groups` sums (adv - shift)^(1 or 2) over
-// the samples w * 256 + lane, + groups * 256, ... in order -- a dead sample contributes 0 --, then the 256 lanes' sums in a fixed
-// tree.  The first pass counts the live samples the same way (an integer held in a double: exact).
-template <bool SQUARE>
-__global__ __launch_bounds__(kRedBlock) void car_rollout_stats_partial_kernel(const float *__restrict__ lines, int64_t count, const double *__restrict__ stats,
-                                                                             double *__restrict__ partials, double *__restrict__ live_partials) {
-    __shared__ double s[kRedBlock], c[kRedBlock];
-    const double shift = SQUARE ? stats[0] : 0.0;
-    double sum = 0.0, cnt = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kRedBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kRedBlock) {
-        const float *line = lines + i * kCarLineWords;
-        if (!(__float_as_uint(line[kCarLineFlags]) & kCarFlagLive)) continue;
-        const double v = (double)line[kCarLineAdv] - shift;
-        sum += SQUARE ? v * v : v;
-        cnt += 1.0;
-    }
-    s[threadIdx.x] = sum, c[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int w = kRedBlock / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w], c[threadIdx.x] += c[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x] = s[0];
-        if (!SQUARE) live_partials[blockIdx.x] = c[0];
-    }
-}
-
-// ... and the one final workgroup: stats[2] = L, stats[0] = sum / L (0 where L = 0), or stats[1] = sqrt(sum / (L - 1)) (0 where L < 2)
-template <bool SQUARE>
-__global__ __launch_bounds__(kRedGroups) void car_rollout_stats_final_kernel(const double *__restrict__ partials, const double *__restrict__ live_partials,
-                                                                            int groups, double *__restrict__ stats) {
-    __shared__ double s[kRedGroups], c[kRedGroups];
-    s[threadIdx.x] = (int)threadIdx.x < groups ? partials[threadIdx.x] : 0.0;
-    c[threadIdx.x] = (!SQUARE && (int)threadIdx.x < groups) ? live_partials[threadIdx.x] : 0.0;
-    __syncthreads();
-    for (int w = kRedGroups / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w], c[threadIdx.x] += c[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (SQUARE) {
-            const double L = stats[2];
-            stats[1] = L > 1.0 ? sqrt(s[0] / (L - 1.0)) : 0.0;
-        } else {
-            stats[2] = c[0];
-            stats[0] = c[0] > 0.0 ? s[0] / c[0] : 0.0;
-        }
-    }
-}
+struct CarAdvSrc {  // the statistics' source (rollout_core.h): the advantages of the LIVE samples, stats[2] = their count L
+    static constexpr bool kCounted = true;
+    const float *__restrict__ lines;
+    __device__ bool live(int64_t i) const { return (__float_as_uint(lines[i * kCarLineWords + kCarLineFlags]) & kCarFlagLive) != 0; }
+    __device__ float adv(int64_t i) const { return lines[i * kCarLineWords + kCarLineAdv]; }
+};
 
 struct CarGatherArgs {
     const float *lines;
@@ -166,31 +114,23 @@ __global__ __launch_bounds__(256) void car_rollout_gather_kernel(CarGatherArgs a
     } else if (w == kCarLineReturn) {
         if (a.ret) a.ret[b] = v;
     } else if (w == kCarLineAdv) {
-        if (a.adv) a.adv[b] = car_adv_out(v, a.stats);
+        if (a.adv) a.adv[b] = adv_out(v, a.stats);
     } else if (w == kCarLineFlags) {
         if (a.live) a.live[b] = (uint8_t)(__float_as_uint(v) & kCarFlagLive);
     }
 }
 
-static inline unsigned blocks_of(int64_t lanes) { return (unsigned)((lanes + 255) / 256); }
-
 }  // namespace crl
 
 using namespace crl;
 
-enum car_rollout_state { kFresh = 0, kActive = 1, kFinished = 2 };
-
-struct crl_car_rollout {
+struct crl_car_rollout : RolloutSteps {
     crl_car_ctx *car = nullptr;
     int64_t n = 0;
     int players = 0, cars = 0, first = 0, mask = 0;
-    int steps = 0;
-    int state = kFresh;
-    int recorded = 0, outcomes = 0;
-    bool normalize = false;
     float *lines = nullptr;      // [T * R][32]
     int32_t *assign = nullptr;   // [N][players]: the policy's assignment at the last record
-    double *stats = nullptr;     // mean, std, L, then kRedGroups partial sums and kRedGroups partial counts
+    double *stats = nullptr;     // mean, std, L, then kRedGroups partial sums and kRedGroups partial counts (kStatsDoubles)
 };
 
 namespace crl {
@@ -225,7 +165,7 @@ int crl_car_rollout_create(crl_ctx *ctx, int64_t num_steps, int32_t cars_mask, c
     const char *who = "crl_car_rollout_create";
     int rc = crl_dev_zalloc(&r->lines, (size_t)num_steps * r->n * cars * kCarLineWords * sizeof(float), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&r->assign, (size_t)r->n * r->players * sizeof(int32_t), who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&r->stats, (3 + 2 * kRedGroups) * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&r->stats, kStatsDoubles<CarAdvSrc> * sizeof(double), who);
     if (rc == CRL_OK) {
         const hipError_t e = hipDeviceSynchronize();
         if (e != hipSuccess) rc = crl_hip_fail(e, who);
@@ -251,9 +191,7 @@ int crl_car_rollout_record(crl_car_rollout *r, int64_t t, crl_car_policy *policy
     if (!r || !policy || !obs_dev || !actions_dev || !values_dev || !log_probs_dev) return crl_fail(CRL_EINVAL, "crl_car_rollout_record: null argument");
     if (((uintptr_t)obs_dev | (uintptr_t)actions_dev | (uintptr_t)values_dev | (uintptr_t)log_probs_dev) & 3)
         return crl_fail(CRL_EINVAL, "crl_car_rollout_record: the tensors must be 4-byte aligned");
-    if (r->state == kFinished) return crl_fail(CRL_EINVAL, "crl_car_rollout_record: the rollout is finished; crl_car_rollout_begin starts the next one");
-    if (t != r->recorded || t >= r->steps)
-        return crl_fail(CRL_EINVAL, "crl_car_rollout_record: step %lld is not the next step (%d of %d steps recorded)", (long long)t, r->recorded, r->steps);
+    if (int rc = r->check_record("crl_car_rollout_record", t)) return rc;
     int32_t flag = 0;
     if (int rc = crl_car_policy_get_weights(policy, slot, nullptr, &flag, nullptr)) return rc;  // (refuses a bad or an empty slot)
     if (flag != 0) return crl_fail(CRL_EINVAL, "crl_car_rollout_record: slot %d is deterministic: its log-probs are 0, which is not training material", slot);
@@ -272,9 +210,7 @@ int crl_car_rollout_outcome(crl_car_rollout *r, int64_t t, const float *rewards_
     crl_fail_no_ctx();
     if (!r || !rewards_dev || !done_dev) return crl_fail(CRL_EINVAL, "crl_car_rollout_outcome: null argument");
     if ((uintptr_t)rewards_dev & 3) return crl_fail(CRL_EINVAL, "crl_car_rollout_outcome: rewards must be 4-byte aligned");
-    if (r->state != kActive || t != r->outcomes || t >= r->recorded)
-        return crl_fail(CRL_EINVAL, "crl_car_rollout_outcome: step %lld has no record, or has its outcome (%d steps recorded, %d outcomes)", (long long)t,
-                        r->state == kActive ? r->recorded : 0, r->state == kActive ? r->outcomes : 0);
+    if (int rc = r->check_outcome("crl_car_rollout_outcome", t)) return rc;
     const int64_t rows = r->n * r->cars;
     hipLaunchKernelGGL(car_rollout_outcome_kernel, dim3(blocks_of(rows)), dim3(256), 0, (hipStream_t)stream, rewards_dev, done_dev, crl_car_done_flags(r->car),
                        r->lines + t * rows * kCarLineWords, r->n, r->players, r->cars, r->first);
@@ -287,8 +223,7 @@ int crl_car_rollout_finish(crl_car_rollout *r, const float *last_values_dev, dou
     crl_fail_no_ctx();
     if (!r) return crl_fail(CRL_EINVAL, "crl_car_rollout_finish: null storage");
     if ((uintptr_t)last_values_dev & 3) return crl_fail(CRL_EINVAL, "crl_car_rollout_finish: last_values must be 4-byte aligned");
-    if (r->state == kFresh || r->outcomes != r->steps)
-        return crl_fail(CRL_EINVAL, "crl_car_rollout_finish: %d of %d steps have their outcome", r->state == kFresh ? 0 : r->outcomes, r->steps);
+    if (int rc = r->check_finish("crl_car_rollout_finish")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows = r->n * r->cars, total = rows * r->steps;
     const float g = (float)gamma;
@@ -296,15 +231,7 @@ int crl_car_rollout_finish(crl_car_rollout *r, const float *last_values_dev, dou
     hipLaunchKernelGGL(car_rollout_gae_kernel, dim3(blocks_of(rows)), dim3(256), 0, st, r->lines, last_values_dev, g, gl, r->n, r->players, r->cars, r->first,
                        r->steps);
     HIP_TRY(hipGetLastError());
-    if (normalize) {
-        const int groups = (int)(blocks_of(total) < (unsigned)kRedGroups ? blocks_of(total) : (unsigned)kRedGroups);
-        double *partials = r->stats + 3, *live = r->stats + 3 + kRedGroups;
-        hipLaunchKernelGGL(car_rollout_stats_partial_kernel<false>, dim3(groups), dim3(kRedBlock), 0, st, r->lines, total, r->stats, partials, live);
-        hipLaunchKernelGGL(car_rollout_stats_final_kernel<false>, dim3(1), dim3(kRedGroups), 0, st, partials, live, groups, r->stats);
-        hipLaunchKernelGGL(car_rollout_stats_partial_kernel<true>, dim3(groups), dim3(kRedBlock), 0, st, r->lines, total, r->stats, partials, live);
-        hipLaunchKernelGGL(car_rollout_stats_final_kernel<true>, dim3(1), dim3(kRedGroups), 0, st, partials, live, groups, r->stats);
-        HIP_TRY(hipGetLastError());
-    }
+    if (normalize) HIP_TRY(rollout_stats_launch(CarAdvSrc{r->lines}, total, r->stats, st));
     r->normalize = normalize != 0;
     r->state = kFinished;
     return CRL_OK;
@@ -318,7 +245,7 @@ int crl_car_rollout_gather(crl_car_rollout *r, const int64_t *idx_dev, int64_t c
     if (((uintptr_t)idx_dev & 7) || (((uintptr_t)obs_out_dev | (uintptr_t)actions_out_dev | (uintptr_t)logp_out_dev | (uintptr_t)values_out_dev |
                                       (uintptr_t)returns_out_dev | (uintptr_t)adv_out_dev) & 3))
         return crl_fail(CRL_EINVAL, "crl_car_rollout_gather: misaligned pointer (idx 8 bytes, every float32 output 4)");
-    if (r->state != kFinished) return crl_fail(CRL_EINVAL, "crl_car_rollout_gather: the rollout is not finished (crl_car_rollout_finish computes what a sample holds)");
+    if (int rc = r->check_finished("crl_car_rollout_gather")) return rc;
     if (count == 0) return CRL_OK;
     CarGatherArgs a{r->lines,       idx_dev,         count,       (uint32_t)(r->n * r->cars * r->steps - 1), obs_out_dev, actions_out_dev, logp_out_dev,
                     values_out_dev, returns_out_dev, adv_out_dev, live_out_dev,                              r->normalize ? r->stats : nullptr};
@@ -340,9 +267,7 @@ int crl_car_rollout_stats(crl_car_rollout *r, double *out3_host) {
 int crl_car_rollout_get_info(crl_car_rollout *r, int32_t *out8_host) {
     crl_fail_no_ctx();
     if (!r || !out8_host) return crl_fail(CRL_EINVAL, "crl_car_rollout_get_info: null argument");
-    out8_host[0] = r->state, out8_host[1] = r->recorded, out8_host[2] = r->outcomes, out8_host[3] = r->normalize ? 1 : 0;
-    if (r->state == kFinished) out8_host[1] = out8_host[2] = r->steps;
-    if (r->state == kFresh) out8_host[1] = out8_host[2] = 0;
+    r->info(out8_host);
     out8_host[4] = r->steps, out8_host[5] = r->cars, out8_host[6] = r->mask, out8_host[7] = kCarLineWords;
     return CRL_OK;
 }
@@ -361,18 +286,13 @@ int crl_car_rollout_get_state(crl_car_rollout *r, int64_t steps, float *lines_ou
 int crl_car_rollout_set_state(crl_car_rollout *r, const int32_t *info4_host, int64_t steps, const float *lines_dev, const double *stats_dev, void *stream) {
     crl_fail_no_ctx();
     if (!r || !info4_host) return crl_fail(CRL_EINVAL, "crl_car_rollout_set_state: null argument");
-    const int state = info4_host[0], recorded = info4_host[1], outcomes = info4_host[2];
-    const bool ok = state >= kFresh && state <= kFinished && outcomes >= 0 && outcomes <= recorded && recorded <= r->steps &&
-                    (state != kFresh || recorded == 0) && (state != kFinished || outcomes == r->steps);
-    if (!ok)
-        return crl_fail(CRL_EINVAL, "crl_car_rollout_set_state: state %d with %d steps recorded and %d outcomes does not fit a storage of %d steps", state,
-                        recorded, outcomes, r->steps);
+    if (int rc = r->check_restore("crl_car_rollout_set_state", info4_host)) return rc;
     if (steps < 0 || steps > r->steps) return crl_fail(CRL_EINVAL, "crl_car_rollout_set_state: steps %lld outside [0, %d]", (long long)steps, r->steps);
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = (size_t)steps * r->n * r->cars * kCarLineWords * sizeof(float);
     if (lines_dev && bytes) HIP_TRY(hipMemcpyAsync(r->lines, lines_dev, bytes, hipMemcpyDeviceToDevice, st));
     if (stats_dev) HIP_TRY(hipMemcpyAsync(r->stats, stats_dev, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    r->state = state, r->recorded = recorded, r->outcomes = outcomes, r->normalize = info4_host[3] != 0;
+    r->restore(info4_host);
     return CRL_OK;
 }
 

@@ -9,6 +9,7 @@
 #include "crl_internal.h"
 #include "pong_ring.h"
 #include "pong_rollout.h"
+#include "rollout_core.h"
 #include "ppo_optim.h"
 
 namespace crl {
@@ -84,7 +85,7 @@ __device__ inline PpoSample sample_scalars(const RolloutView &r, uint32_t flat, 
     const int32_t ai = r.actions[flat];
     s.act = ai < 0 ? 0 : ai > 2 ? 2 : ai;
     s.olp = r.logp[flat], s.target = r.ret[flat], s.adv = r.adv[flat];  // (all loads in flight before the first is waited for)
-    if (r.stats) s.adv = (s.adv - (float)r.stats[0]) / ((float)r.stats[1] + 1e-5f);
+    s.adv = adv_out(s.adv, r.stats);
     if (t) {
         if (t->logits) s.tr.l[0] = t->logits[3 * (int64_t)flat], s.tr.l[1] = t->logits[3 * (int64_t)flat + 1], s.tr.l[2] = t->logits[3 * (int64_t)flat + 2];
         else s.tr.label = t->labels[flat];

@@ -6,14 +6,14 @@
 // Stands in for the rollout storage a trainer around the reference keeps on the host side of its loop (a float32 FrameStackTensor copy
 // per step, utils/utils.py:145-173): 28 224 bytes per env and step there, 1 776 + 27 here.  An object of its own: nothing here reaches
 // into a crl_policy, the caller passes the act call's inputs and outputs in.
+#include <string.h>
 #include "pong_ring.h"
 #include "pong_rollout.h"
+#include "rollout_core.h"
 
 namespace crl {
 
 static constexpr int kHist = CRL_POLICY_STACK - 1;  // rows 0..2 of `planes`: the three frames before step 0, oldest first
-static constexpr int kRedBlock = 256;               // the statistics' fixed shape: at most kRedGroups workgroups of kRedBlock lanes, then one
-static constexpr int kRedGroups = 256;
 
 // crl_rollout_begin with a stack: planes 1..3 of u8 [n][4][42][42] -> rows 0..2 (a lane per dword; the 12 bytes of padding stay zero)
 __global__ __launch_bounds__(256) void rollout_history_kernel(uint32_t *__restrict__ planes, const uint32_t *__restrict__ stack, int64_t n) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void rollout_outcome_kernel(const float *__res
     done_out[e] = (uint8_t)(done[e] != 0);
 }
 
-// include/crl.h "GAE rule": a lane per env walks t = T-1 .. 0; float32, one rounding per operation (-ffp-contract=off)
+// include/crl.h "GAE rule" (rollout_core.h): a lane per env walks t = T-1 .. 0 over the arrays
 __global__ __launch_bounds__(256) void rollout_gae_kernel(const float *__restrict__ rewards, const float *__restrict__ values, const uint8_t *__restrict__ done,
                                                          const float *__restrict__ last_values, float g, float gl, float *__restrict__ adv,
                                                          float *__restrict__ ret, int64_t n, int steps) {
@@ -94,53 +94,18 @@ __global__ __launch_bounds__(256) void rollout_gae_kernel(const float *__restric
     float vnext = last_values ? last_values[e] : 0.0f;
     for (int t = steps - 1; t >= 0; t--) {
         const int64_t k = (int64_t)t * n + e;
-        const float nd = done[k] ? 0.0f : 1.0f;
+        const bool d = done[k] != 0;  // (the loads in the order they always had: done, value, reward)
         const float v = values[k];
-        const float delta = (rewards[k] + (g * vnext) * nd) - v;
-        acc = delta + (gl * nd) * acc;
-        adv[k] = acc;
-        ret[k] = acc + v;
-        vnext = v;
+        gae_step(rewards[k], v, d, g, gl, acc, vnext, adv[k], ret[k]);
     }
 }
 
-// The statistics' partial sums, float64: workgroup w of `groups` sums (x - shift)^(1 or 2) over elements w * 256 + lane, + groups * 256,
-// ... in order, then the 256 lanes' sums in a fixed tree.  No atomics: the same T * N gives the same bits.
-template <bool SQUARE>
-__global__ __launch_bounds__(kRedBlock) void rollout_stats_partial_kernel(const float *__restrict__ x, int64_t count, const double *__restrict__ stats,
-                                                                         double *__restrict__ partials) {
-    __shared__ double s[kRedBlock];
-    const double shift = SQUARE ? stats[0] : 0.0;
-    double sum = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kRedBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kRedBlock) {
-        const double v = (double)x[i] - shift;
-        sum += SQUARE ? v * v : v;
-    }
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    for (int w = kRedBlock / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
-}
-
-// ... and the one final workgroup: stats[0] = sum / count (the mean), or stats[1] = sqrt(sum / (count - 1)) (the unbiased deviation; 0
-// for a single advantage, which has none)
-template <bool SQUARE>
-__global__ __launch_bounds__(kRedGroups) void rollout_stats_final_kernel(const double *__restrict__ partials, int groups, int64_t count, double *__restrict__ stats) {
-    __shared__ double s[kRedGroups];
-    s[threadIdx.x] = (int)threadIdx.x < groups ? partials[threadIdx.x] : 0.0;
-    __syncthreads();
-    for (int w = kRedGroups / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (SQUARE) stats[1] = count > 1 ? sqrt(s[0] / (double)(count - 1)) : 0.0;
-        else stats[0] = s[0] / (double)count;
-    }
-}
+struct PongAdvSrc {  // the statistics' source (rollout_core.h): every one of the T * n advantages takes part
+    static constexpr bool kCounted = false;
+    const float *__restrict__ x;
+    __device__ bool live(int64_t) const { return true; }
+    __device__ float adv(int64_t i) const { return x[i]; }
+};
 
 struct GatherArgs {
     const uint32_t *planes;  // [T + 3][n][kPlanePad / 4]
@@ -201,29 +166,17 @@ __global__ __launch_bounds__(256) void rollout_gather_kernel(GatherArgs a) {
         if (a.logp_out) a.logp_out[b] = a.logp[flat];
         if (a.values_out) a.values_out[b] = a.values[flat];
         if (a.ret_out) a.ret_out[b] = a.ret[flat];
-        if (a.adv_out) {
-            float x = a.adv[flat];
-            if (a.stats) x = (x - (float)a.stats[0]) / ((float)a.stats[1] + 1e-5f);  // float32, true division
-            a.adv_out[b] = x;
-        }
+        if (a.adv_out) a.adv_out[b] = adv_out(a.adv[flat], a.stats);
     }
 }
-
-static inline unsigned blocks_of(int64_t lanes) { return (unsigned)((lanes + 255) / 256); }
 
 }  // namespace crl
 
 using namespace crl;
 
-enum rollout_state { kFresh = 0, kActive = 1, kFinished = 2 };
-
-struct crl_rollout {
+struct crl_rollout : RolloutSteps {
     int device = 0;
     int64_t n = 0;
-    int steps = 0;
-    int state = kFresh;
-    int recorded = 0, outcomes = 0;  // steps that have their record / their outcome
-    bool normalize = false;
     uint8_t *planes = nullptr, *reset = nullptr, *depth = nullptr, *depth_carry = nullptr, *done = nullptr;
     int32_t *actions = nullptr;
     float *logp = nullptr, *values = nullptr, *rewards = nullptr, *adv = nullptr, *ret = nullptr;
@@ -231,6 +184,42 @@ struct crl_rollout {
 };
 
 namespace crl {
+
+// ---- rollout_core.h, the step counters' refusals, for both storages.  A text that names a sibling call forms it from who's prefix
+static int family(const char *who) { return (int)(strrchr(who, '_') - who) + 1; }  // the length of crl_<storage>_
+
+int RolloutSteps::check_record(const char *who, int64_t t) const {
+    if (state == kFinished) return crl_fail(CRL_EINVAL, "%s: the rollout is finished; %.*sbegin starts the next one", who, family(who), who);
+    if (t != recorded || t >= steps) return crl_fail(CRL_EINVAL, "%s: step %lld is not the next step (%d of %d steps recorded)", who, (long long)t, recorded, steps);
+    return CRL_OK;
+}
+
+int RolloutSteps::check_outcome(const char *who, int64_t t) const {
+    if (state == kActive && t == outcomes && t < recorded) return CRL_OK;
+    return crl_fail(CRL_EINVAL, "%s: step %lld has no record, or has its outcome (%d steps recorded, %d outcomes)", who, (long long)t,
+                    state == kActive ? recorded : 0, state == kActive ? outcomes : 0);
+}
+
+int RolloutSteps::check_finish(const char *who) const {
+    return state != kFresh && outcomes == steps ? CRL_OK : crl_fail(CRL_EINVAL, "%s: %d of %d steps have their outcome", who, state == kFresh ? 0 : outcomes, steps);
+}
+
+int RolloutSteps::check_finished(const char *who) const {
+    return state == kFinished ? CRL_OK : crl_fail(CRL_EINVAL, "%s: the rollout is not finished (%.*sfinish computes what a sample holds)", who, family(who), who);
+}
+
+int RolloutSteps::check_restore(const char *who, const int32_t *info4) const {
+    const int st = info4[0], rec = info4[1], out = info4[2];
+    if (st >= kFresh && st <= kFinished && out >= 0 && out <= rec && rec <= steps && (st != kFresh || rec == 0) && (st != kFinished || out == steps)) return CRL_OK;
+    return crl_fail(CRL_EINVAL, "%s: state %d with %d steps recorded and %d outcomes does not fit a storage of %d steps", who, st, rec, out, steps);
+}
+
+void RolloutSteps::info(int32_t *out4) const {
+    out4[0] = state, out4[1] = recorded, out4[2] = outcomes, out4[3] = normalize ? 1 : 0;
+    if (state == kFinished) out4[1] = out4[2] = steps;
+    if (state == kFresh) out4[1] = out4[2] = 0;
+}
+
 RolloutView rollout_view(const crl_rollout *r) {
     return RolloutView{r->planes, r->depth, r->actions, r->logp, r->ret, r->adv, r->normalize ? r->stats : nullptr, (uint32_t)r->n,
                        (uint32_t)(r->n * r->steps - 1), r->state == kFinished};
@@ -269,7 +258,7 @@ int crl_rollout_create(int32_t device, int64_t num_envs, int64_t num_steps, crl_
     if (rc == CRL_OK) rc = crl_dev_zalloc(&r->rewards, tn * 4, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&r->adv, tn * 4, who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&r->ret, tn * 4, who);
-    if (rc == CRL_OK) rc = crl_dev_zalloc(&r->stats, (2 + kRedGroups) * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&r->stats, kStatsDoubles<PongAdvSrc> * sizeof(double), who);
     if (rc == CRL_OK) {
         hipError_t e = hipMemset(r->depth_carry, kHist, n);  // zero history rows are physically what a fresh ring holds: depth 3
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -317,9 +306,7 @@ int crl_rollout_record(crl_rollout *r, int64_t t, const uint8_t *frame_dev, int6
     if (int rc = ring_check_act("crl_rollout_record", frame_dev, frame_stride, action_stride)) return rc;
     if (((uintptr_t)actions_dev & 3) || ((uintptr_t)values_dev & 3) || ((uintptr_t)logp_dev & 3))
         return crl_fail(CRL_EINVAL, "crl_rollout_record: actions, values and log-probs must be 4-byte aligned");
-    if (r->state == kFinished) return crl_fail(CRL_EINVAL, "crl_rollout_record: the rollout is finished; crl_rollout_begin starts the next one");
-    if (t != r->recorded || t >= r->steps)
-        return crl_fail(CRL_EINVAL, "crl_rollout_record: step %lld is not the next step (%d of %d steps recorded)", (long long)t, r->recorded, r->steps);
+    if (int rc = r->check_record("crl_rollout_record", t)) return rc;
     const int64_t n = r->n;
     RecordArgs a{frame_dev, frame_stride, reset_dev, actions_dev, action_stride, values_dev, logp_dev, t == 0 ? r->depth_carry : r->depth + (t - 1) * n,
                  reinterpret_cast<uint32_t *>(r->planes + (t + kHist) * n * kPlanePad), r->reset + t * n, r->depth + t * n, r->actions + t * n,
@@ -335,9 +322,7 @@ int crl_rollout_outcome(crl_rollout *r, int64_t t, const float *rewards_dev, int
     if (!r || !rewards_dev || !done_dev) return crl_fail(CRL_EINVAL, "crl_rollout_outcome: null argument");
     if (reward_stride < 1 || ((uintptr_t)rewards_dev & 3))
         return crl_fail(CRL_EINVAL, "crl_rollout_outcome: reward_stride must be >= 1 (float32 elements), rewards 4-byte aligned");
-    if (r->state != kActive || t != r->outcomes || t >= r->recorded)
-        return crl_fail(CRL_EINVAL, "crl_rollout_outcome: step %lld has no record, or has its outcome (%d steps recorded, %d outcomes)", (long long)t,
-                        r->state == kActive ? r->recorded : 0, r->state == kActive ? r->outcomes : 0);
+    if (int rc = r->check_outcome("crl_rollout_outcome", t)) return rc;
     const int64_t n = r->n;
     hipLaunchKernelGGL(rollout_outcome_kernel, dim3(blocks_of(n)), dim3(256), 0, (hipStream_t)stream, rewards_dev, reward_stride, done_dev, r->rewards + t * n,
                        r->done + t * n, n);
@@ -350,8 +335,7 @@ int crl_rollout_finish(crl_rollout *r, const float *last_values_dev, double gamm
     crl_fail_no_ctx();
     if (!r) return crl_fail(CRL_EINVAL, "crl_rollout_finish: null storage");
     if ((uintptr_t)last_values_dev & 3) return crl_fail(CRL_EINVAL, "crl_rollout_finish: last_values must be 4-byte aligned");
-    if (r->state == kFresh || r->outcomes != r->steps)
-        return crl_fail(CRL_EINVAL, "crl_rollout_finish: %d of %d steps have their outcome", r->state == kFresh ? 0 : r->outcomes, r->steps);
+    if (int rc = r->check_finish("crl_rollout_finish")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = r->n, tn = n * r->steps;
     const float g = (float)gamma;
@@ -359,15 +343,7 @@ int crl_rollout_finish(crl_rollout *r, const float *last_values_dev, double gamm
     hipLaunchKernelGGL(rollout_gae_kernel, dim3(blocks_of(n)), dim3(256), 0, st, r->rewards, r->values, r->done, last_values_dev, g, gl, r->adv, r->ret, n,
                        r->steps);
     HIP_TRY(hipGetLastError());
-    if (normalize) {
-        const int groups = (int)(blocks_of(tn) < (unsigned)kRedGroups ? blocks_of(tn) : (unsigned)kRedGroups);
-        double *partials = r->stats + 2;
-        hipLaunchKernelGGL(rollout_stats_partial_kernel<false>, dim3(groups), dim3(kRedBlock), 0, st, r->adv, tn, r->stats, partials);
-        hipLaunchKernelGGL(rollout_stats_final_kernel<false>, dim3(1), dim3(kRedGroups), 0, st, partials, groups, tn, r->stats);
-        hipLaunchKernelGGL(rollout_stats_partial_kernel<true>, dim3(groups), dim3(kRedBlock), 0, st, r->adv, tn, r->stats, partials);
-        hipLaunchKernelGGL(rollout_stats_final_kernel<true>, dim3(1), dim3(kRedGroups), 0, st, partials, groups, tn, r->stats);
-        HIP_TRY(hipGetLastError());
-    }
+    if (normalize) HIP_TRY(rollout_stats_launch(PongAdvSrc{r->adv}, tn, r->stats, st));
     r->normalize = normalize != 0;
     r->state = kFinished;
     return CRL_OK;
@@ -382,7 +358,7 @@ int crl_rollout_gather(crl_rollout *r, const int64_t *idx_dev, int64_t count, vo
     if (((uintptr_t)idx_dev & 7) || ((uintptr_t)obs_out_dev & (obs_dtype == CRL_OBS_F32 ? 15 : 3)) || ((uintptr_t)actions_out_dev & 3) ||
         ((uintptr_t)logp_out_dev & 3) || ((uintptr_t)values_out_dev & 3) || ((uintptr_t)returns_out_dev & 3) || ((uintptr_t)adv_out_dev & 3))
         return crl_fail(CRL_EINVAL, "crl_rollout_gather: misaligned pointer (idx 8 bytes, a float32 observation 16, everything else 4)");
-    if (r->state != kFinished) return crl_fail(CRL_EINVAL, "crl_rollout_gather: the rollout is not finished (crl_rollout_finish computes what a sample holds)");
+    if (int rc = r->check_finished("crl_rollout_gather")) return rc;
     if (count == 0) return CRL_OK;
     GatherArgs a{reinterpret_cast<const uint32_t *>(r->planes), r->depth, idx_dev, count, (uint32_t)r->n, (uint32_t)(r->n * r->steps - 1), obs_out_dev, r->actions, r->logp, r->values, r->ret,
                  r->adv, actions_out_dev, logp_out_dev, values_out_dev, returns_out_dev, adv_out_dev, r->normalize ? r->stats : nullptr};
@@ -407,9 +383,7 @@ int crl_rollout_stats(crl_rollout *r, double *out2_host) {
 int crl_rollout_get_info(crl_rollout *r, int32_t *out4_host) {
     crl_fail_no_ctx();
     if (!r || !out4_host) return crl_fail(CRL_EINVAL, "crl_rollout_get_info: null argument");
-    out4_host[0] = r->state, out4_host[1] = r->recorded, out4_host[2] = r->outcomes, out4_host[3] = r->normalize ? 1 : 0;
-    if (r->state == kFinished) out4_host[1] = out4_host[2] = r->steps;
-    if (r->state == kFresh) out4_host[1] = out4_host[2] = 0;
+    r->info(out4_host);
     return CRL_OK;
 }
 
@@ -471,18 +445,13 @@ int crl_rollout_set_state(crl_rollout *r, const int32_t *info4_host, int64_t row
                           const uint8_t *done_dev, const float *returns_dev, const float *adv_dev, const double *stats_dev, void *stream) {
     crl_fail_no_ctx();
     if (!r || !info4_host) return crl_fail(CRL_EINVAL, "crl_rollout_set_state: null argument");
-    const int state = info4_host[0], recorded = info4_host[1], outcomes = info4_host[2];
-    const bool ok = state >= kFresh && state <= kFinished && outcomes >= 0 && outcomes <= recorded && recorded <= r->steps &&
-                    (state != kFresh || recorded == 0) && (state != kFinished || outcomes == r->steps);
-    if (!ok)
-        return crl_fail(CRL_EINVAL, "crl_rollout_set_state: state %d with %d steps recorded and %d outcomes does not fit a storage of %d steps", state, recorded,
-                        outcomes, r->steps);
+    if (int rc = r->check_restore("crl_rollout_set_state", info4_host)) return rc;
     const RolloutArrays x{const_cast<uint8_t *>(planes_dev), const_cast<uint8_t *>(front_depth_dev), const_cast<uint8_t *>(reset_dev),
                           const_cast<uint8_t *>(depth_dev), const_cast<int32_t *>(actions_dev), const_cast<float *>(logp_dev),
                           const_cast<float *>(values_dev), const_cast<float *>(rewards_dev), const_cast<uint8_t *>(done_dev),
                           const_cast<float *>(returns_dev), const_cast<float *>(adv_dev), const_cast<double *>(stats_dev)};
     if (int rc = rollout_copy_state("crl_rollout_set_state", r, true, row0, rows, steps, x, (hipStream_t)stream)) return rc;
-    r->state = state, r->recorded = recorded, r->outcomes = outcomes, r->normalize = info4_host[3] != 0;
+    r->restore(info4_host);
     return CRL_OK;
 }
 

@@ -159,7 +159,6 @@ class _PPOLearner:
     _SIZED = True                # crl_ppo_get_state / set_state carry the blob's size and scratch_rows: one C object, two networks
     _weights_of = staticmethod(_learner_weights)
     _views = staticmethod(blob_views)                                  # a flat blob as the tensors' views by key
-    _samples = staticmethod(lambda s: s.num_steps * s.num_envs)        # the samples a finished storage holds
 
     def _open(self, device, hyper):
         """What every constructor starts with: the GPU, the hyper-parameters, the device."""
@@ -215,7 +214,7 @@ class _PPOLearner:
         if teacher is not None:
             if not isinstance(teacher, Teacher):
                 raise ValueError(f"teacher must be a Teacher or None, not {type(teacher).__name__}")
-            native = teacher._native(self.device, self._samples(storage))
+            native = teacher._native(self.device, storage._total())
         with torch.cuda.device(self.device):
             ip = C.c_void_p(idx.data_ptr()) if idx.numel() else None
             if teacher is None:
@@ -238,7 +237,7 @@ class _PPOLearner:
         """``num_epochs`` passes over the finished ``storage``: per pass one ``torch.randperm`` on the device (``generator``: a device
         generator, for a reproducible order) cut into ``num_mini_batch`` batches of T * N // num_mini_batch samples, ``grad`` and ``step``
         per batch; ``teacher`` goes to every ``grad``.  Nothing synchronises."""
-        total = self._samples(storage)
+        total = storage._total()
         size = total // int(num_mini_batch)
         assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
         extra = () if teacher is None else (teacher,)  # (a learner without a teacher term takes none)

@@ -47,7 +47,73 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class RolloutStorage:
+class _RolloutBase:
+    """What the rollout storages share (``RolloutStorage`` here, ``car_learner.CarRolloutStorage``): the step counters' side of the
+    object.  A subclass names its C prefix and what a sample is: ``_total()``, ``gather`` and the arrays of its state dict."""
+    _C = "crl_rollout_"  # the C prefix of the storage's calls
+    _NSTATS = 2          # the doubles ``stats()`` reads
+    _STATES = ("fresh", "active", "finished")
+
+    def _c(self, name):
+        return getattr(self._L, self._C + name)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _on_device(self):
+        """The storage's calls launch on the device that is current (include/crl.h): every one of them runs inside this."""
+        return torch.cuda.device(self.device)
+
+    def _info(self, contents=True):
+        """(state, recorded, outcomes, normalised); ``contents``: that of the ``state_dict`` which asks"""
+        out = (C.c_int32 * 8)()  # (the car's call appends its sizes)
+        N.check(self._c("get_info")(self._h, out))
+        if not contents and self._STATES[out[0]] == "active" and out[1]:
+            raise ValueError("state_dict(contents=False) in the middle of a rollout would drop the steps recorded so far: pass contents=True")
+        return self._STATES[out[0]], out[1], out[2], bool(out[3])
+
+    def _finish(self, last_values):
+        with self._on_device():
+            N.check(self._c("finish")(self._h, _ptr(last_values), self.gamma, self.gae_lambda, int(self.normalize_advantage), self._stream()))
+
+    def stats(self):
+        out = (C.c_double * self._NSTATS)()
+        with self._on_device():
+            N.check(self._c("stats")(self._h, out))
+        return tuple(out)
+
+    def minibatches(self, num_mini_batch, generator=None, **how):
+        total = self._total()
+        size = total // int(num_mini_batch)
+        assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
+        perm = torch.randperm(total, device=self.device, generator=generator)
+        for k in range(int(num_mini_batch)):
+            yield self.gather(perm[k * size:(k + 1) * size], **how)
+
+    def _check_state_header(self, sd, **sizes):
+        """What ``load_state_dict`` looks at before the arrays: (state, step, outcomes, gamma, gae_lambda, normalize_advantage, contents)"""
+        what, T = type(self).__name__, self.num_steps
+        K.check_header(sd, what, what, num_steps=T, num_envs=self.num_envs, **sizes)
+        state = sd.get("state")
+        if state not in self._STATES:
+            raise K.refuse(f"{what}: state must be fresh, active or finished, not {state!r}")
+        step, outcomes = K.check_counter(sd.get("step"), 31, "step", what), K.check_counter(sd.get("outcomes"), 31, "outcomes", what)
+        if step > T or outcomes > step or (state == "finished" and outcomes != T) or (state == "fresh" and step):
+            raise K.refuse(f"{what}: step {step} and {outcomes} outcomes do not fit a {state} rollout of {T} steps")
+        try:
+            gamma, lam, norm = float(sd["gamma"]), float(sd["gae_lambda"]), bool(sd["normalize_advantage"])
+        except (KeyError, TypeError, ValueError):
+            raise K.refuse(f"{what}: gamma, gae_lambda and normalize_advantage are needed") from None
+        c = sd.get("contents")
+        if c is None:
+            if state == "active" and step:
+                raise K.refuse(f"{what}: a state dict without contents cannot continue in the middle of a rollout (step {step})")
+        elif not isinstance(c, dict):
+            raise K.refuse(f"{what}: contents must be a dict")
+        return state, step, outcomes, gamma, lam, norm, c
+
+
+class RolloutStorage(_RolloutBase):
     def __init__(self, num_steps, num_envs, device=None, gamma=0.99, gae_lambda=0.95, normalize_advantage=True, debug=False):
         """``debug``: assert on the host that every index handed to ``gather`` lies in [0, T * N) -- a device synchronisation per call,
         so not for the hot path, where the validity of the indices is the caller's."""
@@ -65,14 +131,8 @@ class RolloutStorage:
         self._h = h
         self.step = 0  # the step the next ``record`` writes
 
+    _total = lambda self: self.num_steps * self.num_envs  # noqa: E731  (the samples a finished storage holds)
     _frames = Policy._frames  # what ``record`` takes as ``obs`` is what ``Policy.act_rollout`` takes (it reads num_envs and device only)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _on_device(self):
-        """The ``crl_rollout_*`` calls launch on the device that is current (include/crl.h): every one of them runs inside this."""
-        return torch.cuda.device(self.device)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -137,26 +197,15 @@ class RolloutStorage:
     def finish(self, last_values=None):
         """Returns and advantages by GAE (``rules.gae_reference``) and, with ``normalize_advantage``, the advantages' mean and standard
         deviation.  ``last_values``: the critic's values of the observation after the last step, float32 (N,); None: zeros."""
-        if last_values is not None:
-            last_values = self._per_env(last_values, (torch.float32,), "last_values").reshape(-1).contiguous()
-        with self._on_device():
-            N.check(self._L.crl_rollout_finish(self._h, _ptr(last_values), self.gamma, self.gae_lambda, int(self.normalize_advantage), self._stream()))
+        self._finish(None if last_values is None else self._per_env(last_values, (torch.float32,), "last_values").reshape(-1).contiguous())
 
     def stats(self):
         """(mean, std) of the advantages as the device computed them, float64.  Synchronises the device: logging and tests."""
-        out = (C.c_double * 2)()
-        with self._on_device():
-            N.check(self._L.crl_rollout_stats(self._h, out))
-        return out[0], out[1]
+        return super().stats()
 
     # ---- checkpoint / resume (include/crl.h "checkpoint / resume")
     _STEP_FIELDS = (("reset", torch.uint8), ("depth", torch.uint8), ("actions", torch.int32), ("log_probs", torch.float32), ("values", torch.float32))
     _OUTCOME_FIELDS = (("rewards", torch.float32), ("dones", torch.uint8))
-
-    def _info(self):
-        out = (C.c_int32 * 4)()
-        N.check(self._L.crl_rollout_get_info(self._h, out))
-        return ("fresh", "active", "finished")[out[0]], out[1], out[2], bool(out[3])
 
     def _copy_state(self, call, info, row0, planes, front_depth, steps, per_step, returns=None, adv=None, stats=None):
         """``crl_rollout_get_state`` / ``_set_state`` over device tensors; ``per_step``: dict name -> tensor or None"""
@@ -189,10 +238,8 @@ class RolloutStorage:
         ``contents=False`` is the small form for a checkpoint BETWEEN iterations (after the update, before the next ``begin(None)``):
         5 293 bytes per env (``state_nbytes``) instead of ``nbytes()``'s (T + 3) * 1776 + 27 T.  Loaded, the storage stands in front of
         ``begin(None)`` with that carry; what was recorded is gone.  In the middle of a rollout it is refused."""
-        state, recorded, outcomes, normalized = self._info()
+        state, recorded, outcomes, normalized = self._info(contents)
         T, n, dev = self.num_steps, self.num_envs, self.device
-        if not contents and state == "active" and recorded:
-            raise ValueError("state_dict(contents=False) in the middle of a rollout would drop the steps recorded so far: pass contents=True")
         sd = {"kind": "RolloutStorage", "num_steps": T, "num_envs": n, "gamma": self.gamma, "gae_lambda": self.gae_lambda,
               "normalize_advantage": self.normalize_advantage, "step": self.step, "outcomes": outcomes, "state": state, "finished": state == "finished",
               "carry_planes": None, "carry_depth": None, "contents": None}
@@ -229,28 +276,13 @@ class RolloutStorage:
         ``gamma``, ``gae_lambda`` and ``normalize_advantage`` become the dict's.  Ordered on the current stream and SYNCHRONISES with it
         (the staging tensors are the call's own)."""
         T, n, dev, what = self.num_steps, self.num_envs, self.device, "RolloutStorage"
-        K.check_header(sd, what, what, num_steps=T, num_envs=n)
-        state = sd.get("state")
-        if state not in ("fresh", "active", "finished"):
-            raise K.refuse(f"{what}: state must be fresh, active or finished, not {state!r}")
-        step, outcomes = K.check_counter(sd.get("step"), 31, "step", what), K.check_counter(sd.get("outcomes"), 31, "outcomes", what)
-        if step > T or outcomes > step or (state == "finished" and outcomes != T) or (state == "fresh" and step):
-            raise K.refuse(f"{what}: step {step} and {outcomes} outcomes do not fit a {state} rollout of {T} steps")
-        try:
-            gamma, lam, norm = float(sd["gamma"]), float(sd["gae_lambda"]), bool(sd["normalize_advantage"])
-        except (KeyError, TypeError, ValueError):
-            raise K.refuse(f"{what}: gamma, gae_lambda and normalize_advantage are needed") from None
-        c = sd.get("contents")
+        state, step, outcomes, gamma, lam, norm, c = self._check_state_header(sd)
         np_of = {torch.uint8: 1, torch.int32: 4, torch.float32: 4}
         if c is None:
-            if state == "active" and step:
-                raise K.refuse(f"{what}: a state dict without contents cannot continue in the middle of a rollout (step {step})")
             planes = K.check_array(sd, "carry_planes", (3, n, 42, 42), 1, what).view(np.uint8)
             front = K.check_array(sd, "carry_depth", (n,), 1, what).view(np.uint8)
             info, recorded, f, g, fin = (C.c_int32 * 4)(0, 0, 0, 0), 0, {}, {}, None
         else:
-            if not isinstance(c, dict):
-                raise K.refuse(f"{what}: contents must be a dict")
             recorded = T if state == "finished" else step
             planes = K.check_array(c, "planes", (recorded + 3, n, 42, 42), 1, what).view(np.uint8)
             front = K.check_array(c, "front_depth", (n,), 1, what).view(np.uint8)
@@ -264,7 +296,7 @@ class RolloutStorage:
                     fin.append(np.array([float(c["adv_mean"]), float(c["adv_std"])], np.float64))
                 except (KeyError, TypeError, ValueError):
                     raise K.refuse(f"{what}: adv_mean and adv_std are needed after a finish") from None
-            info = (C.c_int32 * 4)(("fresh", "active", "finished").index(state), recorded, outcomes, int(normalized))
+            info = (C.c_int32 * 4)(self._STATES.index(state), recorded, outcomes, int(normalized))
 
         def up(a, dtype):  # (the bits as they are, under the storage's dtype)
             as_np = {torch.uint8: np.uint8, torch.int32: np.int32, torch.float32: np.float32, torch.float64: np.float64}[dtype]
@@ -317,9 +349,4 @@ class RolloutStorage:
     def minibatches(self, num_mini_batch, generator=None, obs_dtype=torch.float32):
         """``num_mini_batch`` batches of T * N // num_mini_batch samples each, drawn without replacement by ``torch.randperm`` on the
         device (``generator``: a device generator, for a reproducible order)."""
-        total = self.num_steps * self.num_envs
-        size = total // int(num_mini_batch)
-        assert size >= 1, f"{total} samples cannot fill {num_mini_batch} minibatches"
-        perm = torch.randperm(total, device=self.device, generator=generator)
-        for k in range(int(num_mini_batch)):
-            yield self.gather(perm[k * size:(k + 1) * size], obs_dtype=obs_dtype)
+        return super().minibatches(num_mini_batch, generator, obs_dtype=obs_dtype)

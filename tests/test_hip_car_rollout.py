@@ -250,3 +250,62 @@ def test_state_dict_round_trips_into_a_fresh_object(contents):
     for x, y in zip(a, b):
         assert torch.equal(x.view(torch.uint8), y.view(torch.uint8))
     fresh.close(), r.close()
+
+
+def made_up_lines(rows, T, seed):
+    """Host data of an unfinished rollout in the shape of tests/car_ppo_cases.Pool.lines(): uint32 [T * rows, 32] with made-up
+    observations, actions, log-probs, values and rewards, 20 % dones and every seventh sample dead (zeros, as the device stores a done
+    car); returns and advantages are left at 0 for ``finish``.  Also (live [T * rows], rewards, values, dones [T, rows], last [rows])."""
+    rs = np.random.RandomState(seed)
+    S = T * rows
+    live = np.arange(S) % 7 != 6
+    ln = np.zeros((S, 32), F)
+    ln[:, :26] = rs.standard_normal((S, 26)).astype(F)
+    ln[~live, :25] = 0
+    dones = rs.random_sample((T, rows)) < 0.2
+    last = rs.standard_normal(rows).astype(F)
+    out = ln.view(np.uint32)
+    out[:, 28] = live.astype(np.uint32) | (dones.reshape(-1).astype(np.uint32) << 1)
+    return out, live, ln[:, 25].reshape(T, rows).copy(), ln[:, 24].reshape(T, rows).copy(), dones, last
+
+
+def test_statistics_where_a_lane_takes_a_second_trip():
+    """260 rows x 253 steps = 65 780 samples, just over the 65 536 that 256 workgroups of 256 lanes cover in one trip: the first 244
+    lanes of workgroup 0 add a second sample.  Loaded as an active rollout whose steps all have their outcome; no env step."""
+    _need_gpu()
+    import competitive_rl_amd as crl
+    from competitive_rl_amd import rules as R
+
+    n, T = 130, 253
+    rows, total = 2 * n, 2 * n * T
+    assert 65536 < total < 65536 + 256
+    lines, live, rew, val, dones, last = made_up_lines(rows, T, 31)
+    env = crl.HipCarVecEnv(n, seed=2)
+    st = crl.CarRolloutStorage(env, T, cars=(0, 1))
+    st.load_state_dict({"kind": "CarRolloutStorage", "num_steps": T, "num_envs": n, "players": 2, "cars": (0, 1), "gamma": 0.99, "gae_lambda": 0.95,
+                        "normalize_advantage": True, "state": "active", "step": T, "outcomes": T,
+                        "contents": {"lines": lines, "stats": np.zeros(3), "normalized": False}})
+    st.finish(torch.from_numpy(last.reshape(n, 2)).cuda())
+    adv, ret = R.gae_reference(rew, val, dones, last, 0.99, 0.95)
+    adv, ret = adv.reshape(-1), ret.reshape(-1)
+    stored = st.state_dict()["contents"]["lines"]
+    assert np.array_equal(stored[:, 26], bits(ret)) and np.array_equal(stored[:, 27], bits(adv))
+    assert np.array_equal(np.delete(stored, (26, 27), axis=1), np.delete(lines, (26, 27), axis=1))
+    x = [float(v) for v in adv[live]]
+    L = len(x)
+    mean = math.fsum(x) / L
+    std = math.sqrt(math.fsum((v - mean) ** 2 for v in x) / (L - 1))
+    got_mean, got_std, got_live = st.stats()
+    sum_abs = math.fsum(abs(v) for v in x)
+    print("car rollout statistics, second trip: L %d of %d, mean error %.3g (bound %.3g)  std relative error %.3g (bound %.3g)" % (
+        L, total, abs(got_mean - mean), total * 2.0 ** -53 * sum_abs / L, abs(got_std - std) / std, total * 2.0 ** -50))
+    assert got_live == L == total - total // 7
+    assert abs(got_mean - mean) <= total * 2.0 ** -53 * sum_abs / L
+    assert abs(got_std - std) <= total * 2.0 ** -50 * std
+    idx = np.random.RandomState(0).permutation(total).astype(np.int64)
+    got = st.gather(torch.from_numpy(idx).cuda(), fields=("returns", "advantages", "live"))
+    want = ((adv - F(got_mean)) / (F(got_std) + F(1e-5))).astype(F)
+    assert np.array_equal(bits(got.returns.cpu().numpy()), bits(ret[idx]))
+    assert np.array_equal(bits(got.advantages.cpu().numpy()), bits(want[idx]))
+    assert np.array_equal(got.live.cpu().numpy().astype(bool), live[idx])
+    st.close(), env.close()
