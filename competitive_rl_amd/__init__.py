@@ -20,8 +20,8 @@ from .car_drivers import CarDrivers, get_builtin_car_driver_names
 from .rules import car_driver_reference
 from .car_policy import CarPolicy
 from .rules import car_mlp_reference, car_obs_reference, car_policy_reference
-from .car_learner import CarPPO, CarPPOStats, CarRolloutBatch, CarRolloutStorage
-from .rules import car_ppo_loss_reference
+from .car_learner import CarPPO, CarPPOStats, CarRolloutBatch, CarRolloutStorage, CarTeacher, CarTeacherStats
+from .rules import car_ppo_loss_reference, car_ppo_teacher_loss_reference
 from .car_league import CarLeague
 from .rules import car_league_draw_reference, car_league_reference
 from .competitive_car import make_competitive_car_racing
@@ -46,6 +46,6 @@ def register_competitive_envs():
     register_car_racing()
 
 
-__all__ = ["make_envs", "DummyVecEnv", "SubprocVecEnv", "make_env_a2c_atari", "make_car_racing", "make_car_racing_double", "EnvThunk", "HipPongVecEnv", "HipCarVecEnv", "VecEnv", "VecEnvWrapper", "tile_images", "LazyInfos", "FrameStackTensor", "TournamentEnvWrapper", "LeagueEnvWrapper", "LeagueLedger", "ledger_draw_reference", "pfsp_weights_reference", "LeagueArena", "ArenaBooks", "arena_draw_reference", "balance_weights_reference", "Policy", "rollout_logp_reference", "RolloutStorage", "RolloutBatch", "LightPPO", "FullPPO", "PPOStats", "ppo_loss_reference", "ppo_full_loss_reference", "adam_reference", "gae_reference", "rollout_stack_reference", "make_competitive_car_racing", "CarDrivers", "get_builtin_car_driver_names", "car_driver_reference", "CarPolicy", "car_obs_reference", "car_mlp_reference", "car_policy_reference", "CarRolloutStorage", "CarRolloutBatch", "CarPPO", "CarPPOStats", "car_ppo_loss_reference", "CarLeague", "car_league_reference", "car_league_draw_reference", "step_envs", "evaluate", "evaluate_two_policies", "evaluate_two_policies_in_batch", "CHEAT_CODES", "get_builtin_agent_names", "get_compute_action_function", "get_random_policy", "get_rule_based_policy",
+__all__ = ["make_envs", "DummyVecEnv", "SubprocVecEnv", "make_env_a2c_atari", "make_car_racing", "make_car_racing_double", "EnvThunk", "HipPongVecEnv", "HipCarVecEnv", "VecEnv", "VecEnvWrapper", "tile_images", "LazyInfos", "FrameStackTensor", "TournamentEnvWrapper", "LeagueEnvWrapper", "LeagueLedger", "ledger_draw_reference", "pfsp_weights_reference", "LeagueArena", "ArenaBooks", "arena_draw_reference", "balance_weights_reference", "Policy", "rollout_logp_reference", "RolloutStorage", "RolloutBatch", "LightPPO", "FullPPO", "PPOStats", "ppo_loss_reference", "ppo_full_loss_reference", "adam_reference", "gae_reference", "rollout_stack_reference", "make_competitive_car_racing", "CarDrivers", "get_builtin_car_driver_names", "car_driver_reference", "CarPolicy", "car_obs_reference", "car_mlp_reference", "car_policy_reference", "CarRolloutStorage", "CarRolloutBatch", "CarPPO", "CarPPOStats", "CarTeacher", "CarTeacherStats", "car_ppo_loss_reference", "car_ppo_teacher_loss_reference", "CarLeague", "car_league_reference", "car_league_draw_reference", "step_envs", "evaluate", "evaluate_two_policies", "evaluate_two_policies_in_batch", "CHEAT_CODES", "get_builtin_agent_names", "get_compute_action_function", "get_random_policy", "get_rule_based_policy",
            "register_pong", "register_car_racing", "register_competitive_envs",
            "ShardSpec", "shard_of", "all_gather_step", "StepGather"]

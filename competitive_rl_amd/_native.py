@@ -86,6 +86,15 @@ class CrlPpoTeacher(C.Structure):
                 ("temperature", C.c_float), ("coef", C.c_float), ("policy_term", C.c_int32)]
 
 
+class CrlCarPpoTeacher(C.Structure):
+    """crl_car_ppo_teacher (include/crl.h "car ppo update, teacher targets")."""
+    _fields_ = [("target_dev", C.c_void_p), ("value_targets_dev", C.c_void_p), ("rows", C.c_int64), ("teacher_log_std", C.c_float * 2),
+                ("point", C.c_int32), ("kind", C.c_int32), ("coef", C.c_float), ("policy_term", C.c_int32)]
+
+
+CRL_CAR_TEACHER_CE, CRL_CAR_TEACHER_MSE = 0, 1  # enum crl_car_teacher_kind
+
+
 class CrlStackDesc(C.Structure):
     """crl_stack_desc (include/crl.h): a FrameStackTensor drawn by the step."""
     _fields_ = [("stack_dev", C.c_void_p), ("planes", C.c_int32), ("dtype", C.c_int32), ("agent", C.c_int32),
@@ -269,6 +278,8 @@ SIGNATURES = {
     "crl_car_ppo_get_weights": (i32, [vp, vp]),
     "crl_car_ppo_weights_dev": (i32, [vp, P(vp)]),
     "crl_car_ppo_grad": (i32, [vp, vp, vp, i64, vp, vp]),
+    "crl_car_ppo_grad_teacher": (i32, [vp, vp, vp, i64, vp, vp, vp]),
+    "crl_car_ppo_teacher_stats": (i32, [vp, P(f64)]),
     "crl_car_ppo_get_grad": (i32, [vp, P(vp), vp]),
     "crl_car_ppo_step": (i32, [vp, vp, vp]),
     "crl_car_ppo_stats": (i32, [vp, P(f64)]),

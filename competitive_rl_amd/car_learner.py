@@ -27,6 +27,22 @@ The observation of a car is 84 bytes, so the whole loop lives on the device; no 
 Torch allocates, draws the permutation and names the stream; everything else is HIP.  There is no CPU path.  The loss, its summation
 shape and the optimiser step are the header's written rule; ``rules.car_ppo_loss_reference`` (autograd, float64) and
 ``rules.adam_reference`` restate them.
+
+Teacher targets (include/crl.h "car ppo update, teacher targets") add ``coef * term`` towards a per-sample target action or mean.
+Cloning RULE_BASED by DAgger -- the learner drives, a second ``CarDrivers`` answers every visited state into a scratch tensor:
+
+    rule = CarDrivers(env)
+    rule.assign(0, "RULE_BASED"), rule.assign(1, "RULE_BASED")
+    target = torch.zeros((num_steps, n, 2, 2), device=env.device)
+    for t in range(num_steps):
+        rule.act(target[t])                                            # before the step that consumes the learner's action
+        storage.record(t, policy, "learner", obs, actions, values, log_probs)
+        ...
+    learner.update(storage, 4, 8, teacher=CarTeacher(target, loss="mse", policy_term=False))
+    print(learner.teacher_stats())                                     # term, kl, abs_err, taught (synchronises)
+
+``CarTeacher(mean_of_a_snapshot, log_std=snapshot_weights, coef=0.1)`` with the policy term left on is PPO held near that snapshot (a
+deterministic ``CarPolicy`` slot writes its mean the same way); ``rules.car_ppo_teacher_loss_reference`` restates the loss.
 """
 import collections
 import ctypes as C
@@ -40,12 +56,13 @@ from .car_policy import CarPolicy
 from .ppo import _PPOLearner
 from .rollout import _ptr, _RolloutBase
 from .rules import (CAR_POLICY_KEYS, CAR_POLICY_SHAPES, CAR_PPO_DEFAULTS, adam_reference, car_policy_pack, car_policy_unpack,  # noqa: F401  (re-exported)
-                    car_ppo_loss_reference, gae_reference)
+                    car_ppo_loss_reference, car_ppo_teacher_loss_reference, check_car_teacher, gae_reference)
 
-__all__ = ["CarRolloutStorage", "CarRolloutBatch", "CarPPO", "CarPPOStats", "car_blob_views"]
+__all__ = ["CarRolloutStorage", "CarRolloutBatch", "CarPPO", "CarPPOStats", "CarTeacher", "CarTeacherStats", "car_blob_views"]
 
 CarRolloutBatch = collections.namedtuple("CarRolloutBatch", ("obs", "actions", "old_log_probs", "values", "returns", "advantages", "live"))
 CarPPOStats = collections.namedtuple("CarPPOStats", ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "grad_norm", "steps", "live"))
+CarTeacherStats = collections.namedtuple("CarTeacherStats", ("term", "kl", "abs_err", "taught"))
 LINE_WORDS = 32  # one sample = one aligned 128-byte line
 _CARS = {(0,): 1, (1,): 2, (0, 1): 3}
 
@@ -217,10 +234,61 @@ class CarRolloutStorage(_RolloutBase):
         torch.cuda.current_stream(self.device).synchronize()  # the staging tensors above are this call's own
 
 
+class CarTeacher:
+    """Teacher targets for ``CarPPO.grad`` / ``update`` (include/crl.h "car ppo update, teacher targets"): a small value object over the
+    CALLER's tensors, like ``ppo.Teacher`` -- they are not learner state, and the learner keeps no reference beyond the call.
+      target         float32 (T*R, 2), (T, R, 2) or (T, N, C, 2): the teacher's action or mean for every stored sample; a row with a
+                     NaN or an infinity has no teacher term
+      log_std        None: a point teacher (RULE_BASED, a network's mean taken as it is); a pair of floats, or a car policy weight
+                     dict or blob whose ``log_std`` is taken: the Gaussian teacher N(target, exp(log_std)^2)
+      loss           "ce": E_q[-log p], for a point teacher the Gaussian negative log-likelihood of the target; "mse":
+                     0.5 |mean - target|^2, which leaves log_std to the other terms
+      value_targets  optionally float32 (T*R,), (T, R) or (T, N, C) in place of the stored returns (a teacher's critic)
+    All contiguous, on the learner's device, row ``t * R + row`` the sample ``storage.gather`` calls so.  The loss per live sample
+    becomes ``policy_term * policy + vf * value - ent * entropy + coef * term``: ``policy_term=False`` is pure imitation, ``coef=0``
+    with ``policy_term=True`` the plain PPO loss.  A wrong type, dtype or shape raises a ``ValueError`` here; the device and the row
+    count are checked against the learner and the storage by ``grad``, before any native call."""
+
+    def __init__(self, target, log_std=None, loss="ce", value_targets=None, coef=1.0, policy_term=True):
+        self.point, self.log_std, self.kind, self.coef, self.policy_term = check_car_teacher(log_std, loss, coef, policy_term)
+        self.loss, self.target, self.value_targets = loss, target, value_targets
+        rows = set()
+        for name, t, tail in (("target", target, (2,)), ("value_targets", value_targets, ())):
+            if t is None and name != "target":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise ValueError(f"CarTeacher: {name} must be a torch.float32 tensor")
+            lead = t.shape[:t.dim() - len(tail)]
+            if tuple(t.shape[t.dim() - len(tail):]) != tail or len(lead) not in (1, 2, 3) or not t.is_contiguous():
+                raise ValueError(f"CarTeacher: {name} must be contiguous (T*R, ...), (T, R, ...) or (T, N, C, ...) with trailing shape {tail}, "
+                                 f"not {tuple(t.shape)}")
+            if t.data_ptr() % (8 if tail else 4):
+                raise ValueError(f"CarTeacher: {name} must start on a multiple of {8 if tail else 4} bytes")
+            rows.add(int(np.prod(lead)))
+        if len(rows) != 1:
+            raise ValueError(f"CarTeacher: the tensors hold different numbers of samples ({sorted(rows)})")
+        self.rows = rows.pop()
+
+    def _tensors(self):
+        return [t for t in (self.target, self.value_targets) if t is not None]
+
+    def _native(self, device, total):
+        """the crl_car_ppo_teacher of this teacher for a learner on ``device`` and a storage of ``total`` samples"""
+        for t in self._tensors():
+            if t.device != device:
+                raise ValueError(f"CarTeacher: a tensor lives on {t.device}, the learner on {device}")
+        if self.rows != total:
+            raise ValueError(f"CarTeacher: {self.rows} rows, but the storage holds T * R = {total} samples")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return N.CrlCarPpoTeacher(ptr(self.target), ptr(self.value_targets), self.rows, (C.c_float * 2)(*self.log_std), self.point, self.kind,
+                                  self.coef, self.policy_term)
+
+
 class CarPPO(_PPOLearner):
     """``ppo._PPOLearner`` over ``crl_car_ppo_*``: hyper-parameters, ``step``, ``close`` and the optimiser half of the state dict are
     the base's; here is what the MLP(21, 2) and its line storage make different."""
     _C, _DEFAULTS, _FLOATS, _SIZED = "crl_car_ppo_", CAR_PPO_DEFAULTS, N.CRL_CAR_POLICY_BLOB_FLOATS, False
+    _TEACHER = CarTeacher
     _views = staticmethod(car_blob_views)
     _split = staticmethod(car_policy_unpack)
 
@@ -236,12 +304,13 @@ class CarPPO(_PPOLearner):
             N.check(self._L.crl_car_ppo_create(self.device.index or 0, blob.ctypes.data_as(C.c_void_p), C.byref(h)))
         self._h = h
 
-    def grad(self, storage, idx):
+    def grad(self, storage, idx, teacher=None):
         """The gradient of the loss over the samples ``idx`` (int64 on the device, as ``storage.gather`` takes them) of a finished
         ``CarRolloutStorage``, at the learner's weights: a dict of device VIEWS of the seven gradient tensors in torch layout, for
-        callers with their own optimiser (``grad_blob()``: the same memory as one flat blob); the next ``grad`` overwrites them.  No
-        synchronisation."""
-        return super().grad(storage, idx)
+        callers with their own optimiser (``grad_blob()``: the same memory as one flat blob); the next ``grad`` overwrites them.
+        ``teacher``: a ``CarTeacher`` adds its term to the loss (``teacher_stats()`` then has its statistics); None is the plain PPO
+        loss.  A teacher of the wrong type, device or row count raises a ``ValueError`` and changes nothing.  No synchronisation."""
+        return super().grad(storage, idx, teacher)
 
     def grad_blob(self):
         """The last gradient as a device VIEW of the learner's own memory: float32 (2508,) in the weights' layout (include/crl.h "car
@@ -256,10 +325,17 @@ class CarPPO(_PPOLearner):
         the blob follow the new log_std.  No synchronisation."""
         super().step()
 
-    def update(self, storage, num_epochs, num_mini_batch, generator=None):
+    def update(self, storage, num_epochs, num_mini_batch, generator=None, teacher=None):
         """``num_epochs`` passes over the finished ``storage``: per pass one ``torch.randperm`` on the device cut into
-        ``num_mini_batch`` batches of T * R // num_mini_batch samples, ``grad`` and ``step`` per batch.  Nothing synchronises."""
-        super().update(storage, num_epochs, num_mini_batch, generator)
+        ``num_mini_batch`` batches of T * R // num_mini_batch samples, ``grad`` and ``step`` per batch; ``teacher`` goes to every
+        ``grad``.  Nothing synchronises."""
+        super().update(storage, num_epochs, num_mini_batch, generator, teacher)
+
+    def teacher_stats(self):
+        """``CarTeacherStats`` of the last ``grad`` with a teacher: the means over the taught samples of the teacher term, of
+        KL(teacher || learner) (a Gaussian teacher under "ce"; otherwise 0) and of the mean's absolute error per component, and the
+        taught share of the live samples.  Refuses after a plain ``grad``.  Synchronises the device: logging and tests."""
+        return CarTeacherStats(*super().teacher_stats())
 
     def push(self, policy, name):
         """The master weights into network ``name`` of a ``CarPolicy``: one device-to-device copy ordered on the current stream, the

@@ -19,10 +19,16 @@
 // A workgroup writes its blob of partial sums; the reduce kernel adds them in workgroup order and divides by float32(max(L, 1)) (the
 // five float64 sums: added in float64, divided by L in float64 and rounded once).
 // No floating-point atomics: the same idx gives the same bits.
+//
+// Teacher targets ("car ppo update, teacher targets"): the <true> instantiation of the gradient kernel.  A lane loads one more 8-byte
+// row (and 4 bytes of value target) with its line, the teacher term joins the closed forms of the two means and the two log_std in
+// float64 in front of their one rounding, and four more per-lane float64 sums travel in rows of their own (tstat_part), so that the
+// plain launch's rows, and its code, stay what they were.
 #include <float.h>
 #include <math.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "car_learner.h"
@@ -42,6 +48,7 @@ static constexpr int kStride = 68;   // row stride of the transposed LDS arrays
 static constexpr int kHidPad = 112, kW1Row = 24;
 static constexpr int kStat = 6;      // policy loss, value loss, entropy, old_logp - logp, clipped, live
 static constexpr int kStatRow = kStat + 5;  // a workgroup's row of float64 sums: the statistics, then the five bias sums
+static constexpr int kStatT = 4;     // a teacher gradient's own row: term, kl, abs_err, taught
 static constexpr int kRedBlocks = (kBlob + 255) / 256;
 #define CRL_LN_2PI_F64 1.8378770664093453
 
@@ -61,13 +68,32 @@ struct CarGradArgs {
     CarPpoHyperDev h;
 };
 
+// include/crl.h "car ppo update, teacher targets" as the teacher instantiation carries it
+struct CarTeacherDev {
+    const float2 *target;   // [T * R]: the teacher's action or mean
+    const float *vtarget;   // [T * R] or null = the stored returns
+    double *tstat_part;     // [W][kStatT]: the workgroups' teacher sums, a buffer of their own
+    double sq0, sq1;        // exp(2 lsq_d); 0 for a point teacher
+    double hq;              // (lsq_0 + lsq_1) + (1 + ln 2 pi): what kl takes off ce
+    double coef;
+    bool mse, kl, policy_term;
+};
+
+struct CarGradArgsTeacher : CarGradArgs {  // (built as CarGradArgsTeacher{a, t})
+    CarTeacherDev t;
+};
+
 __device__ __forceinline__ double wave_sum_f64(double p) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) p = p + __shfl_xor(p, m, 64);
     return p;
 }
 
-__global__ __launch_bounds__(64) void car_ppo_grad_kernel(CarGradArgs a) {
+// kTeacher: include/crl.h "car ppo update, teacher targets" -- a lane also loads its sample's target row (and value target), the teacher
+// term joins the closed forms in float64 before their one rounding, and four more statistics are summed.  <false> is what
+// crl_car_ppo_grad launches.
+template <bool kTeacher>
+__global__ __launch_bounds__(64) void car_ppo_grad_kernel(std::conditional_t<kTeacher, CarGradArgsTeacher, CarGradArgs> a) {
     __shared__ __attribute__((aligned(16))) float sh_w1[kHid * kW1Row];  // fc1_w[j][k], rows padded to 24
     __shared__ float sh_b1[kHid], sh_wp0[kHidPad], sh_wp1[kHidPad], sh_wv[kHidPad];
     __shared__ float sh_h[kHidPad * kStride];  // relu(a)[j][sample]; rows 100..111 stay zero
@@ -103,6 +129,7 @@ __global__ __launch_bounds__(64) void car_ppo_grad_kernel(CarGradArgs a) {
         for (int jt = 0; jt < 7; jt++) acc[m][jt] = zero4;
     double gb[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // policy_b[0], policy_b[1], value_b, log_std_0, log_std_1
     double st[kStat] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    [[maybe_unused]] double ts[kStatT] = {0.0, 0.0, 0.0, 0.0};
 
     const int64_t ngroups = (a.count + kG - 1) / kG;
     for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
@@ -120,6 +147,12 @@ __global__ __launch_bounds__(64) void car_ppo_grad_kernel(CarGradArgs a) {
         for (int c = 0; c < 8; c++) {
             const float4 v = src[c];
             q[4 * c] = v.x, q[4 * c + 1] = v.y, q[4 * c + 2] = v.z, q[4 * c + 3] = v.w;
+        }
+        [[maybe_unused]] float2 tg = {0.f, 0.f};  // the teacher's row of sample idx[b] (an entry past count reads row 0 and is not live)
+        [[maybe_unused]] float vt = 0.f;
+        if constexpr (kTeacher) {
+            tg = a.t.target[flat];
+            if (a.t.vtarget) vt = a.t.vtarget[flat];
         }
         const bool live = valid && (__float_as_uint(q[kCarLineFlags]) & kCarFlagLive);
 #pragma unroll
@@ -156,14 +189,36 @@ __global__ __launch_bounds__(64) void car_ppo_grad_kernel(CarGradArgs a) {
             const double lo = 1.0 - (double)a.h.clip, hi = 1.0 + (double)a.h.clip;
             const double surr1 = ratio * A, surr2 = fmin(fmax(ratio, lo), hi) * A;
             const bool active = (A >= 0.0 && ratio < hi) || (A < 0.0 && ratio > lo);
-            const double glp = active ? -(A * ratio) : 0.0;
-            const double dm0 = glp * zz0 / sd0, dm1 = glp * zz1 / sd1;
-            const double dif = v - ret;
+            double glp = active ? -(A * ratio) : 0.0;
+            if constexpr (kTeacher) glp = a.t.policy_term ? glp : 0.0;
+            double dm0 = glp * zz0 / sd0, dm1 = glp * zz1 / sd1;
+            double dl0 = glp * (zz0 * zz0 - 1.0) - (double)a.h.ent, dl1 = glp * (zz1 * zz1 - 1.0) - (double)a.h.ent;
+            double target_v = ret;
+            if constexpr (kTeacher) {
+                if (a.t.vtarget) target_v = (double)vt;
+                if (fabsf(tg.x) <= FLT_MAX && fabsf(tg.y) <= FLT_MAX) {  // taught: an untaught sample's term is 0 by selection
+                    const double e0 = mean0 - (double)tg.x, e1 = mean1 - (double)tg.y;
+                    double term, tm0 = e0, tm1 = e1, tl0 = 0.0, tl1 = 0.0;
+                    if (a.t.mse) {
+                        term = 0.5 * (e0 * e0 + e1 * e1);
+                    } else {
+                        const double var0 = sd0 * sd0, var1 = sd1 * sd1;
+                        const double s0 = a.t.sq0 + e0 * e0, s1 = a.t.sq1 + e1 * e1;
+                        term = ((ls0 + s0 / (2.0 * var0)) + (ls1 + s1 / (2.0 * var1))) + CRL_LN_2PI_F64;
+                        tm0 = e0 / var0, tm1 = e1 / var1;
+                        tl0 = 1.0 - s0 / var0, tl1 = 1.0 - s1 / var1;
+                    }
+                    dm0 = dm0 + a.t.coef * tm0, dm1 = dm1 + a.t.coef * tm1;  // (the teacher term is added last)
+                    dl0 = dl0 + a.t.coef * tl0, dl1 = dl1 + a.t.coef * tl1;
+                    ts[0] += term, ts[1] += a.t.kl ? term - a.t.hq : 0.0, ts[2] += (fabs(e0) + fabs(e1)) / 2.0, ts[3] += 1.0;
+                }
+            }
+            const double dif = v - target_v;
             const double dvd = (double)a.h.vf * dif;
             d0 = (float)dm0, d1 = (float)dm1, dv = (float)dvd;
             gb[0] += dm0, gb[1] += dm1, gb[2] += dvd;
-            gb[3] += glp * (zz0 * zz0 - 1.0) - (double)a.h.ent;
-            gb[4] += glp * (zz1 * zz1 - 1.0) - (double)a.h.ent;
+            gb[3] += dl0;
+            gb[4] += dl1;
             st[0] += -fmin(surr1, surr2), st[1] += 0.5 * (dif * dif), st[2] += (ls0 + ls1) + (1.0 + CRL_LN_2PI_F64);
             st[3] += olp - logp, st[4] += (ratio < lo || ratio > hi) ? 1.0 : 0.0, st[5] += 1.0;
         }
@@ -214,6 +269,13 @@ __global__ __launch_bounds__(64) void car_ppo_grad_kernel(CarGradArgs a) {
         const double sum = wave_sum_f64(gb[k]);
         if (lane == 0) a.stat_part[(int64_t)blockIdx.x * kStatRow + kStat + k] = sum;
     }
+    if constexpr (kTeacher) {
+#pragma unroll
+        for (int k = 0; k < kStatT; k++) {
+            const double sum = wave_sum_f64(ts[k]);
+            if (lane == 0) a.t.tstat_part[(int64_t)blockIdx.x * kStatT + k] = sum;
+        }
+    }
 }
 
 // x[0] + x[stride] + .. + x[(count - 1) stride], added in this order; the loads go out kBurst at a time (the sum of up to 1024 partials
@@ -235,8 +297,24 @@ __device__ __forceinline__ T ordered_sum(const T *__restrict__ x, int count, int
 }
 
 // red[1 .. 5] = the statistics' means over the live samples, red[6] = L: lane s adds the workgroups' sums in workgroup order
-__global__ __launch_bounds__(64) void car_ppo_stats_kernel(const double *__restrict__ stat_part, int groups, double *__restrict__ red) {
+// kTeacher: lanes 6 .. 9 fold the teacher rows the same way into tred[0 .. 3]: the means of term, kl and abs_err over the Lt taught
+// samples, and Lt / max(L, 1)
+template <bool kTeacher>
+__global__ __launch_bounds__(64) void car_ppo_stats_kernel(const double *__restrict__ stat_part, int groups, double *__restrict__ red,
+                                                           const double *__restrict__ tstat_part, double *__restrict__ tred) {
     const int s = threadIdx.x;
+    if constexpr (kTeacher) {
+        if (s >= kStat && s < kStat + kStatT) {
+            const int k = s - kStat;
+            const double taught = ordered_sum(tstat_part + kStatT - 1, groups, kStatT);
+            if (k == kStatT - 1) {
+                const double live = ordered_sum(stat_part + kStat - 1, groups, kStatRow);
+                tred[k] = taught / (live > 1.0 ? live : 1.0);
+            } else {
+                tred[k] = ordered_sum(tstat_part + k, groups, kStatT) / (taught > 1.0 ? taught : 1.0);
+            }
+        }
+    }
     if (s >= kStat) return;
     const double live = ordered_sum(stat_part + kStat - 1, groups, kStatRow), sum = ordered_sum(stat_part + s, groups, kStatRow);
     red[1 + s] = s == kStat - 1 ? live : sum / (live > 1.0 ? live : 1.0);
@@ -293,6 +371,8 @@ using namespace crl;
 struct crl_car_ppo : PpoBlobs {  // blob_floats is kBlob
     float *partials = nullptr;
     double *stat_part = nullptr, *sq_part = nullptr, *red = nullptr;  // red[1 .. 5]: the statistics' means, red[6]: L
+    double *tstat_part = nullptr, *tred = nullptr;                    // a teacher gradient's rows [kMaxW][kStatT] and its four statistics
+    bool teacher_grad = false;                                        // the last gradient was crl_car_ppo_grad_teacher's
 };
 
 extern "C" {
@@ -301,7 +381,7 @@ void crl_car_ppo_destroy(crl_car_ppo *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     ppo_free_blobs(p);
-    for (void *q : {(void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red})
+    for (void *q : {(void *)p->partials, (void *)p->stat_part, (void *)p->sq_part, (void *)p->red, (void *)p->tstat_part, (void *)p->tred})
         if (q) (void)hipFree(q);
     delete p;
 }
@@ -330,6 +410,8 @@ int crl_car_ppo_create(int32_t device, const float *blob_host, crl_car_ppo **out
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->stat_part, (size_t)kMaxW * kStatRow * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->sq_part, kRedBlocks * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_dev_zalloc(&p->red, (1 + kStat) * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->tstat_part, (size_t)kMaxW * kStatT * sizeof(double), who);
+    if (rc == CRL_OK) rc = crl_dev_zalloc(&p->tred, kStatT * sizeof(double), who);
     if (rc == CRL_OK) rc = crl_car_ppo_set_weights(p, blob_host);
     if (rc != CRL_OK) {
         crl_car_ppo_destroy(p);
@@ -352,24 +434,79 @@ int crl_car_ppo_weights_dev(crl_car_ppo *p, const float **blob_dev) {
     return CRL_OK;
 }
 
-int crl_car_ppo_grad(crl_car_ppo *p, const crl_car_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper, void *stream) {
-    crl_fail_no_ctx();
-    const char *who = "crl_car_ppo_grad";
+}  // extern "C"
+
+// the three launches; kTeacher chooses the instantiations
+template <bool kTeacher>
+static void car_ppo_launch(crl_car_ppo *p, const std::conditional_t<kTeacher, CarGradArgsTeacher, CarGradArgs> &a, int groups, hipStream_t st) {
+    hipLaunchKernelGGL(car_ppo_grad_kernel<kTeacher>, dim3(groups), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(car_ppo_stats_kernel<kTeacher>, dim3(1), dim3(64), 0, st, p->stat_part, groups, p->red, p->tstat_part, p->tred);
+    hipLaunchKernelGGL(car_ppo_reduce_kernel, dim3(kRedBlocks), dim3(256), 0, st, p->partials, p->stat_part, groups, p->red, p->grad, p->sq_part);
+}
+
+// crl_car_ppo_grad (teacher null) and crl_car_ppo_grad_teacher: everything is looked at before the learner or the GPU is touched
+static int car_ppo_grad(const char *who, crl_car_ppo *p, const crl_car_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper,
+                        const crl_car_ppo_teacher *teacher, void *stream) {
     if (!p || !rollout || !idx_dev) return crl_fail(CRL_EINVAL, "%s: null argument", who);
     if ((uintptr_t)idx_dev & 7) return crl_fail(CRL_EINVAL, "%s: idx must be 8-byte aligned", who);
     if (count < 1 || count > 0x7fffffff) return crl_fail(CRL_EINVAL, "%s: the number of samples must be in [1, 2^31)", who);
     if (int rc = ppo_hyper_check(who, hyper)) return rc;
     const CarRolloutView view = car_rollout_view(rollout);
     if (!view.finished) return crl_fail(CRL_EINVAL, "%s: the rollout is not finished (crl_car_rollout_finish computes returns and advantages)", who);
+    CarTeacherDev t{};
+    if (teacher) {
+        if (!teacher->target_dev) return crl_fail(CRL_EINVAL, "%s: the teacher has no target", who);
+        if (teacher->rows != (int64_t)view.last + 1)
+            return crl_fail(CRL_EINVAL, "%s: the teacher holds %lld rows, the rollout's T * R is %lld", who, (long long)teacher->rows, (long long)view.last + 1);
+        if (teacher->kind != CRL_CAR_TEACHER_CE && teacher->kind != CRL_CAR_TEACHER_MSE)
+            return crl_fail(CRL_EINVAL, "%s: kind must be CRL_CAR_TEACHER_CE or CRL_CAR_TEACHER_MSE, not %d", who, (int)teacher->kind);
+        if (teacher->point != 0 && teacher->point != 1) return crl_fail(CRL_EINVAL, "%s: point must be 0 or 1, not %d", who, (int)teacher->point);
+        if (teacher->policy_term != 0 && teacher->policy_term != 1)
+            return crl_fail(CRL_EINVAL, "%s: policy_term must be 0 or 1, not %d", who, (int)teacher->policy_term);
+        if (!(teacher->coef >= 0.f && teacher->coef <= FLT_MAX)) return crl_fail(CRL_EINVAL, "%s: coef must be finite and >= 0", who);
+        if (!teacher->point && !(fabsf(teacher->teacher_log_std[0]) <= FLT_MAX && fabsf(teacher->teacher_log_std[1]) <= FLT_MAX))
+            return crl_fail(CRL_EINVAL, "%s: teacher_log_std must be finite (point = 1 is the teacher without a spread)", who);
+        if (((uintptr_t)teacher->target_dev & 7) || ((uintptr_t)teacher->value_targets_dev & 3))
+            return crl_fail(CRL_EINVAL, "%s: the target must be 8-byte aligned, the value targets 4-byte aligned", who);
+        const double lsq0 = teacher->point ? 0.0 : (double)teacher->teacher_log_std[0], lsq1 = teacher->point ? 0.0 : (double)teacher->teacher_log_std[1];
+        t.target = reinterpret_cast<const float2 *>(teacher->target_dev), t.vtarget = teacher->value_targets_dev, t.tstat_part = p->tstat_part;
+        t.sq0 = teacher->point ? 0.0 : exp(2.0 * lsq0), t.sq1 = teacher->point ? 0.0 : exp(2.0 * lsq1);
+        t.hq = (lsq0 + lsq1) + (1.0 + CRL_LN_2PI_F64);
+        t.coef = (double)teacher->coef, t.mse = teacher->kind == CRL_CAR_TEACHER_MSE, t.kl = !t.mse && !teacher->point, t.policy_term = teacher->policy_term != 0;
+    }
     hipStream_t st = (hipStream_t)stream;
     const int64_t ngroups = (count + kG - 1) / kG;
     const int groups = (int)(ngroups < kMaxW ? ngroups : kMaxW);
     const CarGradArgs a{view, idx_dev, count, p->raw, p->partials, p->stat_part, CarPpoHyperDev{hyper->clip, hyper->vf_coef, hyper->ent_coef}};
-    hipLaunchKernelGGL(car_ppo_grad_kernel, dim3(groups), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(car_ppo_stats_kernel, dim3(1), dim3(64), 0, st, p->stat_part, groups, p->red);
-    hipLaunchKernelGGL(car_ppo_reduce_kernel, dim3(kRedBlocks), dim3(256), 0, st, p->partials, p->stat_part, groups, p->red, p->grad, p->sq_part);
+    if (teacher) car_ppo_launch<true>(p, CarGradArgsTeacher{a, t}, groups, st);
+    else car_ppo_launch<false>(p, a, groups, st);
     HIP_TRY(hipGetLastError());
-    p->have_grad = true;
+    p->have_grad = true, p->teacher_grad = teacher != nullptr;
+    return CRL_OK;
+}
+
+extern "C" {
+
+int crl_car_ppo_grad(crl_car_ppo *p, const crl_car_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper, void *stream) {
+    crl_fail_no_ctx();
+    return car_ppo_grad("crl_car_ppo_grad", p, rollout, idx_dev, count, hyper, nullptr, stream);
+}
+
+int crl_car_ppo_grad_teacher(crl_car_ppo *p, const crl_car_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper,
+                             const crl_car_ppo_teacher *teacher, void *stream) {
+    crl_fail_no_ctx();
+    if (!teacher) return crl_fail(CRL_EINVAL, "crl_car_ppo_grad_teacher: null teacher (crl_car_ppo_grad is the plain gradient)");
+    return car_ppo_grad("crl_car_ppo_grad_teacher", p, rollout, idx_dev, count, hyper, teacher, stream);
+}
+
+int crl_car_ppo_teacher_stats(crl_car_ppo *p, double *out4_host) {
+    crl_fail_no_ctx();
+    if (!p || !out4_host) return crl_fail(CRL_EINVAL, "crl_car_ppo_teacher_stats: null argument");
+    if (!p->have_grad || !p->teacher_grad)
+        return crl_fail(CRL_EINVAL, "crl_car_ppo_teacher_stats: the last gradient had no teacher (crl_car_ppo_grad_teacher)");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out4_host, p->tred, kStatT * sizeof(double), hipMemcpyDeviceToHost));
     return CRL_OK;
 }
 

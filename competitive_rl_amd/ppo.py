@@ -159,6 +159,7 @@ class _PPOLearner:
     _SIZED = True                # crl_ppo_get_state / set_state carry the blob's size and scratch_rows: one C object, two networks
     _weights_of = staticmethod(_learner_weights)
     _views = staticmethod(blob_views)                                  # a flat blob as the tensors' views by key
+    _TEACHER = Teacher           # the value object ``grad(teacher=)`` takes
 
     def _open(self, device, hyper):
         """What every constructor starts with: the GPU, the hyper-parameters, the device."""
@@ -212,8 +213,8 @@ class _PPOLearner:
         idx = idx.contiguous()
         hyper = self._hyper()
         if teacher is not None:
-            if not isinstance(teacher, Teacher):
-                raise ValueError(f"teacher must be a Teacher or None, not {type(teacher).__name__}")
+            if not isinstance(teacher, self._TEACHER):
+                raise ValueError(f"teacher must be a {self._TEACHER.__name__} or None, not {type(teacher).__name__}")
             native = teacher._native(self.device, storage._total())
         with torch.cuda.device(self.device):
             ip = C.c_void_p(idx.data_ptr()) if idx.numel() else None

@@ -743,6 +743,38 @@ CAR_PPO_DEFAULTS = dict(clip=0.2, vf_coef=0.5, ent_coef=0.0, lr=3e-4, betas=(0.9
 CAR_PPO_STAT_KEYS = ("policy", "value", "entropy", "kl", "clipped")
 
 
+CAR_TEACHER_LOSSES = ("ce", "mse")  # enum crl_car_teacher_kind
+CAR_TEACHER_STAT_KEYS = ("term", "kl_teacher", "abs_err", "taught")
+
+
+def check_car_teacher(log_std=None, loss="ce", coef=1.0, policy_term=True):
+    """What ``crl_car_ppo_grad_teacher`` accepts beside its arrays, as the values it receives (include/crl.h "car ppo update, teacher
+    targets"): ``log_std`` None (a point teacher) or a pair of finite float32 -- or a car policy weight dict or blob, whose
+    ``log_std`` is taken --, ``loss`` one of ``CAR_TEACHER_LOSSES``, a finite float32 ``coef`` >= 0 and a ``policy_term`` of 0 or 1 (a
+    bool).  Returns (point, (lsq_0, lsq_1) as floats, kind, coef, policy_term); a ``ValueError`` otherwise."""
+    if loss not in CAR_TEACHER_LOSSES:
+        raise ValueError(f"loss must be one of {CAR_TEACHER_LOSSES}, not {loss!r}")
+    if log_std is None:
+        point, lsq = 1, (0.0, 0.0)
+    else:
+        if isinstance(log_std, dict):
+            if "log_std" not in log_std:
+                raise ValueError("log_std: the weight dict has no log_std")
+            log_std = log_std["log_std"]
+        try:
+            with np.errstate(over="ignore"):
+                arr = np.asarray(log_std, np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"log_std must be None, a pair of floats, a weight dict or a blob, not {type(log_std).__name__}") from None
+        if arr.size == N.CRL_CAR_POLICY_BLOB_FLOATS:
+            arr = car_policy_unpack(arr)["log_std"]
+        if arr.size != 2 or not np.isfinite(arr).all():
+            raise ValueError(f"log_std must hold two finite floats, not {arr.tolist() if arr.size <= 8 else arr.shape}")
+        point, lsq = 0, (float(arr[0]), float(arr[1]))
+    _, k, policy_term = check_teacher(1.0, coef, policy_term)
+    return point, lsq, CAR_TEACHER_LOSSES.index(loss), k, policy_term
+
+
 def car_ppo_loss_reference(weights, obs, actions, old_logp, returns, adv, live, hyper=None, dtype=None):
     """The loss of include/crl.h "car ppo update" with torch autograd on the CPU; ``dtype=torch.float64`` (the default) is the
     yardstick of the device's gradient.  ``weights``: anything ``car_policy_weights`` takes; ``obs`` float32 [B, 21]; ``actions``
@@ -752,6 +784,21 @@ def car_ppo_loss_reference(weights, obs, actions, old_logp, returns, adv, live, 
     ``kl``, ``clipped`` (means over the live samples), ``live`` (L), ``grads`` (the seven gradient arrays by key) and, per sample,
     ``a`` [B, 100] (the pre-activations), ``mean`` [B, 2], ``v``, ``logp``, ``ratio``, ``active`` (the branch with
     d policy / d logp = -A r).  Host code for tests; the kernels do not use it."""
+    return _car_ppo_loss(weights, obs, actions, old_logp, returns, adv, live, hyper, dtype)
+
+
+def car_ppo_teacher_loss_reference(weights, obs, actions, old_logp, returns, adv, live, hyper=None, dtype=None, teacher=None):
+    """The loss of include/crl.h "car ppo update, teacher targets" with torch autograd on the CPU: ``car_ppo_loss_reference`` plus
+    ``coef * term`` towards a per-sample target, with the policy term switched by ``policy_term``.  ``teacher``: None (then this IS
+    ``car_ppo_loss_reference``) or a dict of PER-SAMPLE rows, already taken at the samples' flat indices: ``target`` float32 [B, 2] (a
+    row with a non-finite float: no teacher term for that sample); optionally ``value_targets`` float32 [B] in place of the returns;
+    ``log_std`` (None: a point teacher), ``loss`` ("ce"), ``coef`` (1), ``policy_term`` (1) as ``check_car_teacher`` takes them.  The
+    return dict gains ``term``, ``kl_teacher`` and ``abs_err`` (means over the Lt taught samples), ``taught`` (Lt / max(L, 1)) and, per
+    sample, ``is_taught``.  Host code for tests; the kernels do not use it."""
+    return _car_ppo_loss(weights, obs, actions, old_logp, returns, adv, live, hyper, dtype, teacher)
+
+
+def _car_ppo_loss(weights, obs, actions, old_logp, returns, adv, live, hyper, dtype, teacher=None):
     import math
 
     import torch
@@ -762,6 +809,8 @@ def car_ppo_loss_reference(weights, obs, actions, old_logp, returns, adv, live, 
     w0 = car_policy_weights(weights)
     w = {k: torch.tensor(w0[k], dtype=dtype, requires_grad=True) for k in CAR_POLICY_KEYS}
     x, u = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (obs, actions))
+    if teacher is not None and teacher.get("value_targets") is not None:
+        returns = np.asarray(teacher["value_targets"], np.float32).reshape(len(x))
     olp, ret, A = (torch.tensor(np.asarray(t, np.float32), dtype=dtype) for t in (old_logp, returns, adv))
     lv = torch.tensor(np.asarray(live) != 0)
     a = x @ w["fc1_w"].t() + w["fc1_b"]
@@ -778,16 +827,40 @@ def car_ppo_loss_reference(weights, obs, actions, old_logp, returns, adv, live, 
     L = max(int(lv.sum()), 1)
     zero = torch.zeros_like(v)
     over = lambda t: torch.where(lv, t, zero).sum() / L  # noqa: E731
-    loss = over(policy + vf * value - ent * entropy)
-    loss.backward()
     n = lambda t: t.detach().numpy()  # noqa: E731
     s = lambda t: float(t.detach())  # noqa: E731
+    extra = {}
+    if teacher is None:
+        loss = over(policy + vf * value - ent * entropy)
+    else:
+        point, lsq, kind, coef, policy_term = check_car_teacher(teacher.get("log_std"), teacher.get("loss", "ce"), teacher.get("coef", 1.0),
+                                                                teacher.get("policy_term", 1))
+        tg = np.asarray(teacher["target"], np.float32).reshape(len(x), 2)
+        finite = np.isfinite(tg).all(1)
+        taught = lv & torch.tensor(finite)
+        t = torch.tensor(np.where(finite[:, None], tg, np.float32(0)), dtype=dtype)  # (an untaught row is never looked at: selected out below)
+        sq = torch.tensor([0.0, 0.0] if point else [math.exp(2.0 * lsq[0]), math.exp(2.0 * lsq[1])], dtype=dtype)
+        dm = mean - t
+        sd = torch.exp(ls)
+        var = sd * sd
+        if CAR_TEACHER_LOSSES[kind] == "ce":
+            per = ls + (sq + dm ** 2) / (2 * var)
+            term = (per[:, 0] + per[:, 1]) + math.log(2 * math.pi)
+            kl_t = term - ((lsq[0] + lsq[1]) + (1 + math.log(2 * math.pi))) if not point else zero
+        else:
+            term, kl_t = 0.5 * (dm[:, 0] ** 2 + dm[:, 1] ** 2), zero
+        loss = over(policy_term * policy + vf * value - ent * entropy + coef * torch.where(taught, term, zero))
+        Lt = max(int(taught.sum()), 1)
+        among = lambda q: s(torch.where(taught, q, zero).sum() / Lt)  # noqa: E731
+        extra = dict(term=among(term), kl_teacher=among(kl_t), abs_err=among((dm[:, 0].abs() + dm[:, 1].abs()) / 2),
+                     taught=int(taught.sum()) / L, is_taught=n(taught))
+    loss.backward()
     r = ratio.detach()
     active = ((A >= 0) & (r < 1 + c)) | ((A < 0) & (r > 1 - c))
     return dict(loss=s(loss), policy=s(over(policy)), value=s(over(value)), entropy=s(over(entropy)), kl=s(over(olp - logp)),
                 clipped=s(over(((r < 1 - c) | (r > 1 + c)).to(dtype))), live=int(lv.sum()),
                 grads={k: (n(w[k].grad) if w[k].grad is not None else np.zeros(CAR_POLICY_SHAPES[k])) for k in CAR_POLICY_KEYS},
-                a=n(a), mean=n(mean), v=n(v), logp=n(logp), ratio=n(r), active=n(active))
+                a=n(a), mean=n(mean), v=n(v), logp=n(logp), ratio=n(r), active=n(active), **extra)
 
 
 # ---- include/crl.h "car league": the draw of car 1's driver and the race books

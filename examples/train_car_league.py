@@ -9,6 +9,8 @@ and that agent's record starts over (``league.reset_agent``).  Nothing synchroni
 read per iteration is the line this script prints, and every --report iterations the per-agent table.
 
     python examples/train_car_league.py --envs 1024 --steps 64 --iterations 40
+
+The learner starts from ``initial_weights``; ``examples/clone_car_driver.py --then-league`` runs this loop from a RULE_BASED clone.
 """
 import argparse
 import os
@@ -33,7 +35,9 @@ def report(league):
             c["length_sum"][a] / max(int(c["episodes"][a]), 1), w[a]))
 
 
-def main():
+def main(argv=None, weights=None):
+    """``weights``: the learner's starting weights in place of ``initial_weights`` (examples/clone_car_driver.py --then-league hands its
+    RULE_BASED clone over here); ``argv``: the command line in place of the process's."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=64, help="steps per rollout")
@@ -47,11 +51,11 @@ def main():
     ap.add_argument("--report", type=int, default=5, help="iterations between per-agent tables")
     ap.add_argument("--start-elapsed", type=int, default=0,
                     help="start the envs' TimeLimit counters staggered over [this, 1000): episodes end from the first iterations on")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     assert 1 <= a.snapshots <= 7
 
     env = crl.HipCarVecEnv(a.envs, seed=a.seed, done_policy="car0")
-    learner = crl.CarPPO(initial_weights(a.seed), lr=a.lr)
+    learner = crl.CarPPO(initial_weights(a.seed) if weights is None else weights, lr=a.lr)
     policy = crl.CarPolicy(env, seed=a.seed)
     drivers = crl.CarDrivers(env, seed=a.seed)
     policy.add_network("learner", learner.weights())

@@ -1424,6 +1424,65 @@ int crl_car_ppo_stats(crl_car_ppo *p, double *out8_host);
 int crl_car_ppo_get_state(crl_car_ppo *p, float *blob_out_host, float *m_out_host, float *v_out_host, int64_t *steps_out, void *stream);
 int crl_car_ppo_set_state(crl_car_ppo *p, const float *blob_host, const float *m_host, const float *v_host, int64_t steps, void *stream);
 
+/* ---- car ppo update, teacher targets: imitation and KL-to-teacher for the car policy's learner ----------------
+ * Extends "car ppo update"; nothing in that section changes.  One term is added to d loss / d mean and d loss / d log_std in the heads;
+ * everything behind the heads -- the matrix-instruction backward, the five float64 bias sums, the summation shape, the reduce, the
+ * optimiser step, the push, resume -- is untouched.  Serves cloning a rule (a second crl_car_driver with RULE_BASED and epsilon 0 writes
+ * what it would do into a scratch action array), distilling one network into another (a deterministic crl_car_policy slot writes its mean
+ * the same way) and PPO held near a teacher.  rules.car_ppo_teacher_loss_reference (torch autograd) restates the loss.
+ *
+ * Target of sample b, from row s = idx[b] (the flat t * R + row index; never row b) of two device arrays:
+ *   target         float32 [T * R][2]: the teacher's action or mean t_d;
+ *   value_targets  float32 [T * R], optional: target_v = value_targets[s] in place of the stored return (a teacher's critic).
+ * A sample is TAUGHT iff it is live and both floats of its target are finite.  An untaught sample has teacher term 0, teacher
+ * derivatives 0 and teacher statistics 0, by selection, not by a product with 0: a NaN target never reaches a sum.
+ * Teacher spread: two host floats teacher_log_std[2] = lsq_d give sq_d = exp(2 (double) lsq_d), formed in float64 from the float32
+ * values; point = 1 sets sq_d = 0 (and lsq_d is not read): a deterministic teacher such as RULE_BASED.
+ * Kinds.  With mean_d, std_d, log_std_d the learner's as "car ppo update" forms them in float64, dm_d = mean_d - t_d and
+ * var_d = std_d std_d:
+ *   CRL_CAR_TEACHER_CE    term = ((log_std_0 + (sq_0 + dm_0^2) / (2 var_0)) + (log_std_1 + (sq_1 + dm_1^2) / (2 var_1))) + ln(2 pi)
+ *                         = E_q[-log p] for the teacher q = N(t, sq) -- for a point teacher the Gaussian negative log-likelihood of t;
+ *                         t_mean_d = dm_d / var_d;   t_ls_d = 1 - (sq_d + dm_d^2) / var_d;
+ *   CRL_CAR_TEACHER_MSE   term = 0.5 (dm_0^2 + dm_1^2);   t_mean_d = dm_d;   t_ls_d = 0.
+ * Loss, per LIVE sample:   loss_b = policy_term * policy + vf * value - ent * entropy + coef * [taught] * term,   the sum divided by
+ * max(L, 1) as before;
+ *   policy_term in {0, 1}: at 0 the rule sets g = d policy / d logp = 0 -- pure imitation; the stored advantage and old log-prob then
+ *   play no part in the gradient (they still enter the existing statistics);  coef >= 0, finite;
+ *   value = 0.5 (target_v - v)^2.
+ * Closed forms, float64, rounded once to float32, the teacher term added last:
+ *   d loss_b / d mean_d = (the expression of "car ppo update") + coef t_mean_d;
+ *   d loss_b / d log_std_d = (the expression) + coef t_ls_d;     d loss_b / d v = vf (v - target_v).
+ * With coef = 0, policy_term = 1 and no value targets the gradient therefore equals crl_car_ppo_grad's as numbers.
+ * Statistics: the six of "car ppo update" as always, and four more, float64 sums in the summation shape of the six (per lane over
+ * its samples, the butterfly, the workgroups in order): term; kl = term - ((lsq_0 + lsq_1) + (1 + ln(2 pi))) for CE with point = 0
+ * (= KL(q || p)), 0 otherwise; abs_err = (|dm_0| + |dm_1|) / 2 -- the three as means over the Lt taught samples, divisor
+ * max(Lt, 1) --; and taught = Lt / max(L, 1).
+ * The kernels: the teacher instantiations of the gradient and statistics kernels; the plain instantiations are what crl_car_ppo_grad
+ * launches, with no teacher load, select or statistic in them.  A lane loads its sample's 8-byte target row and, when value targets
+ * are given, their 4 bytes.  The same launches, no floating-point atomics, the same call gives the same bits on every run, nothing
+ * synchronises, all work is ordered on the caller's stream. */
+enum crl_car_teacher_kind { CRL_CAR_TEACHER_CE = 0, CRL_CAR_TEACHER_MSE = 1 };
+typedef struct crl_car_ppo_teacher {
+    const float *target_dev;          /* [rows][2] */
+    const float *value_targets_dev;   /* [rows] or null = the stored returns */
+    int64_t rows;                     /* must equal T * R of the rollout */
+    float teacher_log_std[2];         /* read when point = 0 */
+    int32_t point;                    /* 1: a deterministic teacher, sq_d = 0 */
+    int32_t kind;                     /* enum crl_car_teacher_kind */
+    float coef;
+    int32_t policy_term;
+} crl_car_ppo_teacher;
+/* crl_car_ppo_grad with a teacher; crl_car_ppo_step, _stats, _get_grad and _weights_dev work behind it as behind crl_car_ppo_grad.  The
+ * teacher's arrays are the caller's and must stay valid until the launches have run.  Refuses (CRL_EINVAL, before any GPU call, the
+ * learner as it was): everything crl_car_ppo_grad refuses; a null teacher or target; rows != T * R; a kind outside the enum; point or
+ * policy_term outside {0, 1}; a coef that is not finite and >= 0; a teacher_log_std that is not finite when point = 0; a target that
+ * is not 8-byte aligned or value targets that are not 4-byte aligned. */
+int crl_car_ppo_grad_teacher(crl_car_ppo *p, const crl_car_rollout *rollout, const int64_t *idx_dev, int64_t count, const crl_ppo_hyper *hyper,
+                             const crl_car_ppo_teacher *teacher, void *stream);
+/* out4_host: term, kl, abs_err, taught of the last crl_car_ppo_grad_teacher.  Synchronises the device, like crl_car_ppo_stats.  Refuses
+ * (CRL_EINVAL) when the learner's last gradient was a plain crl_car_ppo_grad's, or when it has none. */
+int crl_car_ppo_teacher_stats(crl_car_ppo *p, double *out4_host);
+
 /* ---- car league: per-env opponents for car 1 and race books on the device --------------
  * What "league" and "league ledger" are for cPongTournament, for a two-car CarRacing context: a pool of opponents, a per-env draw of
  * who drives car 1, and books of how car 0 (the caller's car, the seat make_competitive_car_racing gives its agent,
